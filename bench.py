@@ -122,11 +122,13 @@ def parse(argv=None):
     ap.add_argument('--train', action='store_true',
                     help='time one DDP training iteration of the fusion head (configs[2]) '
                          'instead of inference')
-    ap.add_argument('--min-window-s', type=float, default=1.0,
-                    help='the K-step window is repeated until this much time has been measured; '
-                         'the MEDIAN window is reported (a 20-step window is 7 ms)')
     ap.add_argument('--warmup-s', type=float, default=0.5,
-                    help='after the W warm-up steps, keep stepping until this much time has passed')
+                    help='after the W warm-up steps, rehearse the K-step window (untimed) until this much time '
+                         'has passed; then exactly K steps are timed, in one window (a 20-step window is 7 ms)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='inference: after the timed window, write what its last step computed (head outputs and '
+                         'decoded boxes of that step\'s frames) as DIR/<name>.npy, float32; the inputs are seeded, '
+                         'so two builds can be compared output for output')
     ap.add_argument('--backend', default=None, choices=['nccl', 'gloo'],
                     help='torch.distributed backend (default: nccl = RCCL on the GPU)')
     ap.add_argument('--share-gpu', action='store_true',
@@ -137,7 +139,12 @@ def parse(argv=None):
     ap.add_argument('--dry-run', action='store_true',
                     help='no GPU work: spawn / rendezvous (gloo) / rank census / the collectives of '
                          'the chosen mode on CPU tensors / the JSON line.  Runs in a CPU container')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.train or args.dry_run):
+        ap.error('--dump-outputs: the inference path only (not with --train or --dry-run)')
+    return args
 
 
 # ---- one process per GPU from a single command (tools/dist_train.sh:7-9) -----------------
@@ -753,7 +760,7 @@ def live_train_traffic(extra_args=(), timeout_s=120):
         paths = []
         for ctr in ('FETCH_SIZE', 'WRITE_SIZE'):
             pth = _pmc_pass(tools[0], tools[1], tmp, ctr, ['--train', '--steps', '9', '--warmup', '2', '--no-roofline', '--main-only',
-                                                          '--min-window-s', '0.02', '--warmup-s', '0.02'] + list(extra_args),
+                                                          '--warmup-s', '0.02'] + list(extra_args),
                             timeout_s)
             if pth is None:
                 return None
@@ -784,7 +791,7 @@ def live_traffic(frames_per_launch, timeout_s=75, extra_args=()):
     try:
         for ctr in ('FETCH_SIZE', 'WRITE_SIZE', 'SQ_VALU_MFMA_BUSY_CYCLES'):
             csv_path = _pmc_pass(exe, py, tmp, ctr, ['--batch', str(frames_per_launch), '--steps', '3', '--warmup', '1',
-                                                     '--main-only', '--no-graph', '--min-window-s', '0.02',
+                                                     '--main-only', '--no-graph',
                                                      '--warmup-s', '0.02'] + list(extra_args), timeout_s)
             if csv_path is None:
                 return {}
@@ -1254,41 +1261,78 @@ def rank_census(dev, world):
     return int(round(float(t.item())))
 
 
-def timed_windows(step, sync, args, dev, world):
-    """W warm-up steps (+ more until --warmup-s has passed), then windows of EXACTLY K steps, each
-    bracketed by barrier + device sync on both sides and reduced with MAX over ranks, repeated
-    until --min-window-s has been measured.  Every rank derives the loop counts from all-reduced
-    numbers, so the ranks stay in step (a training step contains a collective)."""
+def timed_window(step, sync, args, dev, world, phases=1, cycle=1):
+    """W warm-up steps (rounded up to whole `cycle`s), then untimed rehearsals of the timed window (K steps + sync),
+    `phases` in a row, repeated until --warmup-s has passed; then ONE timed window of EXACTLY K steps, bracketed by
+    barrier + device sync on both sides and reduced with MAX over ranks.
+    A frame pipeline's step state (the lane and frame slot it fills next) is back where a fresh pipeline starts after
+    every `cycle` steps, and back where a window started after `phases` windows: the rehearsals and the timed window
+    all start at lane 0, slot 0 -- the timed window repeats a rehearsed one (every graph it replays, partial launches
+    included, is captured before it), and its last step computes the same frame in every run.  (Where a window starts
+    matters: with 3 lanes of 9 frames, 20 steps are 9 + 9 + 2 frames, and which lanes take the full launches moved the
+    rate between 7 000 and 8 900 frames/s on one MI355X.)  Every rank derives the loop counts from all-reduced numbers,
+    so the ranks stay in step (a training step contains a collective)."""
     cpu_or_dev = dev if world > 1 else None
+    warmup = -(-args.warmup // cycle) * cycle
     t0 = time.perf_counter()
-    for _ in range(args.warmup):
+    for _ in range(warmup):
         step()
     sync()
-    dt = D.max_over_ranks(time.perf_counter() - t0, cpu_or_dev)
-    extra = 0
-    if args.warmup > 0 and dt < args.warmup_s:
-        extra = min(100000, int((args.warmup_s - dt) / max(dt / args.warmup, 1e-6)) + 1)
-        for _ in range(extra):
-            step()
-    windows, own, total = [], [], 0.0
+    rounds = 0
     while True:
-        D.barrier()
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        sync()
-        own.append(time.perf_counter() - t0)          # this rank alone, before it waits for the slowest one
-        D.barrier()
+        for _ in range(phases):
+            for _ in range(args.steps):
+                step()
+            sync()
+        rounds += 1
         dt = D.max_over_ranks(time.perf_counter() - t0, cpu_or_dev)
-        windows.append(dt)
-        total += dt
-        if total >= args.min_window_s or len(windows) >= 1000:
+        if dt >= args.warmup_s or rounds * phases * args.steps >= 100000:
             break
-    med = float(np.median(windows))
-    return med, dict(windows=len(windows), warmup_steps_run=args.warmup + extra,
-                     window_ms_min=min(windows) * 1e3, window_ms_median=med * 1e3,
-                     window_ms_max=max(windows) * 1e3, own_window_ms_median=float(np.median(own)) * 1e3)
+    D.barrier()
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    sync()
+    own = time.perf_counter() - t0          # this rank alone, before it waits for the slowest one
+    D.barrier()
+    dt = D.max_over_ranks(time.perf_counter() - t0, cpu_or_dev)
+    return dt, dict(timed_steps=args.steps, warmup_steps_run=warmup + rounds * phases * args.steps,
+                    window_ms=dt * 1e3, own_window_ms=own * 1e3)
+
+
+#: --dump-outputs writes at most this many bytes of array data (64 MB with the .npy headers)
+DUMP_CAP_BYTES = 60 << 20
+
+
+def last_step_outputs(pipe, last):
+    """What the caller of the timed path holds after its last step, on the host as float32 arrays: the head's
+    outputs (all_cls_scores / all_bbox_preds [layers, frames, queries, 10]) and the box decode (boxes [frames, 300, 9],
+    scores, labels, valid [frames, 300]) -- of the frame(s) that step handed over (a frame pipeline that takes one
+    frame per step: that frame's slot of the lane's last launch)."""
+    if 'submitted' in last:
+        lane, slot, _ = last['submitted']
+        _, (outs, dec) = pipe.results(lane)
+        sel = slice(slot, slot + 1)
+    else:
+        outs, dec = last['out']
+        sel = slice(None)
+    arrays = {'all_cls_scores': outs['all_cls_scores'][:, sel], 'all_bbox_preds': outs['all_bbox_preds'][:, sel]}
+    arrays.update(zip(('boxes', 'scores', 'labels', 'valid'), (t[sel] for t in dec)))
+    return {k: v.float().cpu().numpy() for k, v in arrays.items()}
+
+
+def dump_outputs(path, arrays, cap=DUMP_CAP_BYTES):
+    """DIR/<name>.npy per array (float32).  Above `cap` bytes in all, every array is replaced by a fixed, seeded
+    sample of its flattened elements (in order), in proportion to its size."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 4
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > cap:
+            k = a.size * cap // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def per_rank_summary(own_ms, steps, frames_per_step):
@@ -1296,7 +1340,7 @@ def per_rank_summary(own_ms, steps, frames_per_step):
     the spread says whether `value` (MAX over ranks) is one slow rank or all of them."""
     rates = [steps * frames_per_step / (ms * 1e-3) if ms > 0 else 0.0 for ms in own_ms]
     return {'frames_per_s': rates, 'min': min(rates), 'median': float(np.median(rates)), 'max': max(rates),
-            'unit': 'frames/s', 'definition': 'steps / own median window of the rank (value uses the MAX over ranks)'}
+            'unit': 'frames/s', 'definition': 'steps / own timed window of the rank (value uses the MAX over ranks)'}
 
 
 class LookAheadFrames:
@@ -1394,8 +1438,8 @@ def train_bench(args, head, inp, dev, rank, world, affinity=None):
                                                 gts, lbs, prefetch=nxt)
 
     census = rank_census(dev, world)
-    med, win = timed_windows(step, torch.cuda.synchronize, args, dev, world)
-    own = D.gather_floats(win['own_window_ms_median'], dev if world > 1 else None)
+    window_s, win = timed_window(step, torch.cuda.synchronize, args, dev, world)
+    own = D.gather_floats(win['own_window_ms'], dev if world > 1 else None)
     # what the gradient exchange costs the compute stream: between the end of the backward and the optimizer's first
     # kernel (events of 20 extra iterations, outside the timed windows).  One rank: no collective, the figure is the
     # events' own distance; more ranks: the all-reduce's exposed part (it starts asynchronously behind the backward and
@@ -1434,7 +1478,7 @@ def train_bench(args, head, inp, dev, rank, world, affinity=None):
                     step()
                 torch.cuda.synchronize()
                 wins.append((time.perf_counter() - t0) / args.steps * 1e3)
-            det_cost = {'ms_per_step': float(np.median(wins)), 'relative_to_default': float(np.median(wins)) / (med / args.steps * 1e3),
+            det_cost = {'ms_per_step': float(np.median(wins)), 'relative_to_default': float(np.median(wins)) / (window_s / args.steps * 1e3),
                         'what': 'FusionTrainer(deterministic=True): tc_radar_train_bwd_fused_det, bit-identical gradients run to run'}
         finally:
             tr.deterministic = False
@@ -1445,9 +1489,9 @@ def train_bench(args, head, inp, dev, rank, world, affinity=None):
         'per_rank': per_rank_summary(own, args.steps, B), 'cpu_affinity': affinity,
         'metric': 'training frames/sec: fusion head iteration (frozen DETR3D decoder fwd + radar '
                   'stack fwd/bwd + loss + grad all-reduce + AdamW), FPN features resident in HBM',
-        'value': args.steps * B * world / med, 'unit': 'frames/s', 'n_gpus': world,
+        'value': args.steps * B * world / window_s, 'unit': 'frames/s', 'n_gpus': world,
         'rccl_ranks': census,
-        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': med / args.steps * 1e3,
+        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': window_s / args.steps * 1e3,
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
         'data': 'synthetic', 'timing': win,
         'config': {'workload': 'BASELINE.json configs[2]: %s FPN shapes, 900 queries, 255 radar points, '
@@ -1696,14 +1740,14 @@ def dry_run(args, affinity=None):
             bucket.grads.fill_(float(rank + 1))
             bucket.all_reduce()
 
-    med, win = timed_windows(step, lambda: None, args, None, 1 if world == 1 else world)
-    own = D.gather_floats(win['own_window_ms_median'])
+    window_s, win = timed_window(step, lambda: None, args, None, 1 if world == 1 else world)
+    own = D.gather_floats(win['own_window_ms'])
     ok = True
     if bucket is not None and world > 1:
         ok = bool((bucket.grads == world * (world + 1) / 2).all())
     line = {'metric': 'dry run (CPU, gloo): launcher / rendezvous / collectives only', 'value': 0.0,
             'unit': 'frames/s', 'n_gpus': world, 'rccl_ranks': census, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': med / args.steps * 1e3, 'higher_is_better': True,
+            'warmup': args.warmup, 'ms_per_step': window_s / args.steps * 1e3, 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'dry_run': True, 'timing': win, 'bucket_all_reduce_ok': ok, 'cpu_affinity': affinity,
             'per_rank': per_rank_summary(own, args.steps, 1), 'roofline': None,
@@ -1774,12 +1818,15 @@ def main(argv=None):
                                                               matrix_path=args.matrix_path,
                                                               cam_pregather=bool(args.pregather)))
 
+    last = {}                                # what the latest step handed back (--dump-outputs)
+
     def step():
         if pipe is None:
-            return one_step(head, inp)
-        if pair == 1:
-            return pipe.launch()[1]
-        return pipe.submit()
+            last['out'] = one_step(head, inp)
+        elif pair == 1:
+            last['out'] = pipe.launch()[1]
+        else:
+            last['submitted'] = pipe.submit()
 
     def sync():
         if pipe is not None and pair > 1:
@@ -1787,22 +1834,28 @@ def main(argv=None):
         torch.cuda.synchronize()
 
     census = rank_census(dev, world)
-    med, win = timed_windows(step, sync, args, dev, world)
-    own = D.gather_floats(win['own_window_ms_median'], dev if world > 1 else None)
+    # a frame pipeline is back at lane 0, slot 0 after every lane took each of its frame slots once (or, one launch
+    # per step, after one launch per lane); one window per lane brings a window's start lane back
+    cycle = 1 if pipe is None else pipe.lanes * (pipe.frames_per_launch if pair > 1 else 1)
+    window_s, win = timed_window(step, sync, args, dev, world, phases=1 if pipe is None else pipe.lanes, cycle=cycle)
+    if args.dump_outputs and rank == 0:
+        # before the side runs below replay the same lanes
+        dump_outputs(args.dump_outputs, last_step_outputs(pipe, last))
+    own = D.gather_floats(win['own_window_ms'], dev if world > 1 else None)
     frames = args.steps * args.batch * world
     in_flight = 1 if pipe is None else min(pipe.lanes * pipe.frames_per_launch, args.steps * args.batch)
     line = {
         'metric': 'nuScenes frames/sec (6-cam+radar, 900 queries): fusion decoder '
                   '(Detr3DHead.forward + box decode), FPN features resident in HBM',
-        'value': frames / med,
+        'value': frames / window_s,
         'unit': 'frames/s',
         'n_gpus': world,
         'rccl_ranks': census,
         'steps': args.steps,
         'warmup': args.warmup,
-        'ms_per_step': med / args.steps * 1e3,
+        'ms_per_step': window_s / args.steps * 1e3,
         # 1 / throughput with `frames_in_flight` frames overlapping -- NOT the latency of a frame
-        'throughput_inverse_ms_per_frame': med / args.steps * 1e3 / args.batch,
+        'throughput_inverse_ms_per_frame': window_s / args.steps * 1e3 / args.batch,
         'higher_is_better': True,
         'scaling': 'weak',
         'vs_baseline': None,

@@ -4,6 +4,8 @@ REFERENCE's own code (imported unmodified from /root/reference through
 oracle/ref_harness.py) on seeded synthetic inputs.
 
 Run only in the authoring container:   python tests/golden/make_golden.py
+(`... make_golden.py configs`: only g9_reference_configs.json, the values of
+the reference's config files)
 
 Inputs and weights are regenerated from seeds by transcar_amd/synth.py and
 are never stored; only small outputs / intermediates are committed
@@ -252,7 +254,34 @@ def g8_train_grads(ref, tag='tiny'):
           sum(p.numel() for p in head.parameters() if p.requires_grad), 'trainable scalars')
 
 
+#: the reference's three detection config files (projects/configs/detr3d/)
+REF_CONFIG_FILES = ('detr3d_res101_gridmask.py', 'detr3d_res101_gridmask_cbgs.py',
+                    'detr3d_vovnet_gridmask_det_final_trainval_cbgs.py')
+
+
+def g9_reference_configs():
+    """The values the reference's config files define for the head (CFG:51-114, CFG_VOV:55): each file executed as
+    it lies (plain Python, `_base_` is a list of names) and model['pts_bbox_head'], model['train_cfg']['pts'],
+    point_cloud_range and voxel_size stored as JSON (tuples become lists)."""
+    import json
+    import runpy
+    out = {}
+    for name in REF_CONFIG_FILES:
+        ns = runpy.run_path(os.path.join(RH.REF_ROOT, 'projects', 'configs', 'detr3d', name))
+        model = ns['model']
+        out[name] = {'pts_bbox_head': model['pts_bbox_head'], 'train_cfg_pts': model['train_cfg']['pts'],
+                     'point_cloud_range': ns['point_cloud_range'], 'voxel_size': ns['voxel_size']}
+    path = os.path.join(HERE, 'g9_reference_configs.json')
+    with open(path, 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('wrote g9_reference_configs.json (%.1f KB)' % (os.path.getsize(path) / 1024))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'configs':
+        g9_reference_configs()
+        return
     ref = RH.load_reference()
     head, _ = ref_head()
     if len(sys.argv) > 1 and sys.argv[1] == 'vovnet':

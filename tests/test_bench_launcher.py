@@ -12,7 +12,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAST = ['--dry-run', '--steps', '3', '--warmup', '1', '--min-window-s', '0.02', '--warmup-s', '0']
+FAST = ['--dry-run', '--steps', '3', '--warmup', '1', '--warmup-s', '0']
 
 
 def _run(cmd, env=None):
@@ -202,3 +202,47 @@ def test_cpu_baseline_spread_reads_the_committed_lines():
     assert 100.0 < got['min_ms_per_frame'] <= got['median_ms_per_frame'] <= got['max_ms_per_frame']
     base = bench.cpu_baseline_spread()
     assert base['runs'] == got['runs'] - 1 and base['max_ms_per_frame'] < 1000.0
+
+
+def test_timed_window_times_exactly_k_steps_after_whole_rehearsals():
+    """--steps K: ONE timed window of exactly K steps.  Before it: the W warm-up steps rounded up to whole cycles
+    (after which a frame pipeline fills lane 0, slot 0 again), then untimed rehearsals of the window in rounds of
+    `phases` windows (after which it fills the same lane and slot again), so the steps before the timed window depend
+    on the arguments only, whichever number of rounds --warmup-s asks for."""
+    import types
+    import bench
+    for warmup_s in (0.0, 1e9):                     # one round; as many rounds as the step cap allows
+        log = []
+        args = types.SimpleNamespace(steps=7, warmup=4, warmup_s=warmup_s)
+        dt, win = bench.timed_window(lambda: log.append('s'), lambda: log.append('|'), args, None, 1, phases=2, cycle=3)
+        seq = ''.join(log)
+        # warm-up (4 -> 6 steps) + sync, rehearsal windows + sync each, then the timed window between two syncs
+        assert seq.startswith('ssssss|') and seq.endswith('|' + 's' * 7 + '|')
+        body = seq[7:-9]
+        windows = len(body) // 8
+        assert body == 'sssssss|' * windows and windows % 2 == 0 and windows >= 2
+        assert (windows == 2) == (warmup_s == 0.0)
+        assert win['timed_steps'] == 7 and win['warmup_steps_run'] == 6 + 7 * windows and dt > 0
+
+
+def test_dump_outputs_float32_and_a_fixed_sample_above_the_cap(tmp_path):
+    import numpy as np
+    import bench
+    small = {'labels': np.arange(12, dtype=np.int32).reshape(3, 4), 'valid': np.ones((2, 5), np.uint8)}
+    bench.dump_outputs(str(tmp_path / 'a'), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / 'a' / (k + '.npy'))
+        assert got.dtype == np.float32 and got.shape == v.shape and np.array_equal(got, v)
+    big = {'x': np.arange(1000, dtype=np.float32), 'y': -np.arange(3000, dtype=np.float32)}
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), big, cap=1600)
+    x, y = (np.load(tmp_path / 'b' / (k + '.npy')) for k in 'xy')
+    assert (x.size, y.size) == (100, 300)                       # 1600 bytes, shared in proportion to size
+    assert np.all(np.diff(x) > 0) and np.isin(x, big['x']).all()  # elements of the array, in their order
+    for k in 'xy':                                               # the same sample every time
+        assert np.array_equal(np.load(tmp_path / 'b' / (k + '.npy')), np.load(tmp_path / 'c' / (k + '.npy')))
+    for bad in (['--train'], ['--dry-run']):
+        with pytest.raises(SystemExit):
+            bench.parse(bad + ['--dump-outputs', str(tmp_path / 'd')])
+    with pytest.raises(SystemExit):
+        bench.parse(['--steps', '0'])

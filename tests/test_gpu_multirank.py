@@ -68,7 +68,7 @@ def test_training_bench_with_two_ranks_finishes_and_reports_its_roofline():
     is entered by BOTH ranks (round 3: rank 0 alone ran the roofline and the job hung), rank 0 prints one line."""
     import signal
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--train', '--gpus', '2', '--share-gpu', '--backend', 'gloo',
-           '--steps', '6', '--warmup', '2', '--min-window-s', '0.05', '--warmup-s', '0.05']
+           '--steps', '6', '--warmup', '2', '--warmup-s', '0.05']
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     p = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          start_new_session=True)

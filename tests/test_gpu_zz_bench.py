@@ -50,3 +50,31 @@ def test_the_drivers_bench_command_prints_one_complete_line():
     assert 'configs[2]' in d['train']['workload'] and 0.1 < d['train']['ms_per_iteration'] < 5.0
     c = d['cpu_baseline']
     assert c['kind'] == 'port' and c['cores'] >= 1 and c['value'] > 0 and c['sample']
+
+
+def test_dump_outputs_of_the_last_timed_step_are_the_same_every_run(tmp_path):
+    """`bench.py ... --dump-outputs DIR`: what the timed path's last step computed (the head's outputs and the decoded
+    boxes of that step's frame) as float32 .npy files -- the same arrays in two runs with the same arguments, and the
+    decode belongs to the same frame as the head outputs (its best score is the sigmoid of their largest logit)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5',
+                            '--main-only', '--dump-outputs', str(d)], cwd=ROOT, env=env, capture_output=True, text=True,
+                           timeout=420)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len([ln for ln in p.stdout.splitlines() if ln.startswith('{')]) == 1
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ['all_bbox_preds', 'all_cls_scores', 'boxes', 'labels', 'scores', 'valid']
+    layers = a['all_cls_scores'].shape[0]
+    assert a['all_cls_scores'].shape == a['all_bbox_preds'].shape == (layers, 1, 900, 10)
+    assert a['boxes'].shape == (1, 300, 9) and a['scores'].shape == a['labels'].shape == a['valid'].shape == (1, 300)
+    assert sum(v.nbytes for v in a.values()) <= 64e6
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    best = 1.0 / (1.0 + np.exp(-a['all_cls_scores'][-1, 0].astype(np.float64).max()))
+    assert abs(a['scores'][0, 0] - best) < 1e-5
