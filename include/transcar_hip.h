@@ -34,7 +34,9 @@ extern "C" {
 #define TC_MAX_LEVELS 4
 #define TC_MAX_LAYERS 8
 #define TC_MAX_RADAR_LAYERS 3
-#define TC_ABI_VERSION 12
+/* num_cams * num_levels * num_points of Detr3DCrossAtten: the logits of a row fit one 256-wide activation unit */
+#define TC_MAX_CAM_LOGITS 256
+#define TC_ABI_VERSION 13
 
 typedef void* tc_stream_t;
 
@@ -54,7 +56,7 @@ typedef struct { tc_linear in_proj; tc_linear out_proj; } tc_mha;
 typedef struct {
   tc_mha self_attn;                 /* attentions.0.attn                      */
   tc_lnorm norm0;
-  tc_linear attention_weights;      /* attentions.1.attention_weights [N*L,C] */
+  tc_linear attention_weights;      /* attentions.1.attention_weights [N*P*L,C] */
   tc_linear output_proj;            /* attentions.1.output_proj               */
   tc_pos_encoder position_encoder;  /* attentions.1.position_encoder          */
   tc_lnorm norm1;
@@ -102,6 +104,9 @@ typedef struct {
   const float* l0_init_reference;   /* [Q,3]  sigmoid(reference_points(query_pos))      */
   const float* l0_attn_out;         /* [Q,C]  softmax(q k^T / sqrt(d)) v of layer 0     */
   size_t packed16_delta;            /* packed view only, as in tc_decoder_layer         */
+  /* Detr3DCrossAtten.num_points P (0 is read as 1): attention_weights has N*P*L rows, row n*P*L + p*L + l
+   * (XFMR:362-363); num_cams * num_levels * P <= TC_MAX_CAM_LOGITS */
+  int num_points;
 } tc_head_weights;
 
 /* multi-view FPN feature maps, channels-last: level l is [B*num_cams, H, W, C] */
@@ -287,6 +292,17 @@ int tc_cam_sample_fuse_fwd(const tc_feats_nhwc* feats, int B, int Q, int C, int 
                            unsigned long long* pair_counter /*may be NULL*/,
                            tc_stream_t stream);
 
+/* tc_cam_sample_fuse_fwd for Detr3DCrossAtten(num_points > 1): attn_logits [B,Q,N*P*L] (column n*P*L + p*L + l);
+ * level value (n, l) is weighted by mask * sum_p sigmoid(logit[n, p, l]) (XFMR:362-373).  num_points 1 is the
+ * function above; num_points < 1 or N*L*P > TC_MAX_CAM_LOGITS is an error. */
+int tc_cam_sample_fuse_points_fwd(const tc_feats_nhwc* feats, int B, int Q, int C, int num_cams, int num_points,
+                                  const float* lidar2img /*[B,N,4,4]*/, const float* ref /*[B,Q,3]*/,
+                                  const float* attn_logits /*[B,Q,N*P*L]*/,
+                                  const float* pc_range /*host[6]*/, float img_h, float img_w,
+                                  float* out, unsigned char* vis_mask,
+                                  unsigned long long* pair_counter /*may be NULL*/,
+                                  tc_stream_t stream);
+
 /* Detr3DCrossAtten.forward (XFMR:302-378), eval mode: returns
  * output_proj(sampled) + query + position_encoder(inverse_sigmoid(ref)).
  * query/query_pos/out are [B,Q,C] (the reference's [Q,B,C] with B folded
@@ -300,6 +316,16 @@ int tc_cross_atten_fwd(const tc_linear* attention_weights, const tc_linear* outp
                        const float* pc_range /*host[6]*/, float img_h, float img_w,
                        float* out, void* workspace, size_t workspace_bytes,
                        tc_stream_t stream);
+/* the same with num_points P (attention_weights [N*P*L, C]); P = 1 computes what tc_cross_atten_fwd does */
+size_t tc_cross_atten_points_workspace_bytes(int B, int Q, int C, int num_cams, int num_levels, int num_points);
+int tc_cross_atten_points_fwd(const tc_linear* attention_weights, const tc_linear* output_proj,
+                              const tc_pos_encoder* position_encoder,
+                              const tc_feats_nhwc* feats, int B, int Q, int C, int num_cams, int num_points,
+                              const float* query, const float* query_pos,
+                              const float* lidar2img, const float* ref,
+                              const float* pc_range /*host[6]*/, float img_h, float img_w,
+                              float* out, void* workspace, size_t workspace_bytes,
+                              tc_stream_t stream);
 
 /* mmcv MultiheadAttention wrapper as used for decoder self-attention
  * (CFG:68-72): out = x + out_proj(MHA(q=k=x+pos, v=x)).
@@ -317,7 +343,9 @@ int tc_self_attn_fwd(const tc_mha* w, const float* x, const float* pos, float* o
  *   transposed v (vt) when next_in_proj != NULL.
  * `layer` / `next_in_proj` must come from a tc_head_pack_weights view (packed
  * weights).  attn_o, x_in, hs [B*Q,C]; query_embedding [Q,2C]; ref_in/ref_out
- * [B*Q,3]; qk [B*Q,2C]; vt [B,C,qpad]. */
+ * [B*Q,3]; qk [B*Q,2C]; vt [B,C,qpad].
+ * num_points = 1 only: tc_decoder_layer does not carry num_points, and a layer of a head with num_points > 1 would be read
+ * as its first num_cams * num_levels attention-weight rows.  Such heads run through tc_head_forward. */
 int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* next_in_proj,
                               const tc_feats_nhwc* feats, int B, int Q, int num_cams,
                               int code_size, const float* attn_o, const float* x_in,

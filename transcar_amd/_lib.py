@@ -19,13 +19,27 @@ LIB_PATH = os.environ.get('TRANSCAR_HIP_LIB') or os.path.join(_HERE, 'lib', 'lib
 TC_MAX_LEVELS = 4
 TC_MAX_LAYERS = 8
 TC_MAX_RADAR_LAYERS = 3
-TC_ABI_VERSION = 12
+TC_ABI_VERSION = 13
 
 c_fp = C.c_void_p      # device pointers travel as integers
 
 
 class TransCARHipError(RuntimeError):
     pass
+
+
+# num_cams * num_levels * num_points of Detr3DCrossAtten (include/transcar_hip.h)
+TC_MAX_CAM_LOGITS = 256
+
+
+def check_num_points(num_points, num_cams, num_levels):
+    """The library's limit on Detr3DCrossAtten.num_points, checked before
+    anything is packed or launched."""
+    if int(num_points) < 1 or num_cams * num_levels * int(num_points) > TC_MAX_CAM_LOGITS:
+        raise TransCARHipError(
+            'Detr3DCrossAtten(HIP): num_points=%r is not supported (num_points >= 1 and '
+            'num_cams * num_levels * num_points = %d * %d * num_points <= %d)'
+            % (num_points, num_cams, num_levels, TC_MAX_CAM_LOGITS))
 
 
 TC_MAX_RADAR_CHANNELS = 8
@@ -96,7 +110,8 @@ class tc_head_weights(C.Structure):
                 ('radar_feat0', tc_linear), ('radar_feat2', tc_linear),
                 ('radar_feat4', tc_linear),
                 ('radar', tc_radar_layer * TC_MAX_RADAR_LAYERS),
-                ('l0_init_reference', c_fp), ('l0_attn_out', c_fp), ('packed16_delta', C.c_size_t)]
+                ('l0_init_reference', c_fp), ('l0_attn_out', c_fp), ('packed16_delta', C.c_size_t),
+                ('num_points', C.c_int)]
 
 
 class tc_feats_nhwc(C.Structure):
@@ -143,7 +158,15 @@ SIGNATURES = {
     'tc_cam_sample_fuse_fwd': (_i, [_P(tc_feats_nhwc), _i, _i, _i, _i, _vp,
                                     _vp, _vp, _P(_f), _f, _f, _vp, _vp, _vp,
                                     _vp]),
+    'tc_cam_sample_fuse_points_fwd': (_i, [_P(tc_feats_nhwc), _i, _i, _i, _i, _i,
+                                           _vp, _vp, _vp, _P(_f), _f, _f, _vp,
+                                           _vp, _vp, _vp]),
     'tc_cross_atten_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'tc_cross_atten_points_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
+    'tc_cross_atten_points_fwd': (_i, [_P(tc_linear), _P(tc_linear),
+                                       _P(tc_pos_encoder), _P(tc_feats_nhwc),
+                                       _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                       _P(_f), _f, _f, _vp, _vp, _sz, _vp]),
     'tc_cross_atten_fwd': (_i, [_P(tc_linear), _P(tc_linear),
                                 _P(tc_pos_encoder), _P(tc_feats_nhwc), _i, _i,
                                 _i, _i, _vp, _vp, _vp, _vp, _P(_f), _f, _f,

@@ -75,7 +75,12 @@ LEVEL_SHAPES = {
 IMG_SHAPE = (928, 1600, 3)
 
 
-def head_cfg(num_query=900):
+def head_cfg(num_query=900, num_points=None):
+    """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
+    TransCAR configs use 1, CFG:75; the reference class defaults to 5)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
+    if num_points is not None:
+        layers = cfg['transformer']['decoder']['transformerlayers']
+        layers['attn_cfgs'][1]['num_points'] = int(num_points)
     return cfg

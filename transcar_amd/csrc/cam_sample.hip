@@ -33,6 +33,21 @@ __global__ __launch_bounds__(256) void cam_sample_kernel(CamK p) {
     atomicAdd(p.pair_counter, (unsigned long long)nvis);
 }
 
+// num_points np > 1: the row's logits are [num_cams][np][L] (XFMR:362-373), lane (cam, l) sums its np sigmoids
+// (rowdev.hpp points_weight_lane); the taps and the projection are those of np = 1
+template <int L>
+__global__ __launch_bounds__(256) void cam_sample_points_kernel(CamK p, int np) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (row >= p.B * p.Q) return;
+  const int b = row / p.Q;
+  int nvis = 0;
+  const float4 acc = cam_sample_row<L, true>(p, row, b, p.logits + (size_t)row * p.num_cams * np * L, lane, nvis, np);
+  st4(p.out + (size_t)row * 256 + 4 * lane, acc);
+  if (p.pair_counter != nullptr && lane == 0 && nvis > 0)
+    atomicAdd(p.pair_counter, (unsigned long long)nvis);
+}
+
 void fill_camk(const CamSampleArgs& a, CamK& p) {
   for (int l = 0; l < TC_MAX_LEVELS; ++l) {
     p.data[l] = a.feats.data[l]; p.H[l] = a.feats.H[l]; p.W[l] = a.feats.W[l];
@@ -50,10 +65,15 @@ int launch_cam_sample(const CamSampleArgs& a, hipStream_t s) {
   for (int l = 0; l < a.feats.num_levels; ++l)      // pixel indices are 32-bit in the kernels
     TC_REQUIRE((long long)a.B * a.num_cams * a.feats.H[l] * a.feats.W[l] < (1ll << 31),
                "cam_sample: level %d has too many pixels for one call", l);
+  TC_REQUIRE(a.num_points >= 1 && a.num_cams * a.feats.num_levels * a.num_points <= TC_MAX_CAM_LOGITS,
+             "cam_sample: num_points=%d (1 .. %d / (num_cams * num_levels) supported)", a.num_points, TC_MAX_CAM_LOGITS);
   CamK p;
   fill_camk(a, p);
   const int rows = a.B * a.Q;
-  hipLaunchKernelGGL(cam_sample_kernel<4>, dim3((rows + 3) / 4), dim3(256), 0, s, p);
+  if (a.num_points > 1)
+    hipLaunchKernelGGL(cam_sample_points_kernel<4>, dim3((rows + 3) / 4), dim3(256), 0, s, p, a.num_points);
+  else
+    hipLaunchKernelGGL(cam_sample_kernel<4>, dim3((rows + 3) / 4), dim3(256), 0, s, p);
   return check_launch("cam_sample");
 }
 

@@ -390,6 +390,7 @@ struct ChainK : ChainDev {
   const float* d_cls = nullptr; const float* d_box = nullptr;   // backward: given gradients [layers, M, ncls / code]
   float* dkv[TC_MAX_RADAR_LAYERS] = {nullptr, nullptr, nullptr};
   size_t w16_delta = 0;        // packed16_delta of the packed view: 16-row tiles read their own weight copy
+  int npoints = 1;             // decoder: Detr3DCrossAtten.num_points (> 1: the MP instantiations, logits in unit 3)
 };
 
 constexpr int table_steps(int prog) {
@@ -998,6 +999,19 @@ __device__ __forceinline__ void act_st4(float* row, int col, const float4& v) {
     char* p = reinterpret_cast<char*>(row) + (col >> 3) * 32 + (col & 7) * 2;
     *reinterpret_cast<uint2*>(p) = h;
     *reinterpret_cast<uint2*>(p + 16) = l;
+  }
+}
+
+// one value of an LDS row (the same recombination as act_ld4: same bits)
+template <bool PL>
+__device__ __forceinline__ float act_ld1(const float* row, int col) {
+  if constexpr (!PL) {
+    return row[col];
+  } else {
+    const char* p = reinterpret_cast<const char*>(row) + (col >> 3) * 32 + (col & 7) * 2;
+    const _Float16 h = *reinterpret_cast<const _Float16*>(p), l = *reinterpret_cast<const _Float16*>(p + 16);
+    constexpr float US = 1.0f / H_ACT_SCALE, UL = 1.0f / H_LO_SCALE;
+    return fmaf((float)l, UL, (float)h) * US;
   }
 }
 
@@ -1619,7 +1633,12 @@ __device__ int g_wg_cu[2048][2];
 // PRE (round 6; decoder program on the f16x2 path only): the sampling step reads the level values the pre-gather workgroups
 // of the attention-core launch stored -- its own instantiations, so that the kernels that gather for themselves keep
 // their code and registers exactly (with both paths in one kernel the direct-gather launches lost 2 us to 12 more spills)
-template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false>
+// MP (decoder program, Detr3DCrossAtten.num_points P > 1): the attention-weights step writes its N * P * L logits to
+// unit 3 (the host resolver redirects it: the logit buffer `l` holds 32 floats a row, and unit 3 is free until the
+// sampling step writes its output there) and the sampling step weighs level value (n, l) by sum_p sigmoid(.) of them
+// (rowdev.hpp points_weight_lane), reading a row's logits before it stores the row's output.  MP = false is the P = 1
+// kernel as it was.
+template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false, bool MP = false>
 __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_of(R)>* __restrict__ recs, const int block) {
   constexpr int NW = nw_of(R), NT = NW * 64;        // waves / threads of the workgroup
   constexpr bool PL = R == 32;                      // the activation units hold planes (act_ld4 / act_st4)
@@ -2119,7 +2138,13 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
 #pragma unroll
           for (int i = 0; i < NR; ++i) {
             const int row = wave + NW * i;
-            const float sg_lane = sigmoidf_(S.l[row][min(lane, NC * 4 - 1)]);
+            float sg_lane;
+            if constexpr (MP) {
+              const float* lg = buf_ptr(S, B_U3) + row * LD2;
+              sg_lane = points_weight_lane<4>([lg](int j) { return act_ld1<PL>(lg, j); }, lane, NC, k.nlogits / (NC * 4));
+            } else {
+              sg_lane = sigmoidf_(S.l[row][min(lane, NC * 4 - 1)]);
+            }
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
             int rest = vmask[i];
             if (rest) {                                  // (wave-uniform)
@@ -2173,8 +2198,17 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
           const int row = wave + NW * i;
           const int grow = min(m0 + row, M - 1);
           const unsigned long long vmask = (vm >> (16 * i)) & 0xFFFFull;
-          const float4 o = cam_sample_core<4>(k.cam, grow / k.Q, &S.l[row][0], lane, vmask, pu, pv,
-                                              [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); }, 16 * i, Hl, Wl);
+          float4 o;
+          if constexpr (MP) {
+            const float* lg = buf_ptr(S, B_U3) + row * LD2;
+            const float sg = points_weight_lane<4>([lg](int j) { return act_ld1<PL>(lg, j); }, lane, k.cam.num_cams,
+                                                   k.nlogits / (k.cam.num_cams * 4));
+            o = cam_sample_core_w<4>(k.cam, grow / k.Q, sg, lane, vmask, pu, pv,
+                                     [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); }, 16 * i, Hl, Wl);
+          } else {
+            o = cam_sample_core<4>(k.cam, grow / k.Q, &S.l[row][0], lane, vmask, pu, pv,
+                                   [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); }, 16 * i, Hl, Wl);
+          }
           act_st4<PL>(buf_ptr(S, r.dst) + row * LD2, 4 * lane, o);
           if (m0 + row < M) pairs += __popcll(vmask);
         }
@@ -2519,21 +2553,21 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
   WG_STAMP(1);
 }
 
-template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false>
+template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false, bool MP = false>
 __global__ __launch_bounds__(nw_of(R) * 64, 2) void chain_kernel(ChainDev k, Recs<rec_cap(PROG), nw_of(R)> recs) {
-  chain_body<R, PROG, DROP, MM, PRE>(k, recs.s, blockIdx.x);
+  chain_body<R, PROG, DROP, MM, PRE, MP>(k, recs.s, blockIdx.x);
 }
 
 // Two programs in one launch: workgroups [0, na) run the decoder layer `ka` on RA-row
 // tiles, the rest the radar encoders `kb` on RB-row tiles.  Decoder layer 0 carries the
 // encoders this way: as a branch of the hipGraph on a side stream, the fork and the join
 // each left a ~10 us hole in the replayed frame (profiles: rocprofv3 kernel trace).
-template <int RA, int RB, int PROGB, int MM = 0, bool PRE = false>
+template <int RA, int RB, int PROGB, int MM = 0, bool PRE = false, bool MP = false>
 __global__ __launch_bounds__(nw_of(RA) * 64, 2) void chain_dual_kernel(ChainDev ka, ChainDev kb, int na,
                                                            Recs<rec_cap(PROG_DECODER), nw_of(RA)> ra,
                                                            Recs<rec_cap(PROGB), nw_of(RB)> rb) {
   static_assert(nw_of(RA) == nw_of(RB), "both programs of a launch run with the same workgroup size");
-  if ((int)blockIdx.x < na) chain_body<RA, PROG_DECODER, false, MM, PRE>(ka, ra.s, blockIdx.x);
+  if ((int)blockIdx.x < na) chain_body<RA, PROG_DECODER, false, MM, PRE, MP>(ka, ra.s, blockIdx.x);
   else chain_body<RB, PROGB, false, MM>(kb, rb.s, (int)blockIdx.x - na);
 }
 
@@ -2617,6 +2651,7 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
       if (ts != T_NONE && r.gd == nullptr) { r.gd = k.tape[ts]; r.gld = 256; taped = true; }
       if (ts2 != T_NONE) r.gt = k.tape[ts2];
     }
+    if (PROG == PROG_DECODER && d.N == N_LOGITS && k.npoints > 1) r.dst = B_U3;   // MP: N * P * L logits (chain_body)
     if (d.kind == K_LINEAR) {
       const tc_linear pr = k.pairs[pair0 + d.wp];
       r.K = d.K == 36 ? k.RI : d.K == N_CODE ? k.code : d.K == N_CLS ? k.ncls : d.K;
@@ -2695,12 +2730,12 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
   k.early_n = early;
 }
 
-template <int RA, int RB, int PROGB, int MM = 0, bool PRE = false>
+template <int RA, int RB, int PROGB, int MM = 0, bool PRE = false, bool MP = false>
 int launch_dual_r(const ChainK& ka_, const ChainK& kb_, hipStream_t s, const char* what) {
   constexpr size_t lds = chain_lds_bytes<RA, PROG_DECODER>() > chain_lds_bytes<RB, PROGB>() ? chain_lds_bytes<RA, PROG_DECODER>() : chain_lds_bytes<RB, PROGB>();
   static DeviceOnce once;
   if (const int once_dev = once.need(); once_dev >= 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_dual_kernel<RA, RB, PROGB, MM, PRE>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_dual_kernel<RA, RB, PROGB, MM, PRE, MP>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { set_error("chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     once.done(once_dev);
@@ -2713,16 +2748,16 @@ int launch_dual_r(const ChainK& ka_, const ChainK& kb_, hipStream_t s, const cha
   resolve_program<RA, PROG_DECODER, MM>(ka, ra.s);
   resolve_program<RB, PROGB, MM>(kb, rb.s);
   const int na = (ka.M + RA - 1) / RA, nb = (kb.M + RB - 1) / RB;
-  hipLaunchKernelGGL((chain_dual_kernel<RA, RB, PROGB, MM, PRE>), dim3(na + nb), dim3(nw_of(RA) * 64), lds, s,
+  hipLaunchKernelGGL((chain_dual_kernel<RA, RB, PROGB, MM, PRE, MP>), dim3(na + nb), dim3(nw_of(RA) * 64), lds, s,
                      static_cast<const ChainDev&>(ka), static_cast<const ChainDev&>(kb), na, ra, rb);
   return check_launch(what);
 }
 
-template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false>
+template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false, bool MP = false>
 int launch_r(const ChainK& k_, hipStream_t s, const char* what) {
   static DeviceOnce once;
   if (const int once_dev = once.need(); once_dev >= 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<R, PROG, DROP, MM, PRE>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<R, PROG, DROP, MM, PRE, MP>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)chain_lds_bytes<R, PROG>());
     if (e != hipSuccess) { set_error("chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
@@ -2734,7 +2769,7 @@ int launch_r(const ChainK& k_, hipStream_t s, const char* what) {
   Recs<rec_cap(PROG), nw_of(R)> recs;
   resolve_program<R, PROG, MM>(k, recs.s);
   constexpr size_t lds = chain_lds_bytes<R, PROG>();
-  hipLaunchKernelGGL((chain_kernel<R, PROG, DROP, MM, PRE>), dim3((k.M + R - 1) / R), dim3(nw_of(R) * 64), lds, s,
+  hipLaunchKernelGGL((chain_kernel<R, PROG, DROP, MM, PRE, MP>), dim3((k.M + R - 1) / R), dim3(nw_of(R) * 64), lds, s,
                      static_cast<const ChainDev&>(k), recs);
   return check_launch(what);
 }
@@ -2772,38 +2807,45 @@ int tile_rows(const ChainK& k) {
 // stream, and both copies are 4 bytes per weight).
 bool use_f16x2(const ChainK& k) { return k.matrix_path != TC_MATRIX_F32; }
 
-template <int PROG>
+template <int PROG, bool MP = false>
 int launch_rows(const ChainK& k, hipStream_t s, const char* what) {
   const int rows = tile_rows(k);
-  if (rows == 4) return launch_r<4, PROG>(k, s, what);
-  if (rows == 8) return launch_r<8, PROG>(k, s, what);
+  if (rows == 4) return launch_r<4, PROG, false, 0, false, MP>(k, s, what);
+  if (rows == 8) return launch_r<8, PROG, false, 0, false, MP>(k, s, what);
   if (rows == 32) {
     TC_REQUIRE(use_f16x2(k), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
-    if constexpr (PROG == PROG_DECODER) { if (k.pre != nullptr) return launch_r<32, PROG, false, 1, true>(k, s, what); }
-    return launch_r<32, PROG, false, 1>(k, s, what);
+    if constexpr (PROG == PROG_DECODER) { if (k.pre != nullptr) return launch_r<32, PROG, false, 1, true, MP>(k, s, what); }
+    return launch_r<32, PROG, false, 1, false, MP>(k, s, what);
   }
-  if constexpr (PROG == PROG_DECODER) { if (k.pre != nullptr && use_f16x2(k)) return launch_r<16, PROG, false, 1, true>(k, s, what); }
-  if (use_f16x2(k)) return launch_r<16, PROG, false, 1>(k, s, what);
-  return launch_r<16, PROG>(k, s, what);
+  if constexpr (PROG == PROG_DECODER) { if (k.pre != nullptr && use_f16x2(k)) return launch_r<16, PROG, false, 1, true, MP>(k, s, what); }
+  if (use_f16x2(k)) return launch_r<16, PROG, false, 1, false, MP>(k, s, what);
+  return launch_r<16, PROG, false, 0, false, MP>(k, s, what);
+}
+
+// the decoder program; MP: num_points > 1 (chain_body)
+template <bool MP>
+int launch_decoder(const ChainK& k, hipStream_t s, const char* what) {
+  if (k.drop.thr != 0) {            // train-mode dropout: its own instantiations -- 4- and 8-row tiles, and the
+    //                                  16-row tiles of the f16x2 path (several frames per launch: the trainer's
+    //                                  batched look-ahead of the frozen decoder, round 4)
+    TC_REQUIRE((unsigned long long)(k.drop.rows_per_sample ? k.drop.rows_per_sample : k.M) * 512ull < (1ull << 32),
+               "decoder_chain: dropout index space");
+    const int rows = tile_rows(k);
+    if (rows == 32) {
+      TC_REQUIRE(use_f16x2(k), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
+      return launch_r<32, PROG_DECODER, true, 1, false, MP>(k, s, what);
+    }
+    if (rows == 16 && use_f16x2(k)) return launch_r<16, PROG_DECODER, true, 1, false, MP>(k, s, what);
+    return rows == 4 ? launch_r<4, PROG_DECODER, true, 0, false, MP>(k, s, what)
+                     : launch_r<8, PROG_DECODER, true, 0, false, MP>(k, s, what);
+  }
+  return launch_rows<PROG_DECODER, MP>(k, s, what);
 }
 
 int launch(const ChainK& k, hipStream_t s, const char* what) {
   switch (k.program) {
     case PROG_DECODER:
-      if (k.drop.thr != 0) {            // train-mode dropout: its own instantiations -- 4- and 8-row tiles, and the
-        //                                  16-row tiles of the f16x2 path (several frames per launch: the trainer's
-        //                                  batched look-ahead of the frozen decoder, round 4)
-        TC_REQUIRE((unsigned long long)(k.drop.rows_per_sample ? k.drop.rows_per_sample : k.M) * 512ull < (1ull << 32),
-                   "decoder_chain: dropout index space");
-        const int rows = tile_rows(k);
-        if (rows == 32) {
-          TC_REQUIRE(use_f16x2(k), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
-          return launch_r<32, PROG_DECODER, true, 1>(k, s, what);
-        }
-        if (rows == 16 && use_f16x2(k)) return launch_r<16, PROG_DECODER, true, 1>(k, s, what);
-        return rows == 4 ? launch_r<4, PROG_DECODER, true>(k, s, what) : launch_r<8, PROG_DECODER, true>(k, s, what);
-      }
-      return launch_rows<PROG_DECODER>(k, s, what);
+      return k.npoints > 1 ? launch_decoder<true>(k, s, what) : launch_decoder<false>(k, s, what);
     case PROG_RADAR: return launch_rows<PROG_RADAR>(k, s, what);
     // training forward: 4-row tiles up to 1024 rows (one frame per GPU, CFG:188), 8 beyond; always the DROP
     // instantiation (thr 0 keeps everything)
@@ -2887,13 +2929,16 @@ int launch_prologue(const PrologueArgs& a, hipStream_t s) {
 
 static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   TC_REQUIRE(a.code <= 12 && a.cam.num_cams * a.cam.feats.num_levels <= 32, "decoder_chain: code/logit width");
+  TC_REQUIRE(a.cam.num_points >= 1 && a.cam.num_cams * a.cam.feats.num_levels * a.cam.num_points <= TC_MAX_CAM_LOGITS,
+             "decoder_chain: num_points=%d (num_cams * num_levels * num_points <= %d)", a.cam.num_points, TC_MAX_CAM_LOGITS);
   TC_REQUIRE(a.cam.num_cams <= 8, "decoder_chain: num_cams=%d (<= 8)", a.cam.num_cams);
   for (int l = 0; l < a.cam.feats.num_levels; ++l)      // pixel indices are 32-bit in the kernel
     TC_REQUIRE((long long)a.cam.B * a.cam.num_cams * a.cam.feats.H[l] * a.cam.feats.W[l] < (1ll << 31),
                "decoder_chain: level %d has too many pixels for one call", l);
   init_k(k);
   k.program = PROG_DECODER; k.M = a.M; k.Q = a.Q; k.code = a.code;
-  k.nlogits = a.cam.num_cams * a.cam.feats.num_levels;
+  k.nlogits = a.cam.num_cams * a.cam.feats.num_levels * a.cam.num_points;
+  k.npoints = a.cam.num_points;
   const tc_decoder_layer& w = *a.w;
   const tc_pos_encoder& pe = w.position_encoder;
   k.pairs[0] = w.self_attn.in_proj; k.pairs[1] = w.self_attn.out_proj;
@@ -2963,6 +3008,30 @@ int launch_radar_encode(const RadarEncodeArgs& a, hipStream_t s) {
   return launch(k, s, "chain(radar_encode)");
 }
 
+template <bool MP>
+static int launch_dual(const ChainK& kd, const ChainK& ke, int part, hipStream_t s) {
+  const int rows = tile_rows(kd);
+  const char* what = "chain(decoder + radar_encode)";
+#define TC_DUAL(RA, RB, MM, PRE)                                                                      \
+  (part == 1 ? launch_dual_r<RA, RB, PROG_RADAR_ENC_A, MM, PRE, MP>(kd, ke, s, what)                  \
+   : part == 2 ? launch_dual_r<RA, RB, PROG_RADAR_ENC_B, MM, PRE, MP>(kd, ke, s, what)                \
+               : launch_dual_r<RA, RB, PROG_RADAR_ENC, MM, PRE, MP>(kd, ke, s, what))
+  // 4-row decoder tiles run two workgroups per CU (256 VGPRs): the encoder rows then use 4-row
+  // tiles too -- a 16-row body in the same kernel would spill ~100 registers at that budget,
+  // and 225 + T/4 workgroups fit the chip at two per CU
+  if (rows == 4) return TC_DUAL(4, 4, 0, false);
+  if (rows == 8) return TC_DUAL(8, 8, 0, false);
+  if (rows == 32) {
+    TC_REQUIRE(use_f16x2(kd), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
+    if (kd.pre != nullptr) return TC_DUAL(32, 32, 1, true);
+    return TC_DUAL(32, 32, 1, false);
+  }
+  if (use_f16x2(kd) && kd.pre != nullptr) return TC_DUAL(16, 16, 1, true);
+  if (use_f16x2(kd)) return TC_DUAL(16, 16, 1, false);
+  return TC_DUAL(16, 16, 0, false);
+#undef TC_DUAL
+}
+
 // a decoder layer and (a part of) the radar encoders in one launch;
 // part 0: the whole encoder program, 1 / 2: its halves (PROG_RADAR_ENC_A / _B)
 int launch_decoder_chain_with_encoders(const DecoderChainArgs& d, const RadarEncodeArgs& e, int part,
@@ -2973,26 +3042,7 @@ int launch_decoder_chain_with_encoders(const DecoderChainArgs& d, const RadarEnc
   rc = make_radar_enc_k(e, ke, part);
   if (rc != 0) return rc;
   TC_REQUIRE(kd.drop.thr == 0, "decoder dropout: launch the encoders on their own (launch_radar_encode)");
-  const int rows = tile_rows(kd);
-  const char* what = "chain(decoder + radar_encode)";
-#define TC_DUAL(RA, RB, MM, ...)                                                              \
-  (part == 1 ? launch_dual_r<RA, RB, PROG_RADAR_ENC_A, MM, ##__VA_ARGS__>(kd, ke, s, what)       \
-   : part == 2 ? launch_dual_r<RA, RB, PROG_RADAR_ENC_B, MM, ##__VA_ARGS__>(kd, ke, s, what)     \
-               : launch_dual_r<RA, RB, PROG_RADAR_ENC, MM, ##__VA_ARGS__>(kd, ke, s, what))
-  // 4-row decoder tiles run two workgroups per CU (256 VGPRs): the encoder rows then use 4-row
-  // tiles too -- a 16-row body in the same kernel would spill ~100 registers at that budget,
-  // and 225 + T/4 workgroups fit the chip at two per CU
-  if (rows == 4) return TC_DUAL(4, 4, 0);
-  if (rows == 8) return TC_DUAL(8, 8, 0);
-  if (rows == 32) {
-    TC_REQUIRE(use_f16x2(kd), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
-    if (kd.pre != nullptr) return TC_DUAL(32, 32, 1, true);
-    return TC_DUAL(32, 32, 1);
-  }
-  if (use_f16x2(kd) && kd.pre != nullptr) return TC_DUAL(16, 16, 1, true);
-  if (use_f16x2(kd)) return TC_DUAL(16, 16, 1);
-  return TC_DUAL(16, 16, 0);
-#undef TC_DUAL
+  return kd.npoints > 1 ? launch_dual<true>(kd, ke, part, s) : launch_dual<false>(kd, ke, part, s);
 }
 
 int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {

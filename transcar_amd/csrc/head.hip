@@ -88,12 +88,13 @@ static int cross_atten_parts(const tc_linear& aw, const tc_linear& oproj, const 
                              const tc_feats_nhwc* feats, int B, int Q, int C, int ncams,
                              const float* query, const float* pos, const float* l2i,
                              const float* ref, const float* pc, float img_h, float img_w,
-                             const CrossWs& ws, unsigned long long* pair_counter, hipStream_t s) {
+                             const CrossWs& ws, unsigned long long* pair_counter, hipStream_t s,
+                             int np = 1) {
   const int rows = B * Q;
-  const int NL = ncams * feats->num_levels;
+  const int NL = ncams * feats->num_levels * np;       // attention_weights: N * P * L columns (XFMR:362-363)
   TC_TRY(linear(query, C, aw, rows, C, NL, 0, ws.logits, NL, s, pos));
   CamSampleArgs c;
-  c.feats = *feats; c.B = B; c.Q = Q; c.C = C; c.num_cams = ncams;
+  c.feats = *feats; c.B = B; c.Q = Q; c.C = C; c.num_cams = ncams; c.num_points = np;
   c.lidar2img = l2i; c.ref = ref; c.logits = ws.logits;
   for (int i = 0; i < 6; ++i) c.pc[i] = pc[i];
   c.img_h = img_h; c.img_w = img_w; c.out = ws.sampled; c.vis = nullptr; c.pair_counter = pair_counter;
@@ -102,6 +103,9 @@ static int cross_atten_parts(const tc_linear& aw, const tc_linear& oproj, const 
   TC_TRY(launch_posenc_l1(ref, 3, 1, pe.l0.w, pe.l0.b, pe.n1.g, pe.n1.b, ws.pe0, rows, s));
   return linear(ws.pe0, C, pe.l3, rows, C, C, 0, ws.pe1, C, s);
 }
+
+// Detr3DCrossAtten.num_points of a head (0 in a struct that does not set it: 1)
+static int head_points(const tc_head_weights* w) { return w->num_points > 0 ? w->num_points : 1; }
 
 static int check_dims(const tc_head_weights* w) {
   TC_REQUIRE(w != nullptr, "weights pointer is null");
@@ -113,6 +117,8 @@ static int check_dims(const tc_head_weights* w) {
   TC_REQUIRE(w->num_radar_layers >= 0 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
              "num_radar_layers=%d", w->num_radar_layers);
   TC_REQUIRE(w->num_levels == 4, "num_levels=%d (4 supported)", w->num_levels);
+  TC_REQUIRE(w->num_points >= 0 && w->num_cams * w->num_levels * head_points(w) <= TC_MAX_CAM_LOGITS,
+             "num_points=%d (num_cams * num_levels * num_points <= %d supported)", w->num_points, TC_MAX_CAM_LOGITS);
   TC_REQUIRE((w->ffn_dims & 31) == 0 && (w->radar_in_dims & 3) == 0, "ffn_dims/radar_in_dims alignment");
   return 0;
 }
@@ -140,7 +146,7 @@ static size_t head_ws_layout(const tc_head_weights* w, int B, int T, void* base,
   h.attn_o = a.take<float>(rows * C);
   h.t0 = a.take<float>(rows * C); h.t1 = a.take<float>(rows * C); h.t2 = a.take<float>(rows * C);
   h.ffn_h = a.take<float>(rows * F);
-  h.logits = a.take<float>(rows * w->num_cams * w->num_levels);
+  h.logits = a.take<float>(rows * w->num_cams * w->num_levels * head_points(w));
   h.sampled = a.take<float>(rows * C);
   h.init_ref = a.take<float>(rows * 3); h.inter_refs = a.take<float>((size_t)L * rows * 3);
   h.hs = a.take<float>((size_t)L * rows * C);
@@ -237,6 +243,7 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
     d.qscale = attn_qscale;
     d.hs = h.hs + (size_t)lid * rows * C; d.qk = h.qk; d.vt = h.vt; d.qpad = h.qpad;
     d.cam.feats = *feats; d.cam.B = B; d.cam.Q = Q; d.cam.C = C; d.cam.num_cams = w->num_cams;
+    d.cam.num_points = head_points(w);
     d.cam.lidar2img = lidar2img; d.cam.ref = ref_in; d.cam.logits = nullptr;
     for (int i = 0; i < 6; ++i) d.cam.pc[i] = w->pc_range[i];
     d.cam.img_h = img_h; d.cam.img_w = img_w; d.cam.out = nullptr; d.cam.vis = nullptr;
@@ -313,7 +320,7 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
 struct PackItem { const float* src; int N, K; const float** slot; bool narrow; };
 
 static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, PackItem* it) {
-  const int C = w->embed_dims, F = w->ffn_dims, NL = w->num_cams * w->num_levels;
+  const int C = w->embed_dims, F = w->ffn_dims, NL = w->num_cams * w->num_levels * head_points(w);
   const int code = w->code_size, ncls = w->num_classes;
   int n = 0;
   // narrow: the three 10-column heads the chains evaluate as wave-per-row dot products (K_NARROW): they
@@ -431,9 +438,57 @@ int tc_cam_sample_fuse_fwd(const tc_feats_nhwc* feats, int B, int Q, int C, int 
   return launch_cam_sample(c, as_stream(stream));
 }
 
-size_t tc_cross_atten_workspace_bytes(int B, int Q, int C, int num_cams, int num_levels) {
+int tc_cam_sample_fuse_points_fwd(const tc_feats_nhwc* feats, int B, int Q, int C, int num_cams, int num_points,
+                                  const float* lidar2img, const float* ref, const float* attn_logits,
+                                  const float* pc_range, float img_h, float img_w, float* out,
+                                  unsigned char* vis_mask, unsigned long long* pair_counter,
+                                  tc_stream_t stream) {
+  TC_REQUIRE(feats != nullptr, "feats is null");
+  CamSampleArgs c;
+  c.feats = *feats; c.B = B; c.Q = Q; c.C = C; c.num_cams = num_cams; c.num_points = num_points;
+  c.lidar2img = lidar2img; c.ref = ref; c.logits = attn_logits;
+  for (int i = 0; i < 6; ++i) c.pc[i] = pc_range[i];
+  c.img_h = img_h; c.img_w = img_w; c.out = out; c.vis = vis_mask; c.pair_counter = pair_counter;
+  return launch_cam_sample(c, as_stream(stream));
+}
+
+size_t tc_cross_atten_points_workspace_bytes(int B, int Q, int C, int num_cams, int num_levels, int num_points) {
   const size_t rows = (size_t)B * Q;
-  return arena_slice(rows * num_cams * num_levels, 4) + 4 * arena_slice(rows * C, 4);
+  return arena_slice(rows * num_cams * num_levels * (size_t)(num_points > 0 ? num_points : 1), 4) +
+         4 * arena_slice(rows * C, 4);
+}
+
+size_t tc_cross_atten_workspace_bytes(int B, int Q, int C, int num_cams, int num_levels) {
+  return tc_cross_atten_points_workspace_bytes(B, Q, C, num_cams, num_levels, 1);
+}
+
+int tc_cross_atten_points_fwd(const tc_linear* attention_weights, const tc_linear* output_proj,
+                              const tc_pos_encoder* position_encoder, const tc_feats_nhwc* feats, int B,
+                              int Q, int C, int num_cams, int num_points, const float* query, const float* query_pos,
+                              const float* lidar2img, const float* ref, const float* pc_range, float img_h,
+                              float img_w, float* out, void* workspace, size_t workspace_bytes,
+                              tc_stream_t stream) {
+  TC_REQUIRE(C == 256, "cross_atten: C=%d (256 supported)", C);
+  TC_REQUIRE(feats != nullptr, "feats is null");
+  TC_REQUIRE(num_points >= 1 && num_cams * feats->num_levels * num_points <= TC_MAX_CAM_LOGITS,
+             "cross_atten: num_points=%d (1 .. %d / (num_cams * num_levels) supported)", num_points, TC_MAX_CAM_LOGITS);
+  TC_REQUIRE(workspace_bytes >= tc_cross_atten_points_workspace_bytes(B, Q, C, num_cams, feats->num_levels, num_points),
+             "cross_atten: workspace too small");
+  const size_t rows = (size_t)B * Q;
+  Arena a(workspace, workspace_bytes);
+  CrossWs ws;
+  ws.logits = a.take<float>(rows * num_cams * feats->num_levels * num_points);
+  ws.sampled = a.take<float>(rows * C); ws.t0 = a.take<float>(rows * C);
+  ws.pe0 = a.take<float>(rows * C); ws.pe1 = a.take<float>(rows * C);
+  hipStream_t s = as_stream(stream);
+  TC_TRY(cross_atten_parts(*attention_weights, *output_proj, *position_encoder, feats, B, Q, C,
+                           num_cams, query, query_pos, lidar2img, ref, pc_range, img_h, img_w, ws,
+                           nullptr, s, num_points));
+  // XFMR:378: output + inp_residual + relu(LN(position_encoder.3(.)))
+  LnArgs l;
+  l.a = ws.t0; l.c = ws.pe1; l.g2 = position_encoder->n4.g; l.b2 = position_encoder->n4.b;
+  l.y = out; l.M = (int)rows;
+  return launch_ln256(l, s);
 }
 
 int tc_cross_atten_fwd(const tc_linear* attention_weights, const tc_linear* output_proj,
@@ -442,24 +497,9 @@ int tc_cross_atten_fwd(const tc_linear* attention_weights, const tc_linear* outp
                        const float* lidar2img, const float* ref, const float* pc_range, float img_h,
                        float img_w, float* out, void* workspace, size_t workspace_bytes,
                        tc_stream_t stream) {
-  TC_REQUIRE(C == 256, "cross_atten: C=%d (256 supported)", C);
-  TC_REQUIRE(workspace_bytes >= tc_cross_atten_workspace_bytes(B, Q, C, num_cams, feats->num_levels),
-             "cross_atten: workspace too small");
-  const size_t rows = (size_t)B * Q;
-  Arena a(workspace, workspace_bytes);
-  CrossWs ws;
-  ws.logits = a.take<float>(rows * num_cams * feats->num_levels);
-  ws.sampled = a.take<float>(rows * C); ws.t0 = a.take<float>(rows * C);
-  ws.pe0 = a.take<float>(rows * C); ws.pe1 = a.take<float>(rows * C);
-  hipStream_t s = as_stream(stream);
-  TC_TRY(cross_atten_parts(*attention_weights, *output_proj, *position_encoder, feats, B, Q, C,
-                           num_cams, query, query_pos, lidar2img, ref, pc_range, img_h, img_w, ws,
-                           nullptr, s));
-  // XFMR:378: output + inp_residual + relu(LN(position_encoder.3(.)))
-  LnArgs l;
-  l.a = ws.t0; l.c = ws.pe1; l.g2 = position_encoder->n4.g; l.b2 = position_encoder->n4.b;
-  l.y = out; l.M = (int)rows;
-  return launch_ln256(l, s);
+  return tc_cross_atten_points_fwd(attention_weights, output_proj, position_encoder, feats, B, Q, C, num_cams, 1,
+                                   query, query_pos, lidar2img, ref, pc_range, img_h, img_w, out, workspace,
+                                   workspace_bytes, stream);
 }
 
 size_t tc_self_attn_workspace_bytes(int B, int Q, int C) {
@@ -856,7 +896,7 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
     CrossWs cw{h.logits, h.sampled, h.t0, h.t2, h.attn_o};
     TC_TRY(cross_atten_parts(ly.attention_weights, ly.output_proj, ly.position_encoder, feats, B, Q,
                              C, w->num_cams, h.t1, h.pos, lidar2img, ref_in, pc, img_h, img_w, cw,
-                             pairs, s));
+                             pairs, s, head_points(w)));
     {
       LnArgs l;
       l.a = h.t0; l.c = h.attn_o; l.g2 = ly.position_encoder.n4.g; l.b2 = ly.position_encoder.n4.b;

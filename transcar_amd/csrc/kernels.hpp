@@ -72,6 +72,7 @@ struct CamSampleArgs {
   const float* lidar2img; const float* ref; const float* logits;
   float pc[6]; float img_h, img_w;
   float* out; unsigned char* vis; unsigned long long* pair_counter;
+  int num_points = 1;           // Detr3DCrossAtten.num_points: logits are [B*Q][num_cams][num_points][levels]
 };
 int launch_cam_sample(const CamSampleArgs& a, hipStream_t s);
 

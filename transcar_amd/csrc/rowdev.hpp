@@ -250,16 +250,14 @@ __device__ __forceinline__ float4 cam_level_value(const float4 (&tap)[4], const 
 // fetch(c, l, t, ptr): this lane's 4 channels of tap t of level l of the c-th visible camera.
 // lane0: lane lane0 + c holds camera c's coordinates (0 for a single projected row; the row chains project
 // the four rows of a wave at once, 16 lanes apart)
+// sg_lane: lane cam * L + l holds the weight of level value (cam, l) -- sigmoid of its logit, or with num_points > 1
+// the sum over the points (points_weight_lane).
 template <int L, typename Fetch>
-__device__ __forceinline__ float4 cam_sample_core(const CamK& p, int b, const float* lg, int lane,
-                                                  unsigned long long vmask, float u, float v, Fetch fetch,
-                                                  int lane0 = 0, int Hl = -1, int Wl = -1) {
+__device__ __forceinline__ float4 cam_sample_core_w(const CamK& p, int b, float sg_lane, int lane,
+                                                    unsigned long long vmask, float u, float v, Fetch fetch,
+                                                    int lane0 = 0, int Hl = -1, int Wl = -1) {
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int c = 0;
-  // XFMR:370: the num_cams * L attention weights of the query, one per lane, ONCE (round 3: every lane evaluated
-  // sigmoid(lg[cam * L + l]) for itself inside the camera loop -- ~80 of its ~330 VALU instructions per visible
-  // camera; same function of the same value: bit-identical)
-  const float sg_lane = sigmoidf_(lg[min(lane, p.num_cams * L - 1)]);
   while (vmask) {
     const int cam = __ffsll((long long)vmask) - 1;
     vmask &= vmask - 1;
@@ -290,6 +288,30 @@ __device__ __forceinline__ float4 cam_sample_core(const CamK& p, int b, const fl
     ++c;
   }
   return acc;
+}
+template <int L, typename Fetch>
+__device__ __forceinline__ float4 cam_sample_core(const CamK& p, int b, const float* lg, int lane,
+                                                  unsigned long long vmask, float u, float v, Fetch fetch,
+                                                  int lane0 = 0, int Hl = -1, int Wl = -1) {
+  // XFMR:370: the num_cams * L attention weights of the query, one per lane, ONCE (round 3: every lane evaluated
+  // sigmoid(lg[cam * L + l]) for itself inside the camera loop -- ~80 of its ~330 VALU instructions per visible
+  // camera; same function of the same value: bit-identical)
+  const float sg_lane = sigmoidf_(lg[min(lane, p.num_cams * L - 1)]);
+  return cam_sample_core_w<L>(p, b, sg_lane, lane, vmask, u, v, fetch, lane0, Hl, Wl);
+}
+
+// num_points P > 1 (XFMR:362-373): the logits of a query are [num_cams][P][L] (Linear(C, N*P*L) viewed as
+// [.., N, P, L]) and the sampled value does not depend on the point, so `output * sigmoid(w) * mask` summed over
+// L, P, N weighs level value (n, l) by mask[n] * sum_p sigmoid(a[n, p, l]).  Lane n L + l sums its P sigmoids
+// in point order; ld(i) reads logit i of the row.
+template <int L, typename Ld>
+__device__ __forceinline__ float points_weight_lane(Ld ld, int lane, int num_cams, int np) {
+  const int j = min(lane, num_cams * L - 1), n = j / L, l = j - n * L;
+  const int base = n * np * L + l;
+  float s = sigmoidf_(ld(base));
+#pragma unroll 1
+  for (int pt = 1; pt < np; ++pt) s += sigmoidf_(ld(base + pt * L));
+  return s;
 }
 
 // ---- round 6: the camera gather off the decoder chain's critical path ------------------------------
@@ -361,14 +383,22 @@ __device__ __forceinline__ void cam_pregather_rows(const PreGatherK& g, int r0, 
   }
 }
 
-template <int L>
+// MP: num_points np > 1 (lg holds num_cams * np * L logits); otherwise the P = 1 code, unchanged
+template <int L, bool MP = false>
 __device__ __forceinline__ float4 cam_sample_row(const CamK& p, int row, int b, const float* lg,
-                                                 int lane, int& nvis) {
+                                                 int lane, int& nvis, int np = 1) {
   CAM_STAMP(0);
   float u, v;
   const unsigned long long vmask = cam_project(p, row, b, lane, u, v);
   nvis = __popcll(vmask);
   CAM_STAMP(1);
+  if constexpr (MP) {
+    const float sg = points_weight_lane<L>([lg](int i) { return lg[i]; }, lane, p.num_cams, np);
+    const float4 acc = cam_sample_core_w<L>(p, b, sg, lane, vmask, u, v,
+                                            [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); });
+    CAM_STAMP(4);
+    return acc;
+  }
   const float4 acc = cam_sample_core<L>(p, b, lg, lane, vmask, u, v,
                                         [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); });
   CAM_STAMP(4);

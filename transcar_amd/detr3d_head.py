@@ -268,6 +268,15 @@ class Detr3DHead(BaseModule):
         w.num_layers = dec.num_layers
         w.num_cams = dec.layers[0].attentions[1].num_cams
         w.num_levels = dec.layers[0].attentions[1].num_levels
+        w.num_points = dec.layers[0].attentions[1].num_points
+        for ly in dec.layers:
+            ca = ly.attentions[1]
+            if (ca.num_cams, ca.num_levels, ca.num_points) != (
+                    w.num_cams, w.num_levels, w.num_points):
+                raise NotImplementedError(
+                    'Detr3DCrossAtten: num_cams / num_levels / num_points '
+                    'differ between decoder layers')
+        L.check_num_points(w.num_points, w.num_cams, w.num_levels)
         w.num_classes, w.code_size = self.cls_out_channels, self.code_size
         w.radar_in_dims, w.num_radar_layers = radar.NUM_FEATURES, 3
         w.num_radar_tokens_ref = radar.NUM_RADAR_TOKENS

@@ -65,10 +65,7 @@ class Detr3DCrossAtten(BaseModule):
         if embed_dims % num_heads != 0:
             raise ValueError('embed_dims must be divisible by num_heads, '
                              'but got %d and %d' % (embed_dims, num_heads))
-        if num_points != 1:
-            raise NotImplementedError(
-                'Detr3DCrossAtten(HIP): num_points=1 (the TransCAR configs, '
-                'CFG:75)')
+        L.check_num_points(num_points, num_cams, num_levels)
         self.norm_cfg = norm_cfg
         self.dropout = nn.Dropout(dropout)
         self.pc_range = pc_range
@@ -117,7 +114,7 @@ class Detr3DCrossAtten(BaseModule):
             ops.linear_view(self.output_proj.weight, self.output_proj.bias),
             pos_encoder_view(self.position_encoder), feats, q, pos, l2i,
             reference_points.contiguous(), self.pc_range, img_hw,
-            self.num_cams)
+            self.num_cams, self.num_points)
         return out.transpose(0, 1)
 
 

@@ -152,38 +152,59 @@ def refine_reference(reg_out, ref):
 
 
 def cam_sample_fuse(feats_nhwc, lidar2img, ref, attn_logits, pc_range, img_hw,
-                    num_cams=6, return_mask=False):
+                    num_cams=6, return_mask=False, num_points=1):
     """feature_sampling + sigmoid-weighted (cam, level) reduction
-    (XFMR:365-373, 381-422).  ref [B,Q,3], attn_logits [B,Q,N*L] -> [B,Q,C]."""
+    (XFMR:365-373, 381-422).  ref [B,Q,3], attn_logits [B,Q,N*P*L] -> [B,Q,C];
+    with num_points P > 1 level value (n, l) weighs sum_p sigmoid(logit[n,p,l])."""
     _chk(ref, 'ref'); _chk(attn_logits, 'attn_logits'); _chk(lidar2img, 'l2i')
     B, Q = ref.shape[:2]
     Cdim = feats_nhwc[0].shape[-1]
     fv = feats_view(feats_nhwc)
+    L.check_num_points(num_points, num_cams, fv.num_levels)
     out = torch.empty((B, Q, Cdim), dtype=torch.float32, device=ref.device)
     vis = torch.empty((B, Q, num_cams), dtype=torch.uint8,
                       device=ref.device) if return_mask else None
-    L.check(L.lib().tc_cam_sample_fuse_fwd(
-        C.byref(fv), B, Q, Cdim, num_cams, _p(lidar2img), _p(ref),
-        _p(attn_logits), L.f6(pc_range), float(img_hw[0]), float(img_hw[1]),
-        _p(out), _p(vis), None, _stream()), 'tc_cam_sample_fuse_fwd')
+    if num_points == 1:
+        L.check(L.lib().tc_cam_sample_fuse_fwd(
+            C.byref(fv), B, Q, Cdim, num_cams, _p(lidar2img), _p(ref),
+            _p(attn_logits), L.f6(pc_range), float(img_hw[0]), float(img_hw[1]),
+            _p(out), _p(vis), None, _stream()), 'tc_cam_sample_fuse_fwd')
+    else:
+        L.check(L.lib().tc_cam_sample_fuse_points_fwd(
+            C.byref(fv), B, Q, Cdim, num_cams, int(num_points), _p(lidar2img),
+            _p(ref), _p(attn_logits), L.f6(pc_range), float(img_hw[0]),
+            float(img_hw[1]), _p(out), _p(vis), None, _stream()),
+            'tc_cam_sample_fuse_points_fwd')
     return (out, vis) if return_mask else out
 
 
 def cross_atten(aw, oproj, pe, feats_nhwc, query, query_pos, lidar2img, ref,
-                pc_range, img_hw, num_cams=6):
-    """Detr3DCrossAtten.forward (XFMR:302-378); query/query_pos [B,Q,C]."""
+                pc_range, img_hw, num_cams=6, num_points=1):
+    """Detr3DCrossAtten.forward (XFMR:302-378); query/query_pos [B,Q,C];
+    aw = attention_weights [num_cams*num_points*L, C]."""
     _chk(query, 'query'); _chk(query_pos, 'query_pos'); _chk(ref, 'ref')
     B, Q, Cdim = query.shape
     fv = feats_view(feats_nhwc)
-    nbytes = L.lib().tc_cross_atten_workspace_bytes(B, Q, Cdim, num_cams,
-                                                    fv.num_levels)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+    L.check_num_points(num_points, num_cams, fv.num_levels)
     out = torch.empty_like(query)
-    L.check(L.lib().tc_cross_atten_fwd(
+    if num_points == 1:
+        nbytes = L.lib().tc_cross_atten_workspace_bytes(B, Q, Cdim, num_cams,
+                                                        fv.num_levels)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+        L.check(L.lib().tc_cross_atten_fwd(
+            C.byref(aw), C.byref(oproj), C.byref(pe), C.byref(fv), B, Q, Cdim,
+            num_cams, _p(query), _p(query_pos), _p(lidar2img), _p(ref),
+            L.f6(pc_range), float(img_hw[0]), float(img_hw[1]), _p(out), _p(ws),
+            nbytes, _stream()), 'tc_cross_atten_fwd')
+        return out
+    nbytes = L.lib().tc_cross_atten_points_workspace_bytes(
+        B, Q, Cdim, num_cams, fv.num_levels, int(num_points))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+    L.check(L.lib().tc_cross_atten_points_fwd(
         C.byref(aw), C.byref(oproj), C.byref(pe), C.byref(fv), B, Q, Cdim,
-        num_cams, _p(query), _p(query_pos), _p(lidar2img), _p(ref),
-        L.f6(pc_range), float(img_hw[0]), float(img_hw[1]), _p(out), _p(ws),
-        nbytes, _stream()), 'tc_cross_atten_fwd')
+        num_cams, int(num_points), _p(query), _p(query_pos), _p(lidar2img),
+        _p(ref), L.f6(pc_range), float(img_hw[0]), float(img_hw[1]), _p(out),
+        _p(ws), nbytes, _stream()), 'tc_cross_atten_points_fwd')
     return out
 
 
@@ -224,7 +245,9 @@ def decoder_layer_tail(packed_layer, packed_next_in_proj, feats_nhwc, attn_o, x_
                        query_embedding, lidar2img, ref_in, pc_range, img_hw, code_size=10,
                        num_cams=6, tile_rows=0, matrix_path=0):
     """One decoder layer after its attention core as the fused row chain
-    (tc_decoder_layer_tail_fwd).  packed_*: members of the head's packed view
+    (tc_decoder_layer_tail_fwd).  Detr3DCrossAtten.num_points = 1 only (the C
+    layer struct does not carry num_points; P > 1 heads run through
+    tc_head_forward).  packed_*: members of the head's packed view
     (``head._packed_view.layers[l]``, ``.layers[l + 1].self_attn.in_proj`` or
     None).  matrix_path: TC_MATRIX_* of 16-row tiles (tc_head_options.matrix_path).
     Returns (hs [B,Q,C], ref_out [B,Q,3], qk [B,Q,2C], vt [B,C,qpad])."""

@@ -61,7 +61,7 @@ def _pos_encoder(spec, name, c):
 
 def state_dict_spec(num_query=900, embed=256, ffn=512, num_layers=6,
                     num_classes=10, code_size=10, num_cams=6, num_levels=4,
-                    radar_in=36):
+                    radar_in=36, num_points=1):
     """[(key, shape, kind)] for ``pts_bbox_head.*`` (HEAD:43-238, XFMR:61-63,
     XFMR:280-292; mmcv brick names per SURVEY.md section 8(b))."""
     c = embed
@@ -73,7 +73,7 @@ def state_dict_spec(num_query=900, embed=256, ffn=512, num_layers=6,
         p = 'transformer.decoder.layers.%d.' % i
         _mha(s, p + 'attentions.0.attn', c)
         _linear(s, p + 'attentions.1.attention_weights',
-                num_cams * num_levels, c)
+                num_cams * num_points * num_levels, c)
         _linear(s, p + 'attentions.1.output_proj', c, c)
         _pos_encoder(s, p + 'attentions.1.position_encoder', c)
         _linear(s, p + 'ffns.0.layers.0.0', ffn, c)
