@@ -64,6 +64,14 @@ typedef struct {
   tc_linear ffn1;                   /* ffns.0.layers.1   [C,F]                */
   tc_lnorm norm2;
   tc_reg_branch reg;                /* reg_branches.{lid}                     */
+  /* Box refinement (Detr3DHead.with_box_refine, HEAD:45): a head without it hands the decoder
+   * reg_branches=None (XFMR:183-203) and is expressed as reg.l0.w == NULL in layers 0 .. L-2 (reg.l2 /
+   * reg.l4 are then not read): every layer samples at the initial reference points and every level's
+   * inter_references equals init_reference.  layers[L-1].reg stays required: it is the head's
+   * reg_branches[-1] (HEAD:287-293), taken against the initial reference for the last level's box.
+   * Below the last layer the branches are all set or all NULL; anything else is refused naming the
+   * layer (tc_head_packed_bytes returns 0, tc_head_pack_weights / tc_head_forward fail).  A one-layer
+   * decoder refines.  tc_decoder_layer_tail_fwd on a layer with reg.l0.w == NULL: ref_out = ref_in. */
   /* Set by tc_head_pack_weights in the packed view only (0 in the caller's struct): every packed
    * linear weight has a second copy, laid out for the 16-row tiles' 16x16x4 MFMA, this many FLOATS
    * behind the first (the same distance for all weights of a packed buffer). */
@@ -339,7 +347,8 @@ int tc_self_attn_fwd(const tc_mha* w, const float* x, const float* pos, float* o
  * kernel of tc_head_forward; mmcv layer order CFG:81-82, XFMR:346-378, 190-203):
  *   x1 = norm0(x_in + out_proj(attn_o)); camera cross-attention (attention
  *   weights, sampling, output_proj, position encoder); norm1; FFN; norm2 -> hs;
- *   reg branch -> ref_out = refined reference points; next layer's q,k (qk) and
+ *   reg branch -> ref_out = refined reference points (a layer with reg.l0.w == NULL, see
+ *   tc_decoder_layer.reg: no reg branch, ref_out = ref_in); next layer's q,k (qk) and
  *   transposed v (vt) when next_in_proj != NULL.
  * `layer` / `next_in_proj` must come from a tc_head_pack_weights view (packed
  * weights).  attn_o, x_in, hs [B*Q,C]; query_embedding [Q,2C]; ref_in/ref_out

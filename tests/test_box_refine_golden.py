@@ -1,0 +1,89 @@
+"""The CPU oracle without box refinement (box_refine_oracle.py, patched over the oracle's transformer) against the
+fixtures the REFERENCE's own Detr3DHead(with_box_refine=False) produced (tests/golden/make_golden_norefine.py).  CPU;
+the fixtures are committed, so the reference itself is not needed."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import box_refine_oracle as BRO
+import num_points_oracle as NPO
+from oracle import transcar_oracle as O
+from transcar_amd import configs, synth
+
+PCR = configs.point_cloud_range
+HW = configs.IMG_SHAPE[:2]
+E2E_TOL = 5e-4          # test_oracle_golden.test_g5_full_head
+
+FIXTURES = [('tiny', 1, 'g5_head_tiny_norefine.npz'), ('res101', 1, 'g5_head_res101_norefine.npz'),
+            ('tiny', 5, 'g5_head_tiny_p5_norefine.npz')]
+
+
+@pytest.fixture(autouse=True)
+def _no_grad():
+    with torch.no_grad():
+        yield
+
+
+@pytest.fixture
+def patched(monkeypatch):
+    monkeypatch.setattr(O, 'transformer', BRO.transformer)
+    monkeypatch.setattr(O, 'cross_atten', NPO.cross_atten)      # (P = 1: the oracle's own arithmetic)
+    return O
+
+
+def _g(golden_dir, name):
+    return np.load(os.path.join(golden_dir, name))
+
+
+def test_shared_branch_state_dict():
+    """synth's with_box_refine=False weights hold one branch under every index; the default output is untouched."""
+    sd = synth.make_state_dict(seed=3, with_box_refine=False)
+    ref = synth.make_state_dict(seed=3)
+    assert set(sd) == set(ref)
+    for k in sd:
+        if k.startswith(('cls_branches.', 'reg_branches.')):
+            stem, _, rest = k.split('.', 2)
+            assert np.array_equal(sd[k], ref['%s.0.%s' % (stem, rest)]), k
+        else:
+            assert np.array_equal(sd[k], ref[k]), k
+    assert not np.array_equal(ref['reg_branches.0.0.weight'], ref['reg_branches.5.0.weight'])
+
+
+@pytest.mark.parametrize('shapes,P,name', FIXTURES)
+def test_fixture_inter_references_are_the_initial_one(golden_dir, shapes, P, name):
+    g = _g(golden_dir, name)
+    assert g['inter_refs'].shape[0] == 6
+    for l in range(6):
+        assert np.array_equal(g['inter_refs'][l], g['init_ref']), l
+
+
+@pytest.mark.parametrize('shapes,P,name', FIXTURES)
+def test_g5_head_norefine(golden_dir, patched, shapes, P, name):
+    g = _g(golden_dir, name)
+    sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_points=P, with_box_refine=False))
+    feats = [torch.from_numpy(f) for f in synth.make_feats(shapes, seed=1, smooth=(4, 6))]
+    l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
+    f36 = O.build_radar_features(synth.make_radar_frame(seed=2, n_per_radar=51, centres=g['radar_centres']))
+    np.testing.assert_allclose(f36.astype(np.float32), g['radar_tokens'], atol=1e-6, rtol=1e-6)
+    outs, dbg = patched.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True)
+    np.testing.assert_allclose(dbg['inter_refs'].numpy(), g['inter_refs'], atol=2e-6, rtol=0)
+    hs = dbg['hs'].permute(0, 2, 1, 3).numpy()
+    np.testing.assert_allclose(hs[:, ::16, 0, :], g['hs_rows'], atol=5e-5, rtol=0)
+    for i in range(3):
+        assert len(dbg['hit_rows'][i]) == int(g['Lq'][i])
+    for k in ('all_cls_scores', 'all_bbox_preds'):
+        d = np.abs(outs[k].numpy() - g[k]).max(axis=(0, 1, 3))
+        bad = np.where(d > E2E_TOL)[0]
+        assert len(bad) <= 2 and (len(bad) == 0 or d.max() < 1e-2), (k, bad.tolist(), d[bad].tolist())
+
+
+def test_refining_oracle_does_not_match(golden_dir):
+    """The fixtures tell the two modes apart: the refining oracle's references leave the initial ones."""
+    g = _g(golden_dir, 'g5_head_tiny_norefine.npz')
+    sd = O.to_torch_sd(synth.make_state_dict(seed=3, with_box_refine=False))
+    feats = [torch.from_numpy(f) for f in synth.make_feats('tiny', seed=1, smooth=(4, 6))]
+    l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
+    _, _, refs, _ = O.transformer(sd, feats, PCR, l2i, HW)
+    assert float(np.abs(refs.numpy()[-1] - g['inter_refs'][-1]).max()) > 1e-3

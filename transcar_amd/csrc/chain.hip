@@ -391,6 +391,7 @@ struct ChainK : ChainDev {
   float* dkv[TC_MAX_RADAR_LAYERS] = {nullptr, nullptr, nullptr};
   size_t w16_delta = 0;        // packed16_delta of the packed view: 16-row tiles read their own weight copy
   int npoints = 1;             // decoder: Detr3DCrossAtten.num_points (> 1: the MP instantiations, logits in unit 3)
+  int refine = 1;              // decoder: the layer has a reg branch (0: reg.0 / .2 / .4 and K_REFUPD are K_NOP)
 };
 
 constexpr int table_steps(int prog) {
@@ -2608,6 +2609,11 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
     r.kind = d.kind; r.src = d.src; r.src2 = d.src2; r.dst = d.dst; r.res = d.res; r.act = d.act;
     r.flags = d.flags; r.sync = d.sync; r.rep = (short)rep; r.si = (short)si;
     if ((d.flags & F_SKIP_NONEXT) && !k.has_next) r.kind = K_NOP;
+    // a decoder layer without box refinement (tc_decoder_layer.reg.l0.w == NULL): no reg branch, no reference update
+    // (only the barriers of the four steps remain).  The last layer of such a decoder has its branch: the box
+    if (PROG == PROG_DECODER && !k.refine &&
+        (d.kind == K_REFUPD || ((d.kind == K_LINEAR || d.kind == K_NARROW) && d.wp >= 13 && d.wp <= 15)))
+      r.kind = K_NOP;
     // inference opt-in (tc_head_options.last_level_cls_only): get_bboxes decodes the last level
     // only and levels 1-2 hand only their BOX to the next gate (HEAD:615-617, 1003-1023), so the
     // class MLPs (pairs 6..10: final_cls.0 / n1 / .3 / n4 / .6) of the earlier layers are dropped
@@ -2948,6 +2954,9 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   k.pairs[9] = tc_linear{w.norm1.g, w.norm1.b}; k.pairs[10] = w.ffn0; k.pairs[11] = w.ffn1;
   k.pairs[12] = tc_linear{w.norm2.g, w.norm2.b};
   k.pairs[13] = w.reg.l0; k.pairs[14] = w.reg.l2; k.pairs[15] = w.reg.l4;
+  // without a reg branch (no box refinement) the layer writes neither ref_out nor a box
+  k.refine = w.reg.l0.w != nullptr;
+  TC_REQUIRE(k.refine || a.box_m == nullptr, "decoder_chain: a layer without a reg branch writes no box");
   k.has_next = a.next_in_proj != nullptr;
   if (k.has_next) k.pairs[16] = *a.next_in_proj;
   k.w16_delta = w.packed16_delta;

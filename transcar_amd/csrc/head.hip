@@ -123,6 +123,22 @@ static int check_dims(const tc_head_weights* w) {
   return 0;
 }
 
+// Box refinement (with_box_refine, HEAD:45): a head without it hands the decoder reg_branches=None (XFMR:183-203) --
+// layers 0 .. L-2 carry reg.l0.w == NULL, and only the last layer's branch (the head's reg_branches[-1], HEAD:287-293)
+// exists.  Mixed NULL / set branches below the last layer are refused.  A one-layer decoder always refines.
+static int decoder_refines(const tc_head_weights* w, bool* refine) {
+  const int L = w->num_layers;
+  const bool r = L < 2 || w->layers[0].reg.l0.w != nullptr;
+  for (int l = 1; l + 1 < L; ++l)
+    TC_REQUIRE((w->layers[l].reg.l0.w != nullptr) == r,
+               "layers[%d].reg is %s but layers[0].reg is %s: below the last layer the reg branches are all set (box "
+               "refinement) or all NULL (none)", l, r ? "NULL" : "set", r ? "set" : "NULL");
+  TC_REQUIRE(w->layers[L - 1].reg.l0.w != nullptr, "layers[%d].reg is NULL: the last layer's reg branch "
+             "(reg_branches[-1]) is required with and without box refinement", L - 1);
+  *refine = r;
+  return 0;
+}
+
 struct HeadWs {
   float *pos, *x, *qk, *vt, *attn_o, *t0, *t1, *t2, *ffn_h, *logits, *sampled;
   float *init_ref, *inter_refs, *hs, *reg_tmp, *box_m;
@@ -185,6 +201,8 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
   }
   unsigned long long* pairs = aux ? aux->sample_pairs : nullptr;
   const bool radar = w->num_radar_layers > 0;
+  bool refine = true;
+  TC_TRY(decoder_refines(w, &refine));
 
   // the radar encoders and K/V projections do not depend on the decoder: they ride in the launches of two
   // decoder layers as extra workgroups (chain_dual_kernel): layers 0 and 1 in the one-call forward; the LAST
@@ -224,20 +242,25 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
   }
   for (int lid = lid_begin; lid < lid_end; ++lid) {
     const bool l0c = folded && lid == 0;
-    const float* ref_in = l0c ? w->l0_init_reference
-                              : lid == 0 ? h.init_ref : h.inter_refs + (size_t)(lid - 1) * rows * 3;
+    // without box refinement every layer samples at the initial reference points (the folded one when layer 0 is)
+    const bool init_in = lid == 0 || !refine;
+    const float* ref_in = init_in ? (folded ? w->l0_init_reference : h.init_ref)
+                                  : h.inter_refs + (size_t)(lid - 1) * rows * 3;
     DecoderChainArgs d;
     if (ddrop) {
       d.drop = make_drop(opt.decoder_dropout_p, opt.dropout_seed, 16u + 8u * (unsigned)lid, 0u);
       if (opt.dropout_seed_stride != 0) { d.drop.seed_stride = opt.dropout_seed_stride; d.drop.rows_per_sample = (unsigned)Q; }
     }
     d.attn_o = l0c ? w->l0_attn_out : h.attn_o;
-    d.attn_mod = l0c ? Q : 0; d.ref_mod = l0c ? Q : 0;
+    d.attn_mod = l0c ? Q : 0; d.ref_mod = folded && init_in ? Q : 0;
     if (lid == 0) { d.x_in = w->query_embedding + C; d.x_ld = 2 * C; d.x_mod = Q; }
     else { d.x_in = h.hs + (size_t)(lid - 1) * rows * C; d.x_ld = C; d.x_mod = 0; }
     d.qe = w->query_embedding; d.Q = Q;
     d.ref_in = ref_in; d.ref_out = h.inter_refs + (size_t)lid * rows * 3;
     d.box_m = lid == L - 1 ? h.box_m : nullptr;
+    // without box refinement only the last layer has a reg branch (its box); the point it refines is not used
+    // (h.addref: the operator-by-operator path's scratch), every level's reference is filled below
+    if (!refine) d.ref_out = h.addref;
     d.w = &w->layers[lid];
     d.next_in_proj = lid + 1 < L ? &w->layers[lid + 1].self_attn.in_proj : nullptr;
     d.qscale = attn_qscale;
@@ -280,6 +303,8 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
     else TC_TRY(launch_decoder_chain(d, s));
   }
   if (opt.phase == 1) return 0;
+  if (!refine)   // inter_references[l] = init_reference (XFMR:183-203 with reg_branches=None): what the radar part reads
+    TC_TRY(launch_ref_broadcast(folded ? w->l0_init_reference : h.init_ref, folded ? Q : 0, h.inter_refs, rows, L, s));
   if (aux) {
     if (aux->init_reference) {
       if (folded) {
@@ -317,7 +342,7 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
 }
 
 // ---- packed weights for the fused chains (pack.hip) --------------------------
-struct PackItem { const float* src; int N, K; const float** slot; bool narrow; };
+struct PackItem { const float* src; int N, K; const float** slot; bool narrow; bool absent; };
 
 static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, PackItem* it) {
   const int C = w->embed_dims, F = w->ffn_dims, NL = w->num_cams * w->num_levels * head_points(w);
@@ -326,8 +351,8 @@ static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, Pack
   // narrow: the three 10-column heads the chains evaluate as wave-per-row dot products (K_NARROW): they
   // stay in the nn.Linear layout (the view keeps the caller's pointer: nothing to re-pack after an
   // optimizer step); listed so that the item order / counts stay what tc_head_repack_trainable assumes
-  auto add = [&](const tc_linear& src, tc_linear& dst, int N, int K, bool narrow = false) {
-    it[n].src = src.w; it[n].N = N; it[n].K = K; it[n].slot = &dst.w; it[n].narrow = narrow; ++n;
+  auto add = [&](const tc_linear& src, tc_linear& dst, int N, int K, bool narrow = false, bool absent = false) {
+    it[n].src = src.w; it[n].N = N; it[n].K = K; it[n].slot = &dst.w; it[n].narrow = narrow; it[n].absent = absent; ++n;
   };
   add(w->reference_points, v->reference_points, 3, C);
   for (int l = 0; l < w->num_layers; ++l) {
@@ -339,9 +364,11 @@ static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, Pack
     add(a.position_encoder.l3, b.position_encoder.l3, C, C);
     add(a.ffn0, b.ffn0, F, C);
     add(a.ffn1, b.ffn1, C, F);
-    add(a.reg.l0, b.reg.l0, C, C);
-    add(a.reg.l2, b.reg.l2, C, C);
-    add(a.reg.l4, b.reg.l4, code, C, true);
+    // a layer without a reg branch (no box refinement, decoder_refines): nothing to pack, the view's slots are NULL
+    const bool noreg = a.reg.l0.w == nullptr;
+    add(a.reg.l0, b.reg.l0, C, C, false, noreg);
+    add(a.reg.l2, b.reg.l2, C, C, false, noreg);
+    add(a.reg.l4, b.reg.l4, code, C, true, noreg);
   }
   if (w->num_radar_layers > 0) {
     add(w->radar_position_encoder.l3, v->radar_position_encoder.l3, C, C);
@@ -544,7 +571,10 @@ int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* ne
   d.cam.pair_counter = nullptr;
   d.code = code_size; d.M = B * Q; d.tile_rows = TC_TILE_ROWS(tile_rows); d.matrix_path = TC_TILE_MATRIX(tile_rows);
   TC_REQUIRE(d.matrix_path <= TC_MATRIX_F16X2 && (tile_rows >> 10) == 0, "decoder_layer_tail: tile_rows=0x%x", tile_rows);
-  return launch_decoder_chain(d, as_stream(stream));
+  TC_TRY(launch_decoder_chain(d, as_stream(stream)));
+  if (layer->reg.l0.w == nullptr)      // no reg branch (a decoder without box refinement): the reference stays
+    TC_HIP(hipMemcpyAsync(ref_out, ref_in, (size_t)B * Q * 3 * 4, hipMemcpyDeviceToDevice, as_stream(stream)));
+  return 0;
 }
 
 int tc_sdpa_fwd(const float* q, const float* k, int ld, const float* vt, int ldt, float* out, int ldo,
@@ -712,12 +742,14 @@ int tc_box_decode_kept(const float* cls_scores, const float* bbox_preds, int B, 
 
 size_t tc_head_packed_bytes(const tc_head_weights* w) {
   if (check_dims(w) != 0) return 0;
+  bool refine;
+  if (decoder_refines(w, &refine) != 0) return 0;
   tc_head_weights view = *w;
   PackItem items[MAX_PACK_ITEMS];
   const int n = collect_pack_items(w, &view, items);
   size_t total = 0;
   for (int i = 0; i < n; ++i)
-    if (!items[i].narrow) total += 3 * arena_slice(packed_floats(items[i].N, items[i].K), 4);   // + the 16x16x4 and the two-plane f16 copies
+    if (!items[i].narrow && !items[i].absent) total += 3 * arena_slice(packed_floats(items[i].N, items[i].K), 4);   // + the 16x16x4 and the two-plane f16 copies
   // layer-0 constants + the scratch they are computed from (see tc_head_pack_weights)
   const size_t Q = w->num_query, C = w->embed_dims, qpad = ((Q + 15) / 16) * 16;
   total += arena_slice(Q * 3, 4) + arena_slice(Q * C, 4) + arena_slice(Q * 2 * C, 4) + arena_slice(C * qpad, 4);
@@ -727,6 +759,8 @@ size_t tc_head_packed_bytes(const tc_head_weights* w) {
 int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_bytes,
                          tc_head_weights* packed_view, tc_stream_t stream) {
   TC_TRY(check_dims(w));
+  bool refine;
+  TC_TRY(decoder_refines(w, &refine));
   TC_REQUIRE(packed != nullptr && packed_view != nullptr, "pack_weights: null output");
   TC_REQUIRE(packed_bytes >= tc_head_packed_bytes(w), "pack_weights: buffer too small");
   *packed_view = *w;
@@ -739,9 +773,10 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
   // too), 2 * packed16_delta from region A
   size_t region_a = 0;
   for (int i = 0; i < n; ++i)
-    if (!items[i].narrow) region_a += arena_slice(packed_floats(items[i].N, items[i].K), 4);
+    if (!items[i].narrow && !items[i].absent) region_a += arena_slice(packed_floats(items[i].N, items[i].K), 4);
   const size_t delta = region_a / sizeof(float);
   for (int i = 0; i < n; ++i) {
+    if (items[i].absent) { *items[i].slot = nullptr; continue; }
     TC_REQUIRE(items[i].src != nullptr, "pack_weights: weight %d is null", i);
     if (items[i].narrow) continue;                     // the view keeps the nn.Linear pointer
     float* dst = a.take<float>(packed_floats(items[i].N, items[i].K));
@@ -750,7 +785,7 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
   }
   for (int rgn = 0; rgn < 2; ++rgn)
     for (int i = 0; i < n; ++i)
-      if (!items[i].narrow) a.take<float>(packed_floats(items[i].N, items[i].K));     // regions B, C
+      if (!items[i].narrow && !items[i].absent) a.take<float>(packed_floats(items[i].N, items[i].K));     // regions B, C
   packed_view->packed16_delta = delta;
   for (int l = 0; l < TC_MAX_LAYERS; ++l) packed_view->layers[l].packed16_delta = delta;
   for (int l = 0; l < TC_MAX_RADAR_LAYERS; ++l) packed_view->radar[l].packed16_delta = delta;
@@ -866,6 +901,8 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   TC_REQUIRE(need <= workspace_bytes, "workspace too small: need %zu, have %zu", need, workspace_bytes);
   TC_REQUIRE(opt.cam_pregather == 0 || opt.cam_pregather_bytes >= tc_cam_pregather_workspace_bytes(w, B),
              "options.cam_pregather_ws holds %zu bytes, %zu needed", opt.cam_pregather_bytes, tc_cam_pregather_workspace_bytes(w, B));
+  bool refine = true;
+  TC_TRY(decoder_refines(w, &refine));
   hipStream_t s = as_stream(stream);
   const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, L = w->num_layers, H = w->num_heads;
   const int code = w->code_size, ncls = w->num_classes;
@@ -886,7 +923,7 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   const float* x = h.x;
   for (int lid = 0; lid < L; ++lid) {
     const tc_decoder_layer& ly = w->layers[lid];
-    const float* ref_in = lid == 0 ? h.init_ref : h.inter_refs + (size_t)(lid - 1) * rows * 3;
+    const float* ref_in = lid == 0 || !refine ? h.init_ref : h.inter_refs + (size_t)(lid - 1) * rows * 3;
     float* ref_out = h.inter_refs + (size_t)lid * rows * 3;
     float* hs_l = h.hs + (size_t)lid * rows * C;
     // self_attn, norm
@@ -908,12 +945,16 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
     TC_TRY(linear(h.ffn_h, F, ly.ffn1, rows, F, C, 0, h.t0, C, s, nullptr, h.t1, C));
     TC_TRY(layernorm(h.t0, ly.norm2, hs_l, rows, 0, s));
     x = hs_l;
-    // XFMR:190-203 box refinement of the reference points
+    // XFMR:190-203 box refinement of the reference points; without it only the last layer's branch runs, for the box
+    if (!refine) {
+      TC_HIP(hipMemcpyAsync(ref_out, h.init_ref, (size_t)rows * 3 * 4, hipMemcpyDeviceToDevice, s));
+      if (lid != L - 1) continue;
+    }
     TC_TRY(linear(hs_l, C, ly.reg.l0, rows, C, C, 1, h.t0, C, s));
     TC_TRY(linear(h.t0, C, ly.reg.l2, rows, C, C, 1, h.t2, C, s));
     TC_TRY(linear(h.t2, C, ly.reg.l4, rows, C, code, 0, h.reg_tmp, code, s));
-    TC_TRY(launch_ref_update(h.reg_tmp, code, ref_in, ref_out, lid == L - 1 ? h.box_m : nullptr, pc,
-                             rows, s));
+    TC_TRY(launch_ref_update(h.reg_tmp, code, ref_in, refine ? ref_out : nullptr, lid == L - 1 ? h.box_m : nullptr,
+                             pc, rows, s));
   }
   if (aux) {
     if (aux->inter_states)

@@ -54,6 +54,10 @@ int launch_split_embed(const float* query_embedding, int Q, int C, int B, float*
 int launch_ref_update(const float* tmp, int code, const float* ref, float* new_ref,
                       float* box_m, const float* pc_range6_host, int M, hipStream_t s);
 
+// a decoder without box refinement: every level's reference is the initial one -- dst [nslots][M,3] = src rows
+// (row % src_rows when src_rows > 0: the packed view's [Q,3] l0_init_reference under B frames)
+int launch_ref_broadcast(const float* src, int src_rows, float* dst, int M, int nslots, hipStream_t s);
+
 // radar layer epilogue: box = reg_out; box[0:2] += ref_xy; box[4] += ref_z  (HEAD:599-600 etc.)
 // and next-layer reference (xy = box[0:2], z = box[4])  (HEAD:615-617)
 int launch_box_add_ref(const float* reg_out, int code, const float* ref_xy, int ld_xy,

@@ -132,6 +132,22 @@ int launch_ref_update(const float* tmp, int code, const float* ref, float* new_r
   return check_launch("ref_update");
 }
 
+// ---- XFMR:183-203 with reg_branches=None: inter_references[l] = init_reference for every l --
+__global__ void ref_broadcast_kernel(const float* __restrict__ src, int src_rows, float* __restrict__ dst, int n,
+                                     int nslots) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;      // float i of one [M,3] slot
+  if (i >= n) return;
+  const int row = i / 3, c = i - 3 * row;
+  const float v = src[(size_t)(src_rows > 0 ? row % src_rows : row) * 3 + c];
+  for (int l = 0; l < nslots; ++l) dst[(size_t)l * n + i] = v;
+}
+int launch_ref_broadcast(const float* src, int src_rows, float* dst, int M, int nslots, hipStream_t s) {
+  TC_REQUIRE((long long)M * 3 < (1ll << 31) && nslots >= 1, "ref_broadcast: M=%d nslots=%d", M, nslots);
+  const int n = 3 * M;
+  hipLaunchKernelGGL(ref_broadcast_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, src_rows, dst, n, nslots);
+  return check_launch("ref_broadcast");
+}
+
 __global__ void box_add_ref_kernel(const float* reg, int code, const float* rxy, int ld_xy,
                                    const float* rz, int ld_z, float* box, float* next_ref3, int M) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;

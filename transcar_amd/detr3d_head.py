@@ -12,6 +12,9 @@ mode.  Differences to the reference that are part of the contract:
   * the six cls branches / five of six reg branches whose results the
     reference computes and throws away (HEAD:277-298, lists reset at
     HEAD:607-608) are not evaluated; their parameters still exist and load;
+  * with_box_refine=False (one shared cls / reg branch, HEAD:223-231): the
+    decoder samples every layer at the initial reference points and runs no
+    reg branch below its last layer (tc_decoder_layer.reg);
   * batch size > 1 is supported for the radar part too (the reference
     hard-codes B = 1: HEAD:301, 523, 568).
 There is no CPU fallback.
@@ -259,6 +262,34 @@ class Detr3DHead(BaseModule):
                     'parameter %s must be contiguous fp32 on the GPU (is %s '
                     'on %s); call head.cuda().float()' % (name, p.dtype,
                                                           p.device))
+        w = self.weights_struct()
+        # one-time re-layout for the fused row-chain kernels (tc_head_pack_weights)
+        return self._pack(w, L.lib())
+
+    def _pack(self, w, lib):
+        nbytes = lib.tc_head_packed_bytes(C.byref(w))
+        if nbytes == 0:
+            raise L.TransCARHipError(lib.tc_last_error().decode())
+        dev = self.query_embedding.weight.device
+        # Re-pack IN PLACE when the buffer fits (load_state_dict / refresh_weights / a
+        # FusionTrainer moving the parameters into its flat bucket): captured hipGraphs hold
+        # raw pointers into it.  A new allocation bumps buffers_generation instead.
+        if self._packed is None or self._packed.numel() != nbytes or self._packed.device != dev:
+            self._packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.buffers_generation += 1
+        self._packed_view = L.tc_head_weights()
+        L.check(lib.tc_head_pack_weights(
+            C.byref(w), self._packed.data_ptr(), nbytes,
+            C.byref(self._packed_view),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+            'tc_head_pack_weights')
+        self._weights = w
+        self._packed_dirty = False
+        return w
+
+    def weights_struct(self):
+        """tc_head_weights over this module's parameters as they are (no device
+        check, nothing packed): what head_weights() hands the library."""
         dec = self.transformer.decoder
         w = L.tc_head_weights()
         w.abi_version = L.TC_ABI_VERSION
@@ -284,9 +315,9 @@ class Detr3DHead(BaseModule):
             w.pc_range[i] = float(self.pc_range[i])
         w.query_embedding = self.query_embedding.weight.data_ptr()
         w.reference_points = _lin(self.transformer.reference_points)
-        if not self.with_box_refine:
-            raise NotImplementedError('with_box_refine=False is not used by '
-                                      'the TransCAR configs (CFG:57)')
+        if not self.with_box_refine and dec.num_layers < 2:
+            raise NotImplementedError('with_box_refine=False with a one-layer '
+                                      'decoder (its reg branch would refine)')
         for i, ly in enumerate(dec.layers):
             if ly.operation_order != ('self_attn', 'norm', 'cross_attn',
                                       'norm', 'ffn', 'norm'):
@@ -300,7 +331,13 @@ class Detr3DHead(BaseModule):
             d.output_proj = _lin(ca.output_proj)
             d.position_encoder = pos_encoder_view(ca.position_encoder)
             d.ffn0, d.ffn1 = _lin(ffn.layers[0][0]), _lin(ffn.layers[1])
-            d.reg = reg_branch_view(self.reg_branches[i])
+            # without box refinement the decoder gets reg_branches=None
+            # (HEAD:271, XFMR:183-203): layers 0 .. L-2 carry NULL branches;
+            # the last one is the head's reg_branches[-1] (HEAD:287-293)
+            if self.with_box_refine or i == dec.num_layers - 1:
+                d.reg = reg_branch_view(self.reg_branches[i])
+            else:
+                d.reg = L.tc_reg_branch()
         w.radar_position_encoder = pos_encoder_view(self.radar_position_encoder)
         w.radar_feat0 = _lin(self.radar_feat_encoder[0])
         w.radar_feat2 = _lin(self.radar_feat_encoder[2])
@@ -315,26 +352,6 @@ class Detr3DHead(BaseModule):
             rl.final_cls = cls_branch_view(getattr(self, 'final_cls' + asfx))
             rl.final_reg = reg_branch_view(getattr(self, 'final_reg' + asfx))
             rl.radius_min, rl.radius_max = RADAR_RADII[r]
-        # one-time re-layout for the fused row-chain kernels (tc_head_pack_weights)
-        lib = L.lib()
-        nbytes = lib.tc_head_packed_bytes(C.byref(w))
-        if nbytes == 0:
-            raise L.TransCARHipError(lib.tc_last_error().decode())
-        dev = self.query_embedding.weight.device
-        # Re-pack IN PLACE when the buffer fits (load_state_dict / refresh_weights / a
-        # FusionTrainer moving the parameters into its flat bucket): captured hipGraphs hold
-        # raw pointers into it.  A new allocation bumps buffers_generation instead.
-        if self._packed is None or self._packed.numel() != nbytes or self._packed.device != dev:
-            self._packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self.buffers_generation += 1
-        self._packed_view = L.tc_head_weights()
-        L.check(lib.tc_head_pack_weights(
-            C.byref(w), self._packed.data_ptr(), nbytes,
-            C.byref(self._packed_view),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-            'tc_head_pack_weights')
-        self._weights = w
-        self._packed_dirty = False
         return w
 
     def refresh_weights(self):

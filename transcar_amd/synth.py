@@ -113,8 +113,13 @@ def make_state_dict(seed=3, **dims):
     DETR3D refinements are small deltas, and with full xavier scale the
     ref-point -> sampling -> ref-point feedback has loop gain ~4 per decoder
     layer, which makes any two fp32 implementations drift apart by >1e-3
-    (DESIGN.md "Conditioning of the parity rig")."""
+    (DESIGN.md "Conditioning of the parity rig").
+
+    ``with_box_refine=False``: the head shares ONE cls and ONE reg branch
+    across the decoder layers (HEAD:223-231); its state_dict still carries
+    them under every index, so the seeded branch ``.0`` is written under all."""
     reg_out_scale = dims.pop('reg_out_scale', 0.1)
+    with_box_refine = dims.pop('with_box_refine', True)
     rng = np.random.RandomState(seed)
     sd = {}
     for key, shape, kind in state_dict_spec(**dims):
@@ -138,6 +143,12 @@ def make_state_dict(seed=3, **dims):
                 and '.4.' in key:
             v = v * reg_out_scale
         sd[key] = np.ascontiguousarray(v, dtype=np.float32)
+    if not with_box_refine:
+        for key in list(sd):
+            for stem in ('cls_branches.', 'reg_branches.'):
+                if key.startswith(stem):
+                    rest = key[len(stem):].split('.', 1)[1]
+                    sd[key] = sd[stem + '0.' + rest].copy()
     return sd
 
 
