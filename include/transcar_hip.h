@@ -95,7 +95,7 @@ typedef struct {
 typedef struct {
   int abi_version;                  /* TC_ABI_VERSION                         */
   int num_query, embed_dims, num_heads, ffn_dims, num_layers;
-  int num_cams, num_levels, num_classes, code_size;
+  int num_cams, num_levels, num_classes, code_size;   /* num_levels: 1 .. TC_MAX_LEVELS */
   int radar_in_dims, num_radar_layers, num_radar_tokens_ref; /* 36, 3, 1500   */
   float pc_range[6];
   const float* query_embedding;     /* [Q, 2C]: (query_pos | query) XFMR:119  */
@@ -117,7 +117,8 @@ typedef struct {
   int num_points;
 } tc_head_weights;
 
-/* multi-view FPN feature maps, channels-last: level l is [B*num_cams, H, W, C] */
+/* multi-view FPN feature maps, channels-last: level l is [B*num_cams, H, W, C]; num_levels 1 .. TC_MAX_LEVELS (entries
+ * from num_levels on are not read) */
 typedef struct {
   int num_levels;
   const float* data[TC_MAX_LEVELS];
@@ -289,7 +290,7 @@ int tc_refine_reference_fwd(const float* reg_out, int code_size, const float* re
 
 /* feature_sampling + the weighting/reduction of Detr3DCrossAtten.forward
  * (XFMR:365-373, XFMR:381-422): projection of the reference points into every
- * camera, visibility mask, bilinear 4-level sampling (align_corners=False,
+ * camera, visibility mask, bilinear sampling of feats->num_levels L levels (1 .. TC_MAX_LEVELS; align_corners=False,
  * zeros padding), NaN->0, sigmoid(attn_logits)*mask weighting, sum over
  * (cam, level).  out [B,Q,C];  vis_mask [B,Q,num_cams] (bytes) may be NULL. */
 int tc_cam_sample_fuse_fwd(const tc_feats_nhwc* feats, int B, int Q, int C, int num_cams,
@@ -312,7 +313,7 @@ int tc_cam_sample_fuse_points_fwd(const tc_feats_nhwc* feats, int B, int Q, int 
                                   tc_stream_t stream);
 
 /* Detr3DCrossAtten.forward (XFMR:302-378), eval mode: returns
- * output_proj(sampled) + query + position_encoder(inverse_sigmoid(ref)).
+ * output_proj(sampled) + query + position_encoder(inverse_sigmoid(ref)).  feats->num_levels 1 .. TC_MAX_LEVELS.
  * query/query_pos/out are [B,Q,C] (the reference's [Q,B,C] with B folded
  * first).  workspace: tc_cross_atten_workspace_bytes(). */
 size_t tc_cross_atten_workspace_bytes(int B, int Q, int C, int num_cams, int num_levels);
@@ -354,7 +355,9 @@ int tc_self_attn_fwd(const tc_mha* w, const float* x, const float* pos, float* o
  * weights).  attn_o, x_in, hs [B*Q,C]; query_embedding [Q,2C]; ref_in/ref_out
  * [B*Q,3]; qk [B*Q,2C]; vt [B,C,qpad].
  * num_points = 1 only: tc_decoder_layer does not carry num_points, and a layer of a head with num_points > 1 would be read
- * as its first num_cams * num_levels attention-weight rows.  Such heads run through tc_head_forward. */
+ * as its first num_cams * num_levels attention-weight rows.  Such heads run through tc_head_forward.
+ * feats->num_levels = 4 only (another level count is refused, naming it); heads with 1 .. 3 levels run through
+ * tc_head_forward as well. */
 int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* next_in_proj,
                               const tc_feats_nhwc* feats, int B, int Q, int num_cams,
                               int code_size, const float* attn_o, const float* x_in,

@@ -42,6 +42,27 @@ def check_num_points(num_points, num_cams, num_levels):
             % (num_points, num_cams, num_levels, TC_MAX_CAM_LOGITS))
 
 
+# FPN levels of tc_feats_nhwc / Detr3DCrossAtten.num_levels (include/transcar_hip.h)
+TC_MAX_LEVELS = 4
+
+
+def check_num_levels(num_levels):
+    """The library's limit on Detr3DCrossAtten.num_levels (1 .. TC_MAX_LEVELS),
+    checked before anything is packed or launched."""
+    if int(num_levels) != num_levels or not 1 <= int(num_levels) <= TC_MAX_LEVELS:
+        raise TransCARHipError(
+            'Detr3DCrossAtten(HIP): num_levels=%r is not supported (1 .. %d FPN levels)'
+            % (num_levels, TC_MAX_LEVELS))
+
+
+def cam_pregather_supported(embed_dims, num_levels, num_cams):
+    """The shapes the camera pre-gather (tc_head_options.cam_pregather) runs:
+    C = 256, 4 levels, at most 8 cameras.  Others take the chain's own gather,
+    with bit-identical outputs; asking the library for the pre-gather on them
+    is an error."""
+    return embed_dims == 256 and num_levels == TC_MAX_LEVELS and num_cams <= 8
+
+
 TC_MAX_RADAR_CHANNELS = 8
 TC_SQ_NORM_PARTIALS = 256
 

@@ -75,11 +75,14 @@ LEVEL_SHAPES = {
 IMG_SHAPE = (928, 1600, 3)
 
 
-def head_cfg(num_query=900, num_points=None, with_box_refine=None):
+def head_cfg(num_query=900, num_points=None, with_box_refine=None,
+             num_levels=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
-    reference class defaults to False, HEAD:45)."""
+    reference class defaults to False, HEAD:45); num_levels sets
+    Detr3DCrossAtten.num_levels and the transformer's num_feature_levels (the
+    configs: the class defaults, 4 FPN levels)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -87,4 +90,8 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None):
     if num_points is not None:
         layers = cfg['transformer']['decoder']['transformerlayers']
         layers['attn_cfgs'][1]['num_points'] = int(num_points)
+    if num_levels is not None:
+        layers = cfg['transformer']['decoder']['transformerlayers']
+        layers['attn_cfgs'][1]['num_levels'] = int(num_levels)
+        cfg['transformer']['num_feature_levels'] = int(num_levels)
     return cfg

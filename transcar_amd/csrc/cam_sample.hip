@@ -59,9 +59,19 @@ void fill_camk(const CamSampleArgs& a, CamK& p) {
   p.out = a.out; p.vis = a.vis; p.pair_counter = a.pair_counter;
 }
 
+template <int L>
+static void launch_cam_sample_l(const CamK& p, int np, hipStream_t s) {
+  const int rows = p.B * p.Q;
+  if (np > 1)
+    hipLaunchKernelGGL(cam_sample_points_kernel<L>, dim3((rows + 3) / 4), dim3(256), 0, s, p, np);
+  else
+    hipLaunchKernelGGL(cam_sample_kernel<L>, dim3((rows + 3) / 4), dim3(256), 0, s, p);
+}
+
 int launch_cam_sample(const CamSampleArgs& a, hipStream_t s) {
   TC_REQUIRE(a.C == 256, "cam_sample: C=%d (256 supported)", a.C);
-  TC_REQUIRE(a.feats.num_levels == 4, "cam_sample: num_levels=%d (4 supported)", a.feats.num_levels);
+  TC_REQUIRE(a.feats.num_levels >= 1 && a.feats.num_levels <= TC_MAX_LEVELS, "cam_sample: num_levels=%d (1 .. %d supported)",
+             a.feats.num_levels, TC_MAX_LEVELS);
   for (int l = 0; l < a.feats.num_levels; ++l)      // pixel indices are 32-bit in the kernels
     TC_REQUIRE((long long)a.B * a.num_cams * a.feats.H[l] * a.feats.W[l] < (1ll << 31),
                "cam_sample: level %d has too many pixels for one call", l);
@@ -69,11 +79,12 @@ int launch_cam_sample(const CamSampleArgs& a, hipStream_t s) {
              "cam_sample: num_points=%d (1 .. %d / (num_cams * num_levels) supported)", a.num_points, TC_MAX_CAM_LOGITS);
   CamK p;
   fill_camk(a, p);
-  const int rows = a.B * a.Q;
-  if (a.num_points > 1)
-    hipLaunchKernelGGL(cam_sample_points_kernel<4>, dim3((rows + 3) / 4), dim3(256), 0, s, p, a.num_points);
-  else
-    hipLaunchKernelGGL(cam_sample_kernel<4>, dim3((rows + 3) / 4), dim3(256), 0, s, p);
+  switch (a.feats.num_levels) {      // one instance per level count (1 .. TC_MAX_LEVELS, checked above)
+    case 1: launch_cam_sample_l<1>(p, a.num_points, s); break;
+    case 2: launch_cam_sample_l<2>(p, a.num_points, s); break;
+    case 3: launch_cam_sample_l<3>(p, a.num_points, s); break;
+    default: launch_cam_sample_l<4>(p, a.num_points, s); break;
+  }
   return check_launch("cam_sample");
 }
 

@@ -394,6 +394,10 @@ struct ChainK : ChainDev {
   int refine = 1;              // decoder: the layer has a reg branch (0: reg.0 / .2 / .4 and K_REFUPD are K_NOP)
 };
 
+// the decoder's cross-attention takes the generic (MP) kernels with num_points > 1 or fewer than 4 levels; P = 1 at
+// 4 levels (the TransCAR configs) keeps kernels of its own
+inline bool generic_xattn(const ChainK& k) { return k.npoints > 1 || k.cam.num_levels < 4; }
+
 constexpr int table_steps(int prog) {
   return (prog == PROG_DECODER ? (int)(sizeof(PROG_DECODER_T) / sizeof(StepDesc))
           : prog == PROG_PROLOGUE ? (int)(sizeof(PROG_PROLOGUE_T) / sizeof(StepDesc))
@@ -1334,7 +1338,10 @@ __device__ __forceinline__ void item32h(Acc32H& acc, WBuf& wb, const float* arow
 // linear_step for R = 32 (8 waves; same contract as linear_step16h: w0 may arrive preloaded with the step's first item in
 // b[0..7], the last item of an even count fetches `next_first`; an odd count -- the radar encoders' two K = 64 steps --
 // ends on buffer 1 and hands nothing over)
-template <bool DROP, typename SpecFn>
+// NB (the generic cross-attention kernels, chain_body MP): N need not be a multiple of 4 -- the N * P * L logits of 1 or
+// 3 levels (6 * 1, 6 * 3 columns).  The float4 bias load below clamps its start to N - 4, which shifts the bias of a
+// partial four-column group; NB loads the four values one by one instead (the same values wherever N % 4 == 0).
+template <bool DROP, bool NB = false, typename SpecFn>
 __device__ __forceinline__ bool linear_step32h(const LinSpec& s, WBuf& w0, bool preloaded, const float* next_first,
                                                SpecFn make_spec, int step_idx) {
   constexpr int NW = 8;
@@ -1384,8 +1391,15 @@ __device__ __forceinline__ bool linear_step32h(const LinSpec& s, WBuf& w0, bool 
       // (see linear_step; columns beyond N are never stored: any valid address will do)
       const float* bsrc = s.bias != nullptr ? s.bias : s.W;
 #pragma unroll
-      for (int jj = 0; jj < 2; ++jj)
-        bias4[jj] = ld4(bsrc + min((wave + tt * NW) * 32 + 16 * jj + 4 * (lane >> 4), max(s.N - 4, 0)));
+      for (int jj = 0; jj < 2; ++jj) {
+        const int c = (wave + tt * NW) * 32 + 16 * jj + 4 * (lane >> 4);
+        if constexpr (NB) {
+          const int cl = s.N - 1;
+          bias4[jj] = make_float4(bsrc[min(c, cl)], bsrc[min(c + 1, cl)], bsrc[min(c + 2, cl)], bsrc[min(c + 3, cl)]);
+        } else {
+          bias4[jj] = ld4(bsrc + min(c, max(s.N - 4, 0)));
+        }
+      }
     }
     item32h<BUF>(acc, w0, arow0, arow1, kb * KB, nload, lo);
     SUB_STAMP(3 + tt * nkb + kb);
@@ -1445,12 +1459,12 @@ __device__ __forceinline__ bool linear_step32h(const LinSpec& s, WBuf& w0, bool 
 // SRC2: the A operand is src + src2 (the prologue's x + query_pos only: a run-time test of the pointer
 // put branches between the operand reads of every item, and hipcc waits vmcnt(0) at their joins, i.e.
 // for the item's whole weight fetch)
-template <int R, bool DROP, bool SRC2, int MM, typename SpecFn>
+template <int R, bool DROP, bool SRC2, int MM, bool NB = false, typename SpecFn>
 __device__ __forceinline__ bool linear_step(const LinSpec& s, WBuf& w0, bool preloaded,
                                             const float* next_first, SpecFn make_spec, int step_idx) {
   // 16-row tiles: ONE weight buffer refilled in place, 16x16x4 f32 MFMAs (linear_step16) or the two-plane f16
   // form on the matrix cores (linear_step16h, MM = 1)
-  if constexpr (R == 32) return linear_step32h<DROP>(s, w0, preloaded, next_first, make_spec, step_idx);
+  if constexpr (R == 32) return linear_step32h<DROP, NB>(s, w0, preloaded, next_first, make_spec, step_idx);
   if constexpr (R == 16 && MM == 1) return linear_step16h<DROP>(s, w0, preloaded, next_first, make_spec, step_idx);
   if constexpr (R == 16) return linear_step16<DROP, SRC2>(s, w0, preloaded, next_first, make_spec, step_idx);
   constexpr int NG = R / 4;
@@ -1638,7 +1652,9 @@ __device__ int g_wg_cu[2048][2];
 // unit 3 (the host resolver redirects it: the logit buffer `l` holds 32 floats a row, and unit 3 is free until the
 // sampling step writes its output there) and the sampling step weighs level value (n, l) by sum_p sigmoid(.) of them
 // (rowdev.hpp points_weight_lane), reading a row's logits before it stores the row's output.  MP = false is the P = 1
-// kernel as it was.
+// kernel as it was.  The MP kernels are the generic cross-attention: they also take the level count at run time
+// (k.cam.num_levels, 1 .. 4; every launch with fewer than 4 levels takes them, P = 1 included -- generic_xattn), the
+// camera pre-gather (PRE) aside, which exists for 4 levels only.
 template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false, bool MP = false>
 __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_of(R)>* __restrict__ recs, const int block) {
   constexpr int NW = nw_of(R), NT = NW * 64;        // waves / threads of the workgroup
@@ -1949,7 +1965,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
 #endif
           if (((wave - s.woff) & (NW - 1)) < (R == 32 ? (s.N + 31) >> 5 : (s.N + 63) >> 6)) {   // else: no column tile here, w0 keeps waiting
             const PreRec pr = load_uniform<PreRec>(S.recs[idx].p[wave]);
-            const bool have = linear_step<R, DROP, PROG == PROG_PROLOGUE, MM>(s, w0, pre_idx == idx, pr.first, epi_spec, idx);
+            const bool have = linear_step<R, DROP, PROG == PROG_PROLOGUE, MM, MP>(s, w0, pre_idx == idx, pr.first, epi_spec, idx);
             pre_idx = have ? pr.nidx : -1;
           }
         } else if (kd == K_LN) {
@@ -2185,7 +2201,8 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
         float pu, pv;
         unsigned long long vm;
         int Hl, Wl;
-        cam_level_dims<4>(k.cam, lane, Hl, Wl);      // once per step, in flight with the projections (not once per row)
+        const int nl = MP ? k.cam.num_levels : 4;    // levels that exist (MP: the generic kernels, 1 .. 4)
+        cam_level_dims<4>(k.cam, lane, Hl, Wl, nl);  // once per step, in flight with the projections (not once per row)
         {
           const int i = lane >> 4, c = lane & 15;
           const int prow = wave + NW * min(i, R / NW - 1);
@@ -2203,9 +2220,10 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
           if constexpr (MP) {
             const float* lg = buf_ptr(S, B_U3) + row * LD2;
             const float sg = points_weight_lane<4>([lg](int j) { return act_ld1<PL>(lg, j); }, lane, k.cam.num_cams,
-                                                   k.nlogits / (k.cam.num_cams * 4));
-            o = cam_sample_core_w<4>(k.cam, grow / k.Q, sg, lane, vmask, pu, pv,
-                                     [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); }, 16 * i, Hl, Wl);
+                                                   k.nlogits / (k.cam.num_cams * nl), nl);
+            o = cam_sample_core_w<4, true>(k.cam, grow / k.Q, sg, lane, vmask, pu, pv,
+                                           [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); }, 16 * i, Hl,
+                                           Wl, nl);
           } else {
             o = cam_sample_core<4>(k.cam, grow / k.Q, &S.l[row][0], lane, vmask, pu, pv,
                                    [](int, int, int, const float* ptr) { return cam_tap_ld(ptr); }, 16 * i, Hl, Wl);
@@ -2657,7 +2675,7 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
       if (ts != T_NONE && r.gd == nullptr) { r.gd = k.tape[ts]; r.gld = 256; taped = true; }
       if (ts2 != T_NONE) r.gt = k.tape[ts2];
     }
-    if (PROG == PROG_DECODER && d.N == N_LOGITS && k.npoints > 1) r.dst = B_U3;   // MP: N * P * L logits (chain_body)
+    if (PROG == PROG_DECODER && d.N == N_LOGITS && generic_xattn(k)) r.dst = B_U3;   // MP: N * P * L logits (chain_body)
     if (d.kind == K_LINEAR) {
       const tc_linear pr = k.pairs[pair0 + d.wp];
       r.K = d.K == 36 ? k.RI : d.K == N_CODE ? k.code : d.K == N_CLS ? k.ncls : d.K;
@@ -2851,7 +2869,7 @@ int launch_decoder(const ChainK& k, hipStream_t s, const char* what) {
 int launch(const ChainK& k, hipStream_t s, const char* what) {
   switch (k.program) {
     case PROG_DECODER:
-      return k.npoints > 1 ? launch_decoder<true>(k, s, what) : launch_decoder<false>(k, s, what);
+      return generic_xattn(k) ? launch_decoder<true>(k, s, what) : launch_decoder<false>(k, s, what);
     case PROG_RADAR: return launch_rows<PROG_RADAR>(k, s, what);
     // training forward: 4-row tiles up to 1024 rows (one frame per GPU, CFG:188), 8 beyond; always the DROP
     // instantiation (thr 0 keeps everything)
@@ -2934,6 +2952,8 @@ int launch_prologue(const PrologueArgs& a, hipStream_t s) {
 }
 
 static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
+  TC_REQUIRE(a.cam.feats.num_levels >= 1 && a.cam.feats.num_levels <= TC_MAX_LEVELS,
+             "decoder_chain: num_levels=%d (1 .. %d supported)", a.cam.feats.num_levels, TC_MAX_LEVELS);
   TC_REQUIRE(a.code <= 12 && a.cam.num_cams * a.cam.feats.num_levels <= 32, "decoder_chain: code/logit width");
   TC_REQUIRE(a.cam.num_points >= 1 && a.cam.num_cams * a.cam.feats.num_levels * a.cam.num_points <= TC_MAX_CAM_LOGITS,
              "decoder_chain: num_points=%d (num_cams * num_levels * num_points <= %d)", a.cam.num_points, TC_MAX_CAM_LOGITS);
@@ -2970,6 +2990,8 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   fill_camk(a.cam, k.cam);
   k.pair_counter = a.cam.pair_counter;
   TC_REQUIRE((a.pre == nullptr) == (a.premask == nullptr), "decoder_chain: pre-gathered values and masks come together");
+  TC_REQUIRE(a.pre == nullptr || a.cam.feats.num_levels == 4,
+             "decoder_chain: num_levels=%d (the camera pre-gather exists for 4 levels)", a.cam.feats.num_levels);
   k.pre = a.pre; k.premask = a.premask;
   TC_REQUIRE(a.tile_rows == 0 || a.tile_rows == 4 || a.tile_rows == 8 || a.tile_rows == 16 || a.tile_rows == 32,
              "decoder_chain: tile_rows=%d (0 = automatic, 4, 8, 16 or 32)", a.tile_rows);
@@ -3051,7 +3073,7 @@ int launch_decoder_chain_with_encoders(const DecoderChainArgs& d, const RadarEnc
   rc = make_radar_enc_k(e, ke, part);
   if (rc != 0) return rc;
   TC_REQUIRE(kd.drop.thr == 0, "decoder dropout: launch the encoders on their own (launch_radar_encode)");
-  return kd.npoints > 1 ? launch_dual<true>(kd, ke, part, s) : launch_dual<false>(kd, ke, part, s);
+  return generic_xattn(kd) ? launch_dual<true>(kd, ke, part, s) : launch_dual<false>(kd, ke, part, s);
 }
 
 int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {

@@ -116,7 +116,8 @@ static int check_dims(const tc_head_weights* w) {
   TC_REQUIRE(w->num_layers >= 1 && w->num_layers <= TC_MAX_LAYERS, "num_layers=%d", w->num_layers);
   TC_REQUIRE(w->num_radar_layers >= 0 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
              "num_radar_layers=%d", w->num_radar_layers);
-  TC_REQUIRE(w->num_levels == 4, "num_levels=%d (4 supported)", w->num_levels);
+  TC_REQUIRE(w->num_levels >= 1 && w->num_levels <= TC_MAX_LEVELS, "num_levels=%d (1 .. %d supported)", w->num_levels,
+             TC_MAX_LEVELS);
   TC_REQUIRE(w->num_points >= 0 && w->num_cams * w->num_levels * head_points(w) <= TC_MAX_CAM_LOGITS,
              "num_points=%d (num_cams * num_levels * num_points <= %d supported)", w->num_points, TC_MAX_CAM_LOGITS);
   TC_REQUIRE((w->ffn_dims & 31) == 0 && (w->radar_in_dims & 3) == 0, "ffn_dims/radar_in_dims alignment");
@@ -497,6 +498,8 @@ int tc_cross_atten_points_fwd(const tc_linear* attention_weights, const tc_linea
                               tc_stream_t stream) {
   TC_REQUIRE(C == 256, "cross_atten: C=%d (256 supported)", C);
   TC_REQUIRE(feats != nullptr, "feats is null");
+  TC_REQUIRE(feats->num_levels >= 1 && feats->num_levels <= TC_MAX_LEVELS, "cross_atten: num_levels=%d (1 .. %d supported)",
+             feats->num_levels, TC_MAX_LEVELS);
   TC_REQUIRE(num_points >= 1 && num_cams * feats->num_levels * num_points <= TC_MAX_CAM_LOGITS,
              "cross_atten: num_points=%d (1 .. %d / (num_cams * num_levels) supported)", num_points, TC_MAX_CAM_LOGITS);
   TC_REQUIRE(workspace_bytes >= tc_cross_atten_points_workspace_bytes(B, Q, C, num_cams, feats->num_levels, num_points),
@@ -557,6 +560,8 @@ int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* ne
                               float img_w, float* hs, float* ref_out, float* qk, float* vt,
                               int qpad, int tile_rows, tc_stream_t stream) {
   TC_REQUIRE(layer != nullptr && feats != nullptr, "decoder_layer_tail: null argument");
+  TC_REQUIRE(feats->num_levels == 4, "decoder_layer_tail: num_levels=%d (4 supported; heads with fewer levels run "
+             "through tc_head_forward)", feats->num_levels);
   const int C = 256;
   DecoderChainArgs d;
   d.attn_o = attn_o; d.x_in = x_in; d.x_ld = C; d.x_mod = 0;
@@ -892,7 +897,9 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   TC_TRY(check_dims(w));
   tc_head_options opt;
   TC_TRY(read_options(options, opt));
-  TC_REQUIRE(feats != nullptr && feats->num_levels == w->num_levels, "feats: num_levels mismatch");
+  TC_REQUIRE(feats != nullptr, "feats is null");
+  TC_REQUIRE(feats->num_levels == w->num_levels, "feats: num_levels=%d, the head's num_levels=%d", feats->num_levels,
+             w->num_levels);
   TC_REQUIRE(B >= 1, "B=%d", B);
   TC_REQUIRE(w->num_radar_layers == 0 || (radar_tokens != nullptr && T >= 1 && pad_mult >= 1),
              "radar tokens missing (T=%d pad_mult=%d)", T, pad_mult);

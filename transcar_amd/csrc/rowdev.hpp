@@ -192,9 +192,10 @@ __device__ __forceinline__ unsigned long long cam_project(const CamK& p, int row
 // the lane's level l = lane >> 2: its map's height and width.  Depends on the lane only: callers that walk several rows
 // fetch it ONCE (round 6: hipcc turns the select chain into an indexed load from the kernel-argument segment -- inside the
 // row loop of the chain's sampling step that was one more dependent memory round trip per row, in front of the taps)
+// nl: the levels that exist (<= L; the generic cross-attention kernels of chain.hip pass k.cam.num_levels with L = 4)
 template <int L>
-__device__ __forceinline__ void cam_level_dims(const CamK& p, int lane, int& H, int& W) {
-  const int l = min(lane >> 2, L - 1);
+__device__ __forceinline__ void cam_level_dims(const CamK& p, int lane, int& H, int& W, int nl = L) {
+  const int l = min(lane >> 2, nl - 1);
   H = p.H[0]; W = p.W[0];
 #pragma unroll
   for (int i = 1; i < L; ++i) {
@@ -205,8 +206,8 @@ __device__ __forceinline__ void cam_level_dims(const CamK& p, int lane, int& H, 
 }
 template <int L>
 __device__ __forceinline__ void cam_tap_lane(const CamK& p, int b, int cam, float u_, float v_, int lane,
-                                             float& wgt, int& pix, int H = -1, int W = -1) {
-  if (H < 0) cam_level_dims<L>(p, lane, H, W);
+                                             float& wgt, int& pix, int H = -1, int W = -1, int nl = L) {
+  if (H < 0) cam_level_dims<L>(p, lane, H, W, nl);
   const float ix = ((u_ + 1.0f) * (float)W - 1.0f) * 0.5f;
   const float iy = ((v_ + 1.0f) * (float)H - 1.0f) * 0.5f;
   const float xw = floorf(ix), yn = floorf(iy);
@@ -250,12 +251,17 @@ __device__ __forceinline__ float4 cam_level_value(const float4 (&tap)[4], const 
 // fetch(c, l, t, ptr): this lane's 4 channels of tap t of level l of the c-th visible camera.
 // lane0: lane lane0 + c holds camera c's coordinates (0 for a single projected row; the row chains project
 // the four rows of a wave at once, 16 lanes apart)
-// sg_lane: lane cam * L + l holds the weight of level value (cam, l) -- sigmoid of its logit, or with num_points > 1
+// sg_lane: lane cam * nl + l holds the weight of level value (cam, l) -- sigmoid of its logit, or with num_points > 1
 // the sum over the points (points_weight_lane).
-template <int L, typename Fetch>
+// RT: the level count nl is a run-time value, wave-uniform, 1 .. L (the generic cross-attention kernels of chain.hip).
+// A level l >= nl then re-reads the taps of level nl - 1 (the same lines: cache hits, no new traffic) and adds them with
+// weight 0; the levels that exist are summed in the same order.  (Skipping those fetches behind wave-uniform branches cost the
+// generic 16-row chain kernels 9 spilled registers; reads and selects spill fewer than the 4-level form did.)
+// RT = false: nl is L and the code is the fixed-level code, instruction for instruction.
+template <int L, bool RT = false, typename Fetch>
 __device__ __forceinline__ float4 cam_sample_core_w(const CamK& p, int b, float sg_lane, int lane,
                                                     unsigned long long vmask, float u, float v, Fetch fetch,
-                                                    int lane0 = 0, int Hl = -1, int Wl = -1) {
+                                                    int lane0 = 0, int Hl = -1, int Wl = -1, int nl = L) {
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int c = 0;
   while (vmask) {
@@ -266,13 +272,15 @@ __device__ __forceinline__ float4 cam_sample_core_w(const CamK& p, int b, float 
     float wgt[L][4];
     float w_lane;
     int pix_lane;
-    cam_tap_lane<L>(p, b, cam, u_, v_, lane, w_lane, pix_lane, Hl, Wl);
+    cam_tap_lane<L>(p, b, cam, u_, v_, lane, w_lane, pix_lane, Hl, Wl, nl);
 #pragma unroll
     for (int l = 0; l < L; ++l) {
+      int ls = l;
+      if constexpr (RT) ls = l < nl ? l : nl - 1;     // (a level that exists)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        wgt[l][t] = lane_f(w_lane, 4 * l + t);
-        tap[l][t] = fetch(c, l, t, cam_tap_ptr(p, l, __builtin_amdgcn_readlane(pix_lane, 4 * l + t), lane));
+        wgt[l][t] = lane_f(w_lane, 4 * ls + t);
+        tap[l][t] = fetch(c, ls, t, cam_tap_ptr(p, ls, __builtin_amdgcn_readlane(pix_lane, 4 * ls + t), lane));
       }
     }
     CAM_STAMP(2);
@@ -280,8 +288,16 @@ __device__ __forceinline__ float4 cam_sample_core_w(const CamK& p, int b, float 
 #pragma unroll
     for (int l = 0; l < L; ++l) {
       const float4 s = cam_level_value(tap[l], wgt[l]);
-      const float a = lane_f(sg_lane, cam * L + l);   // XFMR:370, mask == 1 here
-      camacc.x += s.x * a; camacc.y += s.y * a; camacc.z += s.z * a; camacc.w += s.w * a;
+      if constexpr (RT) {
+        // a level that does not exist weighs 0 (its value is the finite re-read of level nl - 1): the sum keeps the
+        // fixed-level expression, so 4 levels give the bits the fixed-level code gives (a select between the product and
+        // the sum changed them)
+        const float a = l < nl ? lane_f(sg_lane, cam * nl + l) : 0.0f;  // XFMR:370, mask == 1 here
+        camacc.x += s.x * a; camacc.y += s.y * a; camacc.z += s.z * a; camacc.w += s.w * a;
+      } else {
+        const float a = lane_f(sg_lane, cam * L + l);   // XFMR:370, mask == 1 here
+        camacc.x += s.x * a; camacc.y += s.y * a; camacc.z += s.z * a; camacc.w += s.w * a;
+      }
     }
     acc.x += camacc.x; acc.y += camacc.y; acc.z += camacc.z; acc.w += camacc.w;
     CAM_STAMP(3);
@@ -303,14 +319,15 @@ __device__ __forceinline__ float4 cam_sample_core(const CamK& p, int b, const fl
 // num_points P > 1 (XFMR:362-373): the logits of a query are [num_cams][P][L] (Linear(C, N*P*L) viewed as
 // [.., N, P, L]) and the sampled value does not depend on the point, so `output * sigmoid(w) * mask` summed over
 // L, P, N weighs level value (n, l) by mask[n] * sum_p sigmoid(a[n, p, l]).  Lane n L + l sums its P sigmoids
-// in point order; ld(i) reads logit i of the row.
+// in point order; ld(i) reads logit i of the row.  nl: the levels that exist (<= L, default L; the logits are then
+// [num_cams][P][nl] and lane n nl + l holds the weight).
 template <int L, typename Ld>
-__device__ __forceinline__ float points_weight_lane(Ld ld, int lane, int num_cams, int np) {
-  const int j = min(lane, num_cams * L - 1), n = j / L, l = j - n * L;
-  const int base = n * np * L + l;
+__device__ __forceinline__ float points_weight_lane(Ld ld, int lane, int num_cams, int np, int nl = L) {
+  const int j = min(lane, num_cams * nl - 1), n = j / nl, l = j - n * nl;
+  const int base = n * np * nl + l;
   float s = sigmoidf_(ld(base));
 #pragma unroll 1
-  for (int pt = 1; pt < np; ++pt) s += sigmoidf_(ld(base + pt * L));
+  for (int pt = 1; pt < np; ++pt) s += sigmoidf_(ld(base + pt * nl));
   return s;
 }
 

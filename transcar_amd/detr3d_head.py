@@ -307,6 +307,7 @@ class Detr3DHead(BaseModule):
                 raise NotImplementedError(
                     'Detr3DCrossAtten: num_cams / num_levels / num_points '
                     'differ between decoder layers')
+        L.check_num_levels(w.num_levels)
         L.check_num_points(w.num_points, w.num_cams, w.num_levels)
         w.num_classes, w.code_size = self.cls_out_channels, self.code_size
         w.radar_in_dims, w.num_radar_layers = radar.NUM_FEATURES, 3
@@ -353,6 +354,19 @@ class Detr3DHead(BaseModule):
             rl.final_reg = reg_branch_view(getattr(self, 'final_reg' + asfx))
             rl.radius_min, rl.radius_max = RADAR_RADII[r]
         return w
+
+    def cam_pregather_supported(self):
+        """True if this head's shape has the camera pre-gather (_lib.cam_pregather_supported):
+        the plugin graphs and a one-lane FramePipeline turn it on only then."""
+        ca = self.transformer.decoder.layers[0].attentions[1]
+        return L.cam_pregather_supported(self.embed_dims, ca.num_levels, ca.num_cams)
+
+    def check_feature_levels(self, n):
+        """The head samples num_levels FPN levels: a forward handed another count raises, naming both."""
+        nl = self.transformer.decoder.layers[0].attentions[1].num_levels
+        if n != nl:
+            raise L.TransCARHipError('Detr3DHead: %d feature levels given, the head has num_levels=%d'
+                                     % (n, nl))
 
     def refresh_weights(self):
         """Re-read the parameter pointers and re-pack the weights; call after
@@ -472,6 +486,7 @@ class Detr3DHead(BaseModule):
         device works while the host packs the radar frame."""
         if not _allow_train:
             require_eval(self)
+        self.check_feature_levels(len(feats_nhwc))
         w = self.head_weights()
         if not decoder_only:
             self.sync_packed_weights()
@@ -593,6 +608,7 @@ class Detr3DHead(BaseModule):
     def forward(self, mlvl_feats, img_metas, aux=False):
         """HEAD:248-261: mlvl_feats list of [B,N,C,H,W]; img_metas list[dict]
         -> dict(all_cls_scores [3,B,Q,10], all_bbox_preds [3,B,Q,10], enc_*)."""
+        self.check_feature_levels(len(mlvl_feats))
         dev = mlvl_feats[0].device
         if dev.type != 'cuda':
             raise L.TransCARHipError(

@@ -103,6 +103,9 @@ def to_nhwc_levels(feats, out=None):
 def feats_view(feats_nhwc):
     """list of [B*N,H,W,C] -> tc_feats_nhwc."""
     fv = L.tc_feats_nhwc()
+    if not 1 <= len(feats_nhwc) <= L.TC_MAX_LEVELS:
+        raise L.TransCARHipError('%d feature levels (1 .. %d supported)'
+                                 % (len(feats_nhwc), L.TC_MAX_LEVELS))
     fv.num_levels = len(feats_nhwc)
     for i, f in enumerate(feats_nhwc):
         if not (f.is_cuda and f.dtype == torch.float32 and f.is_contiguous()):

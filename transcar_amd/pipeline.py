@@ -91,8 +91,8 @@ class FramePipeline:
             [torch.cuda.Stream() for _ in self.inputs]
         self.done = [torch.cuda.Event() for _ in self.inputs]
         # one lane = one launch sequence at a time: the attention launches have the chip to themselves, which is where the
-        # camera pre-gather pays (+1.3 %, round 6; with three lanes it costs 2.8 %)
-        solo = len(self.inputs) == 1
+        # camera pre-gather pays (+1.3 %, round 6; with three lanes it costs 2.8 %) -- on the shapes it exists for
+        solo = len(self.inputs) == 1 and head.cam_pregather_supported()
         self.options = options if options is not None else head_options(tile_rows=tile_rows, cam_pregather=solo)
         # radar_raw_capacity = N: every lane also owns a raw-radar stage (ops.RadarRawStage: device slabs for
         # N raw points per frame slot + descriptors) and its graph STARTS with the device-side radar ingest

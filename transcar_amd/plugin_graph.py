@@ -103,8 +103,9 @@ class PluginGraphs:
             C.memmove(C.byref(o), C.byref(src), C.sizeof(o))
         o.phase = phase
         # the plugin entry runs ONE launch sequence at a time: the round-6 opt-in that pays exactly there (and costs with
-        # several sequences in flight) is on -- outputs bit-identical either way
-        o.cam_pregather = 1
+        # several sequences in flight) is on where the head's shape has it -- outputs bit-identical either way
+        if self.head.cam_pregather_supported():
+            o.cam_pregather = 1
         return o
 
     def _capture(self, key, mlvl_feats, img_metas):

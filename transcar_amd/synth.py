@@ -97,8 +97,8 @@ def state_dict_spec(num_query=900, embed=256, ffn=512, num_layers=6,
     _linear(s, 'radar_feat_encoder.0', 64, radar_in)
     _linear(s, 'radar_feat_encoder.2', 128, 64)
     _linear(s, 'radar_feat_encoder.4', c, 128)
-    for n in (2, 3):
-        _linear(s, 'attention_weights%d' % n, num_cams * num_levels, c)
+    for n in (2, 3):      # (HEAD:191: 6 * 4 rows whatever the decoder's levels)
+        _linear(s, 'attention_weights%d' % n, num_cams * 4, c)
         _linear(s, 'output_proj%d' % n, c, c)
     return s
 
