@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the TransCAR fusion-decoder hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W]            the headline figure and nothing beside it
+    python bench.py --full [--gpus N] [--steps K] [--warmup W]     ... and every side measurement, in the same line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -12,6 +13,12 @@ configs[1]: 6 cameras, ResNet-101 FPN shapes, 900 queries, 255 radar points)
 already resident in HBM in channels-last layout.  One process per GPU, frames
 are independent (data parallel, no collective on the data path): "weak"
 scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line.  Everything else the benchmark measures or checks (latencies,
+the per-kernel roofline and its counter passes, other precisions, shapes and
+frames-per-launch settings, a training iteration, the CPU baseline) rides in
+the same line with --full; the timed window is the same either way.
 """
 import argparse
 import ctypes as C
@@ -90,9 +97,17 @@ def parse(argv=None):
                     help='tc_head_options.cam_pregather = 1 (round 6, opt-in): extra workgroups of the attention-core launch in '
                          'front of a decoder chain gather its camera taps (bit-identical outputs; default: the chain gathers '
                          'itself -- with three launch sequences in flight the pre-gather costs 2.8 %%)')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline, everything else the benchmark measures, in the same line: single-lane '
+                         'and pipeline latencies, the per-kernel roofline with its rocprofv3 --pmc child passes, the '
+                         'drop-in call, input delivery, hand-off and end-to-end proxy, the frames-per-launch sweep, the '
+                         'plain-f32 path, the VoVNet shapes, a training iteration and the CPU baseline (--train: the '
+                         'exposed collective time, the cost of the order-free backward and the roofline of the three '
+                         'phases); about a minute more.  The --no-* options below take single ones out again.  Without '
+                         '--full a run sets up, warms up, times the steps, writes --dump-outputs and prints the line')
     ap.add_argument('--main-only', action='store_true',
                     help='only the main timed loop: no single-lane, roofline, delivery, hand-off, batched or CPU '
-                         'side measurements (kernel traces of tools/profile_round.sh)')
+                         'side measurements, with or without --full (kernel traces of tools/profile_round.sh)')
     ap.add_argument('--no-live-pmc', action='store_true',
                     help='roofline.traffic: do not measure it in this run (two child passes of rocprofv3 --pmc, ~20 s '
                          'each), take the figure of the latest committed profiles/r*_pmc.json')
@@ -759,8 +774,9 @@ def live_train_traffic(extra_args=(), timeout_s=120):
     try:
         paths = []
         for ctr in ('FETCH_SIZE', 'WRITE_SIZE'):
-            pth = _pmc_pass(tools[0], tools[1], tmp, ctr, ['--train', '--steps', '9', '--warmup', '2', '--no-roofline', '--main-only',
-                                                          '--warmup-s', '0.02'] + list(extra_args),
+            # (--full --main-only: the iterations of a --full run's own measurements outside its roofline)
+            pth = _pmc_pass(tools[0], tools[1], tmp, ctr, ['--train', '--steps', '9', '--warmup', '2', '--full', '--no-roofline',
+                                                          '--main-only', '--warmup-s', '0.02'] + list(extra_args),
                             timeout_s)
             if pth is None:
                 return None
@@ -1445,7 +1461,7 @@ def train_bench(args, head, inp, dev, rank, world, affinity=None):
     # events' own distance; more ranks: the all-reduce's exposed part (it starts asynchronously behind the backward and
     # runs beside the look-ahead decoder; FusionTrainer.step_fused_nhwc)
     exposed = None
-    if not args.train_autograd:
+    if args.full and not args.train_autograd:
         tr.exchange_events = []
         tr.exchange_chunk_events = []
         for _ in range(20):
@@ -1493,7 +1509,7 @@ def train_bench(args, head, inp, dev, rank, world, affinity=None):
         'rccl_ranks': census,
         'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': window_s / args.steps * 1e3,
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
-        'data': 'synthetic', 'timing': win,
+        'data': 'synthetic', 'full': bool(args.full), 'timing': win,
         'config': {'workload': 'BASELINE.json configs[2]: %s FPN shapes, 900 queries, 255 radar points, '
                                '24 GT boxes, batch-per-GPU %d, DDP' % (args.shapes, B),
                    'decoder_lookahead_frames': depth,
@@ -1749,7 +1765,7 @@ def dry_run(args, affinity=None):
             'unit': 'frames/s', 'n_gpus': world, 'rccl_ranks': census, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': window_s / args.steps * 1e3, 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'dry_run': True, 'timing': win, 'bucket_all_reduce_ok': ok, 'cpu_affinity': affinity,
+            'dry_run': True, 'full': bool(args.full), 'timing': win, 'bucket_all_reduce_ok': ok, 'cpu_affinity': affinity,
             'per_rank': per_rank_summary(own, args.steps, 1), 'roofline': None,
             'cpu_baseline': None,
             'config': {'workload': 'none (dry run)', 'mode': 'train' if args.train else 'inference',
@@ -1767,6 +1783,8 @@ def dry_run(args, affinity=None):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
+    if not args.full:                       # a plain run: what the headline figure needs and nothing beside it
+        args.main_only = True
     if args.main_only:
         args.no_roofline = args.no_handoff = args.no_batched = args.no_cpu_baseline = args.no_configs = True
     env_world = os.environ.get('WORLD_SIZE')
@@ -1867,6 +1885,7 @@ def main(argv=None):
                   '4- / 8-row tiles: f32 MFMA)' % F16X2_PRODUCTS)
                  if (pipe is not None and pipe.tile_rows_of() >= 16 and args.matrix_path != 'f32') else 'f32',
         'data': 'synthetic',
+        'full': bool(args.full),
         'timing': win,
         'per_rank': per_rank_summary(own, args.steps, args.batch),
         'cpu_affinity': affinity,

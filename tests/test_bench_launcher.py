@@ -246,3 +246,13 @@ def test_dump_outputs_float32_and_a_fixed_sample_above_the_cap(tmp_path):
             bench.parse(bad + ['--dump-outputs', str(tmp_path / 'd')])
     with pytest.raises(SystemExit):
         bench.parse(['--steps', '0'])
+
+
+def test_full_is_an_option_that_is_off_by_default():
+    """A plain run measures the headline alone; `--full` asks for every side measurement in the same line (the line says
+    which of the two it was)."""
+    import bench
+    assert bench.parse([]).full is False and bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5']).full is False
+    assert bench.parse(['--full']).full is True and bench.parse(['--full', '--train']).full is True
+    assert _run([sys.executable, 'bench.py'] + FAST)['full'] is False
+    assert _run([sys.executable, 'bench.py', '--full'] + FAST)['full'] is True

@@ -1,6 +1,7 @@
-"""The driver's own command, end to end on the GPU box (runs LAST: the file name sorts behind the parity tests):
-`python bench.py --gpus 1 --steps 20 --warmup 5` prints exactly one JSON line with the contract's keys, the roofline
-of the dominant kernel with its HBM-side traffic (measured in the run when rocprofv3 is there) and the CPU baseline."""
+"""The benchmark's commands, end to end on the GPU (runs LAST: the file name sorts behind the parity tests):
+`python bench.py --full --gpus 1 --steps 20 --warmup 5` prints exactly one JSON line with the contract's keys, the roofline
+of the dominant kernel with its HBM-side traffic (measured in the run when rocprofv3 is there) and the CPU baseline;
+the same command without --full prints the headline alone and spends at most 30 s outside its steps."""
 import json
 import os
 import signal
@@ -18,7 +19,7 @@ CONTRACT = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step
 
 def test_the_drivers_bench_command_prints_one_complete_line():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    p = subprocess.Popen([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5'],
+    p = subprocess.Popen([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '1', '--steps', '20', '--warmup', '5'],
                          cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          start_new_session=True)
     try:
@@ -35,6 +36,7 @@ def test_the_drivers_bench_command_prints_one_complete_line():
         assert k in d, k
     assert d['n_gpus'] == 1 and d['steps'] == 20 and d['warmup'] == 5 and d['higher_is_better'] is True
     assert d['unit'] == 'frames/s' and d['value'] > 1000 and d['vs_baseline'] is None
+    assert d['full'] is True
     # fp32 results: the linear steps of the batched launches take two-plane f16 operands on the matrix cores
     assert d['dtype'].startswith('f32') and 'f16x2' in d['dtype']
     assert abs(d['ms_per_step'] * d['value'] - 1e3) < 1.0                  # one frame per step
@@ -50,6 +52,39 @@ def test_the_drivers_bench_command_prints_one_complete_line():
     assert 'configs[2]' in d['train']['workload'] and 0.1 < d['train']['ms_per_iteration'] < 5.0
     c = d['cpu_baseline']
     assert c['kind'] == 'port' and c['cores'] >= 1 and c['value'] > 0 and c['sample']
+
+
+#: what a plain run leaves to --full: keys of the side measurements in the line
+SIDE_KEYS = ('roofline', 'cpu_baseline', 'single_lane', 'latency_ms_per_frame', 'pipeline_latency_ms', 'dropin_forward',
+             'with_input_delivery', 'end_to_end', 'with_handoff', 'frames_per_launch_sweep', 'f32_path', 'vovnet', 'train')
+HEADLINE = ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step')
+
+
+def test_a_plain_run_prints_the_headline_alone_within_30_s_outside_its_steps():
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: set-up, warm-up, the N timed steps, the line -- none of
+    the side measurements, and at most 30 s outside the steps: the whole run in a fresh process, from start to exit,
+    less (N + W) x ms_per_step."""
+    import time
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup',
+                        str(warmup)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, p.stdout[-1000:]
+    d = json.loads(lines[0])
+    for k in HEADLINE:
+        assert k in d, k
+    assert d['full'] is False and not [k for k in SIDE_KEYS if d.get(k) is not None]
+    assert d['steps'] == steps and d['warmup'] == warmup and d['timing']['timed_steps'] == steps
+    assert d['unit'] == 'frames/s' and d['value'] > 1000 and d['higher_is_better'] is True
+    assert d['dtype'].startswith('f32') and 'f16x2' in d['dtype']
+    assert abs(d['ms_per_step'] * d['value'] - 1e3) < 1.0                  # one frame per step
+    outside = wall - (steps + warmup) * d['ms_per_step'] * 1e-3
+    print('plain run: %.1f s in all, %.1f s outside its steps' % (wall, outside))
+    assert outside <= 30.0, outside
 
 
 def test_dump_outputs_of_the_last_timed_step_are_the_same_every_run(tmp_path):

@@ -15,14 +15,14 @@ if [ -z "${SKIP_TESTS:-}" ]; then
 python -m pytest tests -x -q -m gpu > "$OUT/pytest_gpu.log" 2>&1
 echo "pytest rc=$?" >> "$OUT/pytest_gpu.log"
 fi
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench.err"      # the driver's command, everything in one line
-python bench.py --shapes vovnet --no-configs --no-batched --no-handoff > "$OUT/bench_vovnet.json" 2>> "$OUT/bench.err"   # configs[4] shapes as the headline
-python bench.py --matrix-path f32 --no-configs --no-batched --no-handoff --no-cpu-baseline > "$OUT/bench_f32.json" 2>> "$OUT/bench.err"   # the exact-f32 chains
-python bench.py > "$OUT/bench.json" 2>> "$OUT/bench.err"                                   # default: 9 frames per launch x 3 lanes, 200 steps
-python bench.py --pair 1 --no-cpu-baseline --no-batched --no-configs > "$OUT/bench_pair1.json" 2>> "$OUT/bench.err"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench.err"      # the driver's command, everything in one line
+python bench.py --full --shapes vovnet --no-configs --no-batched --no-handoff > "$OUT/bench_vovnet.json" 2>> "$OUT/bench.err"   # configs[4] shapes as the headline
+python bench.py --full --matrix-path f32 --no-configs --no-batched --no-handoff --no-cpu-baseline > "$OUT/bench_f32.json" 2>> "$OUT/bench.err"   # the exact-f32 chains
+python bench.py --full > "$OUT/bench.json" 2>> "$OUT/bench.err"                                   # default: 9 frames per launch x 3 lanes, 200 steps
+python bench.py --full --pair 1 --no-cpu-baseline --no-batched --no-configs > "$OUT/bench_pair1.json" 2>> "$OUT/bench.err"
 python bench.py --pregather --main-only --no-cpu-baseline > "$OUT/bench_pregather.json" 2>> "$OUT/bench.err"      # round 6 opt-in (cam_pregather)
-python bench.py --train --steps 50 --warmup 5 > "$OUT/bench_train.json" 2>> "$OUT/bench.err"
-python bench.py --train --deterministic --steps 50 --warmup 5 --no-live-pmc > "$OUT/bench_train_det.json" 2>> "$OUT/bench.err"   # order-free backward
+python bench.py --full --train --steps 50 --warmup 5 > "$OUT/bench_train.json" 2>> "$OUT/bench.err"
+python bench.py --full --train --deterministic --steps 50 --warmup 5 --no-live-pmc > "$OUT/bench_train_det.json" 2>> "$OUT/bench.err"   # order-free backward
 cd /tmp
 Q="--main-only --warmup-s 0.05"   # the timed loop only, short warm-up: small traces
 # per-kernel durations, one launch sequence at a time (with frames in flight the kernels of different lanes share the GPU)
@@ -36,7 +36,7 @@ for B in 9 1; do
     rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/pmc_${C}_b$B" -- python3 "$REPO/bench.py" --batch $B --steps 5 --warmup 2 $Q --no-graph > "$OUT/pmc_${C}_b$B.log" 2>&1
   done
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_train" -- python3 "$REPO/bench.py" --train --steps 20 --warmup 3 > "$OUT/prof_train.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_train" -- python3 "$REPO/bench.py" --full --train --steps 20 --warmup 3 > "$OUT/prof_train.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_pregather" -- python3 "$REPO/bench.py" --pregather --lanes 1 --pair 9 --steps 54 --warmup 9 $Q > "$OUT/prof_pregather.log" 2>&1
 cd "$REPO"
 python tools/dropin_breakdown.py > "$OUT/dropin_breakdown.txt" 2>&1

@@ -181,7 +181,7 @@ class FusionTrainer:
         # deterministic=True (round 5): the fused backward accumulates order-free
         # (tc_radar_train_bwd_fused_det: integer atomics on a fixed-point shadow of the gradient bucket and of dK | dV) --
         # two runs from the same state give bit-identical gradients and parameters, on any schedule.  The default keeps
-        # the float atomics (what torch's own backward does in the reference): bench.py --train reports both.
+        # the float atomics (what torch's own backward does in the reference): bench.py --full --train reports both.
         self.deterministic = bool(deterministic)
         if self.deterministic and not chain_backward:
             raise ValueError('FusionTrainer(deterministic=True) needs the fused backward (chain_backward=True): the '
@@ -514,7 +514,7 @@ class FusionTrainer:
                               all_box=all_box, d_cls=d_cls, d_box=d_box, tape=tape, seed=drop_seed)
         if update:
             # the gradient exchange starts the moment the backward is enqueued; the optimizer waits on its handle
-            # (tools/train.py:253-260: DDP's buckets overlap the same way).  `exchange_events` (bench.py --train):
+            # (tools/train.py:253-260: DDP's buckets overlap the same way).  `exchange_events` (bench.py --full --train):
             # how long the compute stream stood still between the backward's end and the optimizer's first kernel
             pending = chunk_pending if (self.chain_backward and chunked) else self.bucket.all_reduce_begin()
             ev = None
@@ -556,7 +556,7 @@ class FusionTrainer:
 
     def _optimizer_step(self, lr=None, pending=None, mark=None):
         if mark is not None and isinstance(pending, list):
-            # (bench.py --train: how long the compute stream waits for EACH chunk's all-reduce, in the order it waits)
+            # (bench.py --full --train: how long the compute stream waits for EACH chunk's all-reduce, in the order it waits)
             evs, world = [mark[0]], 1
             for work, wld in pending:
                 if work is not None:
