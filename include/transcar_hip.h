@@ -108,7 +108,14 @@ typedef struct {
    * struct).  Layer 0's self-attention sees nothing but the learned query embedding
    * (XFMR:119-123, config CFG:65-72: q = k = query + query_pos, v = query), so its
    * initial reference points and its attention output do not depend on the frame:
-   * they are evaluated once per checkpoint, not once per forward. */
+   * they are evaluated once per checkpoint, not once per forward.
+   * For heads with num_points 1 and 4 levels the same holds for layer 0's out_proj, norm0 and
+   * position-encoder output (they read the two tensors below and the query embedding only):
+   * the packed buffer holds them behind l0_attn_out, once per row-chain kernel variant (tile
+   * height, matrix path) and made by that variant's own kernels, and an eval-mode
+   * tc_head_forward starts layer 0's chain from them.  tc_head_packed_bytes counts them;
+   * tc_head_repack_trainable leaves them alone (the decoder is frozen).  tc_decoder_layer_tail_fwd
+   * always runs the full chain. */
   const float* l0_init_reference;   /* [Q,3]  sigmoid(reference_points(query_pos))      */
   const float* l0_attn_out;         /* [Q,C]  softmax(q k^T / sqrt(d)) v of layer 0     */
   size_t packed16_delta;            /* packed view only, as in tc_decoder_layer         */

@@ -219,6 +219,47 @@ constexpr StepDesc PROG_DECODER_T[] = {
     {K_NARROW, 15, -1, 256, N_CODE, B_U3, B_U1, B_L, B_NONE, 0, F_PRESYNC, G_NONE, G_NONE, 1},    // reg.4 (partial sums: U1)
     {K_REFUPD, 0, 0, 0, 0, B_L, B_NONE, B_NONE, B_NONE, 0, 0, G_NONE, G_NONE, 0},
     {K_END, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
+// Layer 0 of an eval-mode forward: out_proj, norm0 and pe.3 see nothing but constants of the checkpoint (the folded
+// attention output, the query embedding, the initial reference points), so tc_head_pack_weights runs them once per
+// kernel variant on the Q query rows (PROG_DECODER_L0GEN_T below: the SAME kernels, a truncated record sequence with
+// global destinations) and the layer's launch loads three constants instead: norm0's two outputs and pe.3's.  They are
+// stored as the fp32 values the epilogues hold in front of act_st4 -- K_LOAD's act_st4 makes the same LDS contents of
+// them, planes included.  Record sequences of the PROG_DECODER instantiations, not a program of their own: one code image.
+// What stays: the attention logits and pe.0-2 -- the logit buffer and the inverse-sigmoid reference K_REFUPD reads
+// (S.cen) are not 256-wide units a K_LOAD could fill; pe.0-2's unit is written and never read.
+// Units: pe.3's output waits in U2 from the start, so the sampled features go through U3 into U1 (the full
+// table: U2) -- the same values in other units.
+constexpr StepDesc PROG_DECODER_L0_T[] = {
+    {K_LOAD, 0, 0, 0, 0, B_NONE, B_NONE, B_U1, B_NONE, 0, 0, G_ATTN_O, G_NONE, 0},        // norm0(..) + pos
+    {K_LOAD, 0, 0, 0, 0, B_NONE, B_NONE, B_U2, B_NONE, 0, 0, G_KV1, G_NONE, 0},           // pe.3(..)
+    {K_LOAD, 0, 0, 0, 0, B_NONE, B_NONE, B_X, B_NONE, 0, 0, G_XIN, G_NONE, 1},            // norm0(..)
+    {K_LINEAR, 3, -1, 256, N_LOGITS, B_U1, B_NONE, B_L, B_NONE, 0, 0, G_NONE, G_NONE, 0}, // attention_weights(x + pos)
+    {K_POSENC, 5, 6, 0, 0, B_NONE, B_NONE, B_U3, B_NONE, 0, F_NOT_W0, G_NONE, G_NONE, 1}, // pe.0-2: the reference for K_REFUPD
+    {K_SAMPLE, 0, 0, 0, 0, B_L, B_NONE, B_U3, B_NONE, 0, 0, G_NONE, G_NONE, 1},           // camera sampling
+    {K_LINEAR, 4, -1, 256, 256, B_U3, B_NONE, B_U1, B_X, 0, 0, G_NONE, G_NONE, 1},        // x + output_proj
+    {K_LN, 9, 8, 0, 0, B_U1, B_U2, B_X, B_NONE, 0, 0, G_NONE, G_NONE, 1},                 // norm1(U1 + relu(LN(U2)))
+    {K_LINEAR, 10, -1, 256, 512, B_X, B_NONE, B_A, B_NONE, 1, 0, G_NONE, G_NONE, 1},      // from here on: PROG_DECODER_T
+    {K_LINEAR, 11, -1, 512, 256, B_A, B_NONE, B_U3, B_X, 0, 0, G_NONE, G_NONE, 1},
+    {K_LN, 12, -1, 0, 0, B_U3, B_NONE, B_X, B_U1, 0, F_LN_XP, G_HS, G_NONE, 1},
+    {K_LINEAR, 13, -1, 256, 256, B_X, B_NONE, B_U2, B_NONE, 1, 0, G_NONE, G_NONE, 0},
+    {K_LINEAR, 16, -1, 256, 512, B_U1, B_NONE, B_NONE, B_NONE, 0, F_SCALEQ | F_SKIP_NONEXT, G_QK, G_NONE, 0},
+    {K_LINEAR, 16, -1, 256, 256, B_X, B_NONE, B_NONE, B_NONE, 0, F_WOFF | F_SKIP_NONEXT, G_NONE, G_VT, 1},
+    {K_LINEAR, 14, -1, 256, 256, B_U2, B_NONE, B_U3, B_NONE, 1, 0, G_NONE, G_NONE, 0},
+    {K_NARROW, 15, -1, 256, N_CODE, B_U3, B_U1, B_L, B_NONE, 0, F_PRESYNC, G_NONE, G_NONE, 1},
+    {K_REFUPD, 0, 0, 0, 0, B_L, B_NONE, B_NONE, B_NONE, 0, 0, G_NONE, G_NONE, 0},
+    {K_END, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
+// ... and the sequence that makes the constants: PROG_DECODER_T up to pe.3 without the logits, norm0's result to
+// G_KV0 and pe.3's to G_KV1 ([Q, 256] each; norm0's second output is that result + query_pos: l0_xpos_kernel)
+constexpr StepDesc PROG_DECODER_L0GEN_T[] = {
+    {K_LOAD, 0, 0, 0, 0, B_NONE, B_NONE, B_U1, B_NONE, 0, 0, G_ATTN_O, G_NONE, 0},
+    {K_LOAD, 0, 0, 0, 0, B_NONE, B_NONE, B_X, B_NONE, 0, 0, G_XIN, G_NONE, 1},
+    {K_LINEAR, 1, -1, 256, 256, B_U1, B_NONE, B_U2, B_X, 0, 0, G_NONE, G_NONE, 1},
+    {K_LN, 2, -1, 0, 0, B_U2, B_NONE, B_X, B_U1, 0, F_LN_XP, G_KV0, G_NONE, 1},
+    {K_POSENC, 5, 6, 0, 0, B_NONE, B_NONE, B_U2, B_NONE, 0, F_NOT_W0, G_NONE, G_NONE, 1},
+    {K_LINEAR, 7, -1, 256, 256, B_U2, B_NONE, B_U1, B_NONE, 0, 0, G_KV1, G_NONE, 1},
+    {K_END, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
+static_assert(sizeof(PROG_DECODER_L0_T) <= sizeof(PROG_DECODER_T) && sizeof(PROG_DECODER_L0GEN_T) <= sizeof(PROG_DECODER_T),
+              "the layer-0 sequences fit the decoder program's records");
 // prologue pairs: 0 reference_points 16 layer-0 in_proj
 constexpr StepDesc PROG_PROLOGUE_T[] = {
     {K_LOAD, 0, 0, 0, 0, B_NONE, B_NONE, B_U1, B_NONE, 0, 0, G_POS, G_NONE, 0},
@@ -392,6 +433,7 @@ struct ChainK : ChainDev {
   size_t w16_delta = 0;        // packed16_delta of the packed view: 16-row tiles read their own weight copy
   int npoints = 1;             // decoder: Detr3DCrossAtten.num_points (> 1: the MP instantiations, logits in unit 3)
   int refine = 1;              // decoder: the layer has a reg branch (0: reg.0 / .2 / .4 and K_REFUPD are K_NOP)
+  int l0_seq = 0;              // decoder: the record sequence -- 0 PROG_DECODER_T, 1 PROG_DECODER_L0_T, 2 PROG_DECODER_L0GEN_T
 };
 
 // the decoder's cross-attention takes the generic (MP) kernels with num_points > 1 or fewer than 4 levels; P = 1 at
@@ -2613,7 +2655,11 @@ template <int R, int PROG, int MM = 0>
 void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
   constexpr int NW = nw_of(R);
   const StepDesc* table = prog_table(PROG);
-  constexpr int nsteps = table_steps(PROG);
+  int nsteps = table_steps(PROG);
+  if (PROG == PROG_DECODER && k.l0_seq != 0) {         // layer 0's shorter sequences: same kernels, other records
+    table = k.l0_seq == 1 ? PROG_DECODER_L0_T : PROG_DECODER_L0GEN_T;
+    nsteps = (int)((k.l0_seq == 1 ? sizeof(PROG_DECODER_L0_T) : sizeof(PROG_DECODER_L0GEN_T)) / sizeof(StepDesc)) - 1;
+  }
   const int nrep = (prog_is_radar(PROG) || PROG == PROG_RADAR_BWD) ? k.nlayers : 1;
   const int total = nsteps * nrep;
   memset(out, 0, sizeof(StepAllT<NW>) * rec_cap(PROG));
@@ -2999,7 +3045,54 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   k.matrix_path = a.matrix_path;
   k.drop = a.drop;
   k.range_status = a.range_status;
+  if (a.l0_consts != nullptr) {
+    // layer 0 from its pack-time constants (PROG_DECODER_L0_T): [Q, 256] each, rows % Q
+    TC_REQUIRE(!generic_xattn(k) && k.drop.thr == 0 && a.pre == nullptr,
+               "decoder_chain: layer-0 constants exist for the eval-mode one-point, four-level kernels");
+    const size_t plane = decoder_l0_const_floats(a.Q) / 3;
+    k.l0_seq = 1;
+    k.g[G_XIN] = const_cast<float*>(a.l0_consts); k.g_ld[G_XIN] = 256; k.g_mod[G_XIN] = a.Q;
+    k.g[G_ATTN_O] = const_cast<float*>(a.l0_consts) + plane; k.g_ld[G_ATTN_O] = 256; k.g_mod[G_ATTN_O] = a.Q;
+    k.g[G_KV1] = const_cast<float*>(a.l0_consts) + 2 * plane; k.g_ld[G_KV1] = 256; k.g_mod[G_KV1] = a.Q;
+  }
   return 0;
+}
+
+// ---- layer 0's pack-time constants (PROG_DECODER_L0_T / PROG_DECODER_L0GEN_T) ----
+size_t decoder_l0_const_floats(int Q) { return 3 * (arena_slice((size_t)Q * 256, 4) / 4); }
+
+int decoder_l0_variant(int M, int tile_rows_opt, int matrix_path) {
+  ChainK k;
+  init_k(k);
+  k.M = M; k.tile_rows = tile_rows_opt; k.matrix_path = matrix_path;
+  const int rows = tile_rows(k);
+  return rows == 4 ? 0 : rows == 8 ? 1 : rows == 32 ? 4 : use_f16x2(k) ? 3 : 2;
+}
+
+// norm0's second output, x + query_pos (F_LN_XP: add4 of the fp32 result and the position row)
+__global__ void l0_xpos_kernel(const float* __restrict__ x, const float* __restrict__ qe, float* __restrict__ xp, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) xp[i] = __fadd_rn(x[i], qe[(size_t)(i >> 8) * 512 + (i & 255)]);
+}
+
+int launch_decoder_l0_consts(const DecoderChainArgs& a, int variant, float* consts, hipStream_t s) {
+  static const int rows_of[TC_L0_VARIANTS] = {4, 8, 16, 16, 32};
+  static const int path_of[TC_L0_VARIANTS] = {TC_MATRIX_F32, TC_MATRIX_F32, TC_MATRIX_F32, TC_MATRIX_F16X2, TC_MATRIX_F16X2};
+  TC_REQUIRE(variant >= 0 && variant < TC_L0_VARIANTS && a.M == a.Q, "decoder_l0_consts: variant=%d M=%d Q=%d", variant, a.M, a.Q);
+  ChainK k;
+  int rc = make_decoder_k(a, k);
+  if (rc != 0) return rc;
+  TC_REQUIRE(!generic_xattn(k) && k.drop.thr == 0, "decoder_l0_consts: one-point, four-level eval-mode kernels only");
+  const size_t plane = decoder_l0_const_floats(a.Q) / 3;
+  k.l0_seq = 2; k.has_next = 0;
+  k.tile_rows = rows_of[variant]; k.matrix_path = path_of[variant];
+  k.g[G_KV0] = consts; k.g_ld[G_KV0] = 256;
+  k.g[G_KV1] = consts + 2 * plane; k.g_ld[G_KV1] = 256;
+  rc = launch(k, s, "chain(layer-0 constants)");
+  if (rc != 0) return rc;
+  const int n = a.Q * 256;
+  hipLaunchKernelGGL(l0_xpos_kernel, dim3((n + 255) / 256), dim3(256), 0, s, consts, a.qe, consts + plane, n);
+  return check_launch("l0_xpos");
 }
 
 int launch_decoder_chain(const DecoderChainArgs& a, hipStream_t s) {

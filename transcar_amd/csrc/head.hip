@@ -181,6 +181,21 @@ static size_t head_ws_layout(const tc_head_weights* w, int B, int T, void* base,
   return a.off;
 }
 
+// Layer 0's pack-time constants (chain.hip PROG_DECODER_L0_T) exist for the heads that take the one-point, four-level
+// kernels; they lie behind l0_attn_out in the packed buffer, over the scratch the layer-0 attention was evaluated from:
+// TC_L0_VARIANTS blocks of decoder_l0_const_floats(Q) floats.
+static bool l0_foldable(const tc_head_weights* w) { return head_points(w) == 1 && w->num_levels == TC_MAX_LEVELS; }
+static size_t l0_scratch_bytes(const tc_head_weights* w) {
+  const size_t Q = w->num_query, C = w->embed_dims, qpad = ((Q + 15) / 16) * 16;
+  const size_t scratch = arena_slice(Q * 2 * C, 4) + arena_slice(C * qpad, 4);       // qk, vt of the layer-0 evaluation
+  const size_t consts = l0_foldable(w) ? TC_L0_VARIANTS * decoder_l0_const_floats((int)Q) * sizeof(float) : 0;
+  return consts > scratch ? consts : scratch;
+}
+static const float* l0_consts_of(const tc_head_weights* packed_view, int variant) {
+  const size_t Q = packed_view->num_query, C = packed_view->embed_dims;
+  return packed_view->l0_attn_out + arena_slice(Q * C, 4) / sizeof(float) + (size_t)variant * decoder_l0_const_floats((int)Q);
+}
+
 // ---- fused path: 12 launches per frame (chain.hip) ---------------------------
 static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* feats, int B,
                               const float* lidar2img, float img_h, float img_w,
@@ -234,6 +249,9 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
   // layer 0 up to its attention output is a constant of the checkpoint (pack time) -- in eval
   // mode: with dropout on the attention probabilities it is not
   const bool folded = !ddrop && w->l0_attn_out != nullptr && w->l0_init_reference != nullptr;
+  // ... and so is everything in front of its camera sampling that reads no frame data: out_proj, norm0 and pe.3 come
+  // as constants too, made by the kernel variant this forward selects (bit-identical to running them here)
+  const int l0_variant = folded && l0_foldable(w) ? decoder_l0_variant(rows, opt.chain_tile_rows, opt.matrix_path) : -1;
   if (!folded && opt.phase != 2) {
     PrologueArgs pa;
     pa.qe = w->query_embedding; pa.Q = Q; pa.M = rows; pa.refpts = w->reference_points;
@@ -274,6 +292,7 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
     d.cam.pair_counter = pairs;
     d.code = code; d.M = rows; d.tile_rows = opt.chain_tile_rows; d.matrix_path = opt.matrix_path;
     d.range_status = opt.range_status;
+    if (l0c && l0_variant >= 0) d.l0_consts = l0_consts_of(w, l0_variant);
     // the attention core follows the chains' rule (chain.hip tile_rows / use_f16x2): launches that run 16-row tiles on
     // the f16 matrix cores take the staged two-plane core (self_attn.hip, round 4) -- 4- / 8-row launches (one or two
     // frames: too few workgroups for a form without split keys) and TC_MATRIX_F32 the fp32 core.  A
@@ -756,8 +775,8 @@ size_t tc_head_packed_bytes(const tc_head_weights* w) {
   for (int i = 0; i < n; ++i)
     if (!items[i].narrow && !items[i].absent) total += 3 * arena_slice(packed_floats(items[i].N, items[i].K), 4);   // + the 16x16x4 and the two-plane f16 copies
   // layer-0 constants + the scratch they are computed from (see tc_head_pack_weights)
-  const size_t Q = w->num_query, C = w->embed_dims, qpad = ((Q + 15) / 16) * 16;
-  total += arena_slice(Q * 3, 4) + arena_slice(Q * C, 4) + arena_slice(Q * 2 * C, 4) + arena_slice(C * qpad, 4);
+  const size_t Q = w->num_query, C = w->embed_dims;
+  total += arena_slice(Q * 3, 4) + arena_slice(Q * C, 4) + l0_scratch_bytes(w);
   return total;
 }
 
@@ -815,6 +834,21 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
     TC_TRY(launch_self_attn_core(qk, qk + C, 2 * C, vt, qpad, attn_o, C, 1, Q, H, s));
     packed_view->l0_init_reference = init_ref;
     packed_view->l0_attn_out = attn_o;
+    // Layer 0's chain up to the camera sampling, as far as it reads no frame data (out_proj, norm0, pe.3): once per
+    // kernel variant a forward can select, by that variant's own kernels (chain.hip PROG_DECODER_L0GEN_T).  The
+    // constants overwrite qk / vt, which nothing reads after the attention core above (same stream).
+    if (l0_foldable(w)) {
+      static_assert(sizeof(float) == 4, "slices are counted in floats");
+      DecoderChainArgs d{};
+      d.attn_o = attn_o; d.x_in = w->query_embedding + C; d.x_ld = 2 * C; d.x_mod = Q;
+      d.qe = w->query_embedding; d.Q = Q; d.ref_in = init_ref;
+      d.w = &packed_view->layers[0]; d.qscale = pa.qscale; d.qpad = qpad;
+      d.cam.feats.num_levels = w->num_levels; d.cam.B = 1; d.cam.Q = Q; d.cam.C = C; d.cam.num_cams = w->num_cams;
+      d.cam.num_points = 1; d.cam.ref = init_ref;
+      d.code = w->code_size; d.M = Q;
+      for (int v = 0; v < TC_L0_VARIANTS; ++v)
+        TC_TRY(launch_decoder_l0_consts(d, v, const_cast<float*>(l0_consts_of(packed_view, v)), s));
+    }
   }
   return 0;
 }

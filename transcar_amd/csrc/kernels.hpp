@@ -111,8 +111,20 @@ struct DecoderChainArgs {
   // round 6: the sampling step reads what the pre-gather workgroups of the attention-core launch in front stored
   // (PreGatherArgs::out / mask of the SAME reference points) instead of gathering itself; null: gathers itself
   const float* pre = nullptr; const int* premask = nullptr;
+  // layer 0 of an eval-mode forward: the constants launch_decoder_l0_consts made for the kernel variant this launch
+  // selects (decoder_l0_variant of M, tile_rows, matrix_path); attn_o / x_in are not read then.  null: the full chain
+  const float* l0_consts = nullptr;
 };
 int launch_decoder_chain(const DecoderChainArgs& a, hipStream_t s);
+// Layer 0's frame-independent steps, once per checkpoint and per kernel variant (tile height, matrix path) a forward can
+// select: 0: 4 rows, 1: 8 rows, 2: 16 rows f32, 3: 16 rows f16x2, 4: 32 rows.  A block of constants is
+// decoder_l0_const_floats(Q) floats: norm0's output, that + query_pos, pe.3's output ([Q, 256] each, 256-byte slices).
+constexpr int TC_L0_VARIANTS = 5;
+size_t decoder_l0_const_floats(int Q);
+int decoder_l0_variant(int M, int tile_rows, int matrix_path);
+// `a` as for the full chain of layer 0 on the Q query rows (M = Q; the camera part is not read); runs the variant's own
+// kernels on a truncated step sequence
+int launch_decoder_l0_consts(const DecoderChainArgs& a, int variant, float* consts, hipStream_t s);
 
 struct RadarEncodeArgs {
   const float* tokens; int RI, M;            // [M, RI]
