@@ -5,7 +5,9 @@ oracle/ref_harness.py) on seeded synthetic inputs.
 
 Run only in the authoring container:   python tests/golden/make_golden.py
 (`... make_golden.py configs`: only g9_reference_configs.json, the values of
-the reference's config files)
+the reference's config files).  make_golden_variants.py makes the fixtures of
+the head's other variants (num_points, num_levels, with_box_refine) with the
+same functions.
 
 Inputs and weights are regenerated from seeds by transcar_amd/synth.py and
 are never stored; only small outputs / intermediates are committed
@@ -37,16 +39,35 @@ def save(name, **arrs):
     print('wrote %s (%.1f KB)' % (name, os.path.getsize(path) / 1024))
 
 
-def ref_head():
-    head = RH.build_reference_head(configs.head_cfg())
-    sd = synth.make_state_dict(seed=3)
+def ref_head(num_levels=None, num_points=None, with_box_refine=True, train=False):
+    """The REFERENCE's head of one variant (None: the configs' 4 levels / 1 point) in eval mode, with
+    synth.make_state_dict's seeded weights: the same key set and shapes; attention_weights not the reference's zero
+    init (XFMR:297-300: every sigmoid 0.5 would hide a wrong (camera, point, level) order of the logits); without box
+    refinement ONE cls and ONE reg branch under every index (HEAD:223-231)."""
+    kw = {k: v for k, v in dict(num_levels=num_levels, num_points=num_points).items() if v is not None}
+    if not with_box_refine:
+        kw['with_box_refine'] = False
+    head = RH.build_reference_head(configs.head_cfg(**kw), configs.train_cfg_pts if train else None)
+    assert bool(head.with_box_refine) == with_box_refine
+    assert (head.reg_branches[0] is head.reg_branches[5]) == (head.cls_branches[0] is head.cls_branches[5]) \
+        == (not with_box_refine)
+    assert head.transformer.decoder.layers[0].attentions[1].num_levels == (num_levels or 4)
+    sd = synth.make_state_dict(seed=3, **kw)
     ref_keys = {k: tuple(v.shape) for k, v in head.state_dict().items()}
     my_keys = {k: tuple(v.shape) for k, v in sd.items()}
     assert ref_keys == my_keys, (set(ref_keys) ^ set(my_keys))
+    for i in range(6):
+        w = sd['transformer.decoder.layers.%d.attentions.1.attention_weights.weight' % i]
+        assert w.shape[0] == 6 * (num_points or 1) * (num_levels or 4) and np.abs(w).min() > 0 and w.std() > 0.01
     head.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()},
                          strict=True)
     head.eval()
-    return head, sd
+    return head
+
+
+def level_shapes_of(shapes):
+    """{'level_shapes': ...} for a fixture made on a list of level shapes (a name: the four levels, not stored)"""
+    return {} if isinstance(shapes, str) else {'level_shapes': np.asarray(shapes, np.int64)}
 
 
 def g1_feature_sampling(ref):
@@ -69,10 +90,10 @@ def g1_feature_sampling(ref):
          sampled=sampled.numpy(), mask=mask.numpy())
 
 
-def g2_cross_atten(head):
-    """Detr3DCrossAtten.forward (XFMR:302-378), C=256, Q=900, tiny maps."""
+def g2_cross_atten(head, shapes='tiny', tag=''):
+    """Detr3DCrossAtten.forward (XFMR:302-378), C=256, Q=900, tiny maps (or the given level shapes)."""
     rng = np.random.RandomState(21)
-    feats = synth.make_feats('tiny', seed=22)
+    feats = synth.make_feats(shapes, seed=22)
     l2i = synth.make_lidar2img()
     metas = synth.make_img_metas(1, l2i)
     Q = 900
@@ -84,7 +105,7 @@ def g2_cross_atten(head):
                [torch.from_numpy(f) for f in feats],
                query_pos=torch.from_numpy(qpos),
                reference_points=torch.from_numpy(refp), img_metas=metas)
-    save('g2_cross_atten.npz', out=out.numpy()[::4])
+    save('g2_cross_atten%s.npz' % tag, out=out.numpy()[::4], **level_shapes_of(shapes))
 
 
 def run_head(head, feats, l2i, frame):
@@ -160,7 +181,7 @@ def g345_head(head, ref, shapes, tag):
          hit_counts0=hit_counts[0], hit_counts1=hit_counts[1],
          hit_counts2=hit_counts[2],
          dec_boxes=bb.numpy(), dec_scores=preds['scores'].numpy(),
-         dec_labels=preds['labels'].numpy())
+         dec_labels=preds['labels'].numpy(), **level_shapes_of(shapes))
     print(tag, 'fill_in', fill_in, 'Lq', [cap['Lq%d' % i] for i in range(3)])
 
 
@@ -181,9 +202,7 @@ def g4_radar_empty(head):
 def g7_loss(ref):
     """Detr3DHead.loss (HEAD:919-1001) incl. HungarianAssigner3D / BBox3DL1Cost of the
     reference on the G5 (tiny) head outputs and a seeded ground truth."""
-    head = RH.build_reference_head(configs.head_cfg(), configs.train_cfg_pts)
-    sd = synth.make_state_dict(seed=3)
-    head.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    head = ref_head(train=True)
     g5 = np.load(os.path.join(HERE, 'g5_head_tiny.npz'))
     outs = {'all_cls_scores': torch.from_numpy(g5['all_cls_scores']),
             'all_bbox_preds': torch.from_numpy(g5['all_bbox_preds']),
@@ -209,33 +228,13 @@ def freeze_like_train_py(head):
             p.requires_grad = False
 
 
-def g8_train_grads(ref, tag='tiny'):
-    """One training iteration's gradients from the reference: Detr3DHead.forward (tiny
-    shapes -- or, tag 'res101', the ResNet-101 FPN shapes of BASELINE.json configs[2] -- radar near the G5 centres) -> loss() -> sum of the six losses (mmdet
-    `_parse_losses`) -> backward, dropout off (eval mode), frozen groups as in
-    tools/train.py:245-252.  Stored per trainable parameter: [sum, sum|.|, l2] in
-    float64 and the first 16 entries."""
-    head = RH.build_reference_head(configs.head_cfg(), configs.train_cfg_pts)
-    sd = synth.make_state_dict(seed=3)
-    head.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    head.eval()
-    freeze_like_train_py(head)
-    g5 = np.load(os.path.join(HERE, 'g5_head_%s.npz' % tag))
-    feats = synth.make_feats(tag, seed=1, smooth=SMOOTH)
-    l2i = synth.make_lidar2img()
-    frame = synth.make_radar_frame(seed=2, n_per_radar=51, centres=g5['radar_centres'])
-    boxes, labels = synth.make_gt(seed=7, n=24)
-    with torch.enable_grad():
-        outs, cap, _ = run_head(head, feats, l2i, frame)
-        d = np.abs(outs['all_cls_scores'].detach().numpy() - g5['all_cls_scores']).max()
-        assert d < 5e-4, d                      # same frame as fixture G5
-        losses = head.loss([RH.GtBoxes(torch.from_numpy(boxes))], [torch.from_numpy(labels)], outs)
-        total = sum(v for k, v in losses.items() if 'loss' in k)
-        total.backward()
+def write_g8(name, head, outs, cap, losses, total, **extra):
+    """A gradient fixture, after backward: the forward's outputs and losses and, per trainable parameter, [sum, sum|.|,
+    l2] of its gradient in float64 and the first 16 entries."""
     out = {'total_loss': float(total),
            'all_cls_scores': outs['all_cls_scores'].detach().numpy(),
            'all_bbox_preds': outs['all_bbox_preds'].detach().numpy(),
-           'Lq': np.array([cap['Lq%d' % i] for i in range(3)])}
+           'Lq': np.array([cap['Lq%d' % i] for i in range(3)]), **extra}
     out.update({'loss__' + k.replace('.', '_'): float(v) for k, v in losses.items()})
     names = []
     for k, p in head.named_parameters():
@@ -249,9 +248,37 @@ def g8_train_grads(ref, tag='tiny'):
         out[key + '__stats'] = np.array([g.sum(), g.abs().sum(), g.norm()], np.float64)
         out[key + '__head'] = g[:16].float().numpy()
         names.append(k)
-    save('g8_train_grads.npz' if tag == 'tiny' else 'g8_train_grads_%s.npz' % tag, **out)
+    save(name, **out)
     print('g8: total loss', float(total), len(names), 'parameters with gradients,',
           sum(p.numel() for p in head.parameters() if p.requires_grad), 'trainable scalars')
+
+
+def g8_train_grads(tag='tiny', suffix='', shapes=None, radar_seed=2, **variant):
+    """One training iteration's gradients from the reference: Detr3DHead.forward (tiny
+    shapes -- or, tag 'res101', the ResNet-101 FPN shapes of BASELINE.json configs[2] -- radar near the G5 centres) -> loss() -> sum of the six losses (mmdet
+    `_parse_losses`) -> backward, dropout off (eval mode), frozen groups as in
+    tools/train.py:245-252.  Stored as write_g8 says.
+
+    suffix, variant: of another head variant (fixture g5_head_<tag><suffix>.npz holds the centres); shapes: its level
+    shapes where they are not the four of `tag`; radar_seed: another radar frame than G5's, stored with the shapes."""
+    head = ref_head(train=True, **variant)
+    freeze_like_train_py(head)
+    g5 = np.load(os.path.join(HERE, 'g5_head_%s%s.npz' % (tag, suffix)))
+    feats = synth.make_feats(shapes or tag, seed=1, smooth=SMOOTH)
+    l2i = synth.make_lidar2img()
+    frame = synth.make_radar_frame(seed=radar_seed, n_per_radar=51, centres=g5['radar_centres'])
+    boxes, labels = synth.make_gt(seed=7, n=24)
+    with torch.enable_grad():
+        outs, cap, _ = run_head(head, feats, l2i, frame)
+        if radar_seed == 2:
+            d = np.abs(outs['all_cls_scores'].detach().numpy() - g5['all_cls_scores']).max()
+            assert d < 5e-4, d                      # same frame as fixture G5
+        losses = head.loss([RH.GtBoxes(torch.from_numpy(boxes))], [torch.from_numpy(labels)], outs)
+        total = sum(v for k, v in losses.items() if 'loss' in k)
+        total.backward()
+    extra = dict(level_shapes_of(shapes), radar_seed=radar_seed) if shapes else {}
+    write_g8('g8_train_grads%s%s.npz' % ('' if tag == 'tiny' else '_' + tag, suffix), head, outs, cap, losses, total,
+             **extra)
 
 
 #: the reference's three detection config files (projects/configs/detr3d/)
@@ -283,12 +310,12 @@ def main():
         g9_reference_configs()
         return
     ref = RH.load_reference()
-    head, _ = ref_head()
+    head = ref_head()
     if len(sys.argv) > 1 and sys.argv[1] == 'vovnet':
         # round 3: BASELINE.json configs[4] (VoVNet FPN shapes 232x400 ... 29x50): the head's inference
         # fixture and one training iteration's gradients, from the reference itself
         g345_head(head, ref, 'vovnet', 'vovnet')
-        g8_train_grads(ref, 'vovnet')
+        g8_train_grads('vovnet')
         return
     g1_feature_sampling(ref)
     g2_cross_atten(head)
@@ -296,8 +323,8 @@ def main():
     g345_head(head, ref, 'res101', 'res101')
     g4_radar_empty(head)
     g7_loss(ref)
-    g8_train_grads(ref)
-    g8_train_grads(ref, 'res101')
+    g8_train_grads()
+    g8_train_grads('res101')
 
 
 if __name__ == '__main__':

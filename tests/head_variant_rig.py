@@ -1,0 +1,359 @@
+"""The rig the GPU tests of the head's variants share (num_points > 1, num_levels < 4, with_box_refine=False and
+decoder layer 0's fold): heads and frames, the CPU oracle's forward, and the checks every variant repeats -- against
+the oracle, against the reference's fixtures, the train-mode decoder with read-back dropout masks, a training iteration
+against the reference's gradients, the plugin graphs, FramePipeline and a frame inside a nine-frame launch.
+
+A plain helper module (as adverse_rig.py): the test modules import the fixtures `T` and `no_grad` by name.  The
+checkers take torch tensors on any device; tests/test_head_variant_rig.py pins their caps on the CPU."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import transcar_oracle as O
+from transcar_amd import configs, synth
+
+PCR = configs.point_cloud_range
+HW = configs.IMG_SHAPE[:2]
+SMOOTH = (4, 6)
+TINY = configs.LEVEL_SHAPES['tiny']
+E2E_TOL = 1e-3          # test_gpu_parity.test_head_end_to_end
+# the decoder states on the f16x2 matrix path: at P = 5 the sampling weights are sums of five sigmoids, so the sampled
+# values (and the two-plane path's absolute error, which scales with them) are up to five times those of P = 1.  Measured
+# on the 32-row tiles: 3 of 1 382 400 states beyond 1e-3, the largest 1.20e-3.  The f32 paths keep E2E_TOL, and box
+# codes, logits and reference points keep test_head_end_to_end's tolerances on every path.
+HS_TOL_F16X2 = 2e-3
+REFS_TOL = 5e-5         # inter_references against the oracle and the reference
+MAX_GATE_ROWS = 6       # rows whose radar gate decisions (hit counts) may differ: the gate is discontinuous
+CONFIGS = dict(num_levels=4, num_points=1, with_box_refine=True)      # the TransCAR configs' variant
+
+
+@pytest.fixture(autouse=True)
+def no_grad():
+    with torch.no_grad():
+        yield
+
+
+@pytest.fixture(scope='module')
+def T():
+    import transcar_amd
+    assert torch.cuda.is_available(), 'gpu tests need a GPU'
+    transcar_amd.lib()
+    return transcar_amd
+
+
+def dev():
+    return torch.device('cuda:0')
+
+
+def gpu(x):
+    return torch.as_tensor(x).float().contiguous().to(dev())
+
+
+def gold(name):
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', name))
+
+
+# ---- heads and frames ---------------------------------------------------------------------------------------------------
+def variant_kw(**variant):
+    """The arguments of configs.head_cfg / synth.make_state_dict that leave the configs' values."""
+    assert set(variant) <= set(CONFIGS), variant
+    return {k: v for k, v in variant.items() if v != CONFIGS[k]}
+
+
+def make_head(T, *, seed=3, shared_branches=False, **variant):
+    """A fresh eval-mode head of the variant with seeded weights, and those weights as the oracle takes them.
+    shared_branches: the weights of with_box_refine=False (one cls / reg branch under every index) whatever the head."""
+    kw = variant_kw(**variant)
+    sd_np = synth.make_state_dict(seed=seed, **(dict(kw, with_box_refine=False) if shared_branches else kw))
+    h = T.build_head(configs.head_cfg(**kw))
+    h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
+    return h.to(dev()).eval(), O.to_torch_sd(sd_np)
+
+
+_HEADS = {}
+
+
+def shared_head(T, **variant):
+    """make_head(T, **variant), one per variant for the tests that leave it as they found it."""
+    key = tuple(sorted(variant_kw(**variant).items()))
+    if key not in _HEADS:
+        _HEADS[key] = make_head(T, **variant)
+    return _HEADS[key]
+
+
+def train_head(**variant):
+    import transcar_amd as T_
+    kw = variant_kw(**variant)
+    cfg = configs.head_cfg(**kw)
+    cfg['train_cfg'] = configs.train_cfg_pts
+    h = T_.build_head(cfg)
+    h.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(3, **kw).items()})
+    return h.to(dev()).freeze_decoder().set_dropout(0.0)
+
+
+def g8_frame(g5_name, shapes='tiny', radar_seed=2):
+    """The frame of a gradient fixture: G5's maps, the radar near the centres that fixture `g5_name` stores, G7's
+    ground truth."""
+    feats = synth.make_feats(shapes, seed=1, smooth=SMOOTH)
+    l2i = synth.make_lidar2img()
+    frame = synth.make_radar_frame(seed=radar_seed, n_per_radar=51, centres=gold(g5_name)['radar_centres'])
+    boxes, labels = synth.make_gt(seed=7, n=24)
+    metas = synth.make_img_metas(1, l2i)
+    metas[0]['radar'] = frame
+    gt = torch.from_numpy(boxes).clone()
+    gt[:, 2] += gt[:, 5] * 0.5
+    return [gpu(f) for f in feats], metas, gt.to(dev()), torch.from_numpy(labels).to(dev()), feats, l2i
+
+
+_ORACLE = {}
+
+
+def oracle_head(sd, feats_np, frame, with_box_refine=True, key=None):
+    """The oracle's head_forward with its debug dict.  key: keep the result under it (one forward for the parametrised
+    cases that share weights, maps and radar frame)."""
+    if key is None or key not in _ORACLE:
+        l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
+        res = O.head_forward(sd, [torch.from_numpy(f) for f in feats_np], l2i, HW, O.build_radar_features(frame), PCR,
+                             return_debug=True, with_box_refine=with_box_refine)
+        if key is None:
+            return res
+        _ORACLE[key] = res
+    return _ORACLE[key]
+
+
+def run_head(head, feats_np, frame, **options):
+    """One frame through the module entry with aux outputs, under head_options(**options) (none: the automatic ones)."""
+    from transcar_amd.detr3d_head import head_options
+    head.forward_options = head_options(**options) if options else None
+    try:
+        outs = head([gpu(f) for f in feats_np], synth.make_img_metas(1, synth.make_lidar2img(), radar=frame), aux=True)
+        torch.cuda.synchronize()
+    finally:
+        head.forward_options = None
+    return outs
+
+
+# ---- the checkers (torch tensors on any device) ----------------------------------------------------------------------------
+def _np(t):
+    return t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def refs_are_initial(aux):
+    """without box refinement: inter_references[l] is init_reference bit for bit, every l"""
+    init, refs = aux['init_reference'], aux['inter_references']
+    for l in range(refs.shape[0]):
+        assert torch.equal(refs[l], init), l
+
+
+def assert_all_but_two_queries(got, want, tol, what):
+    """[layers, Q, D]: every query within tol but at most two, and those within 1e-2.  At res101 shapes and P = 5, two
+    of the 900 queries (220, 324) carry a reference point the free-running decoder puts next to a sampling
+    discontinuity: there ANY two fp32 evaluation orders part by up to 3e-3 -- measured, the oracle on two different
+    CPUs against the same reference fixture: 5e-4 on one, 2.4e-3 on query 324 on the other; the library: query 220
+    3.0e-3 on both matrix paths, every other query within 1e-3."""
+    d = np.abs(got - want).max(axis=(0, 2))
+    bad = np.where(d > tol)[0]
+    assert len(bad) <= 2 and (len(bad) == 0 or d.max() < 1e-2), (what, bad.tolist(), d[bad].tolist())
+
+
+def check_against_oracle(outs, want, dbg, hs_tol=E2E_TOL, refs_initial=False):
+    """A free-running head's outputs against oracle_head's: reference points, decoder states, and scores and boxes on
+    the rows whose radar gate decisions agree."""
+    aux = outs['aux']
+    if refs_initial:
+        refs_are_initial(aux)
+    np.testing.assert_allclose(_np(aux['inter_references']), _np(dbg['inter_refs']), atol=REFS_TOL, rtol=0)
+    np.testing.assert_allclose(_np(aux['inter_states']), _np(dbg['hs']), atol=hs_tol, rtol=0)
+    want_hits = np.stack([_np(h) for h in dbg['hit_counts']])
+    agree = np.all(_np(aux['radar_hit_counts'][:, 0]) == want_hits, axis=0)
+    assert int((~agree).sum()) <= MAX_GATE_ROWS
+    for k in ('all_cls_scores', 'all_bbox_preds'):
+        np.testing.assert_allclose(_np(outs[k][:, 0])[:, agree], _np(want[k][:, 0])[:, agree], atol=E2E_TOL, rtol=0)
+
+
+def check_against_fixture(outs, want, dbg, fixture, tie_rule=False, refs_initial=False):
+    """A free-running head's outputs against the reference's (a G5 fixture) on the rows whose radar gate decisions
+    agree with the oracle's AND the reference's, and against the oracle on the same rows.
+
+    tie_rule: a radar gate decision of the rig can sit within 1e-4 m of its radius (G5-L2: query 880, 2.1e-4 m in fusion
+    layer 3): where the oracle on this machine and the reference took it differently, the stored hit counts cannot say
+    which row flipped (the fixture keeps the selected rows only, and their count then differs).  Such a query departs
+    from the reference in the ORACLE too (by more than 1e-2; at most two may); it is left out of the comparison with the
+    reference only -- the library is held to the oracle on every agreeing row."""
+    aux = outs['aux']
+    if refs_initial:
+        refs_are_initial(aux)
+    np.testing.assert_allclose(_np(aux['inter_references']), fixture['inter_refs'], atol=REFS_TOL, rtol=0)
+    # the fixture stores the hit counts of the selected rows; rebuilt to [3, Q] as test_head_end_to_end does
+    want_hits = np.stack([_np(h) for h in dbg['hit_counts']])
+    gold_hits = np.zeros_like(want_hits)
+    for i in range(3):
+        rows = np.where(want_hits[i] > 0)[0]
+        gold_hits[i] = want_hits[i]
+        if len(rows) == int(fixture['Lq'][i]):
+            gold_hits[i] = 0
+            gold_hits[i, rows] = fixture['hit_counts%d' % i]
+    hits = _np(aux['radar_hit_counts'][:, 0])
+    agree = np.all(hits == want_hits, axis=0) & np.all(hits == gold_hits, axis=0)
+    assert int((~agree).sum()) <= MAX_GATE_ROWS
+    tie = np.zeros(agree.shape, bool)
+    if tie_rule:
+        for k in ('all_cls_scores', 'all_bbox_preds'):
+            tie |= np.abs(_np(want[k][:, 0]) - fixture[k][:, 0]).max(axis=(0, 2)) > 1e-2
+        assert int(tie.sum()) <= 2, np.where(tie)[0].tolist()
+    for k in ('all_cls_scores', 'all_bbox_preds'):
+        got = _np(outs[k][:, 0])
+        assert_all_but_two_queries(got[:, agree & ~tie], fixture[k][:, 0][:, agree & ~tie], E2E_TOL, k + ' vs reference')
+        # and the oracle, which tests/test_*_golden.py hold to the same fixture
+        assert_all_but_two_queries(got[:, agree], _np(want[k][:, 0])[:, agree], E2E_TOL, k + ' vs oracle')
+
+
+# ---- dropout masks as the kernels draw them ------------------------------------------------------------------------------
+def dropout_mask(p, seed, site, n):
+    """The n multipliers (0 | 1/(1-p)) the kernels draw at a dropout site, read back through tc_dropout_mask (CPU)."""
+    from transcar_amd import _lib as L
+    out = torch.empty(n, dtype=torch.float32, device=dev())
+    L.check(L.lib().tc_dropout_mask(p, seed, site, n, out.data_ptr(),
+                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'tc_dropout_mask')
+    return out.cpu()
+
+
+def decoder_dropout_masks(p, seed, Q, Cd=256, Fd=512, H=8, layers=6):
+    """The oracle's ``dec_drop`` for one frame: site = 16 + 8 * layer + {0 probs [B*heads,Q,Q], 1 self-attn out,
+    2 cross-attn out, 3 FFN hidden, 4 FFN out}."""
+    def m(site, *shape):
+        return dropout_mask(p, seed, site, int(np.prod(shape))).view(*shape)
+    return [dict(probs=m(s0, H, Q, Q), sa=m(s0 + 1, Q, 1, Cd), ca=m(s0 + 2, Q, 1, Cd), ffn_h=m(s0 + 3, Q, 1, Fd),
+                 ffn_o=m(s0 + 4, Q, 1, Cd)) for s0 in range(16, 16 + 8 * layers, 8)]
+
+
+# ---- the checks every variant repeats ------------------------------------------------------------------------------------
+def check_train_mode_decoder(frame, rows, matrix, refs_atol=2e-4, **variant):
+    """The frozen decoder's train-mode forward (dropout on, layer 0 not folded: the DROP instantiations of the chain
+    kernels) against the oracle's decoder with the SAME masks, as
+    test_gpu_training.test_decoder_train_mode_dropout_matches_reference_formula does for the configs' head.
+    frame: g8_frame(...); without box refinement the references are also the initial one, bit for bit."""
+    from transcar_amd import ops
+    from transcar_amd.detr3d_head import head_options
+    p, seed = 0.1, 0x5EED1234ABCD
+    h = train_head(**variant)
+    h.set_decoder_dropout(p)
+    feats, metas, _, _, feats_np, l2i_np = frame
+    nhwc = ops.to_nhwc_levels(feats)
+    l2i = ops.lidar2img_tensor(metas, dev())
+    img_hw = metas[0]['img_shape'][0][:2]
+    tokens, pad_mult = h.radar_tokens(metas, dev())
+    h.train()
+    opts = dict(decoder_dropout_p=p, dropout_seed=seed, tile_rows=rows, matrix_path=matrix)
+    a = h.forward_nhwc(nhwc, l2i, img_hw, tokens, pad_mult, aux=True, _allow_train=True, options=head_options(**opts))
+    b = h.forward_nhwc(nhwc, l2i, img_hw, tokens, pad_mult, aux=True, _allow_train=True, options=head_options(**opts))
+    hs = a['aux']['inter_states']
+    assert torch.equal(hs, b['aux']['inter_states'])                 # same seed, same masks
+    refine = variant.get('with_box_refine', True)
+    if not refine:
+        refs_are_initial(a['aux'])
+    want_hs, init_ref, want_refs, _ = O.transformer(
+        O.to_torch_sd(synth.make_state_dict(3, **variant_kw(**variant))), [torch.from_numpy(f) for f in feats_np], PCR,
+        torch.from_numpy(l2i_np).float()[None], HW, dec_drop=decoder_dropout_masks(p, seed, h.num_query),
+        with_box_refine=refine)
+    np.testing.assert_allclose(a['aux']['init_reference'].cpu().numpy(), init_ref.numpy(), atol=1e-6, rtol=0)
+    np.testing.assert_allclose(a['aux']['inter_references'].cpu().numpy(), want_refs.numpy(), atol=refs_atol, rtol=0)
+    np.testing.assert_allclose(hs.cpu().numpy()[:, 0], want_hs[:, :, 0].numpy(), atol=2e-3, rtol=0)
+
+
+def check_training_iteration(frame, g8_name, what, **variant):
+    """One FusionTrainer iteration (frozen decoder -> radar stack -> loss -> backward) against the reference's losses
+    and gradients (a G8 fixture), 2e-3 as test_training's oracle-vs-reference check.  frame: g8_frame(...)."""
+    from test_training import check_grads_against_g8, trainable
+    from transcar_amd import ops
+    from transcar_amd.trainer import FusionTrainer
+    g8 = gold(g8_name)
+    h = train_head(**variant)
+    feats, metas, gt, labels, _, _ = frame
+    nhwc = [ops.to_nhwc(f) for f in feats]
+    l2i = ops.lidar2img_tensor(metas, dev())
+    tokens, pad_mult = h.radar_tokens(metas, dev())
+    tr = FusionTrainer(h, dropout=0.0)
+    with torch.enable_grad():
+        losses = tr.step_fused_nhwc(nhwc, l2i, metas[0]['img_shape'][0][:2], tokens, pad_mult, [gt], [labels],
+                                    update=False)
+    for k, v in losses.items():
+        ref = float(g8['loss__' + k.replace('.', '_')])
+        assert abs(float(v) - ref) < 2e-3 * max(1.0, abs(ref)), (k, float(v), ref)
+    used = {n for n, _ in h.trainable_parameters()}
+    grads = {k: (p.grad.clone() if (p.grad is not None and k in used) else None)
+             for k, p in h.named_parameters() if trainable(k)}
+    assert check_grads_against_g8(grads, g8, 2e-3, what) == 98
+
+
+def check_plugin_graph_replay(hg, he, shapes='tiny'):
+    """The plugin entry's captured graphs (plugin_graph.py) of head `hg` replay, bit for bit, what the eager entry of
+    its twin `he` computes.  Two fresh heads: `he` loses its graphs."""
+    if isinstance(shapes, str):
+        shapes = configs.LEVEL_SHAPES[shapes]
+    he.plugin_graphs = False
+    g = torch.Generator(device=dev())
+    g.manual_seed(5)
+    feats = [torch.randn((1, 6, 256, h_, w_), device=dev(), generator=g) for (h_, w_) in shapes]
+    hg(feats, synth.make_img_metas(1, radar=synth.make_radar_frame(seed=39, n_per_radar=30)))
+    base = dict(hg._plugin_graphs.stats)
+    for it in range(3):
+        for f in feats:
+            f.mul_(0.9).add_(0.01 * (it + 1))
+        metas = synth.make_img_metas(1, radar=synth.make_radar_frame(seed=40 + it, n_per_radar=30))
+        og, oe = hg(feats, metas), he(feats, metas)
+        torch.cuda.synchronize()
+        for k in ('all_cls_scores', 'all_bbox_preds'):
+            assert torch.equal(og[k], oe[k]), (it, k)
+    st = {k: v - base[k] for k, v in hg._plugin_graphs.stats.items()}
+    assert st['replays'] >= 1, st
+
+
+def check_frame_pipeline(head, nlanes=2, shapes='tiny', pregather_off=False):
+    """A FramePipeline of `nlanes` lanes (bench.make_inputs' lane layout) gives bit for bit what forward_nhwc gives.
+    pregather_off: the pipeline must have left the camera pre-gather off."""
+    import bench
+    bench._imports()
+    from transcar_amd.pipeline import FramePipeline
+    lanes = [bench.make_inputs(head, dev(), shapes, 1, seed=11 + i) for i in range(nlanes)]
+    want = []
+    for inp in lanes:
+        outs, dec = bench.one_step(head, inp)
+        want.append([outs['all_cls_scores'].clone(), outs['all_bbox_preds'].clone()] + [d.clone() for d in dec])
+    torch.cuda.synchronize()
+    pipe = FramePipeline(head, lanes)
+    if pregather_off:
+        assert pipe.options.cam_pregather == 0
+    for _ in range(2):
+        for _ in range(nlanes):
+            pipe.launch()
+    pipe.synchronize()
+    for i in range(nlanes):
+        outs, dec = pipe.outputs[i]
+        for a_, b_ in zip([outs['all_cls_scores'], outs['all_bbox_preds']] + list(dec), want[i]):
+            assert torch.equal(a_, b_)
+
+
+def check_frame_of_nine(head, shapes='tiny', refs_initial=False):
+    """One frame of a nine-frame launch (32-row tiles) is bit-identical to that frame launched alone with the same
+    tile height and matrix path.  refs_initial (no box refinement): so are its reference points, the initial ones."""
+    from transcar_amd.detr3d_head import head_options
+    l2i = synth.make_lidar2img()
+    feats = [synth.make_feats(shapes, seed=40 + i, smooth=SMOOTH) for i in range(9)]
+    frames = [synth.make_radar_frame(seed=60 + i, n_per_radar=45) for i in range(9)]
+    kw = dict(aux=True) if refs_initial else {}
+    head.forward_options = head_options(tile_rows=32, matrix_path='f16x2')
+    try:
+        many = head([gpu(np.concatenate([f[l] for f in feats], 0)) for l in range(len(feats[0]))],
+                    synth.make_img_metas(9, l2i, radar=frames), **kw)
+        one = head([gpu(f) for f in feats[4]], synth.make_img_metas(1, l2i, radar=frames[4]), **kw)
+    finally:
+        head.forward_options = None
+    for k in ('all_cls_scores', 'all_bbox_preds'):
+        assert torch.equal(many[k][:, 4], one[k][:, 0]), k
+    if refs_initial:
+        assert torch.equal(many['aux']['inter_references'][:, 4], one['aux']['inter_references'][:, 0])
+        refs_are_initial(many['aux'])

@@ -1,5 +1,5 @@
-"""The CPU oracle without box refinement (box_refine_oracle.py, patched over the oracle's transformer) against the
-fixtures the REFERENCE's own Detr3DHead(with_box_refine=False) produced (tests/golden/make_golden_norefine.py).  CPU;
+"""The CPU oracle without box refinement (with_box_refine=False) against the
+fixtures the REFERENCE's own Detr3DHead(with_box_refine=False) produced (tests/golden/make_golden_variants.py norefine).  CPU;
 the fixtures are committed, so the reference itself is not needed."""
 import os
 
@@ -7,8 +7,6 @@ import numpy as np
 import pytest
 import torch
 
-import box_refine_oracle as BRO
-import num_points_oracle as NPO
 from oracle import transcar_oracle as O
 from transcar_amd import configs, synth
 
@@ -24,13 +22,6 @@ FIXTURES = [('tiny', 1, 'g5_head_tiny_norefine.npz'), ('res101', 1, 'g5_head_res
 def _no_grad():
     with torch.no_grad():
         yield
-
-
-@pytest.fixture
-def patched(monkeypatch):
-    monkeypatch.setattr(O, 'transformer', BRO.transformer)
-    monkeypatch.setattr(O, 'cross_atten', NPO.cross_atten)      # (P = 1: the oracle's own arithmetic)
-    return O
 
 
 def _g(golden_dir, name):
@@ -60,14 +51,14 @@ def test_fixture_inter_references_are_the_initial_one(golden_dir, shapes, P, nam
 
 
 @pytest.mark.parametrize('shapes,P,name', FIXTURES)
-def test_g5_head_norefine(golden_dir, patched, shapes, P, name):
+def test_g5_head_norefine(golden_dir, shapes, P, name):
     g = _g(golden_dir, name)
     sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_points=P, with_box_refine=False))
     feats = [torch.from_numpy(f) for f in synth.make_feats(shapes, seed=1, smooth=(4, 6))]
     l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
     f36 = O.build_radar_features(synth.make_radar_frame(seed=2, n_per_radar=51, centres=g['radar_centres']))
     np.testing.assert_allclose(f36.astype(np.float32), g['radar_tokens'], atol=1e-6, rtol=1e-6)
-    outs, dbg = patched.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True)
+    outs, dbg = O.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True, with_box_refine=False)
     np.testing.assert_allclose(dbg['inter_refs'].numpy(), g['inter_refs'], atol=2e-6, rtol=0)
     hs = dbg['hs'].permute(0, 2, 1, 3).numpy()
     np.testing.assert_allclose(hs[:, ::16, 0, :], g['hs_rows'], atol=5e-5, rtol=0)

@@ -7,53 +7,20 @@ import numpy as np
 import pytest
 import torch
 
-from transcar_amd import configs, synth
+from head_variant_rig import (HW, PCR, SMOOTH, TINY, T, dev, gpu, no_grad,  # noqa: F401  (T, no_grad: fixtures)
+                              shared_head)
+from transcar_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-PCR = configs.point_cloud_range
-HW = configs.IMG_SHAPE[:2]
-SMOOTH = (4, 6)
-TINY = configs.LEVEL_SHAPES['tiny']
 MATRIX = {None: 0, 'f32': 1, 'f16x2': 2}          # TC_MATRIX_*
 
 # every (tile height, matrix path) tc_head_forward selects a row-chain kernel variant by, and the automatic choice
 VARIANTS = [(4, 'f32'), (8, 'f32'), (16, 'f32'), (16, 'f16x2'), (32, 'f16x2'), (None, None)]
 
 
-@pytest.fixture(autouse=True)
-def _no_grad():
-    with torch.no_grad():
-        yield
-
-
-def dev():
-    return torch.device('cuda:0')
-
-
-def gpu(x):
-    return torch.as_tensor(x).float().contiguous().to(dev())
-
-
-@pytest.fixture(scope='module')
-def T():
-    import transcar_amd
-    assert torch.cuda.is_available(), 'gpu tests need a GPU'
-    transcar_amd.lib()
-    return transcar_amd
-
-
-_HEADS = {}
-
-
-def make_head(T, **kw):
-    key = tuple(sorted(kw.items()))
-    if key not in _HEADS:
-        sd = synth.make_state_dict(seed=3, **kw)
-        h = T.build_head(configs.head_cfg(**kw))
-        h.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-        _HEADS[key] = h.to(dev()).eval()
-    return _HEADS[key]
+def make_head(T, **variant):
+    return shared_head(T, **variant)[0]
 
 
 def _inputs(head, B, nl=4):

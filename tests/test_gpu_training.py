@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from head_variant_rig import decoder_dropout_masks, dropout_mask
 from oracle import transcar_oracle as O
 from test_training import check_grads_against_g8, g8_inputs, g8_name, trainable
 from transcar_amd import configs, synth
@@ -613,8 +614,6 @@ def test_fused_training_with_dropout_matches_reference_formula(A, golden_dir, pa
     tc_radar_train_fwd / _bwd.  The masks are counter-based, so the check is: with the SAME masks
     (read back through tc_dropout_mask) the reference formula -- the oracle in train mode with given
     masks, torch autograd -- gives the same outputs, losses and gradients."""
-    import ctypes as C
-    from transcar_amd import _lib as L
     from transcar_amd import ops
     from transcar_amd.trainer import FusionTrainer
     p = 0.1
@@ -655,14 +654,11 @@ def test_fused_training_with_dropout_matches_reference_formula(A, golden_dir, pa
         assert float((again['all_cls_scores'] - outs['all_cls_scores']).abs().max()) > 1e-4
 
     # ---- the masks
-    lib = L.lib()
     Q, Cd, Fd, H, TR = h.num_query, 256, 512, 8, 1500
 
     def mask(site, n):
-        out = torch.empty(n, dtype=torch.float32, device=dev())
-        L.check(lib.tc_dropout_mask(p, seed, site, n, out.data_ptr(),
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'tc_dropout_mask')
-        return out.cpu()
+        return dropout_mask(p, seed, site, n)
+
     drop = []
     for r in range(3):
         pm = mask(4 * r + 0, Q * H * TR).view(Q, H, TR).permute(1, 0, 2).contiguous()
@@ -710,8 +706,6 @@ def test_decoder_train_mode_dropout_matches_reference_formula(A, golden_dir):
     masks are counter-based, so the check is: with the SAME masks (read back through
     tc_dropout_mask) the reference formula -- the oracle's decoder with given masks -- gives the
     same decoder states and reference points."""
-    import ctypes as C
-    from transcar_amd import _lib as L
     from transcar_amd import ops
     from transcar_amd.detr3d_head import head_options
     p, seed = 0.1, 0x5EED1234ABCD
@@ -742,21 +736,7 @@ def test_decoder_train_mode_dropout_matches_reference_formula(A, golden_dir):
     assert torch.equal(off['aux']['inter_states'], ev['aux']['inter_states'])   # p = 0: the eval kernels
 
     # ---- the masks, site = 16 + 8 * layer + {0 probs, 1 self-attn out, 2 cross-attn out, 3 FFN hidden, 4 FFN out}
-    lib = L.lib()
-    Q, Cd, Fd, H = h.num_query, 256, 512, 8
-
-    def mask(site, n):
-        out = torch.empty(n, dtype=torch.float32, device=dev())
-        L.check(lib.tc_dropout_mask(p, seed, site, n, out.data_ptr(),
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'tc_dropout_mask')
-        return out.cpu()
-    dec_drop = []
-    for l in range(6):
-        s0 = 16 + 8 * l
-        dec_drop.append(dict(
-            probs=mask(s0 + 0, H * Q * Q).view(H, Q, Q),              # [B*heads, Q, Q], B = 1
-            sa=mask(s0 + 1, Q * Cd).view(Q, 1, Cd), ca=mask(s0 + 2, Q * Cd).view(Q, 1, Cd),
-            ffn_h=mask(s0 + 3, Q * Fd).view(Q, 1, Fd), ffn_o=mask(s0 + 4, Q * Cd).view(Q, 1, Cd)))
+    dec_drop = decoder_dropout_masks(p, seed, h.num_query)
     keep = float((dec_drop[2]['probs'] > 0).float().mean())
     assert abs(keep - (1 - p)) < 1e-3, keep                      # 6.5 M Bernoulli draws
     g_feats, g_l2i, frame, _, _ = g8_inputs(golden_dir)

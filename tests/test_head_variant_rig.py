@@ -1,0 +1,139 @@
+"""The caps of head_variant_rig.py's checkers, on small synthetic tensors (CPU; no oracle forward, no reference): the
+GPU tests of every head variant go through these checkers, so a loosened cap here would loosen all of them."""
+import numpy as np
+import pytest
+import torch
+
+import head_variant_rig as R
+
+LAYERS, Q, C = 6, 16, 256
+
+
+def _case(seed=0):
+    """(outs, want, dbg, fixture) of a head that agrees with the oracle and the reference exactly: 6 decoder layers,
+    batch 1, 16 queries, 3 fusion layers; queries 0 .. 11 hit radar returns in every fusion layer."""
+    g = torch.Generator().manual_seed(seed)
+    refs = torch.rand((LAYERS, 1, Q, 3), generator=g)
+    hs = torch.randn((LAYERS, 1, Q, C), generator=g)
+    hits = torch.zeros((3, Q), dtype=torch.int64)
+    hits[:, :12] = torch.randint(1, 9, (3, 12), generator=g)
+    want = {k: torch.randn((3, 1, Q, 10), generator=g) for k in ('all_cls_scores', 'all_bbox_preds')}
+    outs = {k: v.clone() for k, v in want.items()}
+    outs['aux'] = dict(inter_references=refs.clone(), inter_states=hs.clone(), init_reference=refs[0].clone(),
+                       radar_hit_counts=hits[:, None].clone())
+    dbg = dict(inter_refs=refs, hs=hs, hit_counts=list(hits))
+    fixture = dict(inter_refs=refs.numpy().copy(), Lq=np.array([12, 12, 12]),
+                   **{'hit_counts%d' % i: hits[i, :12].numpy().copy() for i in range(3)},
+                   **{k: v.numpy().copy() for k, v in want.items()})
+    return outs, want, dbg, fixture
+
+
+def test_checkers_accept_an_exact_copy():
+    outs, want, dbg, fixture = _case()
+    R.check_against_oracle(outs, want, dbg)
+    R.check_against_fixture(outs, want, dbg, fixture)
+    R.check_against_fixture(outs, want, dbg, fixture, tie_rule=True)
+    outs['aux']['inter_references'][:] = outs['aux']['init_reference']
+    R.refs_are_initial(outs['aux'])
+
+
+@pytest.mark.parametrize('hs_tol', [R.E2E_TOL, R.HS_TOL_F16X2])
+def test_oracle_check_rejects_one_state_beyond_its_tolerance(hs_tol):
+    assert (R.E2E_TOL, R.HS_TOL_F16X2) == (1e-3, 2e-3)
+    outs, want, dbg, _ = _case()
+    outs['aux']['inter_states'][3, 0, 5, 100] += 2 * hs_tol
+    with pytest.raises(AssertionError):
+        R.check_against_oracle(outs, want, dbg, hs_tol)
+
+
+def test_checks_reject_one_reference_coordinate_off_by_1e_4():
+    outs, want, dbg, fixture = _case()
+    outs['aux']['inter_references'][4, 0, 7, 1] += 1e-4
+    with pytest.raises(AssertionError):
+        R.check_against_oracle(outs, want, dbg)
+    with pytest.raises(AssertionError):
+        R.check_against_fixture(outs, want, dbg, fixture)
+
+
+def _flip_gates(outs, n):
+    outs['aux']['radar_hit_counts'][1, 0, :n] += 1
+
+
+def test_gate_rows_six_may_disagree_and_carry_wrong_scores_seven_may_not():
+    outs, want, dbg, fixture = _case()
+    _flip_gates(outs, 6)
+    outs['all_cls_scores'][2, 0, 3, 4] += 0.5
+    R.check_against_oracle(outs, want, dbg)
+    R.check_against_fixture(outs, want, dbg, fixture)
+    _flip_gates(outs, 7)
+    with pytest.raises(AssertionError):
+        R.check_against_oracle(outs, want, dbg)
+    with pytest.raises(AssertionError):
+        R.check_against_fixture(outs, want, dbg, fixture)
+
+
+@pytest.mark.parametrize('k', ['all_cls_scores', 'all_bbox_preds'])
+def test_oracle_check_rejects_one_score_off_by_2e_3_on_an_agreeing_row(k):
+    outs, want, dbg, _ = _case()
+    _flip_gates(outs, 6)
+    outs[k][0, 0, 9, 2] += 2e-3
+    with pytest.raises(AssertionError):
+        R.check_against_oracle(outs, want, dbg)
+
+
+def _queries_off(n, by):
+    want = np.zeros((3, Q, 10), np.float32)
+    got = want.copy()
+    got[1, :n, 3] += by
+    return got, want
+
+
+def test_all_but_two_queries():
+    R.assert_all_but_two_queries(*_queries_off(2, 5e-3), 1e-3, 'two')
+    with pytest.raises(AssertionError):
+        R.assert_all_but_two_queries(*_queries_off(3, 5e-3), 1e-3, 'three')
+    with pytest.raises(AssertionError):
+        R.assert_all_but_two_queries(*_queries_off(1, 2e-2), 1e-3, 'one, far')
+
+
+def test_fixture_check_holds_the_head_to_both():
+    """three queries off by 5e-3 from the reference and the oracle alike are refused, with or without the tie rule"""
+    outs, want, dbg, fixture = _case()
+    outs['all_bbox_preds'][0, 0, 2:4, 1] += 5e-3
+    R.check_against_fixture(outs, want, dbg, fixture)
+    outs['all_bbox_preds'][0, 0, 4, 1] += 5e-3
+    for tie_rule in (False, True):
+        with pytest.raises(AssertionError):
+            R.check_against_fixture(outs, want, dbg, fixture, tie_rule=tie_rule)
+
+
+def test_tie_rule_leaves_two_queries_to_the_oracle_alone_and_rejects_three():
+    outs, want, dbg, fixture = _case()
+    for n in (1, 2):
+        fixture['all_cls_scores'][2, 0, n, 0] += 0.1         # oracle and reference part: a gate tie
+    with pytest.raises(AssertionError):
+        R.check_against_fixture(outs, want, dbg, fixture)    # (without the rule the head is off the reference)
+    R.check_against_fixture(outs, want, dbg, fixture, tie_rule=True)
+    outs['all_cls_scores'][2, 0, 1, 0] += 2e-2               # ... but a tie query is still held to the oracle
+    with pytest.raises(AssertionError):
+        R.check_against_fixture(outs, want, dbg, fixture, tie_rule=True)
+    outs['all_cls_scores'][2, 0, 1, 0] = want['all_cls_scores'][2, 0, 1, 0]
+    fixture['all_cls_scores'][2, 0, 3, 0] += 0.1
+    with pytest.raises(AssertionError, match=r'\[1, 2, 3\]'):
+        R.check_against_fixture(outs, want, dbg, fixture, tie_rule=True)
+
+
+def test_refs_are_initial_rejects_one_ulp():
+    outs, want, dbg, fixture = _case()
+    aux = outs['aux']
+    aux['inter_references'][:] = aux['init_reference']
+    v = aux['inter_references'][5, 0, 3, 2]
+    aux['inter_references'][5, 0, 3, 2] = torch.nextafter(v, v + 1)
+    with pytest.raises(AssertionError):
+        R.refs_are_initial(aux)
+    dbg['inter_refs'], fixture['inter_refs'] = aux['inter_references'], aux['inter_references'].numpy()
+    R.check_against_oracle(outs, want, dbg)
+    with pytest.raises(AssertionError):
+        R.check_against_oracle(outs, want, dbg, refs_initial=True)
+    with pytest.raises(AssertionError):
+        R.check_against_fixture(outs, want, dbg, fixture, refs_initial=True)

@@ -1,5 +1,5 @@
-"""The levels-aware oracle (num_levels_oracle.py, patched over the oracle's cross_atten) against the fixtures the
-REFERENCE produced with 1, 2 and 3 FPN levels (tests/golden/make_golden_levels.py).  CPU; the fixtures are committed,
+"""The CPU oracle, which reads the level count from the feature maps it is given, against the fixtures the
+REFERENCE produced with 1, 2 and 3 FPN levels (tests/golden/make_golden_variants.py levels).  CPU; the fixtures are committed,
 so the reference itself is not needed."""
 import os
 
@@ -7,8 +7,6 @@ import numpy as np
 import pytest
 import torch
 
-import box_refine_oracle as BRO
-import num_levels_oracle as NLO
 from oracle import transcar_oracle as O
 from transcar_amd import configs, synth
 
@@ -66,7 +64,7 @@ def test_g2_cross_atten_levels(golden_dir, name):
     g = _g(golden_dir, name)
     sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_levels=nl))
     feats, l2i, query, qpos, refp = _g2_inputs(shapes)
-    out = NLO.cross_atten(sd, XA, query, qpos, feats, refp, PCR, l2i, HW)
+    out = O.cross_atten(sd, XA, query, qpos, feats, refp, PCR, l2i, HW)
     np.testing.assert_allclose(out.numpy()[::4], g['out'], atol=1e-5, rtol=0)
     if nl > 1:
         # the (camera, level) order matters: the same logits read as [L, N] give another result
@@ -74,16 +72,13 @@ def test_g2_cross_atten_levels(golden_dir, name):
         for k in ('.weight', '.bias'):
             v = sd[XA + '.attention_weights' + k]
             sw[XA + '.attention_weights' + k] = v.view(6, nl, *v.shape[1:]).transpose(0, 1).reshape(v.shape).contiguous()
-        other = NLO.cross_atten(sw, XA, query, qpos, feats, refp, PCR, l2i, HW)
+        other = O.cross_atten(sw, XA, query, qpos, feats, refp, PCR, l2i, HW)
         assert float(np.abs(other.numpy()[::4] - g['out']).max()) > 1e-3
 
 
 @pytest.mark.parametrize('name', sorted(G5))
-def test_g5_head_levels(golden_dir, monkeypatch, name):
+def test_g5_head_levels(golden_dir, name):
     shapes, nl, P, refine = G5[name]
-    monkeypatch.setattr(O, 'cross_atten', NLO.cross_atten)
-    if not refine:
-        monkeypatch.setattr(O, 'transformer', BRO.transformer)
     g = _g(golden_dir, name)
     sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_levels=nl, num_points=P, with_box_refine=refine))
     feats = [torch.from_numpy(f) for f in synth.make_feats(shapes, seed=1, smooth=(4, 6))]
@@ -91,7 +86,7 @@ def test_g5_head_levels(golden_dir, monkeypatch, name):
     l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
     f36 = O.build_radar_features(synth.make_radar_frame(seed=2, n_per_radar=51, centres=g['radar_centres']))
     np.testing.assert_allclose(f36.astype(np.float32), g['radar_tokens'], atol=1e-6, rtol=1e-6)
-    outs, dbg = O.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True)
+    outs, dbg = O.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True, with_box_refine=refine)
     np.testing.assert_allclose(dbg['inter_refs'].numpy(), g['inter_refs'], atol=2e-5, rtol=0)
     hs = dbg['hs'].permute(0, 2, 1, 3).numpy()
     # (res101 maps: fp32 evaluation orders part by up to 7.3e-5 in a handful of the 87 552 stored elements)
@@ -105,9 +100,8 @@ def test_g5_head_levels(golden_dir, monkeypatch, name):
         assert len(bad) <= 2 and (len(bad) == 0 or d.max() < 1e-2), (k, bad.tolist(), d[bad].tolist())
 
 
-def test_g8_forward_is_the_oracle_head(golden_dir, monkeypatch):
-    """The gradient fixture's forward (two tiny levels, its own radar frame) is the levels-aware oracle's head."""
-    monkeypatch.setattr(O, 'cross_atten', NLO.cross_atten)
+def test_g8_forward_is_the_oracle_head(golden_dir):
+    """The gradient fixture's forward (two tiny levels, its own radar frame) is the oracle's head."""
     g8, g5 = _g(golden_dir, 'g8_train_grads_l2.npz'), _g(golden_dir, 'g5_head_tiny_l2.npz')
     assert np.isfinite(g8['total_loss']) and int(g8['radar_seed']) != 2
     sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_levels=2))
@@ -127,7 +121,7 @@ def test_single_level_is_not_level_zero(golden_dir):
     assert g['level_shapes'].tolist() == [[2, 3]]
     sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_levels=1))
     feats, l2i, query, qpos, refp = _g2_inputs([TINY[0]])
-    a = NLO.cross_atten(sd, XA, query, qpos, feats, refp, PCR, l2i, HW)
+    a = O.cross_atten(sd, XA, query, qpos, feats, refp, PCR, l2i, HW)
     feats2, *_ = _g2_inputs([TINY[2]])
-    b = NLO.cross_atten(sd, XA, query, qpos, feats2, refp, PCR, l2i, HW)
+    b = O.cross_atten(sd, XA, query, qpos, feats2, refp, PCR, l2i, HW)
     assert float((a - b).abs().max()) > 1e-3

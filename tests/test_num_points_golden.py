@@ -1,5 +1,5 @@
-"""The num_points-aware oracle (num_points_oracle.py, patched over the oracle's cross_atten) against the fixtures
-the REFERENCE produced at num_points 5 and 3 (tests/golden/make_golden_points.py).  CPU; the fixtures are committed,
+"""The CPU oracle, which reads num_points from the shape of attention_weights, against the fixtures
+the REFERENCE produced at num_points 5 and 3 (tests/golden/make_golden_variants.py points).  CPU; the fixtures are committed,
 so the reference itself is not needed."""
 import os
 
@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 import torch
 
-import num_points_oracle as NPO
 from oracle import transcar_oracle as O
 from transcar_amd import configs, synth
 
@@ -20,12 +19,6 @@ E2E_TOL = 5e-4          # test_oracle_golden.test_g5_full_head
 def _no_grad():
     with torch.no_grad():
         yield
-
-
-@pytest.fixture
-def patched(monkeypatch):
-    monkeypatch.setattr(O, 'cross_atten', NPO.cross_atten)
-    return O
 
 
 def _g(golden_dir, name):
@@ -47,7 +40,7 @@ def test_g2_cross_atten_p5(golden_dir):
     query = torch.from_numpy(rng.standard_normal((900, 1, 256)).astype(np.float32))
     qpos = torch.from_numpy(rng.standard_normal((900, 1, 256)).astype(np.float32))
     refp = torch.from_numpy(rng.uniform(0.02, 0.98, (1, 900, 3)).astype(np.float32))
-    out = NPO.cross_atten(sd, 'transformer.decoder.layers.2.attentions.1', query, qpos, feats, refp, PCR, l2i, HW)
+    out = O.cross_atten(sd, 'transformer.decoder.layers.2.attentions.1', query, qpos, feats, refp, PCR, l2i, HW)
     np.testing.assert_allclose(out.numpy()[::4], g['out'], atol=1e-5, rtol=0)
     # the (p, l) order matters: the same logits read as [N, L, P] give another result
     name = 'transformer.decoder.layers.2.attentions.1.attention_weights'
@@ -55,19 +48,19 @@ def test_g2_cross_atten_p5(golden_dir):
     for k in ('.weight', '.bias'):
         v = sd[name + k]
         sw[name + k] = v.view(6, 5, 4, *v.shape[1:]).transpose(1, 2).reshape(v.shape).contiguous()
-    other = NPO.cross_atten(sw, 'transformer.decoder.layers.2.attentions.1', query, qpos, feats, refp, PCR, l2i, HW)
+    other = O.cross_atten(sw, 'transformer.decoder.layers.2.attentions.1', query, qpos, feats, refp, PCR, l2i, HW)
     assert float(np.abs(other.numpy()[::4] - g['out']).max()) > 1e-3
 
 
 @pytest.mark.parametrize('shapes,P', [('tiny', 5), ('res101', 5), ('tiny', 3)])
-def test_g5_head_points(golden_dir, patched, shapes, P):
+def test_g5_head_points(golden_dir, shapes, P):
     g = _g(golden_dir, 'g5_head_%s_p%d.npz' % (shapes, P))
     sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_points=P))
     feats = [torch.from_numpy(f) for f in synth.make_feats(shapes, seed=1, smooth=(4, 6))]
     l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
     f36 = O.build_radar_features(synth.make_radar_frame(seed=2, n_per_radar=51, centres=g['radar_centres']))
     np.testing.assert_allclose(f36.astype(np.float32), g['radar_tokens'], atol=1e-6, rtol=1e-6)
-    outs, dbg = patched.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True)
+    outs, dbg = O.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True)
     np.testing.assert_allclose(dbg['inter_refs'].numpy(), g['inter_refs'], atol=2e-5, rtol=0)
     hs = dbg['hs'].permute(0, 2, 1, 3).numpy()
     np.testing.assert_allclose(hs[:, ::16, 0, :], g['hs_rows'], atol=5e-5, rtol=0)
@@ -76,7 +69,7 @@ def test_g5_head_points(golden_dir, patched, shapes, P):
     for k in ('all_cls_scores', 'all_bbox_preds'):
         # [layers, B, Q, D]: at most two queries beyond the tolerance, those within 1e-2 (at res101 shapes and P = 5 a
         # reference point sits next to a sampling discontinuity: fp32 evaluation orders part there by up to 2.4e-3 --
-        # test_gpu_num_points.assert_all_but_two_queries)
+        # head_variant_rig.assert_all_but_two_queries)
         d = np.abs(outs[k].numpy() - g[k]).max(axis=(0, 1, 3))
         bad = np.where(d > E2E_TOL)[0]
         assert len(bad) <= 2 and (len(bad) == 0 or d.max() < 1e-2), (k, bad.tolist(), d[bad].tolist())
