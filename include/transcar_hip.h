@@ -36,6 +36,9 @@ extern "C" {
 #define TC_MAX_RADAR_LAYERS 3
 /* num_cams * num_levels * num_points of Detr3DCrossAtten: the logits of a row fit one 256-wide activation unit */
 #define TC_MAX_CAM_LOGITS 256
+/* Heads of the radar fusion attention (rf_multihead_attn{,2,3}): the reference builds it as
+ * nn.MultiheadAttention(embed_dims, 8) (HEAD:129-171) whatever the decoder's self-attention uses. */
+#define TC_RADAR_HEADS 8
 #define TC_ABI_VERSION 13
 
 typedef void* tc_stream_t;
@@ -94,6 +97,9 @@ typedef struct {
 /* All parameters Detr3DHead.forward reads (HEAD:43-238), in eval mode. */
 typedef struct {
   int abi_version;                  /* TC_ABI_VERSION                         */
+  /* num_heads: heads of the DECODER's self-attention (attn_cfgs[0].num_heads): 4, 8 or 16 at embed_dims 256 (head
+   * dimension 64, 32, 16); another count is refused naming it (tc_head_packed_bytes / tc_head_workspace_bytes return 0).
+   * The radar fusion attention does not read it: it has TC_RADAR_HEADS heads. */
   int num_query, embed_dims, num_heads, ffn_dims, num_layers;
   int num_cams, num_levels, num_classes, code_size;   /* num_levels: 1 .. TC_MAX_LEVELS */
   int radar_in_dims, num_radar_layers, num_radar_tokens_ref; /* 36, 3, 1500   */
@@ -345,7 +351,7 @@ int tc_cross_atten_points_fwd(const tc_linear* attention_weights, const tc_linea
 
 /* mmcv MultiheadAttention wrapper as used for decoder self-attention
  * (CFG:68-72): out = x + out_proj(MHA(q=k=x+pos, v=x)).
- * x/pos/out [B,Q,C]. */
+ * x/pos/out [B,Q,C].  C = 256; num_heads 4, 8 or 16. */
 size_t tc_self_attn_workspace_bytes(int B, int Q, int C);
 int tc_self_attn_fwd(const tc_mha* w, const float* x, const float* pos, float* out,
                      int B, int Q, int C, int num_heads,
@@ -393,11 +399,20 @@ int tc_sdpa_fwd(const float* q, const float* k, int ld, const float* vt, int ldt
 size_t tc_sdpa_f16x2_workspace_bytes(int B, int Q, int num_heads);
 int tc_sdpa_fwd_f16x2(const float* qk, const float* vt, int ldt, float* out, int ldo, int B, int Q, int num_heads,
                       void* workspace, size_t workspace_bytes, tc_stream_t stream);
+/* Both cores with the head dimension given: head_dim 16, 32 or 64 (another is refused naming it); head h at columns
+ * h*head_dim.. of q / k and rows h*head_dim.. of vt [B, num_heads*head_dim, ldt]; q pre-scaled by
+ * log2(e)/sqrt(head_dim); C = num_heads*head_dim in the f16x2 form's q | k rows.  head_dim = 32 is tc_sdpa_fwd /
+ * tc_sdpa_fwd_f16x2, bit for bit.  Neither needs a workspace. */
+int tc_sdpa_fwd_hd(const float* q, const float* k, int ld, const float* vt, int ldt,
+                   float* out, int ldo, int B, int Q, int num_heads, int head_dim, tc_stream_t stream);
+int tc_sdpa_fwd_f16x2_hd(const float* qk, const float* vt, int ldt, float* out, int ldo, int B, int Q, int num_heads,
+                         int head_dim, tc_stream_t stream);
 
 /* Distance-gated radar cross-attention, one fusion layer's attention step
  * (HEAD:549-581 / :619-653 / :675-711): three-circle gate around
  * (centre, front, rear), masked nn.MultiheadAttention of the gated queries
  * over the radar tokens, residual add on the rows that have at least one hit.
+ * num_heads = TC_RADAR_HEADS only.
  *   query      [B,Q,C]   query_feat before the layer
  *   centre_xy  [B,Q,2]   metres;  box [B,Q,code]: log-length at [3], sin/cos at [6],[7]
  *   radar_feat [B,T,C]   encoded tokens; radar_xy [B,T,2]

@@ -55,6 +55,21 @@ def check_num_levels(num_levels):
             % (num_levels, TC_MAX_LEVELS))
 
 
+# heads of the decoder's MultiheadAttention at embed_dims 256: head dimension 64, 32, 16 (include/transcar_hip.h)
+TC_NUM_HEADS = (4, 8, 16)
+# heads of the radar fusion attention: nn.MultiheadAttention(embed_dims, 8) in the reference, whatever the decoder uses
+TC_RADAR_HEADS = 8
+
+
+def check_num_heads(num_heads):
+    """The library's limit on the decoder MultiheadAttention's num_heads (4, 8
+    or 16 at embed_dims 256), checked before anything is packed or launched."""
+    if isinstance(num_heads, bool) or not isinstance(num_heads, int) or num_heads not in TC_NUM_HEADS:
+        raise TransCARHipError(
+            'MultiheadAttention(HIP): num_heads=%r is not supported (4, 8 or 16 heads at embed_dims 256: '
+            'head dimension 64, 32 or 16)' % (num_heads,))
+
+
 def cam_pregather_supported(embed_dims, num_levels, num_cams):
     """The shapes the camera pre-gather (tc_head_options.cam_pregather) runs:
     C = 256, 4 levels, at most 8 cameras.  Others take the chain's own gather,
@@ -202,6 +217,8 @@ SIGNATURES = {
     'tc_sdpa_fwd': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     'tc_sdpa_f16x2_workspace_bytes': (_sz, [_i, _i, _i]),
     'tc_sdpa_fwd_f16x2': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'tc_sdpa_fwd_hd': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    'tc_sdpa_fwd_f16x2_hd': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     'tc_radar_xattn_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'tc_radar_gate_selfcheck': (_i, [_i, C.c_ulonglong, _vp, _vp]),
     'tc_rowops_selfcheck': (_i, [_i, C.c_ulonglong, _vp, _vp]),

@@ -59,6 +59,7 @@ class MultiheadAttention(BaseModule):
         if 'dropout' in kwargs:                # deprecated kwarg in the config
             attn_drop = kwargs['dropout']
             drop_prob = kwargs.pop('dropout')
+        L.check_num_heads(num_heads)
         self.embed_dims = embed_dims
         self.num_heads = num_heads
         self.batch_first = batch_first

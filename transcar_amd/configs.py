@@ -76,13 +76,15 @@ IMG_SHAPE = (928, 1600, 3)
 
 
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
-             num_levels=None):
+             num_levels=None, num_heads=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
     reference class defaults to False, HEAD:45); num_levels sets
     Detr3DCrossAtten.num_levels and the transformer's num_feature_levels (the
-    configs: the class defaults, 4 FPN levels)."""
+    configs: the class defaults, 4 FPN levels); num_heads overrides the
+    decoder MultiheadAttention's (attn_cfgs[0]; the configs: 8, CFG:69; 4, 8
+    or 16 -- the radar fusion attention keeps its 8, HEAD:129-171)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -94,4 +96,9 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
         layers = cfg['transformer']['decoder']['transformerlayers']
         layers['attn_cfgs'][1]['num_levels'] = int(num_levels)
         cfg['transformer']['num_feature_levels'] = int(num_levels)
+    if num_heads is not None:
+        from ._lib import check_num_heads
+        check_num_heads(num_heads)
+        layers = cfg['transformer']['decoder']['transformerlayers']
+        layers['attn_cfgs'][0]['num_heads'] = num_heads
     return cfg

@@ -76,7 +76,7 @@ static int self_attn(const tc_mha& w, const float* x, const float* pos, float* o
   // q * log2(e)/sqrt(head_dim): the attention core exponentiates with 2^x
   g.scale = 1.4426950408889634f / sqrtf((float)(C / H)); g.scale_cols = C;
   TC_TRY(launch_gemm(g, s));
-  TC_TRY(launch_self_attn_core(qk, qk + C, 2 * C, vt, qpad, attn_o, C, B, Q, H, s));
+  TC_TRY(launch_self_attn_core(qk, qk + C, 2 * C, vt, qpad, attn_o, C, B, Q, H, C / H, s));
   return linear(attn_o, C, w.out_proj, rows, C, C, 0, out, C, s, nullptr, x, C);
 }
 
@@ -111,7 +111,7 @@ static int check_dims(const tc_head_weights* w) {
   TC_REQUIRE(w != nullptr, "weights pointer is null");
   TC_REQUIRE(w->abi_version == TC_ABI_VERSION, "tc_head_weights.abi_version=%d, library=%d",
              w->abi_version, TC_ABI_VERSION);
-  TC_REQUIRE(w->embed_dims == 256 && w->num_heads == 8, "embed_dims=%d num_heads=%d (256/8 supported)",
+  TC_REQUIRE(w->embed_dims == 256 && heads_ok(w->num_heads), "embed_dims=%d num_heads=%d (256 with 4, 8 or 16 heads supported)",
              w->embed_dims, w->num_heads);
   TC_REQUIRE(w->num_layers >= 1 && w->num_layers <= TC_MAX_LAYERS, "num_layers=%d", w->num_layers);
   TC_REQUIRE(w->num_radar_layers >= 0 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
@@ -311,10 +311,10 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
           pga.cam = d.cam; pga.M = rows; pga.ref_mod = d.ref_mod; pga.out = pbuf; pga.mask = pmask;
           d.pre = pbuf; d.premask = pmask;
         }
-        TC_TRY(launch_self_attn_core_x(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, s, ddrop ? &d.drop : nullptr,
+        TC_TRY(launch_self_attn_core_x(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, C / H, s, ddrop ? &d.drop : nullptr,
                                        pre ? &pga : nullptr));
       } else {
-        TC_TRY(launch_self_attn_core(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, s, ddrop ? &d.drop : nullptr));
+        TC_TRY(launch_self_attn_core(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, C / H, s, ddrop ? &d.drop : nullptr));
       }
     }
     // the radar encoders ride in two launches, half each (all in layer 0 when there is only one layer)
@@ -343,7 +343,7 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
   rc.box_m = h.box_m; rc.tokens = radar_tokens; rc.RI = w->radar_in_dims;
   for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) { rc.kv[r] = h.kv3[r]; rc.w[r] = w->radar[r]; }
   rc.nlayers = w->num_radar_layers; rc.Q = Q; rc.T = T; rc.pad_mult = pad_mult; rc.code = code;
-  rc.ncls = ncls; rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / H));
+  rc.ncls = ncls; rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   for (int i = 0; i < 6; ++i) rc.pc[i] = w->pc_range[i];
   rc.all_cls = all_cls_scores; rc.all_box = all_bbox_preds; rc.hits = h.hits;
   rc.tile_rows = opt.chain_tile_rows; rc.last_cls_only = opt.last_level_cls_only; rc.matrix_path = opt.matrix_path;
@@ -560,7 +560,7 @@ size_t tc_self_attn_workspace_bytes(int B, int Q, int C) {
 int tc_self_attn_fwd(const tc_mha* w, const float* x, const float* pos, float* out, int B, int Q,
                      int C, int num_heads, void* workspace, size_t workspace_bytes,
                      tc_stream_t stream) {
-  TC_REQUIRE(C == 256 && num_heads == 8, "self_attn: C=%d heads=%d (256/8 supported)", C, num_heads);
+  TC_REQUIRE(C == 256 && heads_ok(num_heads), "self_attn: C=%d num_heads=%d (256 with 4, 8 or 16 heads supported)", C, num_heads);
   TC_REQUIRE(workspace_bytes >= tc_self_attn_workspace_bytes(B, Q, C), "self_attn: workspace too small");
   const size_t rows = (size_t)B * Q;
   const int qpad = ((Q + 15) / 16) * 16;
@@ -603,7 +603,12 @@ int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* ne
 
 int tc_sdpa_fwd(const float* q, const float* k, int ld, const float* vt, int ldt, float* out, int ldo,
                 int B, int Q, int num_heads, tc_stream_t stream) {
-  return launch_self_attn_core(q, k, ld, vt, ldt, out, ldo, B, Q, num_heads, as_stream(stream));
+  return launch_self_attn_core(q, k, ld, vt, ldt, out, ldo, B, Q, num_heads, 32, as_stream(stream));
+}
+
+int tc_sdpa_fwd_hd(const float* q, const float* k, int ld, const float* vt, int ldt, float* out, int ldo,
+                   int B, int Q, int num_heads, int head_dim, tc_stream_t stream) {
+  return launch_self_attn_core(q, k, ld, vt, ldt, out, ldo, B, Q, num_heads, head_dim, as_stream(stream));
 }
 
 size_t tc_sdpa_f16x2_workspace_bytes(int, int, int) { return 0; }     // (the staged form needs none)
@@ -611,7 +616,14 @@ size_t tc_sdpa_f16x2_workspace_bytes(int, int, int) { return 0; }     // (the st
 int tc_sdpa_fwd_f16x2(const float* qk, const float* vt, int ldt, float* out, int ldo, int B, int Q, int num_heads,
                       void* workspace, size_t workspace_bytes, tc_stream_t stream) {
   (void)workspace; (void)workspace_bytes;          // (an earlier form built f16 planes there; the staged form converts in LDS)
-  return launch_self_attn_core_x(qk, qk + num_heads * 32, 2 * num_heads * 32, vt, ldt, out, ldo, B, Q, num_heads, as_stream(stream));
+  return launch_self_attn_core_x(qk, qk + num_heads * 32, 2 * num_heads * 32, vt, ldt, out, ldo, B, Q, num_heads, 32, as_stream(stream));
+}
+
+int tc_sdpa_fwd_f16x2_hd(const float* qk, const float* vt, int ldt, float* out, int ldo, int B, int Q, int num_heads,
+                         int head_dim, tc_stream_t stream) {
+  TC_REQUIRE(num_heads > 0 && head_dim > 0, "sdpa(f16x2): num_heads=%d head_dim=%d", num_heads, head_dim);
+  const int C = num_heads * head_dim;
+  return launch_self_attn_core_x(qk, qk + C, 2 * C, vt, ldt, out, ldo, B, Q, num_heads, head_dim, as_stream(stream));
 }
 
 size_t tc_radar_xattn_workspace_bytes(int B, int Q, int T, int C) {
@@ -625,7 +637,7 @@ int tc_radar_gated_xattn_fwd(const tc_mha* w, const float* query, const float* c
                              int pad_mult, float radius_min, float radius_max, float* out,
                              int* hit_counts, void* workspace, size_t workspace_bytes,
                              tc_stream_t stream) {
-  TC_REQUIRE(C == 256 && num_heads == 8, "radar_xattn: C=%d heads=%d (256/8 supported)", C, num_heads);
+  TC_REQUIRE(C == 256 && num_heads == TC_RADAR_HEADS, "radar_xattn: C=%d heads=%d (256/%d supported)", C, num_heads, TC_RADAR_HEADS);
   TC_REQUIRE(workspace_bytes >= tc_radar_xattn_workspace_bytes(B, Q, T, C), "radar_xattn: workspace too small");
   hipStream_t s = as_stream(stream);
   const int rows = B * Q, rt = B * T;
@@ -692,7 +704,7 @@ int tc_radar_fusion_fwd(const tc_head_weights* packed_view, const float* hs_last
   const size_t need = head_ws_layout(w, B, T, workspace, workspace_bytes, &h);
   TC_REQUIRE(need <= workspace_bytes, "workspace too small: need %zu, have %zu", need, workspace_bytes);
   hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, H = w->num_heads, rows = B * Q, rt = B * T;
+  const int Q = w->num_query, C = w->embed_dims, rows = B * Q, rt = B * T;
   const int code = w->code_size, ncls = w->num_classes;
   // encoders + K/V projections of all layers (stand-alone encoder program)
   RadarEncodeArgs re;
@@ -713,7 +725,7 @@ int tc_radar_fusion_fwd(const tc_head_weights* packed_view, const float* hs_last
   rc.RI = w->radar_in_dims;
   for (int r = 0; r < num_layers; ++r) { rc.kv[r] = h.kv3[first_layer + r]; rc.w[r] = w->radar[first_layer + r]; }
   rc.nlayers = num_layers; rc.Q = Q; rc.T = T; rc.pad_mult = pad_mult; rc.code = code; rc.ncls = ncls;
-  rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / H));
+  rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   for (int i = 0; i < 6; ++i) rc.pc[i] = w->pc_range[i];
   rc.all_cls = all_cls_scores + (size_t)first_layer * rows * ncls;
   rc.all_box = all_bbox_preds + (size_t)first_layer * rows * code;
@@ -831,7 +843,7 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
     pa.qpad = qpad; pa.qscale = 1.4426950408889634f / sqrtf((float)(C / H));
     pa.w16_delta = delta;
     TC_TRY(launch_prologue(pa, s));
-    TC_TRY(launch_self_attn_core(qk, qk + C, 2 * C, vt, qpad, attn_o, C, 1, Q, H, s));
+    TC_TRY(launch_self_attn_core(qk, qk + C, 2 * C, vt, qpad, attn_o, C, 1, Q, H, C / H, s));
     packed_view->l0_init_reference = init_ref;
     packed_view->l0_attn_out = attn_o;
     // Layer 0's chain up to the camera sampling, as far as it reads no frame data (out_proj, norm0, pe.3): once per
@@ -1027,7 +1039,7 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   // HEAD:543-547, 596-598
   TC_TRY(launch_radar_ref_l1(h.inter_refs + (size_t)(L - 1) * rows * 3, pc, h.cxy, h.addref, rows, s));
   const float* qf = h.hs + (size_t)(L - 1) * rows * C;
-  const float qscale = 1.0f / sqrtf((float)(C / H));
+  const float qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   for (int r = 0; r < w->num_radar_layers; ++r) {
     const tc_radar_layer& rl = w->radar[r];
     float* cls_out = all_cls_scores + (size_t)r * rows * ncls;
@@ -1044,7 +1056,7 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
     ra.qproj = h.qproj; ra.ldq = C; ra.kv = h.kv; ra.ldkv = 2 * C;
     ra.centre_xy = r == 0 ? h.cxy : box_prev; ra.ld_c = r == 0 ? 2 : code;
     ra.box = box_prev; ra.code = code; ra.radar_xy = radar_tokens; ra.ld_xy = RI;
-    ra.B = B; ra.Q = Q; ra.T = T; ra.C = C; ra.H = H; ra.pad_mult = pad_mult;
+    ra.B = B; ra.Q = Q; ra.T = T; ra.C = C; ra.H = TC_RADAR_HEADS; ra.pad_mult = pad_mult;
     ra.rmin = rl.radius_min; ra.rmax = rl.radius_max; ra.attn_out = h.rattn; ra.hit_counts = hits;
     TC_TRY(launch_radar_attn(ra, s));
     // HEAD:581-586

@@ -198,10 +198,12 @@ int launch_gate_selfcheck(int n_radii, unsigned long long seed, unsigned long lo
 int launch_rowops_selfcheck(int n_blocks, unsigned long long seed, unsigned long long* mismatches, hipStream_t s);   // chain.hip
 
 // ---- self_attn.hip ---------------------------------------------------------
-// q,k: [B*Q, ld] token-major with head h at column h*32; vt: [B, C, ldt] (V transposed)
+// head counts of the decoder's self-attention at embed_dims 256: head dimension 64, 32, 16
+inline bool heads_ok(int num_heads) { return num_heads == 4 || num_heads == 8 || num_heads == 16; }
+// q,k: [B*Q, ld] token-major with head h at column h*D; vt: [B, C, ldt] (V transposed), C = H*D; head dimension D: 16, 32, 64
 // drop (may be null / thr 0 = eval): dropout on the attention probabilities, index ((b*H+h)*Q+i)*Q+j
 int launch_self_attn_core(const float* q, const float* k, int ld, const float* vt, int ldt,
-                          float* out, int ldo, int B, int Q, int H, hipStream_t s,
+                          float* out, int ldo, int B, int Q, int H, int D, hipStream_t s,
                           const DropK* drop = nullptr);
 // the same on the f16 matrix cores, fp32-accurate (round 4): two-plane f16 operands (hi, lo), fp32 accumulate; K / V^T are
 // split and staged through LDS inside the kernel, every wave walks all keys.  Same operands as launch_self_attn_core.
@@ -212,7 +214,7 @@ struct PreGatherArgs {
   CamSampleArgs cam; int M, ref_mod; float* out; int* mask;
 };
 int launch_self_attn_core_x(const float* q, const float* k, int ld, const float* vt, int ldt, float* out, int ldo,
-                            int B, int Q, int H, hipStream_t s, const DropK* drop = nullptr,
+                            int B, int Q, int H, int D, hipStream_t s, const DropK* drop = nullptr,
                             const PreGatherArgs* pregather = nullptr);
 
 // ---- radar_attn.hip --------------------------------------------------------

@@ -1,6 +1,8 @@
 // Decoder self-attention core: softmax(Q K^T) V for 900 queries,
 // 8 heads of 32, fp32, without materialising the 8 x 900 x 900 score tensor the
-// reference's nn.MultiheadAttention builds (25.9 MB per layer).
+// reference's nn.MultiheadAttention builds (25.9 MB per layer).  4 heads of 64 and
+// 16 heads of 16 run the same kernels, instantiated on the head dimension D; the
+// text below describes D = 32.
 //
 // Flash-style on the f32 matrix core, laid out for wave64 / 16x16x4 MFMA:
 //   * a workgroup = 8 waves = one (batch, head, 16-query tile); the waves
@@ -53,16 +55,22 @@ __device__ __forceinline__ float max_lanes_16_32(float x) {
   return a;
 }
 
-struct KVFrag { float4 ka, kb, v0, v1; };
+// Head dimension D in {16, 32, 64} (embed_dims 256 split into 16, 8 or 4 heads): a lane group holds D/4 channels of
+// q and k (D/16 float4: a 16-key tile takes D/4 score MFMAs) and O^T is D/16 accumulators of 16 channels.  D = 32 is
+// the form this kernel was written in; its instantiation is that code, instruction for instruction.
+template <int D> struct KVFrag { float4 k[D / 16], v[D / 16]; };
 
-// per-lane pointers of a wave's current key tile: K rows (lane r = key, 8 channels of group g) and
-// the two V^T channel rows (r, r + 16; 4 keys of group g); advanced by whole strides, no index math
-struct KVPtr { const float* k; const float* v0; const float* v1; };
+// per-lane pointers of a wave's current key tile: K rows (lane r = key, D/4 channels of group g) and
+// the D/16 V^T channel rows (r, r + 16, ...; 4 keys of group g); advanced by whole strides, no index math
+template <int D> struct KVPtr { const float* k; const float* v[D / 16]; };
 
-__device__ __forceinline__ KVFrag load_kv(const KVPtr& p) {
-  KVFrag f;
-  f.ka = ld4(p.k); f.kb = ld4(p.k + 4);
-  f.v0 = ld4(p.v0); f.v1 = ld4(p.v1);
+template <int D>
+__device__ __forceinline__ KVFrag<D> load_kv(const KVPtr<D>& p) {
+  KVFrag<D> f;
+#pragma unroll
+  for (int j = 0; j < D / 16; ++j) f.k[j] = ld4(p.k + 4 * j);
+#pragma unroll
+  for (int j = 0; j < D / 16; ++j) f.v[j] = ld4(p.v[j]);
   return f;
 }
 
@@ -76,9 +84,9 @@ __device__ __forceinline__ bool any_above(float a, float b, float c, float d, fl
   return m > __builtin_bit_cast(int, tau);
 }
 
-// Running softmax state of one 16-query sub-tile: O^T (2 x 16 channels x 16 queries), the partial
+// Running softmax state of one 16-query sub-tile: O^T (D/16 x 16 channels x 16 queries), the partial
 // normaliser and the NEGATED running reference as the four equal entries of an MFMA C operand.
-struct SAState { f32x4 o0, o1, negm; float l; };
+template <int D> struct SAState { f32x4 o[D / 16], negm; float l; };
 
 // One 16-key tile against one 16-query sub-tile.
 //
@@ -90,22 +98,28 @@ struct SAState { f32x4 o0, o1, negm; float l; };
 // that does (always the wave's first) pays for the cross-lane max, alpha and the rescale of O.
 // softmax is shift invariant: the result is the running-max formulation's up to rounding.
 // nvalid < 16 (the ragged last tile): keys >= nvalid are masked.
-template <bool DROP>
-__device__ __forceinline__ void sa_tile(const KVFrag& f, const float4& qa, const float4& qb, SAState& st,
+template <int D, bool DROP>
+__device__ __forceinline__ void sa_tile(const KVFrag<D>& f, const float4* q, SAState<D>& st,
                                         bool first, int nvalid, int g, const DropK& drop, unsigned drop_base) {
-  f32x4 s = MFMA4(f.ka.x, qa.x, st.negm);
-  s = MFMA4(f.ka.y, qa.y, s); s = MFMA4(f.ka.z, qa.z, s); s = MFMA4(f.ka.w, qa.w, s);
-  s = MFMA4(f.kb.x, qb.x, s); s = MFMA4(f.kb.y, qb.y, s);
-  s = MFMA4(f.kb.z, qb.z, s); s = MFMA4(f.kb.w, qb.w, s);
+  constexpr int NV = D / 16;
+  f32x4 s = MFMA4(f.k[0].x, q[0].x, st.negm);
+  s = MFMA4(f.k[0].y, q[0].y, s); s = MFMA4(f.k[0].z, q[0].z, s); s = MFMA4(f.k[0].w, q[0].w, s);
+#pragma unroll
+  for (int j = 1; j < NV; ++j) {
+    s = MFMA4(f.k[j].x, q[j].x, s); s = MFMA4(f.k[j].y, q[j].y, s);
+    s = MFMA4(f.k[j].z, q[j].z, s); s = MFMA4(f.k[j].w, q[j].w, s);
+  }
   // s[i] = log2(e) * S^T[key0 + 4g + i][query r] + negm
   float s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3];
-  float4 v0 = f.v0, v1 = f.v1;
+  float4 v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) v[j] = f.v[j];
   if (nvalid < 16) {                                   // wave-uniform
     const int kk = 4 * g;
-    if (kk + 0 >= nvalid) { s0 = -INFINITY; v0.x = 0.f; v1.x = 0.f; }
-    if (kk + 1 >= nvalid) { s1 = -INFINITY; v0.y = 0.f; v1.y = 0.f; }
-    if (kk + 2 >= nvalid) { s2 = -INFINITY; v0.z = 0.f; v1.z = 0.f; }
-    if (kk + 3 >= nvalid) { s3 = -INFINITY; v0.w = 0.f; v1.w = 0.f; }
+    if (kk + 0 >= nvalid) { s0 = -INFINITY; for (int j = 0; j < NV; ++j) v[j].x = 0.f; }
+    if (kk + 1 >= nvalid) { s1 = -INFINITY; for (int j = 0; j < NV; ++j) v[j].y = 0.f; }
+    if (kk + 2 >= nvalid) { s2 = -INFINITY; for (int j = 0; j < NV; ++j) v[j].z = 0.f; }
+    if (kk + 3 >= nvalid) { s3 = -INFINITY; for (int j = 0; j < NV; ++j) v[j].w = 0.f; }
   }
   if (first || __builtin_amdgcn_ballot_w64(any_above(s0, s1, s2, s3, SA_TAU)) != 0) {
     const float mx = max_lanes_16_32(fmaxf(fmaxf(s0, s1), fmaxf(s2, s3)));   // finite: key 0 of every tile is valid
@@ -113,7 +127,8 @@ __device__ __forceinline__ void sa_tile(const KVFrag& f, const float4& qa, const
     const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);   // first tile: l = O = 0
     s0 -= delta; s1 -= delta; s2 -= delta; s3 -= delta;
     st.l *= alpha;
-    st.o0 *= alpha; st.o1 *= alpha;      // (scalar multiplies: the library is built without packed-f32 ops, Makefile)
+#pragma unroll
+    for (int j = 0; j < NV; ++j) st.o[j] *= alpha;      // (scalar multiplies: the library is built without packed-f32 ops, Makefile)
     st.negm -= delta;
   }
   const float p0 = __builtin_amdgcn_exp2f(s0), p1 = __builtin_amdgcn_exp2f(s1);
@@ -128,10 +143,14 @@ __device__ __forceinline__ void sa_tile(const KVFrag& f, const float4& qa, const
     d3 = (dm & 8u) ? p3 * drop.scale : 0.0f;
   }
   // O^T[d][q] += V^T[d][key] P^T[key][q]
-  st.o0 = MFMA4(v0.x, d0, st.o0); st.o1 = MFMA4(v1.x, d0, st.o1);
-  st.o0 = MFMA4(v0.y, d1, st.o0); st.o1 = MFMA4(v1.y, d1, st.o1);
-  st.o0 = MFMA4(v0.z, d2, st.o0); st.o1 = MFMA4(v1.z, d2, st.o1);
-  st.o0 = MFMA4(v0.w, d3, st.o0); st.o1 = MFMA4(v1.w, d3, st.o1);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) st.o[j] = MFMA4(v[j].x, d0, st.o[j]);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) st.o[j] = MFMA4(v[j].y, d1, st.o[j]);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) st.o[j] = MFMA4(v[j].z, d2, st.o[j]);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) st.o[j] = MFMA4(v[j].w, d3, st.o[j]);
 }
 
 // QT = 16-query sub-tiles per workgroup: the K/V fragments of a key tile are loaded
@@ -143,7 +162,7 @@ __device__ __forceinline__ void sa_tile(const KVFrag& f, const float4& qa, const
 // probability of (batch b, head h, query i, key j) is multiplied by 0 or 1/(1-p), mask
 // drop_keep(seed, site, ((b*H + h)*Q + i)*Q + j): only the PV product sees the mask, the
 // normaliser l does not.  A separate instantiation: the eval kernel is unchanged.
-template <int QT, bool DROP>
+template <int D, int QT, bool DROP>
 __global__ __launch_bounds__(SA_NW * 64) void self_attn_kernel(const float* __restrict__ q,
                                                                const float* __restrict__ k, int ld,
                                                                const float* __restrict__ vt, int ldt,
@@ -151,21 +170,24 @@ __global__ __launch_bounds__(SA_NW * 64) void self_attn_kernel(const float* __re
                                                                int Q, int C, DropK drop) {
   __shared__ float sm_m[SA_NW][QT][16];
   __shared__ float sm_l[SA_NW][QT][64];
-  __shared__ float4 sm_o[SA_NW][QT][2][64];
+  constexpr int NV = D / 16;                            // 16-channel slices of a head = float4 of q / k per lane
+  static_assert(D == 16 || D == 32 || D == 64, "head dimension");
+  static_assert(QT * NV <= SA_NW, "one wave finalises one (sub-tile, 16-channel slice)");
+  __shared__ float4 sm_o[SA_NW][QT][NV][64];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 16 * QT, h = blockIdx.y, b = blockIdx.z;
   const size_t brow = (size_t)b * Q;
 
-  float4 qa[QT], qb[QT];
-  SAState st[QT];
+  float4 qf[QT][NV];
+  SAState<D> st[QT];
   unsigned dbase[QT];
 #pragma unroll
   for (int u = 0; u < QT; ++u) {
     const int qrow = min(q0 + 16 * u + r, Q - 1);
-    const float* qp = q + (brow + qrow) * ld + h * 32 + 8 * g;
-    qa[u] = ld4(qp); qb[u] = ld4(qp + 4);
-    st[u].o0 = f32x4{0.f, 0.f, 0.f, 0.f}; st[u].o1 = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* qp = q + (brow + qrow) * ld + h * D + (D / 4) * g;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { qf[u][j] = ld4(qp + 4 * j); st[u].o[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     st[u].negm = f32x4{0.f, 0.f, 0.f, 0.f}; st[u].l = 0.0f;
     // (a batch of frames with per-sample seeds: the index is the one sample b has when it is launched alone)
     dbase[u] = DROP ? (((drop.rows_per_sample ? 0u : (unsigned)b) * gridDim.y + h) * Q + (unsigned)qrow) * Q + 4 * g : 0u;
@@ -176,17 +198,22 @@ __global__ __launch_bounds__(SA_NW * 64) void self_attn_kernel(const float* __re
   const int nfull = Q >> 4;
   const int n = wave < nfull ? (nfull - wave + SA_NW - 1) / SA_NW : 0;
   const size_t kstep = (size_t)SA_NW * 16 * ld;
-  KVPtr p;
-  p.k = k + (brow + wave * 16 + r) * ld + h * 32 + 8 * g;
-  p.v0 = vt + ((size_t)b * C + h * 32 + r) * ldt + wave * 16 + 4 * g;
-  p.v1 = p.v0 + (size_t)16 * ldt;
-  auto advance = [&]() { p.k += kstep; p.v0 += SA_NW * 16; p.v1 += SA_NW * 16; };
-  auto tile = [&](const KVFrag& f, int i, int nvalid) {
+  KVPtr<D> p;
+  p.k = k + (brow + wave * 16 + r) * ld + h * D + (D / 4) * g;
+  p.v[0] = vt + ((size_t)b * C + h * D + r) * ldt + wave * 16 + 4 * g;
+#pragma unroll
+  for (int j = 1; j < NV; ++j) p.v[j] = p.v[j - 1] + (size_t)16 * ldt;
+  auto advance = [&]() {
+    p.k += kstep;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) p.v[j] += SA_NW * 16;
+  };
+  auto tile = [&](const KVFrag<D>& f, int i, int nvalid) {
 #pragma unroll
     for (int u = 0; u < QT; ++u)
-      sa_tile<DROP>(f, qa[u], qb[u], st[u], i == 0, nvalid, g, drop, dbase[u] + (unsigned)(wave + i * SA_NW) * 16u);
+      sa_tile<D, DROP>(f, qf[u], st[u], i == 0, nvalid, g, drop, dbase[u] + (unsigned)(wave + i * SA_NW) * 16u);
   };
-  KVFrag fa, fb;
+  KVFrag<D> fa, fb;
   if (n > 0) fa = load_kv(p);
   int i = 0;
   for (; i + 2 <= n; i += 2) {
@@ -202,11 +229,12 @@ __global__ __launch_bounds__(SA_NW * 64) void self_attn_kernel(const float* __re
   if (i < n) { tile(fa, i, 16); ++i; }
   const int rag = Q & 15;
   if (rag != 0 && wave == (nfull % SA_NW)) {           // i == n: this wave's next tile is the ragged one
-    KVPtr pr;
-    pr.k = k + (brow + min(nfull * 16 + r, Q - 1)) * ld + h * 32 + 8 * g;
-    pr.v0 = vt + ((size_t)b * C + h * 32 + r) * ldt + nfull * 16 + 4 * g;    // ldt >= 16 * (nfull + 1)
-    pr.v1 = pr.v0 + (size_t)16 * ldt;
-    const KVFrag fr = load_kv(pr);
+    KVPtr<D> pr;
+    pr.k = k + (brow + min(nfull * 16 + r, Q - 1)) * ld + h * D + (D / 4) * g;
+    pr.v[0] = vt + ((size_t)b * C + h * D + r) * ldt + nfull * 16 + 4 * g;    // ldt >= 16 * (nfull + 1)
+#pragma unroll
+    for (int j = 1; j < NV; ++j) pr.v[j] = pr.v[j - 1] + (size_t)16 * ldt;
+    const KVFrag<D> fr = load_kv(pr);
     tile(fr, i, rag);
     ++i;
   }
@@ -216,13 +244,14 @@ __global__ __launch_bounds__(SA_NW * 64) void self_attn_kernel(const float* __re
   for (int u = 0; u < QT; ++u) {
     if (g == 0) sm_m[wave][u][r] = idle ? -INFINITY : -st[u].negm[0];
     sm_l[wave][u][lane] = st[u].l;
-    sm_o[wave][u][0][lane] = make_float4(st[u].o0[0], st[u].o0[1], st[u].o0[2], st[u].o0[3]);
-    sm_o[wave][u][1][lane] = make_float4(st[u].o1[0], st[u].o1[1], st[u].o1[2], st[u].o1[3]);
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+      sm_o[wave][u][j][lane] = make_float4(st[u].o[j][0], st[u].o[j][1], st[u].o[j][2], st[u].o[j][3]);
   }
   __syncthreads();
-  // wave w finalises (sub-tile w/2, channel half w&1)
-  if (wave >= 2 * QT) return;
-  const int u = wave >> 1, half = wave & 1;
+  // wave w finalises (sub-tile w / NV, 16-channel slice w % NV)
+  if (wave >= NV * QT) return;
+  const int u = wave / NV, half = wave % NV;
   float mstar = sm_m[0][u][r];
 #pragma unroll
   for (int w = 1; w < SA_NW; ++w) mstar = fmaxf(mstar, sm_m[w][u][r]);
@@ -237,7 +266,7 @@ __global__ __launch_bounds__(SA_NW * 64) void self_attn_kernel(const float* __re
   }
   if (q0 + 16 * u + r < Q) {
     const float inv = 1.0f / l;
-    float* op = out + (brow + q0 + 16 * u + r) * ldo + h * 32 + 16 * half + 4 * g;
+    float* op = out + (brow + q0 + 16 * u + r) * ldo + h * D + 16 * half + 4 * g;
     st4(op, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
   }
 }
@@ -284,7 +313,16 @@ __device__ __forceinline__ unsigned sa_pk(float a, float b) {
 #ifndef SX_QT_VALUE
 #define SX_QT_VALUE 2
 #endif
-constexpr int SX_NW = SX_NW_VALUE, SX_CP = 2;
+constexpr int SX_NW = SX_NW_VALUE;
+// Head dimension D in {16, 32, 64}.  The LDS image of a key pair is [ks][tile a, b][hi, lo] K fragments (ks = D/32
+// k-steps of 32 channels; one at D = 16, whose fragments keep lane groups 2 and 3 -- channels 16 .. 31 of the k = 32
+// MFMA -- zero) followed by [D/16 channel tiles][hi, lo] V^T fragments: 6, 8, 16 fragments of 1 KB.  D = 32 is the form
+// this kernel was written in; its instantiation is that code, instruction for instruction.
+// Chunk depth (pairs per barrier), two buffers: 2 at D <= 32 (24 / 32 KB); 1 at D = 64 (32 KB: at 2 the image would be
+// 64 KB, and three workgroups would no longer fit a CU's 160 KB).
+constexpr int sx_cp(int D) { return D == 64 ? 1 : 2; }
+constexpr int sx_ks(int D) { return D == 64 ? 2 : 1; }
+constexpr int sx_nf(int D) { return 4 * sx_ks(D) + 2 * (D / 16); }
 constexpr int SX_PG_ROWS = 32;      // rows of a pre-gather workgroup (8 per wave: two projection rounds of four rows)
 static_assert(SX_PG_ROWS % (4 * SX_NW) == 0, "a pre-gather wave projects four rows at a time");
 #ifndef SX_NPC
@@ -293,6 +331,10 @@ static_assert(SX_PG_ROWS % (4 * SX_NW) == 0, "a pre-gather wave projects four ro
 #ifndef SX_OCC
 #define SX_OCC 3
 #endif
+// D = 64 (four O^T accumulators and two k-steps of Q fragments per sub-tile): 174 VGPRs, 190 with dropout, no scratch
+// under a bound of two waves per SIMD.  Under the bound of three (168 registers) the dropout instantiation spills 15
+// registers to scratch: both instantiations take two.
+constexpr int sx_occ(int D) { return D == 64 ? 2 : SX_OCC; }
 
 // The staged form keeps the LOW planes UNSCALED (lo = f16(x - hi)): the matrix cores honour f16 subnormals
 // (measured: tools/r4_attn_time.py, error unchanged at 3e-7), so a lo plane's error is at most 2^-25 ABSOLUTE per element
@@ -304,7 +346,7 @@ static_assert(SX_PG_ROWS % (4 * SX_NW) == 0, "a pre-gather wave projects four ro
 #ifndef SX_L_MFMA
 #define SX_L_MFMA 0
 #endif
-struct SXState { f32x4 o0, o1, lsum, negm; float l; };
+template <int D> struct SXState { f32x4 o[D / 16], lsum, negm; float l; };
 
 // x (8 fp32) -> hi plane (round to nearest f16) and lo plane f16(x - hi): one v_cvt_pk per two elements + one
 // v_fma_mix{lo,hi}_f16 per element (the packed hi half is an operand as it stands)
@@ -337,21 +379,36 @@ __device__ __forceinline__ void sx_split(const float4& x0, const float4& x1, flo
 // drop_keep(seed, site, ((b * H + h) * Q + query) * Q + key) on the normalised probability, the normaliser does not see
 // it -- on the lane's eight consecutive keys: two hashes (drop_keep4).  dbase[u]: the index of (query r of sub-tile u,
 // key 8 g) at pair 0; key0 = the first key of the chunk's first pair.
-template <int QT, int NP, bool DROP = false>
-__device__ __forceinline__ void sx_chunk(const float4 (*fb)[8][64], int lane, int g, const float4* q_h, const float4* q_l,
-                                         SXState* st, bool first, int nvalid_last, const DropK* drop = nullptr,
+// q_h / q_l: [QT][KS] fragments (k-step ks of sub-tile u at [u * KS + ks]).
+template <int D, int QT, int NP, bool DROP = false>
+__device__ __forceinline__ void sx_chunk(const float4 (*fb)[sx_nf(D)][64], int lane, int g, const float4* q_h, const float4* q_l,
+                                         SXState<D>* st, bool first, int nvalid_last, const DropK* drop = nullptr,
                                          const unsigned* dbase = nullptr, unsigned key0 = 0u) {
+  constexpr int KS = sx_ks(D), NV = D / 16, VF = 4 * KS;      // VF: the first V^T fragment of a pair's image
   float sc[NP][QT][8];
 #pragma unroll
   for (int pp = 0; pp < NP; ++pp) {
-    const float4 ka_h = fb[pp][0][lane], ka_l = fb[pp][1][lane], kb_h = fb[pp][2][lane], kb_l = fb[pp][3][lane];
+    float4 ka_h[KS], ka_l[KS], kb_h[KS], kb_l[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      ka_h[ks] = fb[pp][4 * ks + 0][lane]; ka_l[ks] = fb[pp][4 * ks + 1][lane];
+      kb_h[ks] = fb[pp][4 * ks + 2][lane]; kb_l[ks] = fb[pp][4 * ks + 3][lane];
+    }
     f32x4 sa[QT], sb[QT];
 #pragma unroll
-    for (int u = 0; u < QT; ++u) { sa[u] = MFMAH(ka_h, q_h[u], st[u].negm); sb[u] = MFMAH(kb_h, q_h[u], st[u].negm); }
+    for (int u = 0; u < QT; ++u) { sa[u] = MFMAH(ka_h[0], q_h[u * KS], st[u].negm); sb[u] = MFMAH(kb_h[0], q_h[u * KS], st[u].negm); }
 #pragma unroll
-    for (int u = 0; u < QT; ++u) { sa[u] = MFMAH(ka_l, q_h[u], sa[u]); sb[u] = MFMAH(kb_l, q_h[u], sb[u]); }
+    for (int ks = 1; ks < KS; ++ks)
 #pragma unroll
-    for (int u = 0; u < QT; ++u) { sa[u] = MFMAH(ka_h, q_l[u], sa[u]); sb[u] = MFMAH(kb_h, q_l[u], sb[u]); }
+      for (int u = 0; u < QT; ++u) { sa[u] = MFMAH(ka_h[ks], q_h[u * KS + ks], sa[u]); sb[u] = MFMAH(kb_h[ks], q_h[u * KS + ks], sb[u]); }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int u = 0; u < QT; ++u) { sa[u] = MFMAH(ka_l[ks], q_h[u * KS + ks], sa[u]); sb[u] = MFMAH(kb_l[ks], q_h[u * KS + ks], sb[u]); }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int u = 0; u < QT; ++u) { sa[u] = MFMAH(ka_h[ks], q_l[u * KS + ks], sa[u]); sb[u] = MFMAH(kb_h[ks], q_l[u * KS + ks], sb[u]); }
     // sc[i] = log2(e) * S^T[key0 + 8g + i][query r] + negm
 #pragma unroll
     for (int u = 0; u < QT; ++u)
@@ -388,7 +445,9 @@ __device__ __forceinline__ void sx_chunk(const float4 (*fb)[8][64], int lane, in
       for (int pp = 0; pp < NP; ++pp)
 #pragma unroll
         for (int i = 0; i < 8; ++i) sc[pp][u][i] -= delta;
-      st[u].o0 *= alpha; st[u].o1 *= alpha; st[u].lsum *= alpha; st[u].l *= alpha;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) st[u].o[j] *= alpha;
+      st[u].lsum *= alpha; st[u].l *= alpha;
       st[u].negm -= delta;
     }
   }
@@ -397,7 +456,9 @@ __device__ __forceinline__ void sx_chunk(const float4 (*fb)[8][64], int lane, in
   (void)ones;
 #pragma unroll
   for (int pp = 0; pp < NP; ++pp) {
-    const float4 v0h = fb[pp][4][lane], v0l = fb[pp][5][lane], v1h = fb[pp][6][lane], v1l = fb[pp][7][lane];
+    float4 vh[NV], vl[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { vh[j] = fb[pp][VF + 2 * j][lane]; vl[j] = fb[pp][VF + 2 * j + 1][lane]; }
 #pragma unroll
     for (int u = 0; u < QT; ++u) {
       float p[8];
@@ -427,23 +488,28 @@ __device__ __forceinline__ void sx_chunk(const float4 (*fb)[8][64], int lane, in
       sx_split1(p, p_h, p_l);
 #endif
       // O^T[d][q] += V^T[d][key] P^T[key][q];  l[q] += sum over the keys
-      st[u].o0 = MFMAH(v0h, p_h, st[u].o0); st[u].o1 = MFMAH(v1h, p_h, st[u].o1);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) st[u].o[j] = MFMAH(vh[j], p_h, st[u].o[j]);
       if (SX_L_MFMA) st[u].lsum = MFMAH(ones, p_h, st[u].lsum);
-      st[u].o0 = MFMAH(v0l, p_h, st[u].o0); st[u].o1 = MFMAH(v1l, p_h, st[u].o1);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) st[u].o[j] = MFMAH(vl[j], p_h, st[u].o[j]);
 #ifndef SX_NO_PLO
-      st[u].o0 = MFMAH(v0h, p_l, st[u].o0); st[u].o1 = MFMAH(v1h, p_l, st[u].o1);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) st[u].o[j] = MFMAH(vh[j], p_l, st[u].o[j]);
       if (SX_L_MFMA) st[u].lsum = MFMAH(ones, p_l, st[u].lsum);
 #endif
     }
   }
 }
 
-template <int QT, bool DROP = false>
-__global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(SX_OCC, SX_OCC))) void self_attn_x_kernel(
+template <int D, int QT, bool DROP = false>
+__global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(sx_occ(D), sx_occ(D)))) void self_attn_x_kernel(
     const float* __restrict__ q, const float* __restrict__ k, int ld, const float* __restrict__ vt, int ldt,
     float* __restrict__ out, int ldo, int Q, int C, int H, int BH, DropK drop, PreGatherK pg) {
+  static_assert(D == 16 || D == 32 || D == 64, "head dimension");
   constexpr int QW = 16 * QT * SX_NW;                       // queries per workgroup
-  __shared__ float4 frag[2][SX_CP][8][64];
+  constexpr int SX_CP = sx_cp(D), KS = sx_ks(D), NV = D / 16, NF = sx_nf(D);
+  __shared__ float4 frag[2][SX_CP][NF][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if constexpr (!DROP) {
     // round 6: the LAST pg.nblocks workgroups of the launch gather the camera taps of the decoder chain that follows
@@ -470,22 +536,37 @@ __global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(SX_O
   const size_t brow = (size_t)b * Q;
   const int q0 = qg * QW + wave * 16 * QT;
   const bool active = q0 < Q;                                             // a wave without a real query only stages
-  // the thread's staging tasks of a pair: 256 tasks of 32 bytes (tasks 0..127: key t >> 2 of K, channel group t & 3;
-  // 128..255: channel (t - 128) >> 2 of V^T, key group t & 3), task t + i * threads for thread t
-  constexpr int NT = SX_NW * 64, TPT = NT >= 256 ? 1 : 256 / NT;
-  const bool stager = tid < 256;
+  // the thread's staging tasks of a pair: 8 D tasks of 32 bytes (D = 32: tasks 0..127: key t >> 2 of K, channel group
+  // t & 3; 128..255: channel (t - 128) >> 2 of V^T, key group t & 3; in general 4 D tasks each, D / 8 channel groups per
+  // key), task t + i * threads for thread t
+  constexpr int NTASK = 8 * D, NT = SX_NW * 64, TPT = NT >= NTASK ? 1 : NTASK / NT;
+  constexpr int CG = D / 8, CG_SHIFT = D == 64 ? 3 : D == 32 ? 2 : 1;      // channel groups of a key
+  static_assert((NTASK / 2) % 64 == 0, "a wave's 64 tasks lie on one side");
+  const bool stager = tid < NTASK;
   bool is_k[TPT];
   int gg[TPT], rowi[TPT], dfrag[TPT], dlane[TPT];
   const float* src[TPT];
 #pragma unroll
   for (int tk = 0; tk < TPT; ++tk) {
     const int t = tid + tk * NT;
-    is_k[tk] = __builtin_amdgcn_readfirstlane(t) < 128;                 // (wave-uniform: a wave's 64 tasks lie on one side)
-    const int tt = t & 127;
-    gg[tk] = tt & 3; rowi[tk] = tt >> 2;                                // K: key `rowi` of the pair; V^T: channel `rowi`
-    dfrag[tk] = is_k[tk] ? 2 * ((rowi[tk] >> 2) & 1) : 4 + 2 * (rowi[tk] >> 4);
-    dlane[tk] = is_k[tk] ? 16 * gg[tk] + 4 * (rowi[tk] >> 3) + (rowi[tk] & 3) : 16 * gg[tk] + (rowi[tk] & 15);
-    src[tk] = is_k[tk] ? k + brow * ld + h * 32 + 8 * gg[tk] : vt + ((size_t)b * C + h * 32 + rowi[tk]) * ldt + 8 * gg[tk];
+    is_k[tk] = __builtin_amdgcn_readfirstlane(t) < NTASK / 2;           // (wave-uniform: a wave's 64 tasks lie on one side)
+    const int tt = t & (NTASK / 2 - 1);
+    // K: key `rowi` of the pair, channel group `gg` (k-step gg >> 2, lane group gg & 3); V^T: channel `rowi`, key group `gg`
+    if constexpr (CG == 4) { gg[tk] = tt & 3; rowi[tk] = tt >> 2; }
+    else { gg[tk] = is_k[tk] ? tt & (CG - 1) : tt & 3; rowi[tk] = is_k[tk] ? tt >> CG_SHIFT : tt >> 2; }
+    const int ks = KS == 1 ? 0 : gg[tk] >> 2, lg = KS == 1 ? gg[tk] : gg[tk] & 3;      // (K tasks) k-step, lane group
+    dfrag[tk] = is_k[tk] ? 4 * ks + 2 * ((rowi[tk] >> 2) & 1) : 4 * KS + 2 * (rowi[tk] >> 4);
+    dlane[tk] = is_k[tk] ? 16 * lg + 4 * (rowi[tk] >> 3) + (rowi[tk] & 3) : 16 * gg[tk] + (rowi[tk] & 15);
+    src[tk] = is_k[tk] ? k + brow * ld + h * D + 8 * gg[tk] : vt + ((size_t)b * C + h * D + rowi[tk]) * ldt + 8 * gg[tk];
+  }
+  if constexpr (D == 16) {
+    // channels 16 .. 31 of the k = 32 score products do not exist: lane groups 2 and 3 of every K fragment stay zero
+    // (the staging tasks write lane groups 0 and 1 only), and so do those of the Q fragments below
+    static_assert(D != 16 || (KS == 1 && NT % 32 == 0), "one k-step: K fragments 0 .. 3 of a pair");
+    for (int i = tid; i < 2 * SX_CP * 4 * 32; i += NT) {
+      const int f = i >> 5;                                 // (buffer, pair, K fragment), 32 upper lanes each
+      frag[f / (4 * SX_CP)][(f >> 2) % SX_CP][f & 3][32 + (i & 31)] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
   }
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
   auto fetch = [&](int j, int tk, float4& x0, float4& x1) {
@@ -525,8 +606,8 @@ __global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(SX_O
       for (int tk = 0; tk < TPT; ++tk)
         if (pp < np) fetch(pp, tk, x[pp][tk][0], x[pp][tk][1]);
   }
-  float4 q_h[QT], q_l[QT];
-  SXState st[QT];
+  float4 q_h[QT * KS], q_l[QT * KS];
+  SXState<D> st[QT];
   unsigned dbase[QT];
   if (DROP) drop.seed += (unsigned long long)b * drop.seed_stride;
 #pragma unroll
@@ -534,13 +615,24 @@ __global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(SX_O
     const int qrow = min(q0 + 16 * u + r, Q - 1);                         // (rows past Q: a copy of the last query, not stored)
     // (a batch of frames with per-sample seeds: the index is the one sample b has when it is launched alone)
     dbase[u] = DROP ? (((drop.rows_per_sample ? 0u : (unsigned)b) * (unsigned)H + (unsigned)h) * (unsigned)Q + (unsigned)qrow) * (unsigned)Q + 8u * (unsigned)g : 0u;
-    const float* qp = q + (brow + qrow) * ld + h * 32 + 8 * g;
+    if constexpr (D == 16) {
+      const float* qp = q + (brow + qrow) * ld + h * D + 8 * (g & 1);
+      sx_split(ld4(qp), ld4(qp + 4), q_h[u], q_l[u]);
+      if (g >= 2) q_h[u] = q_l[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const float* qp = q + (brow + qrow) * ld + h * D + 32 * ks + 8 * g;
 #ifdef SX_Q_NT
-    sx_split(ldg4_stream(qp), ldg4_stream(qp + 4), q_h[u], q_l[u]);      // (round-6 experiment: a query row is read by one workgroup only)
+        sx_split(ldg4_stream(qp), ldg4_stream(qp + 4), q_h[u * KS + ks], q_l[u * KS + ks]);      // (round-6 experiment: a query row is read by one workgroup only)
 #else
-    sx_split(ld4(qp), ld4(qp + 4), q_h[u], q_l[u]);
+        sx_split(ld4(qp), ld4(qp + 4), q_h[u * KS + ks], q_l[u * KS + ks]);
 #endif
-    st[u].o0 = st[u].o1 = st[u].lsum = st[u].negm = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) st[u].o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    st[u].lsum = st[u].negm = f32x4{0.f, 0.f, 0.f, 0.f};
     st[u].l = 0.0f;
   }
   if (stager) {
@@ -571,12 +663,13 @@ __global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(SX_O
     if (active) {
       const int left = np - c * SX_CP;                 // pairs in this chunk: SX_CP, or fewer in the last one
       const int nvalid_last = min(32, Q - 32 * (c * SX_CP + min(left, SX_CP) - 1));
-      static_assert(SX_CP == 2, "the chunk dispatch below is written for two pairs");
+      static_assert(SX_CP == 1 || SX_CP == 2, "the chunk dispatch below is written for one or two pairs");
       const unsigned key0 = 32u * (unsigned)(c * SX_CP);
-      if (SX_NPC == 2 && left >= 2) sx_chunk<QT, 2, DROP>(frag[buf], lane, g, q_h, q_l, st, c == 0, nvalid_last, &drop, dbase, key0);
+      if constexpr (SX_CP == 1) sx_chunk<D, QT, 1, DROP>(frag[buf], lane, g, q_h, q_l, st, c == 0, nvalid_last, &drop, dbase, key0);
+      else if (SX_NPC == 2 && left >= 2) sx_chunk<D, QT, 2, DROP>(frag[buf], lane, g, q_h, q_l, st, c == 0, nvalid_last, &drop, dbase, key0);
       else {
-        sx_chunk<QT, 1, DROP>(frag[buf], lane, g, q_h, q_l, st, c == 0, left >= 2 ? 32 : nvalid_last, &drop, dbase, key0);
-        if (left >= 2) sx_chunk<QT, 1, DROP>(frag[buf] + 1, lane, g, q_h, q_l, st, false, nvalid_last, &drop, dbase, key0 + 32u);
+        sx_chunk<D, QT, 1, DROP>(frag[buf], lane, g, q_h, q_l, st, c == 0, left >= 2 ? 32 : nvalid_last, &drop, dbase, key0);
+        if (left >= 2) sx_chunk<D, QT, 1, DROP>(frag[buf] + 1, lane, g, q_h, q_l, st, false, nvalid_last, &drop, dbase, key0 + 32u);
       }
     }
 #endif
@@ -598,9 +691,10 @@ __global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(SX_O
       float l = st[u].lsum[0];                         // SX_L_MFMA: every row of the ones-product holds the sum
       if (!SX_L_MFMA) { l = st[u].l; l += __shfl_xor(l, 16); l += __shfl_xor(l, 32); }   // the lane's keys 8g .. 8g + 7 of every pair
       const float inv = 1.0f / l;
-      float* op = out + (brow + qrow) * ldo + h * 32 + 4 * g;
-      st4(op, make_float4(st[u].o0[0] * inv, st[u].o0[1] * inv, st[u].o0[2] * inv, st[u].o0[3] * inv));
-      st4(op + 16, make_float4(st[u].o1[0] * inv, st[u].o1[1] * inv, st[u].o1[2] * inv, st[u].o1[3] * inv));
+      float* op = out + (brow + qrow) * ldo + h * D + 4 * g;
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+        st4(op + 16 * j, make_float4(st[u].o[j][0] * inv, st[u].o[j][1] * inv, st[u].o[j][2] * inv, st[u].o[j][3] * inv));
     }
   }
 }
@@ -608,54 +702,74 @@ __global__ __launch_bounds__(SX_NW * 64) __attribute__((amdgpu_waves_per_eu(SX_O
 // q, k rows [B*Q, ld] (q pre-scaled), vt [B, C, ldt] fp32 -> out [B*Q, C]: the operands of launch_self_attn_core
 void fill_camk(const CamSampleArgs& a, CamK& p);   // cam_sample.hip
 
+// Head dimension D: 16, 32 or 64; head h is at column h * D of the q / k rows and at rows h * D .. of V^T, C = H * D.
+#define TC_HEAD_DIM_OK(D) ((D) == 16 || (D) == 32 || (D) == 64)
+
+template <int D>
+static void launch_x(bool dropk, int nblocks, hipStream_t s, const float* q, const float* k, int ld, const float* vt, int ldt,
+                     float* out, int ldo, int Q, int H, int BH, const DropK& drop, const PreGatherK& pg) {
+  constexpr int QT = SX_QT_VALUE;
+  if (dropk) hipLaunchKernelGGL((self_attn_x_kernel<D, QT, true>), dim3(nblocks), dim3(SX_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q, H * D, H, BH, drop, pg);
+  else hipLaunchKernelGGL((self_attn_x_kernel<D, QT, false>), dim3(nblocks), dim3(SX_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q, H * D, H, BH, drop, pg);
+}
+
 int launch_self_attn_core_x(const float* q, const float* k, int ld, const float* vt, int ldt, float* out, int ldo,
-                            int B, int Q, int H, hipStream_t s, const DropK* drop, const PreGatherArgs* pregather) {
+                            int B, int Q, int H, int D, hipStream_t s, const DropK* drop, const PreGatherArgs* pregather) {
   TC_REQUIRE(Q > 0 && B > 0 && H > 0, "self_attn(f16x2): empty problem");
+  TC_REQUIRE(TC_HEAD_DIM_OK(D), "self_attn(f16x2): head dimension %d (16, 32 and 64 supported)", D);
   TC_REQUIRE((ldt & 3) == 0 && ldt >= ((Q + 15) / 16) * 16, "self_attn(f16x2): ldt=%d too small for Q=%d", ldt, Q);
   constexpr int QT = SX_QT_VALUE, QW = 16 * QT * SX_NW;
   const int BH = B * H, Gf = Q / QW, G = (Q + QW - 1) / QW;
   const int nattn = BH * Gf + (G > Gf ? BH : 0);
   PreGatherK pg;
   memset(&pg, 0, sizeof(pg));
-  if (drop != nullptr && drop->thr != 0) {
+  const bool dropk = drop != nullptr && drop->thr != 0;
+  if (dropk) {
     TC_REQUIRE(pregather == nullptr, "self_attn(f16x2): the pre-gather rides in eval launches only");
     TC_REQUIRE((unsigned long long)(drop->rows_per_sample ? 1 : B) * H * Q * Q < (1ull << 32),
-               "self_attn(f16x2): dropout index space (B*H*Q*Q) exceeds 32 bits");
-    hipLaunchKernelGGL((self_attn_x_kernel<QT, true>), dim3(nattn), dim3(SX_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q, H * 32, H, BH, *drop, pg);
-  } else {
-    if (pregather != nullptr) {
-      const PreGatherArgs& a = *pregather;
-      TC_REQUIRE(a.out != nullptr && a.mask != nullptr && a.M > 0, "self_attn(f16x2): pre-gather buffers");
-      TC_REQUIRE(a.cam.C == 256 && a.cam.feats.num_levels == 4 && a.cam.num_cams <= 8, "self_attn(f16x2): pre-gather shape");
-      for (int l = 0; l < a.cam.feats.num_levels; ++l)      // pixel indices are 32-bit in the kernels
-        TC_REQUIRE((long long)a.cam.B * a.cam.num_cams * a.cam.feats.H[l] * a.cam.feats.W[l] < (1ll << 31),
-                   "self_attn(f16x2): pre-gather level %d has too many pixels for one call", l);
-      fill_camk(a.cam, pg.cam);
-      pg.cam.vis = nullptr; pg.cam.out = nullptr; pg.cam.pair_counter = nullptr; pg.cam.logits = nullptr;
-      pg.M = a.M; pg.ref_mod = a.ref_mod; pg.out = a.out; pg.mask = a.mask;
-      pg.nblocks = (a.M + SX_PG_ROWS - 1) / SX_PG_ROWS;
-    }
-    hipLaunchKernelGGL((self_attn_x_kernel<QT, false>), dim3(nattn + pg.nblocks), dim3(SX_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q, H * 32, H, BH,
-                       DropK{0, 0, 1.0f, 0, 0, 0, 0, 0}, pg);
+               "self_attn(f16x2): dropout index space (B*H*Q*Q, H=%d) exceeds 32 bits", H);
+  } else if (pregather != nullptr) {
+    const PreGatherArgs& a = *pregather;
+    TC_REQUIRE(a.out != nullptr && a.mask != nullptr && a.M > 0, "self_attn(f16x2): pre-gather buffers");
+    TC_REQUIRE(a.cam.C == 256 && a.cam.feats.num_levels == 4 && a.cam.num_cams <= 8, "self_attn(f16x2): pre-gather shape");
+    for (int l = 0; l < a.cam.feats.num_levels; ++l)      // pixel indices are 32-bit in the kernels
+      TC_REQUIRE((long long)a.cam.B * a.cam.num_cams * a.cam.feats.H[l] * a.cam.feats.W[l] < (1ll << 31),
+                 "self_attn(f16x2): pre-gather level %d has too many pixels for one call", l);
+    fill_camk(a.cam, pg.cam);
+    pg.cam.vis = nullptr; pg.cam.out = nullptr; pg.cam.pair_counter = nullptr; pg.cam.logits = nullptr;
+    pg.M = a.M; pg.ref_mod = a.ref_mod; pg.out = a.out; pg.mask = a.mask;
+    pg.nblocks = (a.M + SX_PG_ROWS - 1) / SX_PG_ROWS;
   }
+  const DropK dk = dropk ? *drop : DropK{0, 0, 1.0f, 0, 0, 0, 0, 0};
+  if (D == 16) launch_x<16>(dropk, nattn + pg.nblocks, s, q, k, ld, vt, ldt, out, ldo, Q, H, BH, dk, pg);
+  else if (D == 32) launch_x<32>(dropk, nattn + pg.nblocks, s, q, k, ld, vt, ldt, out, ldo, Q, H, BH, dk, pg);
+  else launch_x<64>(dropk, nattn + pg.nblocks, s, q, k, ld, vt, ldt, out, ldo, Q, H, BH, dk, pg);
   return check_launch("self_attn(f16x2, staged)");
 }
 
+template <int D>
+static void launch_f32(bool dropk, dim3 grid, hipStream_t s, const float* q, const float* k, int ld, const float* vt, int ldt,
+                       float* out, int ldo, int Q, int H, const DropK& drop) {
+  constexpr int QT = 2;
+  if (dropk) hipLaunchKernelGGL((self_attn_kernel<D, QT, true>), grid, dim3(SA_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q, H * D, drop);
+  else hipLaunchKernelGGL((self_attn_kernel<D, QT, false>), grid, dim3(SA_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q, H * D, drop);
+}
+
 int launch_self_attn_core(const float* q, const float* k, int ld, const float* vt, int ldt,
-                          float* out, int ldo, int B, int Q, int H, hipStream_t s, const DropK* drop) {
+                          float* out, int ldo, int B, int Q, int H, int D, hipStream_t s, const DropK* drop) {
   TC_REQUIRE(Q > 0 && B > 0 && H > 0, "self_attn: empty problem");
+  TC_REQUIRE(TC_HEAD_DIM_OK(D), "self_attn: head dimension %d (16, 32 and 64 supported)", D);
   TC_REQUIRE((ldt & 3) == 0 && ldt >= ((Q + 15) / 16) * 16, "self_attn: ldt=%d too small for Q=%d", ldt, Q);
   constexpr int QT = 2;
   dim3 grid((Q + 16 * QT - 1) / (16 * QT), H, B);
-  if (drop != nullptr && drop->thr != 0) {
+  const bool dropk = drop != nullptr && drop->thr != 0;
+  if (dropk)
     TC_REQUIRE((unsigned long long)(drop->rows_per_sample ? 1 : B) * H * Q * Q < (1ull << 32),
-               "self_attn: dropout index space (B*H*Q*Q) exceeds 32 bits");
-    hipLaunchKernelGGL((self_attn_kernel<QT, true>), grid, dim3(SA_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q,
-                       H * 32, *drop);
-  } else {
-    hipLaunchKernelGGL((self_attn_kernel<QT, false>), grid, dim3(SA_NW * 64), 0, s, q, k, ld, vt, ldt, out, ldo, Q,
-                       H * 32, DropK{0, 0, 1.0f, 0, 0, 0, 0, 0});
-  }
+               "self_attn: dropout index space (B*H*Q*Q, H=%d) exceeds 32 bits", H);
+  const DropK dk = dropk ? *drop : DropK{0, 0, 1.0f, 0, 0, 0, 0, 0};
+  if (D == 16) launch_f32<16>(dropk, grid, s, q, k, ld, vt, ldt, out, ldo, Q, H, dk);
+  else if (D == 32) launch_f32<32>(dropk, grid, s, q, k, ld, vt, ldt, out, ldo, Q, H, dk);
+  else launch_f32<64>(dropk, grid, s, q, k, ld, vt, ldt, out, ldo, Q, H, dk);
   return check_launch("self_attn");
 }
 

@@ -138,18 +138,20 @@ RadarAttnArgs core_args(const tc_head_weights* w, int r, const Tape& t, const fl
   ra.qproj = t.L[r].qp; ra.ldq = C; ra.kv = t.L[r].kv; ra.ldkv = 2 * C;
   ra.centre_xy = r == 0 ? t.cxy : box_prev; ra.ld_c = r == 0 ? 2 : code;
   ra.box = box_prev; ra.code = code; ra.radar_xy = tokens; ra.ld_xy = w->radar_in_dims;
-  ra.B = B; ra.Q = w->num_query; ra.T = T; ra.C = C; ra.H = w->num_heads; ra.pad_mult = pad_mult;
+  ra.B = B; ra.Q = w->num_query; ra.T = T; ra.C = C; ra.H = TC_RADAR_HEADS; ra.pad_mult = pad_mult;
   ra.rmin = w->radar[r].radius_min; ra.rmax = w->radar[r].radius_max;
   ra.attn_out = t.L[r].ao; ra.hit_counts = t.L[r].hits;
-  ra.qscale = 1.0f / sqrtf((float)(C / w->num_heads));
+  ra.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   ra.drop = make_drop(drop_p, seed, 4u * r + 0u, (unsigned)w->num_radar_tokens_ref);
   return ra;
 }
 
 int check(const tc_head_weights* w, int B, int T) {
   TC_REQUIRE(w != nullptr && w->abi_version == TC_ABI_VERSION, "radar_train: bad weights struct");
-  TC_REQUIRE(w->embed_dims == 256 && w->num_heads == 8 && w->num_radar_layers == TC_MAX_RADAR_LAYERS,
-             "radar_train: embed_dims=%d heads=%d radar layers=%d", w->embed_dims, w->num_heads,
+  // (num_heads is the decoder self-attention's; the fusion attention trained here has TC_RADAR_HEADS heads)
+  TC_REQUIRE(w->embed_dims == 256 && heads_ok(w->num_heads) &&
+                 w->num_radar_layers == TC_MAX_RADAR_LAYERS,
+             "radar_train: embed_dims=%d num_heads=%d radar layers=%d", w->embed_dims, w->num_heads,
              w->num_radar_layers);
   TC_REQUIRE(B >= 1 && T >= 1 && (w->radar_in_dims & 3) == 0, "radar_train: B=%d T=%d", B, T);
   return 0;
@@ -292,7 +294,7 @@ int tc_radar_train_fwd_fused(const tc_head_weights* packed_view, const float* hs
   rc.qf = hs_last; rc.ref_last = ref_last; rc.box_m = last_box; rc.tokens = radar_tokens; rc.RI = RI;
   for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) { rc.kv[r] = t.L[r].kv; rc.w[r] = w->radar[r]; }
   rc.nlayers = w->num_radar_layers; rc.Q = Q; rc.T = T; rc.pad_mult = pad_mult; rc.code = code;
-  rc.ncls = w->num_classes; rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / w->num_heads));
+  rc.ncls = w->num_classes; rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   for (int i = 0; i < 6; ++i) rc.pc[i] = w->pc_range[i];
   rc.all_cls = all_cls_scores; rc.all_box = all_bbox_preds; rc.hits = t.L[0].hits;
   rc.tape = slots;
@@ -609,7 +611,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   a.d_cls = d_all_cls; a.d_box = d_all_box; a.loss_vals = layer_losses; a.loss_out = layer_losses_clean;
   a.tokens = radar_tokens; a.RI = RI; a.T = T; a.pad_mult = pad_mult;
   a.nlayers = TC_MAX_RADAR_LAYERS; a.Q = Q; a.M = rows; a.code = code; a.ncls = ncls;
-  a.qscale = 1.0f / sqrtf((float)(C / w->num_heads));
+  a.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   a.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
   {
     // deterministic mode: the chain reads the ranges from a device copy in the last words of the caller's shadow buffer

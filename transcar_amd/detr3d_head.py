@@ -295,6 +295,9 @@ class Detr3DHead(BaseModule):
         w.abi_version = L.TC_ABI_VERSION
         w.num_query, w.embed_dims = self.num_query, self.embed_dims
         w.num_heads = dec.layers[0].attentions[0].num_heads
+        if any(ly.attentions[0].num_heads != w.num_heads for ly in dec.layers):
+            raise NotImplementedError('MultiheadAttention: num_heads differs between decoder layers')
+        L.check_num_heads(w.num_heads)
         w.ffn_dims = dec.layers[0].ffns[0].feedforward_channels
         w.num_layers = dec.num_layers
         w.num_cams = dec.layers[0].attentions[1].num_cams
