@@ -39,6 +39,12 @@ extern "C" {
 /* Heads of the radar fusion attention (rf_multihead_attn{,2,3}): the reference builds it as
  * nn.MultiheadAttention(embed_dims, 8) (HEAD:129-171) whatever the decoder's self-attention uses. */
 #define TC_RADAR_HEADS 8
+/* Box decode (tc_box_decode_*): num_query * num_classes and max_num.  Up to the first pair the select keeps its keys in
+ * registers; beyond it, up to the second pair, a streaming kernel re-reads the logits in every pass of the select. */
+#define TC_BOX_DECODE_MAX_SCORES 12288
+#define TC_BOX_DECODE_MAX_NUM 512
+#define TC_BOX_DECODE_STREAM_MAX_SCORES (1 << 20)
+#define TC_BOX_DECODE_STREAM_MAX_NUM 2048
 #define TC_ABI_VERSION 13
 
 typedef void* tc_stream_t;
@@ -472,7 +478,13 @@ int tc_rowops_selfcheck(int n_blocks, unsigned long long seed, unsigned long lon
  * HEAD:1018): sigmoid, top-`max_num` of Q*num_classes scores, gather,
  * denormalise, centre-range mask, z -= h/2.
  *   boxes [B,max_num,9], scores [B,max_num], labels [B,max_num] (int),
- *   valid [B,max_num] (bytes: 1 = inside post_center_range) */
+ *   valid [B,max_num] (bytes: 1 = inside post_center_range); rows beyond Q*num_classes (max_num larger than
+ *   the number of scores): label -1, score 0, not valid.
+ * One workgroup per sample.  Q*num_classes <= TC_BOX_DECODE_MAX_SCORES and max_num <= TC_BOX_DECODE_MAX_NUM: the
+ * kernel that keeps a thread's keys in registers; any other shape up to TC_BOX_DECODE_STREAM_MAX_SCORES /
+ * TC_BOX_DECODE_STREAM_MAX_NUM: the streaming kernel (the same key, the same select, ties to the lower flat
+ * index: where both apply, the same bits).  Beyond those caps the call is refused.  num_classes itself is free
+ * (label = flat index % num_classes).  No workspace is used (workspace may be null). */
 size_t tc_box_decode_workspace_bytes(int B, int Q, int num_classes);
 int tc_box_decode_topk(const float* cls_scores /*[B,Q,num_classes]*/,
                        const float* bbox_preds /*[B,Q,code]*/, int B, int Q,
@@ -492,6 +504,18 @@ int tc_box_decode_kept(const float* cls_scores, const float* bbox_preds, int B, 
                        float score_threshold, int use_threshold, int z_shift,
                        float* kept_boxes, float* kept_scores, long long* kept_labels, int* kept_count,
                        tc_stream_t stream);
+/* The two entries above with the kernel chosen by the caller (tests, timing): path 0 by shape, as above; 1 the
+ * in-register kernel (refused beyond TC_BOX_DECODE_MAX_SCORES / TC_BOX_DECODE_MAX_NUM); 2 the streaming kernel. */
+int tc_box_decode_topk_path(const float* cls_scores, const float* bbox_preds, int B, int Q,
+                            int num_classes, int code_size, int max_num,
+                            const float* post_center_range /*host[6]*/,
+                            float* boxes, float* scores, int* labels, unsigned char* valid,
+                            void* workspace, size_t workspace_bytes, tc_stream_t stream, int path);
+int tc_box_decode_kept_path(const float* cls_scores, const float* bbox_preds, int B, int Q, int num_classes,
+                            int code_size, int max_num, const float* post_center_range /*host[6]*/,
+                            float score_threshold, int use_threshold, int z_shift,
+                            float* kept_boxes, float* kept_scores, long long* kept_labels, int* kept_count,
+                            tc_stream_t stream, int path);
 
 /* ---- the whole hot path: Detr3DHead.forward (HEAD:248-740), eval mode ----
  *   radar_tokens [B,T,36]: rows of the 36 hand-built features (HEAD:499-510),

@@ -60,6 +60,12 @@ TC_NUM_HEADS = (4, 8, 16)
 # heads of the radar fusion attention: nn.MultiheadAttention(embed_dims, 8) in the reference, whatever the decoder uses
 TC_RADAR_HEADS = 8
 
+# box decode: num_query * num_classes and max_num of the in-register kernel and of the streaming kernel that takes the
+# shapes beyond it (include/transcar_hip.h); path of tc_box_decode_*_path
+TC_BOX_DECODE_MAX_SCORES, TC_BOX_DECODE_MAX_NUM = 12288, 512
+TC_BOX_DECODE_STREAM_MAX_SCORES, TC_BOX_DECODE_STREAM_MAX_NUM = 1 << 20, 2048
+TC_DECODE_AUTO, TC_DECODE_REGISTERS, TC_DECODE_STREAM = 0, 1, 2
+
 
 def check_num_heads(num_heads):
     """The library's limit on the decoder MultiheadAttention's num_heads (4, 8
@@ -231,6 +237,9 @@ SIGNATURES = {
     'tc_box_decode_topk': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(_f), _vp,
                                 _vp, _vp, _vp, _vp, _sz, _vp]),
     'tc_box_decode_kept': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(_f), _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'tc_box_decode_topk_path': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(_f), _vp,
+                                     _vp, _vp, _vp, _vp, _sz, _vp, _i]),
+    'tc_box_decode_kept_path': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(_f), _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     'tc_head_workspace_bytes': (_sz, [_P(tc_head_weights), _i, _i]),
     'tc_cam_pregather_workspace_bytes': (_sz, [_P(tc_head_weights), _i]),
     'tc_head_packed_bytes': (_sz, [_P(tc_head_weights)]),

@@ -776,6 +776,24 @@ int tc_box_decode_kept(const float* cls_scores, const float* bbox_preds, int B, 
                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, as_stream(stream), &k);
 }
 
+int tc_box_decode_topk_path(const float* cls_scores, const float* bbox_preds, int B, int Q,
+                            int num_classes, int code_size, int max_num, const float* post_center_range,
+                            float* boxes, float* scores, int* labels, unsigned char* valid,
+                            void* workspace, size_t workspace_bytes, tc_stream_t stream, int path) {
+  return launch_box_decode(cls_scores, bbox_preds, B, Q, num_classes, code_size, max_num,
+                           post_center_range, boxes, scores, labels, valid, workspace,
+                           workspace_bytes, as_stream(stream), nullptr, path);
+}
+
+int tc_box_decode_kept_path(const float* cls_scores, const float* bbox_preds, int B, int Q, int num_classes, int code_size,
+                            int max_num, const float* post_center_range, float score_threshold, int use_threshold,
+                            int z_shift, float* kept_boxes, float* kept_scores, long long* kept_labels, int* kept_count,
+                            tc_stream_t stream, int path) {
+  BoxDecodeKept k{kept_boxes, kept_scores, kept_labels, kept_count, score_threshold, use_threshold, z_shift};
+  return launch_box_decode(cls_scores, bbox_preds, B, Q, num_classes, code_size, max_num, post_center_range,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, 0, as_stream(stream), &k, path);
+}
+
 size_t tc_head_packed_bytes(const tc_head_weights* w) {
   if (check_dims(w) != 0) return 0;
   bool refine;

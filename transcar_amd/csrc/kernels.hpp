@@ -308,7 +308,8 @@ struct BoxDecodeKept {
 };
 int launch_box_decode(const float* cls, const float* box, int B, int Q, int ncls, int code,
                       int max_num, const float* pcr6_host, float* boxes, float* scores, int* labels,
-                      unsigned char* valid, void* ws, size_t ws_bytes, hipStream_t s, const BoxDecodeKept* kept = nullptr);
+                      unsigned char* valid, void* ws, size_t ws_bytes, hipStream_t s, const BoxDecodeKept* kept = nullptr,
+                      int path = 0);     // 0: by shape, 1: box_decode_kernel (keys in registers), 2: box_decode_stream_kernel
 size_t box_decode_ws_bytes(int B, int Q, int ncls);
 
 }  // namespace tc

@@ -525,9 +525,11 @@ def radar_check_fits(count, T):
                                  'larger T (up to %d)' % (n, T, T - 1, R.NUM_RADAR_TOKENS))
 
 
-def box_decode_topk(cls_scores, bbox_preds, post_center_range, max_num=300):
+def box_decode_topk(cls_scores, bbox_preds, post_center_range, max_num=300, path=0):
     """NMSFreeCoder.decode_single + z-shift (CODER:39-90, HEAD:1018) for a
-    batch: fixed-size outputs + a validity mask."""
+    batch: fixed-size outputs + a validity mask.  path: 0 the kernel the shape
+    asks for, 1 the in-register kernel, 2 the streaming kernel (the same bits
+    where both apply)."""
     _chk(cls_scores, 'cls_scores'); _chk(bbox_preds, 'bbox_preds')
     B, Q, ncls = cls_scores.shape
     dev = cls_scores.device
@@ -535,18 +537,18 @@ def box_decode_topk(cls_scores, bbox_preds, post_center_range, max_num=300):
     scores = torch.empty((B, max_num), dtype=torch.float32, device=dev)
     labels = torch.empty((B, max_num), dtype=torch.int32, device=dev)
     valid = torch.empty((B, max_num), dtype=torch.uint8, device=dev)
-    L.check(L.lib().tc_box_decode_topk(
+    L.check(L.lib().tc_box_decode_topk_path(
         _p(cls_scores), _p(bbox_preds), B, Q, ncls, bbox_preds.shape[-1],
         max_num, L.f6(post_center_range), _p(boxes), _p(scores), _p(labels),
-        _p(valid), None, 0, _stream()), 'tc_box_decode_topk')
+        _p(valid), None, 0, _stream(), int(path)), 'tc_box_decode_topk')
     return boxes, scores, labels, valid
 
 
 def box_decode_kept(cls_scores, bbox_preds, post_center_range, max_num=300, score_threshold=None, z_shift=True,
-                    count_out=None, out=None):
+                    count_out=None, out=None, path=0):
     """NMSFreeCoder.decode_single for a batch (tc_box_decode_kept): the kept rows (inside post_center_range, above
     the score threshold) compacted in score order -> boxes [B,max_num,9], scores [B,max_num], labels [B,max_num]
-    (int64) and count [B] (int32, device); rows beyond count[b] are not written."""
+    (int64) and count [B] (int32, device); rows beyond count[b] are not written.  path: as box_decode_topk."""
     _chk(cls_scores, 'cls_scores'); _chk(bbox_preds, 'bbox_preds')
     B, Q, ncls = cls_scores.shape
     dev = cls_scores.device
@@ -563,10 +565,10 @@ def box_decode_kept(cls_scores, bbox_preds, post_center_range, max_num=300, scor
     # the head's range status, so that ONE small D2H reads both)
     count = count_out if count_out is not None else torch.empty((B,), dtype=torch.int32, device=dev)
     use_thr = bool(score_threshold)                   # CODER:73: `if self.score_threshold:` -- None and 0 are off
-    L.check(L.lib().tc_box_decode_kept(
+    L.check(L.lib().tc_box_decode_kept_path(
         _p(cls_scores), _p(bbox_preds), B, Q, ncls, bbox_preds.shape[-1], max_num, L.f6(post_center_range),
         float(score_threshold) if use_thr else 0.0, int(use_thr), int(bool(z_shift)),
-        _p(boxes), _p(scores), _p(labels), _p(count), _stream()), 'tc_box_decode_kept')
+        _p(boxes), _p(scores), _p(labels), _p(count), _stream(), int(path)), 'tc_box_decode_kept')
     return boxes, scores, labels, count
 
 
