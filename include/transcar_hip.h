@@ -45,6 +45,17 @@ extern "C" {
 #define TC_BOX_DECODE_MAX_NUM 512
 #define TC_BOX_DECODE_STREAM_MAX_SCORES (1 << 20)
 #define TC_BOX_DECODE_STREAM_MAX_NUM 2048
+/* Hungarian assignment on the device (tc_lsa_assign*): num_query and ground-truth boxes per sample.  Up to the
+ * SMALL pair the kernel that keeps a sample's costs in LDS (tc_lsa_assign, tc_lsa_assign_ex); beyond it, up to the
+ * first pair, the kernel that reads them from a transposed workspace (tc_lsa_assign_ws). */
+#define TC_LSA_MAX_QUERIES 4096
+#define TC_LSA_MAX_GT 512
+#define TC_LSA_SMALL_MAX_QUERIES 1024
+#define TC_LSA_SMALL_MAX_GT 128
+/* path of tc_lsa_assign_ws */
+#define TC_LSA_AUTO 0
+#define TC_LSA_SMALL 1
+#define TC_LSA_LARGE 2
 #define TC_ABI_VERSION 13
 
 typedef void* tc_stream_t;
@@ -758,7 +769,8 @@ int tc_dropout_mask(float dropout_p, unsigned long long seed, int site, size_t n
  * tc_match_cost: Hungarian cost for every decoder output in one launch,
  *   cost[l,b,q,g] = cls_weight * FocalLossCost(cls[l,b,q], label[b,g]) + reg_weight * |box[l,b,q,:10] - gt_norm[b,g]|_1
  *   (0 for g >= gt_counts[b]); gt_norm [B,Gmax,10], gt_labels [B,Gmax], gt_counts [B] (device).
- *   The assignment itself stays scipy's linear_sum_assignment on the host, as in the reference.
+ *   The assignment: tc_lsa_assign* below (on the device), or scipy's linear_sum_assignment on the host as in the
+ *   reference (shapes beyond TC_LSA_MAX_QUERIES / TC_LSA_MAX_GT).
  * tc_detr_loss_fwd_bwd: with assigned[l,b,q] = matched gt index or -1: sigmoid focal loss
  *   (mmdet FocalLoss, background = no target) and L1 loss of the matched box codes
  *   (code_weights [code] on the device; rows with a non-finite target are skipped), each
@@ -780,7 +792,7 @@ int tc_detr_loss_fwd_bwd(const float* all_cls, const float* all_box, int num_out
 /* tc_lsa_assign (round 4): the Hungarian assignment ITSELF on the device -- what ASSIGN:117-125 does with a D2H copy
  * and scipy.optimize.linear_sum_assignment on the host (0.30 ms of a 0.96 ms training iteration's critical path).
  * The algorithm scipy implements (shortest augmenting paths, Jonker-Volgenant in Crouse's rectangular form: the
- * ground-truth boxes are the rows), in float64 like scipy, one wavefront per (output, sample).
+ * ground-truth boxes are the rows), in float64 like scipy, one workgroup per (output, sample).
  *   cost      [num_outputs, B, Q, Gmax] from tc_match_cost; gt_counts [B] (device); Q <= 1024, Gmax <= 128, Gmax <= Q
  *   assigned  [num_outputs, B, Q] int: matched gt index or -1 (as HungarianAssigner3D's assigned_gt_inds - 1)
  *   num_pos   [num_outputs, 2] float or NULL: += the number of matched boxes, in both columns (zero first) -- the
@@ -798,6 +810,24 @@ int tc_lsa_assign(const float* cost, const int* gt_counts, int num_outputs, int 
  * (the status word travels back without a synchronisation). */
 int tc_lsa_assign_ex(const float* cost, const int* gt_counts, int num_outputs, int B, int Q, int Gmax, int* assigned,
                      float* num_pos, int* status, float* poison_losses, tc_stream_t stream);
+/* tc_lsa_assign_ex for Q <= TC_LSA_MAX_QUERIES, Gmax <= TC_LSA_MAX_GT, Gmax <= Q: the same algorithm, duals and tie
+ * order.  A shape within TC_LSA_SMALL_MAX_QUERIES / TC_LSA_SMALL_MAX_GT runs tc_lsa_assign_ex's kernel and needs no
+ * workspace.  A larger one does not fit LDS: a pre-pass over the whole chip transposes the costs into
+ * workspace = [num_outputs*B][Gmax][Qpad] floats (Qpad = Q rounded up to 64), looks for non-finite costs on the way
+ * (one flag word per problem behind the costs), and a kernel with 16 columns per thread reads row g as consecutive
+ * words.  Both launches (and the fill of the flag words) are stream-ordered and capturable; nothing allocates.
+ *   tc_lsa_workspace_bytes: roundup256(num_outputs*B*Gmax*Qpad*4) + roundup256(num_outputs*B*4); 0 for a shape that
+ *     needs none (tc_last_error is then empty: an accepted shape clears it); 0 with tc_last_error set for a shape
+ *     beyond the limits.  No device needed.  (path TC_LSA_LARGE at a
+ *     small shape needs the same formula's bytes.)
+ *   path: TC_LSA_AUTO the small kernel wherever it applies; TC_LSA_SMALL that kernel or a refusal; TC_LSA_LARGE the
+ *     workspace kernel at any accepted shape (the two give the same assignment, ties included).
+ * A shape beyond the limits, Gmax > Q, a NULL or short workspace where one is needed and an unknown path are refused
+ * before anything is launched. */
+size_t tc_lsa_workspace_bytes(int num_outputs, int B, int Q, int Gmax);
+int tc_lsa_assign_ws(const float* cost, const int* gt_counts, int num_outputs, int B, int Q, int Gmax, int* assigned,
+                     float* num_pos, int* status, float* poison_losses, void* workspace, size_t workspace_bytes,
+                     int path, tc_stream_t stream);
 /* tc_detr_loss_fwd_bwd with avg_factors = raw counts: the normalisers are max(count, 1) */
 int tc_detr_loss_fwd_bwd_counts(const float* all_cls, const float* all_box, int num_outputs, int B, int Q,
                                 int num_classes, int code_size, const float* gt_norm, const int* gt_labels,

@@ -66,6 +66,20 @@ TC_BOX_DECODE_MAX_SCORES, TC_BOX_DECODE_MAX_NUM = 12288, 512
 TC_BOX_DECODE_STREAM_MAX_SCORES, TC_BOX_DECODE_STREAM_MAX_NUM = 1 << 20, 2048
 TC_DECODE_AUTO, TC_DECODE_REGISTERS, TC_DECODE_STREAM = 0, 1, 2
 
+# Hungarian assignment on the device: num_query and boxes per sample of tc_lsa_assign_ws, and of the kernel that keeps a
+# sample's costs in LDS (tc_lsa_assign / _ex; no workspace); path of tc_lsa_assign_ws (include/transcar_hip.h)
+TC_LSA_MAX_QUERIES, TC_LSA_MAX_GT = 4096, 512
+TC_LSA_SMALL_MAX_QUERIES, TC_LSA_SMALL_MAX_GT = 1024, 128
+TC_LSA_AUTO, TC_LSA_SMALL, TC_LSA_LARGE = 0, 1, 2
+
+
+def lsa_large_workspace_bytes(num_outputs, B, Q, Gmax):
+    """The workspace of tc_lsa_assign_ws's large kernel, whatever the shape: the transposed costs [P][Gmax][Qpad]
+    (float, Qpad = Q rounded up to 64) and one flag word per problem, each rounded up to 256 bytes.
+    tc_lsa_workspace_bytes returns this for a shape beyond the small kernel's limits and 0 within them."""
+    P, qpad = num_outputs * B, (Q + 63) // 64 * 64
+    return (P * Gmax * qpad * 4 + 255) // 256 * 256 + (P * 4 + 255) // 256 * 256
+
 
 def check_num_heads(num_heads):
     """The library's limit on the decoder MultiheadAttention's num_heads (4, 8
@@ -300,6 +314,8 @@ SIGNATURES = {
                                          _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     'tc_lsa_assign': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'tc_lsa_assign_ex': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'tc_lsa_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'tc_lsa_assign_ws': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     'tc_sq_norm': (_i, [_vp, _sz, _vp, _vp]),
     'tc_adamw_step': (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _f,
                            _f, _vp, _vp]),

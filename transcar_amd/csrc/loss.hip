@@ -179,10 +179,21 @@ int launch_detr_loss(const LossK& p, hipStream_t s) {
 // last in its work list) -- same total cost, possibly another of the tied queries.  The order is a property of the
 // COLUMN, not of the thread that holds it: the one-wave build resolved ties the same way.
 // A non-finite cost (scipy raises ValueError) leaves the sample unassigned and sets *status.
+// Two instantiations.  <.., 4, 128> (Q <= 1024, at most 128 boxes: the configs' shapes) keeps ~12 KB of static LDS
+// beside a 140 KB dynamic cost tile.  <LSA_ROWS, 16, 512> (Q <= 4096, at most 512 boxes) holds 16 columns per thread
+// (v[] and spc[] are 64 VGPRs) and ~45 KB of static LDS; its matrix never fits LDS, so lsa_rows_kernel transposes the
+// costs into a [P][Gmax][Qpad] workspace first and a step reads its row as consecutive words of global memory (L2).
+// The tie order and the arg-min are the same code, so the two give the same assignment wherever both apply.
 constexpr int LSA_NT = 256;                        // threads per problem
 constexpr int LSA_COLS = 4;                        // columns per thread: Q <= LSA_NT * LSA_COLS = 1024
 constexpr int LSA_QMAX = LSA_NT * LSA_COLS;
 constexpr int LSA_GMAX = 128;                      // ground-truth boxes per sample
+constexpr int LSA_L_COLS = 16;                     // the large instantiation: Q <= 4096 (lsa_key holds j < 4096), ...
+constexpr int LSA_L_QMAX = LSA_NT * LSA_L_COLS;
+constexpr int LSA_L_GMAX = 512;                    // ... at most 512 boxes
+static_assert(LSA_L_QMAX == TC_LSA_MAX_QUERIES && LSA_L_GMAX == TC_LSA_MAX_GT, "include/transcar_hip.h");
+static_assert(LSA_QMAX == TC_LSA_SMALL_MAX_QUERIES && LSA_GMAX == TC_LSA_SMALL_MAX_GT, "include/transcar_hip.h");
+static_assert(LSA_L_COLS <= 32, "sc holds one bit per column of a thread");
 struct LsaK {
   const float* cost;                               // [P, Q, Gmax] (P = outputs x samples), 0 beyond a sample's count
   const int* gt_counts;                            // [B]
@@ -192,6 +203,8 @@ struct LsaK {
   int* status;                                     // += 1 per sample with a non-finite cost, or null
   float* poison;                                   // [outputs, 2] loss accumulators or null: NaN into the output's pair
                                                    // when a sample of it cannot be assigned (scipy would have raised)
+  const float* rows;                               // LSA_ROWS: [P, Gmax, Qpad], the costs transposed by lsa_rows_kernel
+  const int* flags;                                // LSA_ROWS: [P], != 0: the problem has a non-finite cost
 };
 
 __device__ __forceinline__ double wave_min_f64(double v) {
@@ -211,17 +224,21 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
 __device__ __forceinline__ unsigned lsa_key(int j, bool is_free) { return (is_free ? 0u : 1u << 20) | ((unsigned)(j & 63) << 10) | (unsigned)(j >> 6); }
 __device__ __forceinline__ int lsa_key_col(unsigned key) { return (int)((key >> 10) & 63u) + 64 * (int)(key & 1023u); }
 
-// LDS = true: the sample's costs are transposed into LDS first (a step then reads consecutive words); false (the
-// matrix does not fit: more than ~40 boxes at 900 queries): straight from global memory (L2), stride Gmax
-template <bool LDS>
+// Where a step reads its row of costs.  LSA_LDS: the sample's costs are transposed into LDS first (a step then reads
+// consecutive words); LSA_STRIDED (the matrix does not fit: more than ~40 boxes at 900 queries): straight from global
+// memory (L2), stride Gmax; LSA_ROWS: from the transposed workspace, consecutive words
+enum LsaSrc { LSA_LDS, LSA_STRIDED, LSA_ROWS };
+template <LsaSrc SRC, int COLS, int GMAX>
 __global__ __launch_bounds__(LSA_NT) void lsa_kernel(LsaK p) {
+  constexpr bool LDS = SRC == LSA_LDS;
+  constexpr int QMAX = LSA_NT * COLS;
   extern __shared__ __align__(16) float lsa_cost[];          // [G][Qpad] (transposed: a row = one ground-truth box)
-  __shared__ double u[LSA_GMAX];
-  __shared__ double spc_of_col4row[LSA_GMAX];
-  __shared__ int col4row[LSA_GMAX];
-  __shared__ int SR[LSA_GMAX];
-  __shared__ int path_s[LSA_QMAX];                           // column -> the row it was reached from (this row's search)
-  __shared__ int row4col_s[LSA_QMAX];                        // column -> its row, or -1
+  __shared__ double u[GMAX];
+  __shared__ double spc_of_col4row[GMAX];
+  __shared__ int col4row[GMAX];
+  __shared__ int SR[GMAX];
+  __shared__ int path_s[QMAX];                               // column -> the row it was reached from (this row's search)
+  __shared__ int row4col_s[QMAX];                            // column -> its row, or -1
   __shared__ double red_val[LSA_NT / 64];
   __shared__ unsigned red_key[LSA_NT / 64];
   __shared__ int bad_s;
@@ -233,27 +250,31 @@ __global__ __launch_bounds__(LSA_NT) void lsa_kernel(LsaK p) {
   for (int j = tid; j < Q; j += LSA_NT) out[j] = -1;
   if (G <= 0) return;                                         // (workgroup-uniform)
   if (tid == 0) bad_s = 0;
-  for (int j = tid; j < LSA_QMAX; j += LSA_NT) row4col_s[j] = -1;
+  for (int j = tid; j < QMAX; j += LSA_NT) row4col_s[j] = -1;
   __syncthreads();
   // the sample's costs, transposed into LDS (coalesced global reads: g fastest; 8 loads in flight per thread)
   const float* cg = p.cost + (size_t)prob * Q * p.Gmax;
   const int total = Q * p.Gmax;
   int bad = 0;
+  if constexpr (SRC == LSA_ROWS) {
+    bad = p.flags[prob];                            // (lsa_rows_kernel looked at every cost)
+  } else {
 #pragma unroll 1
-  for (int base = 0; base < total; base += LSA_NT * 8) {
-    float c[8];
+    for (int base = 0; base < total; base += LSA_NT * 8) {
+      float c[8];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int i = base + LSA_NT * t + tid;
-      c[t] = i < total ? ldg1(cg + i) : 0.0f;
-    }
+      for (int t = 0; t < 8; ++t) {
+        const int i = base + LSA_NT * t + tid;
+        c[t] = i < total ? ldg1(cg + i) : 0.0f;
+      }
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int i = base + LSA_NT * t + tid;
-      const int q = i / p.Gmax, g = i - q * p.Gmax;
-      if (i < total && g < G) {
-        bad |= !(fabsf(c[t]) <= 3.0e38f);
-        if (LDS) lsa_cost[g * Qpad + q] = c[t];
+      for (int t = 0; t < 8; ++t) {
+        const int i = base + LSA_NT * t + tid;
+        const int q = i / p.Gmax, g = i - q * p.Gmax;
+        if (i < total && g < G) {
+          bad |= !(fabsf(c[t]) <= 3.0e38f);
+          if (LDS) lsa_cost[g * Qpad + q] = c[t];
+        }
       }
     }
   }
@@ -265,16 +286,16 @@ __global__ __launch_bounds__(LSA_NT) void lsa_kernel(LsaK p) {
     if (tid < 2 && p.poison != nullptr) p.poison[2 * (prob / p.B) + tid] = __int_as_float(0x7fc00000);
     return;
   }
-  double v[LSA_COLS];
-  int row4col[LSA_COLS];
+  double v[COLS];
+  int row4col[COLS];
 #pragma unroll
-  for (int k = 0; k < LSA_COLS; ++k) { v[k] = 0.0; row4col[k] = -1; }
+  for (int k = 0; k < COLS; ++k) { v[k] = 0.0; row4col[k] = -1; }
   const double INF = __longlong_as_double(0x7FF0000000000000ll);
   for (int cur = 0; cur < G; ++cur) {
-    double spc[LSA_COLS];
+    double spc[COLS];
     unsigned sc = 0;                                // bit k: column tid + LSA_NT k has been scanned (left `remaining`)
 #pragma unroll
-    for (int k = 0; k < LSA_COLS; ++k) spc[k] = INF;
+    for (int k = 0; k < COLS; ++k) spc[k] = INF;
     for (int i = tid; i < G; i += LSA_NT) SR[i] = 0;
     __syncthreads();
     double minVal = 0.0;
@@ -283,13 +304,22 @@ __global__ __launch_bounds__(LSA_NT) void lsa_kernel(LsaK p) {
       if (tid == 0) SR[i] = 1;
       const double ui = u[i];
       const float* crow = lsa_cost + i * Qpad;
+      float cg_row[SRC == LSA_ROWS ? COLS : 1];       // LSA_ROWS: the thread's words of row i, all loads in flight at once
+      if constexpr (SRC == LSA_ROWS) {
+        const float* grow = p.rows + ((size_t)prob * p.Gmax + i) * Qpad;
+#pragma unroll
+        for (int k = 0; k < COLS; ++k) {
+          const int j = tid + LSA_NT * k;
+          cg_row[k] = j < Q ? ldg1(grow + j) : 0.0f;
+        }
+      }
       double best = INF;
       unsigned bkey = 0xFFFFFFFFu;
 #pragma unroll
-      for (int k = 0; k < LSA_COLS; ++k) {
+      for (int k = 0; k < COLS; ++k) {
         const int j = tid + LSA_NT * k;
         if (j < Q && !((sc >> k) & 1u)) {
-          const float cij = LDS ? crow[j] : ldg1(cg + (size_t)j * p.Gmax + i);
+          const float cij = LDS ? crow[j] : SRC == LSA_ROWS ? cg_row[SRC == LSA_ROWS ? k : 0] : ldg1(cg + (size_t)j * p.Gmax + i);
           const double r = minVal + (double)cij - ui - v[k];
           if (r < spc[k]) { spc[k] = r; path_s[j] = i; }
           const unsigned key = lsa_key(j, row4col[k] < 0);
@@ -324,7 +354,7 @@ __global__ __launch_bounds__(LSA_NT) void lsa_kernel(LsaK p) {
     // dual update (scipy: u[cur] += minVal; u[i] += minVal - spc[col4row[i]] for the other scanned rows;
     // v[j] -= minVal - spc[j] for the scanned columns)
 #pragma unroll
-    for (int k = 0; k < LSA_COLS; ++k) {
+    for (int k = 0; k < COLS; ++k) {
       if ((sc >> k) & 1u) {
         v[k] -= minVal - spc[k];
         if (row4col[k] >= 0) spc_of_col4row[row4col[k]] = spc[k];      // the row assigned to a scanned column
@@ -349,7 +379,7 @@ __global__ __launch_bounds__(LSA_NT) void lsa_kernel(LsaK p) {
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < LSA_COLS; ++k) row4col[k] = row4col_s[tid + LSA_NT * k];
+    for (int k = 0; k < COLS; ++k) row4col[k] = row4col_s[tid + LSA_NT * k];
   }
   for (int r = tid; r < G; r += LSA_NT) out[col4row[r]] = r;
   if (tid < 2 && p.num_pos != nullptr) atomicAdd(p.num_pos + 2 * (prob / p.B) + tid, (float)G);
@@ -364,17 +394,96 @@ int launch_lsa(const float* cost, const int* gt_counts, int P, int B, int Q, int
   const bool in_lds = lds <= 140 * 1024;        // (beside ~12 KB of static LDS)
   static DeviceOnce once;
   if (const int once_dev = once.need(); once_dev >= 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lsa_kernel<true>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lsa_kernel<LSA_LDS, LSA_COLS, LSA_GMAX>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
     if (e != hipSuccess) { set_error("lsa: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     once.done(once_dev);
   }
   LsaK p;
   p.cost = cost; p.gt_counts = gt_counts; p.P = P; p.B = B; p.Q = Q; p.Gmax = Gmax; p.assigned = assigned;
-  p.num_pos = num_pos; p.status = status; p.poison = poison;
-  if (in_lds) hipLaunchKernelGGL(lsa_kernel<true>, dim3(P), dim3(LSA_NT), lds, s, p);
-  else hipLaunchKernelGGL(lsa_kernel<false>, dim3(P), dim3(LSA_NT), 0, s, p);
+  p.num_pos = num_pos; p.status = status; p.poison = poison; p.rows = nullptr; p.flags = nullptr;
+  if (in_lds) hipLaunchKernelGGL((lsa_kernel<LSA_LDS, LSA_COLS, LSA_GMAX>), dim3(P), dim3(LSA_NT), lds, s, p);
+  else hipLaunchKernelGGL((lsa_kernel<LSA_STRIDED, LSA_COLS, LSA_GMAX>), dim3(P), dim3(LSA_NT), 0, s, p);
   return check_launch("lsa");
+}
+
+// ---- beyond 1024 queries / 128 boxes: transposed costs in a workspace, then lsa_kernel<LSA_ROWS, 16, 512> ----------
+// cost [P][Q][Gmax] -> rows [P][Gmax][Qpad] through a 64 x 64 LDS tile (reads coalesced along g, writes along q), one
+// workgroup per tile over the whole chip; the pad columns q >= Q are written as 0, the rows g >= the sample's count
+// are not written (the solver never reads them).  scipy's check for non-finite entries happens here, on the same
+// entries lsa_kernel looks at (g < count): flags[prob] = 1 (zeroed by the launcher).
+constexpr int LSA_TILE = 64;
+struct LsaTransK { const float* cost; const int* gt_counts; int B, Q, Gmax, Qpad; float* rows; int* flags; };
+__global__ __launch_bounds__(LSA_NT) void lsa_rows_kernel(LsaTransK p) {
+  __shared__ float tile[LSA_TILE][LSA_TILE + 1];
+  const int prob = blockIdx.z, q0 = blockIdx.x * LSA_TILE, g0 = blockIdx.y * LSA_TILE;
+  const int G = min(p.gt_counts[prob % p.B], p.Gmax);
+  if (g0 >= G) return;                                        // (workgroup-uniform)
+  const int tx = threadIdx.x & (LSA_TILE - 1), ty = threadIdx.x / LSA_TILE;
+  const float* src = p.cost + (size_t)prob * p.Q * p.Gmax;
+  int bad = 0;
+#pragma unroll
+  for (int t = 0; t < LSA_TILE * LSA_TILE / LSA_NT; ++t) {
+    const int r = ty + t * (LSA_NT / LSA_TILE), q = q0 + r, g = g0 + tx;
+    float c = 0.0f;
+    if (q < p.Q && g < G) {
+      c = ldg1(src + (size_t)q * p.Gmax + g);
+      bad |= !(fabsf(c) <= 3.0e38f);
+    }
+    tile[r][tx] = c;
+  }
+  __syncthreads();
+  float* dst = p.rows + (size_t)prob * p.Gmax * p.Qpad;
+#pragma unroll
+  for (int t = 0; t < LSA_TILE * LSA_TILE / LSA_NT; ++t) {
+    const int r = ty + t * (LSA_NT / LSA_TILE), g = g0 + r;   // (q0 + tx < Qpad: Qpad is a multiple of the tile)
+    if (g < G) stg1(dst + (size_t)g * p.Qpad + q0 + tx, tile[tx][r]);
+  }
+  if (bad) p.flags[prob] = 1;
+}
+
+// the shapes tc_lsa_assign_ws / tc_lsa_workspace_bytes take at all
+int lsa_check_shape(int P, int B, int Q, int Gmax) {
+  TC_REQUIRE(P >= 1 && B >= 1 && P % B == 0 && P <= 65535, "lsa: num_outputs*B=%d (1..65535) B=%d", P, B);
+  TC_REQUIRE(Q >= 1 && Q <= LSA_L_QMAX, "lsa: Q=%d (1..%d)", Q, LSA_L_QMAX);
+  TC_REQUIRE(Gmax >= 1 && Gmax <= LSA_L_GMAX, "lsa: Gmax=%d (1..%d)", Gmax, LSA_L_GMAX);
+  TC_REQUIRE(Gmax <= Q, "lsa: Gmax=%d > Q=%d (more boxes than queries)", Gmax, Q);
+  return 0;
+}
+inline bool lsa_small_takes(int Q, int Gmax) { return Q <= LSA_QMAX && Gmax <= LSA_GMAX; }
+// [P][Gmax][Qpad] floats, then [P] flag words, each slice rounded up to 256 bytes
+size_t lsa_rows_bytes(int P, int Q, int Gmax) {
+  return arena_slice((size_t)P * Gmax * ((Q + 63) & ~63), sizeof(float)) + arena_slice((size_t)P, sizeof(int));
+}
+
+int launch_lsa_ws(const float* cost, const int* gt_counts, int P, int B, int Q, int Gmax, int* assigned, float* num_pos,
+                  int* status, float* poison, void* ws, size_t ws_bytes, int path, hipStream_t s) {
+  if (const int rc = lsa_check_shape(P, B, Q, Gmax)) return rc;
+  TC_REQUIRE(path >= 0 && path <= 2, "lsa: path=%d (0 automatic, 1 the kernel for Q <= %d and Gmax <= %d, 2 the kernel "
+             "that reads transposed rows)", path, LSA_QMAX, LSA_GMAX);
+  if (path == 1)
+    TC_REQUIRE(lsa_small_takes(Q, Gmax), "lsa: Q=%d (<= %d) Gmax=%d (<= %d): beyond the kernel of path 1", Q, LSA_QMAX,
+               Gmax, LSA_GMAX);
+  if (path == 1 || (path == 0 && lsa_small_takes(Q, Gmax)))
+    return launch_lsa(cost, gt_counts, P, B, Q, Gmax, assigned, num_pos, status, poison, s);
+  const size_t need = lsa_rows_bytes(P, Q, Gmax);
+  TC_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "lsa: workspace %p (16-byte aligned)", ws);
+  TC_REQUIRE(ws_bytes >= need, "lsa: workspace_bytes=%zu < %zu (transposed costs + flag words)", ws_bytes, need);
+  const int Qpad = (Q + 63) & ~63;
+  Arena arena(ws, ws_bytes);
+  float* rows = arena.take<float>((size_t)P * Gmax * Qpad);
+  int* flags = arena.take<int>((size_t)P);
+  hipError_t e = hipMemsetAsync(flags, 0, (size_t)P * sizeof(int), s);
+  if (e != hipSuccess) { set_error("lsa: hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
+  LsaTransK t;
+  t.cost = cost; t.gt_counts = gt_counts; t.B = B; t.Q = Q; t.Gmax = Gmax; t.Qpad = Qpad; t.rows = rows; t.flags = flags;
+  hipLaunchKernelGGL(lsa_rows_kernel, dim3(Qpad / LSA_TILE, (Gmax + LSA_TILE - 1) / LSA_TILE, P), dim3(LSA_NT), 0, s, t);
+  if (const int rc = check_launch("lsa_rows")) return rc;
+  LsaK p;
+  p.cost = cost; p.gt_counts = gt_counts; p.P = P; p.B = B; p.Q = Q; p.Gmax = Gmax; p.assigned = assigned;
+  p.num_pos = num_pos; p.status = status; p.poison = poison; p.rows = rows; p.flags = flags;
+  hipLaunchKernelGGL((lsa_kernel<LSA_ROWS, LSA_L_COLS, LSA_L_GMAX>), dim3(P), dim3(LSA_NT), 0, s, p);
+  return check_launch("lsa_large");
 }
 
 }  // namespace tc
@@ -444,6 +553,22 @@ int tc_lsa_assign_ex(const float* cost, const int* gt_counts, int num_outputs, i
                      float* num_pos, int* status, float* poison_losses, tc_stream_t stream) {
   TC_REQUIRE(cost != nullptr && gt_counts != nullptr && assigned != nullptr, "lsa_assign: null argument");
   return launch_lsa(cost, gt_counts, num_outputs * B, B, Q, Gmax, assigned, num_pos, status, poison_losses, as_stream(stream));
+}
+
+size_t tc_lsa_workspace_bytes(int num_outputs, int B, int Q, int Gmax) {
+  const long long P = (long long)num_outputs * B;
+  if (lsa_check_shape(P >= 1 && P <= 65535 ? (int)P : 0, B, Q, Gmax) != 0) return 0;       // (tc_last_error says why)
+  set_error("%s", "");                              // an accepted shape: a 0 with an empty tc_last_error means "none needed"
+  return lsa_small_takes(Q, Gmax) ? 0 : lsa_rows_bytes((int)P, Q, Gmax);
+}
+
+int tc_lsa_assign_ws(const float* cost, const int* gt_counts, int num_outputs, int B, int Q, int Gmax, int* assigned,
+                     float* num_pos, int* status, float* poison_losses, void* workspace, size_t workspace_bytes,
+                     int path, tc_stream_t stream) {
+  TC_REQUIRE(cost != nullptr && gt_counts != nullptr && assigned != nullptr, "lsa_assign_ws: null argument");
+  const long long P = (long long)num_outputs * B;
+  return launch_lsa_ws(cost, gt_counts, P >= 1 && P <= 65535 ? (int)P : 0, B, Q, Gmax, assigned, num_pos, status,
+                       poison_losses, workspace, workspace_bytes, path, as_stream(stream));
 }
 
 }  // extern "C"

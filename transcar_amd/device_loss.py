@@ -1,8 +1,10 @@
 """Detr3DHead.loss on the device: same numbers as
 ``Detr3DHead.loss`` (HEAD:742-1001) + the gradients of the summed loss with
-respect to ``all_cls_scores`` / ``all_bbox_preds``, from three kernel launches
-and ONE device->host copy per iteration (the Hungarian assignment itself stays
-scipy's ``linear_sum_assignment`` on the host, exactly as in the reference)."""
+respect to ``all_cls_scores`` / ``all_bbox_preds``.  The Hungarian assignment
+runs on the device too (``tc_lsa_assign_ws``: up to 4 096 queries and 512
+ground-truth boxes per sample, no host synchronisation in the iteration);
+shapes beyond that, and ``device_assign=False``, take the reference's route:
+ONE device->host copy and scipy's ``linear_sum_assignment`` on the host."""
 import ctypes as C
 
 import numpy as np
@@ -28,10 +30,16 @@ def gt_tensors(gt_bboxes_list, device):
     return out
 
 
-#: The Hungarian assignment on the device (tc_lsa_assign: the algorithm scipy's linear_sum_assignment implements, in
-#: float64, one wavefront per problem) instead of D2H + scipy + H2D: the iteration then has no host synchronisation
+#: The Hungarian assignment on the device (tc_lsa_assign_ws: the algorithm scipy's linear_sum_assignment implements, in
+#: float64, one workgroup per problem) instead of D2H + scipy + H2D: the iteration then has no host synchronisation
 #: at all.  False = the reference's route (ASSIGN:117-125), kept as the cross-check of the tests.
 DEVICE_ASSIGN = True
+
+
+def device_assign_supported(Q, Gmax):
+    """The shapes the device assignment takes (num_query, most ground-truth boxes of a sample): others take scipy's
+    route on the host, with its synchronisation."""
+    return Q <= L.TC_LSA_MAX_QUERIES and 1 <= Gmax <= L.TC_LSA_MAX_GT and Gmax <= Q
 
 
 def detr_loss_device(head, all_cls, all_box, gt_bboxes_list, gt_labels_list, before_sync=None, defer_guard=False,
@@ -82,7 +90,7 @@ def detr_loss_device(head, all_cls, all_box, gt_bboxes_list, gt_labels_list, bef
         before_sync()
     if device_assign is None:
         device_assign = DEVICE_ASSIGN
-    if device_assign and Q <= 1024 and Gmax <= min(128, Q):
+    if device_assign and device_assign_supported(Q, Gmax):
         return _loss_with_device_assignment(head, lib, all_cls, all_box, cost, cache, defer_guard)
     cost_h = cost.cpu().numpy()                                   # the iteration's one sync
     assigned = np.full((Lyr, B, Q), -1, dtype=np.int32)
@@ -139,7 +147,7 @@ def detr_loss_device(head, all_cls, all_box, gt_bboxes_list, gt_labels_list, bef
 
 
 def _loss_with_device_assignment(head, lib, all_cls, all_box, cost, cache, defer_guard):
-    """cost matrix -> tc_lsa_assign -> losses + gradients, nothing leaves the device (no host sync)."""
+    """cost matrix -> tc_lsa_assign_ws -> losses + gradients, nothing leaves the device (no host sync)."""
     dev = all_cls.device
     Lyr, B, Q, ncls = all_cls.shape
     code = all_box.shape[-1]
@@ -148,8 +156,15 @@ def _loss_with_device_assignment(head, lib, all_cls, all_box, cost, cache, defer
     z = torch.zeros(4 * Lyr + 1, dtype=torch.float32, device=dev)
     num_pos, losses, status = z[:2 * Lyr].view(Lyr, 2), z[2 * Lyr:4 * Lyr].view(Lyr, 2), z[4 * Lyr:].view(torch.int32)
     asg = torch.empty((Lyr, B, Q), dtype=torch.int32, device=dev)
-    L.check(lib.tc_lsa_assign_ex(cost.data_ptr(), cnt.data_ptr(), Lyr, B, Q, Gmax, asg.data_ptr(), num_pos.data_ptr(),
-                                 status.data_ptr(), losses.data_ptr(), _stream()), 'tc_lsa_assign_ex')
+    # beyond 1 024 queries / 128 boxes the solver reads transposed costs from a workspace: kept on the head, replaced
+    # only by a larger one (no allocation in the steady state)
+    need = lib.tc_lsa_workspace_bytes(Lyr, B, Q, Gmax)
+    ws = getattr(head, '_lsa_workspace', None)
+    if need and (ws is None or ws.numel() < need or ws.device != dev):
+        ws = head._lsa_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(lib.tc_lsa_assign_ws(cost.data_ptr(), cnt.data_ptr(), Lyr, B, Q, Gmax, asg.data_ptr(), num_pos.data_ptr(),
+                                 status.data_ptr(), losses.data_ptr(), ws.data_ptr() if need else None,
+                                 ws.numel() if need else 0, L.TC_LSA_AUTO, _stream()), 'tc_lsa_assign_ws')
     # > 0: a sample had a non-finite cost.  scipy raises there (ASSIGN:117-125) and the reference stops; here the
     # output's losses are poisoned (NaN: the backward's guard then sends no gradient down) and the word travels to
     # the host without a synchronisation -- FusionTrainer raises at its next step (check_assign_status)
