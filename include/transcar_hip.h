@@ -564,6 +564,41 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
                     const tc_head_options* options /*may be NULL*/,
                     void* workspace, size_t workspace_bytes, tc_stream_t stream);
 
+/* ---- the DETR3D camera detector's own outputs (HEAD:277-298) -------------------------------------------------
+ * cls_branches[l] / reg_branches[l] of every decoder level on the decoder states tc_head_forward stores in
+ * tc_head_aux -- what the reference computes and drops at HEAD:607-608.  For level l:
+ *   ref = inverse_sigmoid(l == 0 ? init_reference : inter_references[l - 1])            (eps 1e-5 clamp)
+ *   cls[l] = cls_branches[l](hs[l]);  t = reg_branches[l](hs[l])
+ *   t[0:2] = sigmoid(t[0:2] + ref[0:2]), t[4] = sigmoid(t[4] + ref[2]), each scaled to pc_range (x, y, z)
+ * Without box refinement every level names the same branch and inter_references[l - 1] is the initial reference.
+ * tc_decoder_heads is handed over unpacked (nn.Linear layouts); tc_decoder_heads_pack fills `packed`
+ * (tc_decoder_heads_packed_bytes(w) bytes of device memory that must outlive the view) with the three copies
+ * the row chains read of the four 256 x 256 matrices of a level (levels that share a pointer are packed once) and
+ * `packed_view` with a copy of `w` whose l0 / l3 / l2 weights point into it; the last Linear of a branch, biases and
+ * LayerNorm parameters keep the caller's pointers.  ONE launch (chain.hip PROG_DECODER_HEADS), levels x row tiles.
+ * options (may be NULL): chain_tile_rows, matrix_path and range_status are read, with the tile height chosen from
+ * L * B * Q rows as in the other chains; decoder_dropout_p != 0 or unfused is refused.  Enqueue-only: no allocation,
+ * no synchronisation.  embed_dims 256, 1 <= num_levels <= TC_MAX_LAYERS, 1 <= num_classes <= 32, 8 <= code_size <= 10. */
+typedef struct {
+  int abi_version;                  /* TC_ABI_VERSION                                   */
+  int num_levels, embed_dims, num_classes, code_size;
+  float pc_range[6];
+  tc_cls_branch cls[TC_MAX_LAYERS]; /* cls_branches.{l}                                 */
+  tc_reg_branch reg[TC_MAX_LAYERS]; /* reg_branches.{l}                                 */
+  size_t packed16_delta;            /* packed view only, as in tc_decoder_layer         */
+} tc_decoder_heads;
+size_t tc_decoder_heads_packed_bytes(const tc_decoder_heads* w);
+int tc_decoder_heads_pack(const tc_decoder_heads* w, void* packed, size_t packed_bytes,
+                          tc_decoder_heads* packed_view, tc_stream_t stream);
+int tc_decoder_outputs_fwd(const tc_decoder_heads* packed_view,
+                           const float* inter_states     /* [L,B,Q,C] */,
+                           const float* init_reference   /* [B,Q,3]   */,
+                           const float* inter_references /* [L,B,Q,3] */,
+                           int B, int Q,
+                           float* all_cls_scores /* [L,B,Q,num_classes] */,
+                           float* all_bbox_preds /* [L,B,Q,code_size]   */,
+                           const tc_head_options* options /*may be NULL*/, tc_stream_t stream);
+
 
 /* ======================================================================
  * Training.  tools/train.py:245-252

@@ -170,6 +170,15 @@ class tc_head_weights(C.Structure):
                 ('num_points', C.c_int)]
 
 
+class tc_decoder_heads(C.Structure):
+    """cls_branches / reg_branches of the decoder levels (tc_decoder_heads_pack, tc_decoder_outputs_fwd)."""
+    _fields_ = [('abi_version', C.c_int), ('num_levels', C.c_int), ('embed_dims', C.c_int),
+                ('num_classes', C.c_int), ('code_size', C.c_int),
+                ('pc_range', C.c_float * 6),
+                ('cls', tc_cls_branch * TC_MAX_LAYERS), ('reg', tc_reg_branch * TC_MAX_LAYERS),
+                ('packed16_delta', C.c_size_t)]
+
+
 class tc_feats_nhwc(C.Structure):
     _fields_ = [('num_levels', C.c_int),
                 ('data', c_fp * TC_MAX_LEVELS),
@@ -264,6 +273,10 @@ SIGNATURES = {
                              _P(tc_feats_nhwc), _i, _vp,
                              _f, _f, _vp, _i, _i, _vp, _vp, _P(tc_head_aux),
                              _P(tc_head_options), _vp, _sz, _vp]),
+    'tc_decoder_heads_packed_bytes': (_sz, [_P(tc_decoder_heads)]),
+    'tc_decoder_heads_pack': (_i, [_P(tc_decoder_heads), _vp, _sz, _P(tc_decoder_heads), _vp]),
+    'tc_decoder_outputs_fwd': (_i, [_P(tc_decoder_heads), _vp, _vp, _vp, _i, _i, _vp, _vp,
+                                    _P(tc_head_options), _vp]),
     # training (backward of the trainable radar stack + optimizer)
     'tc_linear_gated_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'tc_linear_bwd_data': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f,

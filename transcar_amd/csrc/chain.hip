@@ -162,7 +162,9 @@ enum Kind : short {
   K_LOADG,     // dst[R][0..63] = global [M, N <= 64] rows (zero filled); F_CARRY: + the box gradient carried down
   K_MASKCOPY,  // dst = dropout-keep(site K - 1) (.) [row gate] (.) src, stored to gd
   K_LN_BWD,    // LayerNorm backward of dy (src) at z = tape p1 (+ p2) -> dz (dst), dgamma / dbeta atomics
-  K_ATTN_BWD   // gated attention backward of one row: d(attention output) (src) -> d(projected query) (dst)
+  K_ATTN_BWD,  // gated attention backward of one row: d(attention output) (src) -> d(projected query) (dst)
+  // decoder heads (PROG_DECODER_HEADS)
+  K_BOXSIG     // box of a decoder level, HEAD:287-293: columns 0, 1, 4 = pc_range(sigmoid(. + inverse_sigmoid(reference)))
 };
 enum NSpecial : short { N_LOGITS = -1, N_CODE = -2, N_CLS = -3 };
 enum Flags : short {
@@ -329,6 +331,27 @@ constexpr StepDesc PROG_RADAR_LAYER_T[] = {
     {K_BOXADD, 0, 0, 0, 0, B_L, B_NONE, B_NONE, B_NONE, 0, 0, G_NONE, G_NONE, 1},
     {K_END, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
 
+// The DETR3D camera detector's own outputs (HEAD:277-298): cls_branches[l] / reg_branches[l] of EVERY decoder level on the
+// states the decoder chains stored, one launch after them (launch_decoder_heads).  A workgroup takes a row tile of ONE
+// level -- the grid is levels x row tiles, the level selects the record sequence (its weight pairs, its slice of hs, its
+// reference points and output rows).  The two MLPs interleave as in the tail of PROG_RADAR_LAYER_T, same units.
+// pairs: 0 cls.0 1 cls.n1 2 cls.3 3 cls.n4 4 cls.6 5 reg.0 6 reg.2 7 reg.4
+// K_NARROW computes ONE 16-column sub-tile: the class head takes a second pass for classes 16 .. 31 (`act` of a
+// K_NARROW step of this program: the sub-tile; a pass without columns is a K_NOP).
+constexpr StepDesc PROG_DECODER_HEADS_T[] = {
+    {K_LOAD, 0, 0, 0, 0, B_NONE, B_NONE, B_X, B_NONE, 0, 0, G_HS, G_NONE, 1},                // hs[l]
+    {K_LINEAR, 0, -1, 256, 256, B_X, B_NONE, B_U1, B_NONE, 0, 0, G_NONE, G_NONE, 0},         // cls.0
+    {K_LINEAR, 5, -1, 256, 256, B_X, B_NONE, B_U2, B_NONE, 1, 0, G_NONE, G_NONE, 1},         // reg.0
+    {K_LN, 1, -1, 0, 0, B_U1, B_NONE, B_U1, B_NONE, 0, F_LN_RELU, G_NONE, G_NONE, 0},        // in place
+    {K_LINEAR, 6, -1, 256, 256, B_U2, B_NONE, B_U3, B_NONE, 1, 0, G_NONE, G_NONE, 1},        // reg.2
+    {K_LINEAR, 2, -1, 256, 256, B_U1, B_NONE, B_U2, B_NONE, 0, 0, G_NONE, G_NONE, 1},        // cls.3
+    {K_LN, 3, -1, 0, 0, B_U2, B_NONE, B_U2, B_NONE, 0, F_LN_RELU, G_NONE, G_NONE, 0},        // in place
+    {K_NARROW, 7, -1, 256, N_CODE, B_U3, B_U1, B_L, B_NONE, 0, F_PRESYNC, G_NONE, G_NONE, 0},   // reg.4 (partial sums: U1)
+    {K_NARROW, 4, -1, 256, N_CLS, B_U2, B_U1, B_NONE, B_NONE, 0, F_PRESYNC, G_CLS, G_NONE, 0},  // cls.6, classes 0 .. 15
+    {K_NARROW, 4, -1, 256, N_CLS, B_U2, B_U1, B_NONE, B_NONE, 1, F_PRESYNC, G_CLS, G_NONE, 1},  // cls.6, classes 16 .. 31
+    {K_BOXSIG, 0, 0, 0, 0, B_L, B_NONE, B_NONE, B_NONE, 0, 0, G_NONE, G_NONE, 0},
+    {K_END, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
+
 // PROG_RADAR_TRAIN / PROG_RADAR_ENC_TRAIN: the same step tables as PROG_RADAR / PROG_RADAR_ENC run as the
 // FORWARD OF A TRAINING ITERATION (tc_radar_train_fwd_fused): every activation the backward needs is stored on
 // the tape as it is produced (the steps' global destinations), the four dropout sites of a fusion layer are
@@ -365,7 +388,7 @@ enum DSel : short { D_NONE = -1, D_DBOX = 0, D_DT1, D_DT0, D_DC2, D_DC0, D_DFF, 
 constexpr short BWD_STORE[19] = {D_DBOX, D_DT1, D_DT0, D_NONE, D_DCLS, D_NONE, D_DC2, D_NONE, D_DC0, D_NONE, D_NONE, D_DFF,
                                  D_DH, D_NONE, D_NONE, D_DPROJ, D_NONE, D_DQP, D_NONE};
 enum Program : int { PROG_PROLOGUE = 0, PROG_DECODER, PROG_RADAR_ENC, PROG_RADAR, PROG_RADAR_ENC_A, PROG_RADAR_ENC_B,
-                     PROG_RADAR_TRAIN, PROG_RADAR_ENC_TRAIN, PROG_RADAR_BWD };
+                     PROG_RADAR_TRAIN, PROG_RADAR_ENC_TRAIN, PROG_RADAR_BWD, PROG_DECODER_HEADS };
 constexpr bool prog_is_radar(int p) { return p == PROG_RADAR || p == PROG_RADAR_TRAIN; }     // (forward programs)
 constexpr bool prog_is_enc_full(int p) { return p == PROG_RADAR_ENC || p == PROG_RADAR_ENC_TRAIN; }
 // tape tensors of a fusion layer (layer r: base + r * tape_stride floats) ...
@@ -447,6 +470,7 @@ constexpr int table_steps(int prog) {
           : prog == PROG_RADAR_ENC_A ? (int)(sizeof(PROG_RADAR_ENC_A_T) / sizeof(StepDesc))
           : prog == PROG_RADAR_ENC_B ? (int)(sizeof(PROG_RADAR_ENC_B_T) / sizeof(StepDesc))
           : prog == PROG_RADAR_BWD ? (int)(sizeof(PROG_RADAR_BWD_T) / sizeof(StepDesc))
+          : prog == PROG_DECODER_HEADS ? (int)(sizeof(PROG_DECODER_HEADS_T) / sizeof(StepDesc))
                                      : (int)(sizeof(PROG_RADAR_LAYER_T) / sizeof(StepDesc))) - 1;
 }
 constexpr int rec_cap(int prog) { return table_steps(prog) * ((prog_is_radar(prog) || prog == PROG_RADAR_BWD) ? TC_MAX_RADAR_LAYERS : 1); }
@@ -459,7 +483,8 @@ inline const StepDesc* prog_table(int prog) {
          : prog_is_enc_full(prog) ? PROG_RADAR_ENC_T
          : prog == PROG_RADAR_ENC_A ? PROG_RADAR_ENC_A_T
          : prog == PROG_RADAR_ENC_B ? PROG_RADAR_ENC_B_T
-         : prog == PROG_RADAR_BWD ? PROG_RADAR_BWD_T : PROG_RADAR_LAYER_T;
+         : prog == PROG_RADAR_BWD ? PROG_RADAR_BWD_T
+         : prog == PROG_DECODER_HEADS ? PROG_DECODER_HEADS_T : PROG_RADAR_LAYER_T;
 }
 
 // runtime view of a linear step
@@ -2297,7 +2322,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
         }
       } break;
       } break;
-      case K_NARROW: { if constexpr (PROG == PROG_DECODER || prog_is_radar(PROG)) {
+      case K_NARROW: { if constexpr (PROG == PROG_DECODER || prog_is_radar(PROG) || PROG == PROG_DECODER_HEADS) {
         // The 10-column heads (reg.4, final_reg.4, final_cls.6): as a 64-column tile of the item loop they
         // kept ONE wave busy for four items (13 000 cycles at 16 rows) while three waited at the barrier.
         // Here: ONE 16-column MFMA sub-tile, the 16 k groups of 16 split over the four waves (16
@@ -2306,15 +2331,20 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
         // W[c][16 kg + 4g ..] IS the B operand of the k group's four MFMAs.  Same code at every tile height
         // (rows >= R repeat row R - 1, never stored).
         // 32-row tiles (8 waves): waves 0-3 the first 16 rows, waves 4-7 the second (rgw), the k groups over kq
-        const int N = r.N;                                // <= 12 (launchers check code / num_classes)
+        // N <= 12 in the decoder and radar programs (their launchers check code / num_classes: ONE sub-tile covers N);
+        // the decoder heads pass up to 32 classes and take columns cb .. cb + 15 per pass
+        const int N = r.N;
         const int c = lane & 15, g = lane >> 4;
         const int rgw = wave >> 2, kq = wave & 3;
-        const float* Wn = uptr(r.p0) + (size_t)min(c, N - 1) * 256 + 4 * g;
+        // decoder heads: the sub-tile's first column (classes 16 .. 31 in a second pass); 0 everywhere else
+        int cb = 0;
+        if constexpr (PROG == PROG_DECODER_HEADS) cb = 16 * r.act;
+        const float* Wn = uptr(r.p0) + (size_t)min(cb + c, N - 1) * 256 + 4 * g;
         const float* src = buf_ptr(S, r.src) + min(16 * rgw + c, R - 1) * buf_ld(r.src);
         float4 av[4], bw[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) bw[q] = ld4(Wn + 16 * (4 * kq + q));
-        const float bias = r.p1 != nullptr ? ldg1(uptr(r.p1) + min(c, N - 1)) : 0.0f;
+        const float bias = r.p1 != nullptr ? ldg1(uptr(r.p1) + min(cb + c, N - 1)) : 0.0f;
         if (r.flags & F_PRESYNC) __syncthreads();         // (the source tile is complete behind this barrier)
 #pragma unroll
         for (int q = 0; q < 4; ++q) av[q] = act_ld4<PL>(src, 4 * g + 16 * (4 * kq + q));
@@ -2328,7 +2358,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
 #pragma unroll
         for (int i = 0; i < 4; ++i) part[(wave * 16 + 4 * g + i) * 16 + c] = acc[i];
         __syncthreads();
-        if (kq == 0 && c < N) {
+        if (kq == 0 && cb + c < N) {
           float y[4];
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -2354,7 +2384,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
               if (row < R && m0 + row < M) {
                 int grow = m0 + row;
                 if constexpr (prog_is_radar(PROG)) grow = S.rowg[row];
-                stg1(r.gd + (size_t)grow * r.gld + c, y[i]);
+                stg1(r.gd + (size_t)grow * r.gld + cb + c, y[i]);
               }
             }
           }
@@ -2603,6 +2633,23 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
         }
       } break;
       } break;
+      case K_BOXSIG: { if constexpr (PROG == PROG_DECODER_HEADS) {   // HEAD:287-293, the arithmetic of K_REFUPD
+        // one (row, box column) per thread as K_BOXADD; p0: the level's reference points [M, 3] in global memory
+        // (the initial ones for level 0, inter_references[l - 1] above), gd: the level's boxes [M, code]
+        const int row = threadIdx.x >> 4, j = threadIdx.x & 15;
+        if (row < R && m0 + row < M && j < k.code) {
+          const int grow = m0 + row;
+          float val = S.l[row][j];
+          const int c = j == 0 ? 0 : j == 1 ? 1 : j == 4 ? 2 : -1;      // box columns cx, cy, cz <- reference x, y, z
+          if (c >= 0) {
+            const float n = sigmoidf_(val + inverse_sigmoidf_(ldg1(r.p0 + (size_t)grow * 3 + c)));
+            const float* pc = k.cam.pc;
+            val = n * (pc[3 + c] - pc[c]) + pc[c];
+          }
+          stg1(r.gd + (size_t)grow * k.code + j, val);
+        }
+      } break;
+      } break;
       default: break;
     }
     STEP_STAMP();
@@ -2722,6 +2769,11 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
       if (ts2 != T_NONE) r.gt = k.tape[ts2];
     }
     if (PROG == PROG_DECODER && d.N == N_LOGITS && generic_xattn(k)) r.dst = B_U3;   // MP: N * P * L logits (chain_body)
+    if (PROG == PROG_DECODER_HEADS) {
+      // a sub-tile pass of the class head beyond num_classes: only its barrier remains
+      if (d.kind == K_NARROW && 16 * d.act >= (d.N == N_CODE ? k.code : k.ncls)) r.kind = K_NOP;
+      if (d.kind == K_BOXSIG) { r.p0 = k.ref_in; r.gd = k.box_m; r.gld = k.code; }
+    }
     if (d.kind == K_LINEAR) {
       const tc_linear pr = k.pairs[pair0 + d.wp];
       r.K = d.K == 36 ? k.RI : d.K == N_CODE ? k.code : d.K == N_CLS ? k.ncls : d.K;
@@ -2910,6 +2962,58 @@ int launch_decoder(const ChainK& k, hipStream_t s, const char* what) {
                      : launch_r<8, PROG_DECODER, true, 0, false, MP>(k, s, what);
   }
   return launch_rows<PROG_DECODER, MP>(k, s, what);
+}
+
+// ---- PROG_DECODER_HEADS: levels x row tiles in one launch; workgroup (level, tile) walks the level's record sequence ----
+constexpr int HEADS_STEPS = table_steps(PROG_DECODER_HEADS);
+template <int NW> struct HeadsRecs { StepAllT<NW> s[TC_MAX_LAYERS * HEADS_STEPS]; };
+template <int R, int MM>
+__global__ __launch_bounds__(nw_of(R) * 64, 2) void chain_heads_kernel(ChainDev k, int tiles, HeadsRecs<nw_of(R)> recs) {
+  const int level = (int)blockIdx.x / tiles;
+  chain_body<R, PROG_DECODER_HEADS, false, MM>(k, recs.s + level * HEADS_STEPS, (int)blockIdx.x - level * tiles);
+}
+
+// the ChainK of one level: its weight pairs, its slice of the decoder states, its reference points, its output rows
+ChainK heads_level_k(const DecoderHeadsArgs& a, int l) {
+  ChainK k;
+  init_k(k);
+  k.program = PROG_DECODER_HEADS; k.M = a.M; k.Q = a.M; k.code = a.code; k.ncls = a.ncls; k.has_next = 1;
+  k.w16_delta = a.w16_delta; k.matrix_path = a.matrix_path; k.range_status = a.range_status;
+  const tc_cls_branch& c = a.cls[l]; const tc_reg_branch& g = a.reg[l];
+  k.pairs[0] = c.l0; k.pairs[1] = tc_linear{c.n1.g, c.n1.b}; k.pairs[2] = c.l3; k.pairs[3] = tc_linear{c.n4.g, c.n4.b};
+  k.pairs[4] = c.l6; k.pairs[5] = g.l0; k.pairs[6] = g.l2; k.pairs[7] = g.l4;
+  k.g[G_HS] = const_cast<float*>(a.hs) + (size_t)l * a.M * 256; k.g_ld[G_HS] = 256;
+  k.g[G_CLS] = a.all_cls + (size_t)l * a.M * a.ncls; k.g_ld[G_CLS] = a.ncls;
+  k.ref_in = l == 0 ? a.init_ref : a.inter_refs + (size_t)(l - 1) * a.M * 3;
+  k.box_m = a.all_box + (size_t)l * a.M * a.code;
+  for (int i = 0; i < 6; ++i) k.cam.pc[i] = a.pc[i];
+  return k;
+}
+
+template <int R, int MM>
+int launch_heads_r(const DecoderHeadsArgs& a, hipStream_t s) {
+  const char* what = "chain(decoder heads)";
+  constexpr size_t lds = chain_lds_bytes<R, PROG_DECODER_HEADS>();
+  static DeviceOnce once;
+  if (const int once_dev = once.need(); once_dev >= 0) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_heads_kernel<R, MM>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { set_error("chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+    once.done(once_dev);
+  }
+  TC_REQUIRE(R < 16 || a.w16_delta != 0, "%s: 16- / 32-row tiles need weights from a tc_decoder_heads_pack view", what);
+  HeadsRecs<nw_of(R)> recs;
+  memset(&recs, 0, sizeof(recs));
+  ChainK k0;
+  for (int l = 0; l < a.levels; ++l) {
+    ChainK k = heads_level_k(a, l);
+    resolve_program<R, PROG_DECODER_HEADS, MM>(k, recs.s + l * HEADS_STEPS);
+    if (l == 0) k0 = k;
+  }
+  const int tiles = (a.M + R - 1) / R;
+  hipLaunchKernelGGL((chain_heads_kernel<R, MM>), dim3(a.levels * tiles), dim3(nw_of(R) * 64), lds, s,
+                     static_cast<const ChainDev&>(k0), tiles, recs);
+  return check_launch(what);
 }
 
 int launch(const ChainK& k, hipStream_t s, const char* what) {
@@ -3210,6 +3314,27 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {
     if (k.tile_rows >= 16 || (k.tile_rows == 0 && a.M > 2048)) k.tile_rows = 8;
   }
   return launch(k, s, "chain(radar)");
+}
+
+// cls_branches / reg_branches of every decoder level (HEAD:277-298): one launch after the decoder chains.  The tile
+// height and the matrix path follow the rule of the other chains, from the rows of the launch (levels * M).
+int launch_decoder_heads(const DecoderHeadsArgs& a, hipStream_t s) {
+  TC_REQUIRE(a.levels >= 1 && a.levels <= TC_MAX_LAYERS && a.M >= 1, "decoder_heads: levels=%d M=%d", a.levels, a.M);
+  TC_REQUIRE(a.code >= 1 && a.code <= 12 && a.ncls >= 1 && a.ncls <= 32, "decoder_heads: code=%d ncls=%d", a.code, a.ncls);
+  TC_REQUIRE((long long)a.levels * a.M < (1ll << 24), "decoder_heads: %lld rows in one launch", (long long)a.levels * a.M);
+  TC_REQUIRE(a.tile_rows == 0 || a.tile_rows == 4 || a.tile_rows == 8 || a.tile_rows == 16 || a.tile_rows == 32,
+             "decoder_heads: tile_rows=%d (0 = automatic, 4, 8, 16 or 32)", a.tile_rows);
+  ChainK k;
+  init_k(k);
+  k.M = a.levels * a.M; k.tile_rows = a.tile_rows; k.matrix_path = a.matrix_path;
+  const int rows = tile_rows(k);
+  if (rows == 4) return launch_heads_r<4, 0>(a, s);
+  if (rows == 8) return launch_heads_r<8, 0>(a, s);
+  if (rows == 32) {
+    TC_REQUIRE(use_f16x2(k), "decoder_heads: 32-row tiles exist on the f16x2 matrix path only");
+    return launch_heads_r<32, 1>(a, s);
+  }
+  return use_f16x2(k) ? launch_heads_r<16, 1>(a, s) : launch_heads_r<16, 0>(a, s);
 }
 
 // Backward of the three fusion layers for the query rows: one launch (PROG_RADAR_BWD).

@@ -1105,6 +1105,107 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   return 0;
 }
 
+// ---- the decoder levels' own class / box branches (chain.hip PROG_DECODER_HEADS) ----
+static int check_decoder_heads(const tc_decoder_heads* w, const char* who) {
+  TC_REQUIRE(w != nullptr, "%s: null tc_decoder_heads", who);
+  TC_REQUIRE(w->abi_version == TC_ABI_VERSION, "%s: tc_decoder_heads.abi_version=%d, the library's is %d", who,
+             w->abi_version, TC_ABI_VERSION);
+  TC_REQUIRE(w->embed_dims == 256, "%s: embed_dims=%d (256 supported)", who, w->embed_dims);
+  TC_REQUIRE(w->num_levels >= 1 && w->num_levels <= TC_MAX_LAYERS, "%s: num_levels=%d (1 .. %d)", who, w->num_levels,
+             TC_MAX_LAYERS);
+  TC_REQUIRE(w->num_classes >= 1 && w->num_classes <= 32, "%s: num_classes=%d (1 .. 32)", who, w->num_classes);
+  TC_REQUIRE(w->code_size >= 8 && w->code_size <= 10, "%s: code_size=%d (8 .. 10)", who, w->code_size);
+  for (int l = 0; l < w->num_levels; ++l) {
+    const tc_cls_branch& c = w->cls[l]; const tc_reg_branch& g = w->reg[l];
+    const void* p[] = {c.l0.w, c.l0.b, c.n1.g, c.n1.b, c.l3.w, c.l3.b, c.n4.g, c.n4.b, c.l6.w, c.l6.b,
+                       g.l0.w, g.l0.b, g.l2.w, g.l2.b, g.l4.w, g.l4.b};
+    for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i)
+      TC_REQUIRE(p[i] != nullptr, "%s: a weight of level %d is null (%s pointer %d)", who, l, i < 10 ? "cls_branches" : "reg_branches",
+                 (int)(i < 10 ? i : i - 10));
+  }
+  return 0;
+}
+
+// the four packed matrices of a level and where an earlier level already names the same source
+struct HeadsPackSlot { const float* src; const float** slot; };
+static int decoder_heads_slots(const tc_decoder_heads* w, tc_decoder_heads* v, HeadsPackSlot* it) {
+  int n = 0;
+  for (int l = 0; l < w->num_levels; ++l) {
+    it[n++] = HeadsPackSlot{w->cls[l].l0.w, &v->cls[l].l0.w};
+    it[n++] = HeadsPackSlot{w->cls[l].l3.w, &v->cls[l].l3.w};
+    it[n++] = HeadsPackSlot{w->reg[l].l0.w, &v->reg[l].l0.w};
+    it[n++] = HeadsPackSlot{w->reg[l].l2.w, &v->reg[l].l2.w};
+  }
+  return n;
+}
+static int heads_first_use(const HeadsPackSlot* it, int i) {
+  for (int j = 0; j < i; ++j)
+    if (it[j].src == it[i].src) return j;
+  return i;
+}
+
+size_t tc_decoder_heads_packed_bytes(const tc_decoder_heads* w) {
+  if (check_decoder_heads(w, "decoder_heads_packed_bytes") != 0) return 0;
+  tc_decoder_heads view = *w;
+  HeadsPackSlot it[4 * TC_MAX_LAYERS];
+  const int n = decoder_heads_slots(w, &view, it);
+  size_t total = 0;
+  for (int i = 0; i < n; ++i)
+    if (heads_first_use(it, i) == i) total += 3 * arena_slice(packed_floats(256, 256), 4);
+  return total;
+}
+
+int tc_decoder_heads_pack(const tc_decoder_heads* w, void* packed, size_t packed_bytes, tc_decoder_heads* packed_view,
+                          tc_stream_t stream) {
+  TC_TRY(check_decoder_heads(w, "decoder_heads_pack"));
+  TC_REQUIRE(packed != nullptr && packed_view != nullptr, "decoder_heads_pack: null output");
+  TC_REQUIRE(packed_bytes >= tc_decoder_heads_packed_bytes(w), "decoder_heads_pack: buffer too small");
+  *packed_view = *w;
+  HeadsPackSlot it[4 * TC_MAX_LAYERS];
+  const int n = decoder_heads_slots(w, packed_view, it);
+  // regions as tc_head_pack_weights lays them out: the 4x4x1 copies, then the 16x16x4 copies, then the f16 planes
+  size_t distinct = 0;
+  for (int i = 0; i < n; ++i) distinct += heads_first_use(it, i) == i;
+  const size_t slice = arena_slice(packed_floats(256, 256), 4);
+  const size_t delta = distinct * slice / sizeof(float);
+  Arena a(packed, packed_bytes);
+  for (int i = 0; i < n; ++i) {
+    const int first = heads_first_use(it, i);
+    if (first != i) { *it[i].slot = *it[first].slot; continue; }     // (a shared branch: packed once)
+    float* dst = a.take<float>(packed_floats(256, 256));
+    TC_TRY(launch_pack_linear(it[i].src, 256, 256, dst, dst + delta, dst + 2 * delta, as_stream(stream)));
+    *it[i].slot = dst;
+  }
+  packed_view->packed16_delta = delta;
+  return 0;
+}
+
+int tc_decoder_outputs_fwd(const tc_decoder_heads* packed_view, const float* inter_states, const float* init_reference,
+                           const float* inter_references, int B, int Q, float* all_cls_scores, float* all_bbox_preds,
+                           const tc_head_options* options, tc_stream_t stream) {
+  const tc_decoder_heads* w = packed_view;
+  TC_TRY(check_decoder_heads(w, "decoder_outputs"));
+  TC_REQUIRE(w->packed16_delta != 0, "decoder_outputs: packed_view was not produced by tc_decoder_heads_pack");
+  TC_REQUIRE(inter_states && init_reference && all_cls_scores && all_bbox_preds && (w->num_levels == 1 || inter_references),
+             "decoder_outputs: null argument");
+  TC_REQUIRE(B >= 1 && Q >= 1, "decoder_outputs: B=%d Q=%d", B, Q);
+  tc_head_options opt;
+  TC_TRY(read_options(options, opt));
+  TC_REQUIRE(opt.decoder_dropout_p == 0.0f, "decoder_outputs: options.decoder_dropout_p=%g (eval-mode levels only)",
+             (double)opt.decoder_dropout_p);
+  TC_REQUIRE(!opt.unfused, "decoder_outputs: options.unfused=%d (the decoder heads exist as a row chain only)", opt.unfused);
+  DecoderHeadsArgs a;
+  a.levels = w->num_levels; a.M = B * Q;
+  for (int l = 0; l < w->num_levels; ++l) { a.cls[l] = w->cls[l]; a.reg[l] = w->reg[l]; }
+  a.w16_delta = w->packed16_delta;
+  a.hs = inter_states; a.init_ref = init_reference; a.inter_refs = inter_references;
+  a.all_cls = all_cls_scores; a.all_box = all_bbox_preds;
+  a.ncls = w->num_classes; a.code = w->code_size;
+  for (int i = 0; i < 6; ++i) a.pc[i] = w->pc_range[i];
+  a.tile_rows = opt.chain_tile_rows; a.matrix_path = opt.matrix_path; a.range_status = opt.range_status;
+  return launch_decoder_heads(a, as_stream(stream));
+}
+
 // ---- training entry points (train.hip) ---------------------------------------
 int tc_linear_gated_fwd(const float* x, const float* w, const float* b, const float* res,
                         const int* row_gate, float* y, int M, int K, int N, tc_stream_t stream) {

@@ -188,6 +188,22 @@ enum TapeSlot { TS_QP = 0, TS_AO, TS_X1, TS_X2, TS_H, TS_SUM, TS_X3, TS_C0, TS_C
                 TS_U0, TS_U1, TS_U2, TS_POS, TS_F0, TS_F1, TS_F2, TS_MEM, TS_COUNT };
 int launch_radar_chain(const RadarChainArgs& a, hipStream_t s);
 
+// cls_branches[l] / reg_branches[l] of every decoder level on the stored decoder states (chain.hip PROG_DECODER_HEADS):
+// one launch, levels x row tiles.  cls / reg: a tc_decoder_heads_pack view (the last Linear of a branch unpacked).
+struct DecoderHeadsArgs {
+  int levels, M;                             // M = B * Q rows per level
+  tc_cls_branch cls[TC_MAX_LAYERS]; tc_reg_branch reg[TC_MAX_LAYERS];
+  size_t w16_delta = 0;
+  const float* hs;                           // [levels, M, 256]
+  const float* init_ref;                     // [M, 3]: the reference points of level 0
+  const float* inter_refs;                   // [levels, M, 3]: level l > 0 reads slice l - 1
+  float* all_cls; float* all_box;            // [levels, M, ncls / code]
+  int ncls, code; float pc[6];
+  int tile_rows = 0, matrix_path = 0;
+  int* range_status = nullptr;
+};
+int launch_decoder_heads(const DecoderHeadsArgs& a, hipStream_t s);
+
 // ---- radar_compact.hip: row order for the radar chain (queries with a radar hit first) --------
 // flags [B*Q] scratch, perm [B*Q]: perm[b*Q + i] = a row of sample b
 int launch_radar_compact(const float* ref_last, const float* box, int code, int cen_from_box,

@@ -11,7 +11,8 @@ mode.  Differences to the reference that are part of the contract:
     reads inside forward (HEAD:27, 301-309);
   * the six cls branches / five of six reg branches whose results the
     reference computes and throws away (HEAD:277-298, lists reset at
-    HEAD:607-608) are not evaluated; their parameters still exist and load;
+    HEAD:607-608) are not evaluated by the default ``outputs='fusion'``;
+    ``outputs='camera'`` / ``'all'`` return them (tc_decoder_outputs_fwd);
   * with_box_refine=False (one shared cls / reg branch, HEAD:223-231): the
     decoder samples every layer at the initial reference points and runs no
     reg branch below its last layer (tc_decoder_layer.reg);
@@ -36,6 +37,7 @@ from .registry import (BBOX_ASSIGNERS, HEADS, build_bbox_coder,
                        build_transformer)
 
 RADAR_RADII = ((1.0, 2.0), (1.0, 2.0), (0.5, 1.0))     # HEAD:567, 635, 693
+OUTPUTS = ('fusion', 'camera', 'all')                  # Detr3DHead.outputs
 
 
 def _env_tile_rows():
@@ -120,8 +122,15 @@ class Detr3DHead(BaseModule):
                  positional_encoding=None, loss_cls=None, loss_bbox=None,
                  loss_iou=None, train_cfg=None, test_cfg=None, init_cfg=None,
                  with_box_refine=False, as_two_stage=False, bbox_coder=None,
-                 num_cls_fcs=2, code_weights=None, **kwargs):
+                 num_cls_fcs=2, code_weights=None, outputs='fusion', **kwargs):
         super().__init__(init_cfg)
+        if outputs not in OUTPUTS:
+            raise ValueError("Detr3DHead: outputs=%r (one of 'fusion', 'camera', 'all')" % (outputs,))
+        #: what ``forward`` returns as all_cls_scores / all_bbox_preds: 'fusion' the three radar fusion levels (the
+        #: reference's return value), 'camera' the L decoder levels of the DETR3D camera detector alone (HEAD:277-298;
+        #: radar is neither read nor required), 'all' the decoder levels followed by the fusion levels (the reference
+        #: with HEAD:607-608 commented out).  A plain attribute: it may be changed between forwards.
+        self.outputs = outputs
         if as_two_stage:
             raise NotImplementedError('as_two_stage is not used by TransCAR')
         self.with_box_refine = with_box_refine
@@ -188,6 +197,9 @@ class Detr3DHead(BaseModule):
         self._weights = None
         self._workspace = {}
         self._packed = None
+        #: cls_branches / reg_branches packed for tc_decoder_outputs_fwd: (buffer, view, key), built by the first
+        #: forward with outputs != 'fusion', dropped whenever the packed weights are (refresh_weights, load_state_dict)
+        self._dec_heads = None
         #: the trainable (radar) weights changed in place since they were last re-packed
         #: (an optimizer step): the next forward / pipeline replay that reads them re-packs first
         self._packed_dirty = False
@@ -243,11 +255,13 @@ class Detr3DHead(BaseModule):
         self._weights = None            # pointers move on .to()/.cuda()
         self._workspace = {}
         self._packed = None
+        self._dec_heads = None
         self.buffers_generation += 1
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
         self._weights = None
+        self._dec_heads = None
         return super().load_state_dict(*a, **k)
 
     def head_weights(self):
@@ -358,6 +372,93 @@ class Detr3DHead(BaseModule):
             rl.radius_min, rl.radius_max = RADAR_RADII[r]
         return w
 
+    def decoder_heads_struct(self):
+        """tc_decoder_heads over cls_branches / reg_branches as they are (nothing packed)."""
+        h = L.tc_decoder_heads()
+        h.abi_version = L.TC_ABI_VERSION
+        h.num_levels = self.transformer.decoder.num_layers
+        h.embed_dims = self.embed_dims
+        h.num_classes, h.code_size = self.cls_out_channels, self.code_size
+        for i in range(6):
+            h.pc_range[i] = float(self.pc_range[i])
+        for l in range(h.num_levels):
+            h.cls[l] = cls_branch_view(self.cls_branches[l])
+            h.reg[l] = reg_branch_view(self.reg_branches[l])
+        return h
+
+    def decoder_heads(self):
+        """The packed view of cls_branches / reg_branches (tc_decoder_heads_pack), built on first use and again after
+        the packed weights were invalidated or a parameter moved."""
+        key = self.head_weights()                # (checks the parameters: contiguous fp32 on the GPU; a new object
+        #                                           whenever the packed weights were invalidated and built again)
+        if self._dec_heads is not None and self._dec_heads[2] is key:
+            return self._dec_heads[1]
+        h = self.decoder_heads_struct()
+        lib = L.lib()
+        nbytes = lib.tc_decoder_heads_packed_bytes(C.byref(h))
+        if nbytes == 0:
+            raise L.TransCARHipError(lib.tc_last_error().decode())
+        dev = self.query_embedding.weight.device
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        view = L.tc_decoder_heads()
+        L.check(lib.tc_decoder_heads_pack(C.byref(h), buf.data_ptr(), nbytes, C.byref(view),
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                'tc_decoder_heads_pack')
+        self._dec_heads = (buf, view, key)
+        return view
+
+    def decoder_outputs(self, aux_t, options=None):
+        """cls_branches[l] / reg_branches[l] of every decoder level (HEAD:277-298) from the decoder's kept states and
+        references (``aux`` of a forward): -> (all_cls_scores [L,B,Q,num_classes], all_bbox_preds [L,B,Q,code_size]).
+        One launch (tc_decoder_outputs_fwd), enqueue-only."""
+        hs = aux_t['inter_states']
+        Lyr, B, Q = hs.shape[:3]
+        dev = hs.device
+        view = self.decoder_heads()
+        ncls, code = self.cls_out_channels, self.code_size
+        out = torch.empty(Lyr * B * Q * (ncls + code), dtype=torch.float32, device=dev)
+        cls = out[:Lyr * B * Q * ncls].view(Lyr, B, Q, ncls)
+        box = out[Lyr * B * Q * ncls:].view(Lyr, B, Q, code)
+        own = L.tc_head_options()
+        src = options if options is not None else (self.forward_options if self.forward_options is not None
+                                                   else head_options())
+        own.chain_tile_rows, own.matrix_path = src.chain_tile_rows, src.matrix_path
+        own.range_status = src.range_status or self.status_buffer(dev).data_ptr()
+        if self.matrix_fallback and own.matrix_path == L.TC_MATRIX_AUTO:
+            own.matrix_path = L.TC_MATRIX_F32
+            if own.chain_tile_rows == 32:
+                own.chain_tile_rows = 16
+        L.check(L.lib().tc_decoder_outputs_fwd(
+            C.byref(view), hs.data_ptr(), aux_t['init_reference'].data_ptr(), aux_t['inter_references'].data_ptr(),
+            B, Q, cls.data_ptr(), box.data_ptr(), C.byref(own),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'tc_decoder_outputs_fwd')
+        return cls, box
+
+    def _check_outputs(self):
+        if self.outputs not in OUTPUTS:
+            raise ValueError("Detr3DHead: outputs=%r (one of 'fusion', 'camera', 'all')" % (self.outputs,))
+        if self.outputs != 'fusion' and self.training:
+            raise L.TransCARHipError(
+                "Detr3DHead: outputs=%r is not supported in training mode (the decoder is frozen, the decoder levels' "
+                "loss terms carry no gradient); use outputs='fusion' or head.eval()" % (self.outputs,))
+
+    def _forward_camera(self, mlvl_feats, img_metas, aux):
+        """outputs='camera': the decoder, then its own class / box branches -- no radar anywhere."""
+        dev = mlvl_feats[0].device
+        feats_nhwc = ops.to_nhwc_levels(mlvl_feats)
+        l2i = ops.lidar2img_tensor(img_metas, dev, staged=True)
+        img_hw = img_metas[0]['img_shape'][0][:2]
+        B = l2i.shape[0]
+        # (a decoder-only forward reads no token: the tensor only gives the workspace layout its T)
+        tokens = torch.empty((B, 64, radar.NUM_FEATURES), dtype=torch.float32, device=dev)
+        base = self.forward_nhwc(feats_nhwc, l2i, img_hw, tokens, 1, aux=True, decoder_only=True,
+                                 options=self.forward_options)
+        cls, box = self.decoder_outputs(base['aux'])
+        outs = {'all_cls_scores': cls, 'all_bbox_preds': box, 'enc_cls_scores': None, 'enc_bbox_preds': None}
+        if aux:
+            outs['aux'] = base['aux']
+        return outs
+
     def cam_pregather_supported(self):
         """True if this head's shape has the camera pre-gather (_lib.cam_pregather_supported):
         the plugin graphs and a one-lane FramePipeline turn it on only then."""
@@ -379,6 +480,7 @@ class Detr3DHead(BaseModule):
         buffers_generation and a FramePipeline refuses to replay until recapture()."""
         old = bytes(self._weights) if self._weights is not None else None
         self._weights = None
+        self._dec_heads = None
         w = self.head_weights()
         if old is not None and bytes(w) != old:
             self.buffers_generation += 1
@@ -612,11 +714,14 @@ class Detr3DHead(BaseModule):
         """HEAD:248-261: mlvl_feats list of [B,N,C,H,W]; img_metas list[dict]
         -> dict(all_cls_scores [3,B,Q,10], all_bbox_preds [3,B,Q,10], enc_*)."""
         self.check_feature_levels(len(mlvl_feats))
+        self._check_outputs()
         dev = mlvl_feats[0].device
         if dev.type != 'cuda':
             raise L.TransCARHipError(
                 'Detr3DHead.forward needs the feature maps on the MI355X '
                 '(got %s); transcar_amd has no CPU path' % dev)
+        if self.outputs == 'camera':
+            return self._forward_camera(mlvl_feats, img_metas, aux)
         for m in img_metas:
             if 'radar' not in m:
                 raise KeyError(
@@ -648,6 +753,17 @@ class Detr3DHead(BaseModule):
             return self.forward_train_nhwc(feats_nhwc, l2i, img_hw, tokens,
                                            pad_mult)
         # raw sweeps: the decoder layers that do not read the tokens are enqueued BEFORE the host packs the frame
+        if self.outputs == 'all':
+            # the default forward with the decoder's states kept, then the decoder levels' own branches; the
+            # reference's order with HEAD:607-608 commented out: decoder levels first
+            outs = self.forward_nhwc(feats_nhwc, l2i, img_hw, tokens, pad_mult,
+                                     aux=True, fill_tokens=fill, options=self.forward_options)
+            cls, box = self.decoder_outputs(outs['aux'])
+            outs['all_cls_scores'] = torch.cat((cls, outs['all_cls_scores']))
+            outs['all_bbox_preds'] = torch.cat((box, outs['all_bbox_preds']))
+            if not aux:
+                del outs['aux']
+            return outs
         return self.forward_nhwc(feats_nhwc, l2i, img_hw, tokens, pad_mult,
                                  aux=aux, fill_tokens=fill, options=self.forward_options)
 

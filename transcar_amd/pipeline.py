@@ -73,6 +73,7 @@ class FramePipeline:
             raise ValueError('at least one lane')
         from .detr3d_head import head_options
         self.head, self.decode = head, decode
+        self._check_outputs()
         self.partial_graphs = bool(partial_graphs)
         self.inputs = list(static_inputs)
         #: frames per launch = the batch size of the lanes' static inputs
@@ -171,7 +172,16 @@ class FramePipeline:
             self._status_host[i].copy_(sb[:1], non_blocking=True)      # (a memcpy node of the lane's graph)
         return outs, dec
 
+    def _check_outputs(self):
+        """The lanes capture the fusion outputs only.  ``Detr3DHead.outputs`` is a plain attribute that may change after
+        the pipeline was built: checked at construction, at every capture and at every launch."""
+        if getattr(self.head, 'outputs', 'fusion') != 'fusion':
+            raise TransCARHipError(
+                "FramePipeline: Detr3DHead.outputs=%r is not supported in a pipeline (its lanes capture the fusion "
+                "outputs only); use outputs='fusion' or the eager Detr3DHead.forward" % (self.head.outputs,))
+
     def _capture(self):
+        self._check_outputs()
         self.graphs, self.outputs = [], []
         self._partial = {}
         with torch.no_grad():
@@ -228,6 +238,7 @@ class FramePipeline:
             n = None
         if n is not None and not 1 <= n < self.frames_per_launch:
             raise TransCARHipError('launch: n=%r of %d frame slots' % (n, self.frames_per_launch))
+        self._check_outputs()
         if self.head.buffers_generation != self._generation and \
                 self.head.matrix_fallback_generation == self.head.buffers_generation:
             # the f16-range guard fired (wait() below, or a get_bboxes of the plugin path): the head is on the exact-fp32

@@ -53,6 +53,8 @@ class PluginGraphs:
         h = self.head
         if aux or h.training or not getattr(h, 'plugin_graphs', True):
             return False
+        if getattr(h, 'outputs', 'fusion') != 'fusion':      # the decoder levels' own outputs: eager path
+            return False
         o = h.forward_options
         if o is not None and (o.unfused or o.phase != 0 or o.decoder_dropout_p > 0.0):
             return False
