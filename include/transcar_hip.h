@@ -39,6 +39,9 @@ extern "C" {
 /* Heads of the radar fusion attention (rf_multihead_attn{,2,3}): the reference builds it as
  * nn.MultiheadAttention(embed_dims, 8) (HEAD:129-171) whatever the decoder's self-attention uses. */
 #define TC_RADAR_HEADS 8
+/* num_classes of a head (tc_head_weights, tc_decoder_heads): the class heads of the row chains take one or two
+ * 16-column sub-tiles */
+#define TC_MAX_CLASSES 32
 /* Box decode (tc_box_decode_*): num_query * num_classes and max_num.  Up to the first pair the select keeps its keys in
  * registers; beyond it, up to the second pair, a streaming kernel re-reads the logits in every pass of the select. */
 #define TC_BOX_DECODE_MAX_SCORES 12288

@@ -60,6 +60,9 @@ TC_NUM_HEADS = (4, 8, 16)
 # heads of the radar fusion attention: nn.MultiheadAttention(embed_dims, 8) in the reference, whatever the decoder uses
 TC_RADAR_HEADS = 8
 
+# num_classes of a head (tc_head_weights, tc_decoder_heads)
+TC_MAX_CLASSES = 32
+
 # box decode: num_query * num_classes and max_num of the in-register kernel and of the streaming kernel that takes the
 # shapes beyond it (include/transcar_hip.h); path of tc_box_decode_*_path
 TC_BOX_DECODE_MAX_SCORES, TC_BOX_DECODE_MAX_NUM = 12288, 512
@@ -88,6 +91,15 @@ def check_num_heads(num_heads):
         raise TransCARHipError(
             'MultiheadAttention(HIP): num_heads=%r is not supported (4, 8 or 16 heads at embed_dims 256: '
             'head dimension 64, 32 or 16)' % (num_heads,))
+
+
+def check_num_classes(num_classes):
+    """The library's limit on a head's num_classes (1 .. 32: the class heads of the
+    row chains take one or two 16-column sub-tiles), checked before anything is
+    packed or launched."""
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= TC_MAX_CLASSES:
+        raise TransCARHipError(
+            'Detr3DHead(HIP): num_classes=%r is not supported (1 .. %d classes)' % (num_classes, TC_MAX_CLASSES))
 
 
 def cam_pregather_supported(embed_dims, num_levels, num_cams):

@@ -76,7 +76,7 @@ IMG_SHAPE = (928, 1600, 3)
 
 
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
-             num_levels=None, num_heads=None):
+             num_levels=None, num_heads=None, num_classes=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -84,7 +84,10 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     Detr3DCrossAtten.num_levels and the transformer's num_feature_levels (the
     configs: the class defaults, 4 FPN levels); num_heads overrides the
     decoder MultiheadAttention's (attn_cfgs[0]; the configs: 8, CFG:69; 4, 8
-    or 16 -- the radar fusion attention keeps its 8, HEAD:129-171)."""
+    or 16 -- the radar fusion attention keeps its 8, HEAD:129-171);
+    num_classes sets the head's and the bbox_coder's (the configs: 10, CFG:54
+    and :89; 1 .. 32 -- the coder's is the modulus that turns a score index
+    into a label, CODER:54-55)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -101,4 +104,9 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
         check_num_heads(num_heads)
         layers = cfg['transformer']['decoder']['transformerlayers']
         layers['attn_cfgs'][0]['num_heads'] = num_heads
+    if num_classes is not None:
+        from ._lib import check_num_classes
+        check_num_classes(num_classes)
+        cfg['num_classes'] = num_classes
+        cfg['bbox_coder']['num_classes'] = num_classes
     return cfg

@@ -156,7 +156,7 @@ static_assert(LD5 * 1 <= 2 * LD2, "the 512-wide tile must fit two units");
 enum Buf : short { B_NONE = -1, B_A = 0 /* units 1+2, row stride LD5 */, B_X /* unit 0 */, B_U1, B_U2, B_U3, B_L };
 enum Kind : short {
   K_END = 0, K_LOAD, K_LINEAR, K_LN, K_POSENC, K_SAMPLE, K_REFUPD, K_TOKENS, K_RADAR_ATTN, K_BOXADD, K_RADAR_GATE,
-  K_NARROW,   // y[R, N <= 12] = x[R, 256] W^T + b: one 16x16 MFMA sub-tile, k split over the waves, W in the nn.Linear layout
+  K_NARROW,   // y[R, N] = x[R, 256] W^T + b in 16-column MFMA sub-tiles (N <= 12: one; the class heads: up to two), k split over the waves, W in the nn.Linear layout
   K_NOP,  // a step switched off at run time (no next layer): only its barrier remains
   // backward row chain (PROG_RADAR_BWD)
   K_LOADG,     // dst[R][0..63] = global [M, N <= 64] rows (zero filled); F_CARRY: + the box gradient carried down
@@ -2331,21 +2331,26 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
         // W[c][16 kg + 4g ..] IS the B operand of the k group's four MFMAs.  Same code at every tile height
         // (rows >= R repeat row R - 1, never stored).
         // 32-row tiles (8 waves): waves 0-3 the first 16 rows, waves 4-7 the second (rgw), the k groups over kq
-        // N <= 12 in the decoder and radar programs (their launchers check code / num_classes: ONE sub-tile covers N);
-        // the decoder heads pass up to 32 classes and take columns cb .. cb + 15 per pass
+        // N <= 12 in the decoder program (its launcher checks code: ONE sub-tile covers N); the class heads pass up to
+        // 32 classes and take columns cb .. cb + 15 per pass: the decoder heads as two steps of their table (cb from
+        // `act`), the fusion layers as a second trip of the loop below INSIDE the one step -- a head of <= 16 classes
+        // keeps its record sequence and makes exactly one trip, and the record array (hence every LDS offset) of the
+        // radar kernels stays what it is.  The second trip starts like a F_PRESYNC step: weight loads, then a barrier
+        // (wave 0 has read the first trip's partial sums behind it), then the partial-sum barrier.
         const int N = r.N;
         const int c = lane & 15, g = lane >> 4;
         const int rgw = wave >> 2, kq = wave & 3;
-        // decoder heads: the sub-tile's first column (classes 16 .. 31 in a second pass); 0 everywhere else
         int cb = 0;
         if constexpr (PROG == PROG_DECODER_HEADS) cb = 16 * r.act;
+#pragma unroll 1
+        for (bool again = false;; again = true) {
         const float* Wn = uptr(r.p0) + (size_t)min(cb + c, N - 1) * 256 + 4 * g;
         const float* src = buf_ptr(S, r.src) + min(16 * rgw + c, R - 1) * buf_ld(r.src);
         float4 av[4], bw[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) bw[q] = ld4(Wn + 16 * (4 * kq + q));
         const float bias = r.p1 != nullptr ? ldg1(uptr(r.p1) + min(cb + c, N - 1)) : 0.0f;
-        if (r.flags & F_PRESYNC) __syncthreads();         // (the source tile is complete behind this barrier)
+        if ((r.flags & F_PRESYNC) || again) __syncthreads();   // (the source tile is complete behind this barrier)
 #pragma unroll
         for (int q = 0; q < 4; ++q) av[q] = act_ld4<PL>(src, 4 * g + 16 * (4 * kq + q));
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -2388,6 +2393,10 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
               }
             }
           }
+        }
+        if constexpr (!prog_is_radar(PROG)) break;
+        cb += 16;
+        if (cb >= N) break;
         }
       } break;
       } break;
@@ -2696,6 +2705,11 @@ int lds_off(int id) {     // float offset of an LDS buffer from the start of sha
 }
 template <int R, int PROG>
 constexpr size_t chain_lds_bytes() { return sizeof(ChainLds<R, rec_cap(PROG)>); }
+// The fusion layers' kernels sit next to the limits: two 16-row workgroups share a CU's 160 KB (81 440 of 81 920 bytes
+// each), a 32-row workgroup takes 154 720.  A step added to PROG_RADAR_LAYER_T is three records (672 / 864 bytes at 4 /
+// 8 waves): at 16 rows the second workgroup of a CU would go.  (The class head's second sub-tile, 17 .. 32 classes, is a
+// second trip inside its K_NARROW step for this reason, not a step of a longer table.)
+static_assert(chain_lds_bytes<16, PROG_RADAR>() <= 80 * 1024 && chain_lds_bytes<32, PROG_RADAR>() <= 160 * 1024, "radar programs: LDS per workgroup");
 inline int buf_ld_h(int id) { return id == B_A ? LD5 : id == B_L ? LDL : LD2; }
 
 template <int R, int PROG, int MM = 0>

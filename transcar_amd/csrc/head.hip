@@ -120,6 +120,8 @@ static int check_dims(const tc_head_weights* w) {
              TC_MAX_LEVELS);
   TC_REQUIRE(w->num_points >= 0 && w->num_cams * w->num_levels * head_points(w) <= TC_MAX_CAM_LOGITS,
              "num_points=%d (num_cams * num_levels * num_points <= %d supported)", w->num_points, TC_MAX_CAM_LOGITS);
+  TC_REQUIRE(w->num_classes >= 1 && w->num_classes <= TC_MAX_CLASSES, "num_classes=%d (1 .. %d supported)", w->num_classes,
+             TC_MAX_CLASSES);
   TC_REQUIRE((w->ffn_dims & 31) == 0 && (w->radar_in_dims & 3) == 0, "ffn_dims/radar_in_dims alignment");
   return 0;
 }

@@ -326,6 +326,7 @@ class Detr3DHead(BaseModule):
                     'differ between decoder layers')
         L.check_num_levels(w.num_levels)
         L.check_num_points(w.num_points, w.num_cams, w.num_levels)
+        L.check_num_classes(self.cls_out_channels)
         w.num_classes, w.code_size = self.cls_out_channels, self.code_size
         w.radar_in_dims, w.num_radar_layers = radar.NUM_FEATURES, 3
         w.num_radar_tokens_ref = radar.NUM_RADAR_TOKENS
@@ -378,6 +379,7 @@ class Detr3DHead(BaseModule):
         h.abi_version = L.TC_ABI_VERSION
         h.num_levels = self.transformer.decoder.num_layers
         h.embed_dims = self.embed_dims
+        L.check_num_classes(self.cls_out_channels)
         h.num_classes, h.code_size = self.cls_out_channels, self.code_size
         for i in range(6):
             h.pc_range[i] = float(self.pc_range[i])
