@@ -140,12 +140,8 @@ def radar_case(rig, name):
             tok_np, pad_mult = R.pack_tokens([rows[:R.NUM_RADAR_TOKENS]], T=R.NUM_RADAR_TOKENS)
         else:
             tok_np, pad_mult = R.pack_tokens([rows])
-        saved = O.transformer
-        O.transformer = lambda *a, **k: rig['xfmr']             # the decoder's trace is the rig's: evaluate it once
-        try:
-            trace = O.head_forward(rig['sd'], rig['feats'], rig['l2i'], HW, f36, PCR, return_debug=True)
-        finally:
-            O.transformer = saved
+        trace = O.head_forward(rig['sd'], rig['feats'], rig['l2i'], HW, f36, PCR, return_debug=True,
+                               decoder_trace=rig['xfmr'])       # the decoder's trace is the rig's: evaluate it once
         assert trace[1]['inter_refs'] is rig['inter_refs'] and torch.equal(trace[1]['hs'], rig['hs'].permute(0, 2, 1, 3))
         hits = np.stack([h.numpy() for h in trace[1]['hit_counts']])
         cache[name] = dict(frame=frame, f36=f36, rows=rows, tok_np=tok_np, pad_mult=pad_mult, trace=trace, hits=hits)

@@ -6,8 +6,8 @@ oracle/ref_harness.py) on seeded synthetic inputs.
 Run only in the authoring container:   python tests/golden/make_golden.py
 (`... make_golden.py configs`: only g9_reference_configs.json, the values of
 the reference's config files).  make_golden_variants.py makes the fixtures of
-the head's other variants (num_points, num_levels, with_box_refine) with the
-same functions.
+the head's other variants (num_points, num_levels, with_box_refine, num_heads,
+num_classes, the decoder levels' own outputs) with the same functions.
 
 Inputs and weights are regenerated from seeds by transcar_amd/synth.py and
 are never stored; only small outputs / intermediates are committed
@@ -39,23 +39,35 @@ def save(name, **arrs):
     print('wrote %s (%.1f KB)' % (name, os.path.getsize(path) / 1024))
 
 
-def ref_head(num_levels=None, num_points=None, with_box_refine=True, train=False):
-    """The REFERENCE's head of one variant (None: the configs' 4 levels / 1 point) in eval mode, with
-    synth.make_state_dict's seeded weights: the same key set and shapes; attention_weights not the reference's zero
+def ref_head(num_levels=None, num_points=None, with_box_refine=True, num_heads=None, num_classes=None, train=False):
+    """The REFERENCE's head of one variant (None: the configs' 4 levels / 1 point / 8 heads / 10 classes) in eval mode,
+    with synth.make_state_dict's seeded weights: the same key set and shapes; attention_weights not the reference's zero
     init (XFMR:297-300: every sigmoid 0.5 would hide a wrong (camera, point, level) order of the logits); without box
-    refinement ONE cls and ONE reg branch under every index (HEAD:223-231)."""
-    kw = {k: v for k, v in dict(num_levels=num_levels, num_points=num_points).items() if v is not None}
+    refinement ONE cls and ONE reg branch under every index (HEAD:223-231).  num_heads is the decoder self-attention's:
+    the state dict does not depend on it, and the radar fusion attention keeps the 8 heads the reference builds it with
+    (HEAD:129-171)."""
+    kw = {k: v for k, v in dict(num_levels=num_levels, num_points=num_points, num_classes=num_classes).items()
+          if v is not None}
     if not with_box_refine:
         kw['with_box_refine'] = False
-    head = RH.build_reference_head(configs.head_cfg(**kw), configs.train_cfg_pts if train else None)
+    cfg = configs.head_cfg(num_heads=num_heads, **kw)
+    assert cfg['num_classes'] == cfg['bbox_coder']['num_classes'] == (num_classes or 10)
+    head = RH.build_reference_head(cfg, configs.train_cfg_pts if train else None)
     assert bool(head.with_box_refine) == with_box_refine
     assert (head.reg_branches[0] is head.reg_branches[5]) == (head.cls_branches[0] is head.cls_branches[5]) \
         == (not with_box_refine)
     assert head.transformer.decoder.layers[0].attentions[1].num_levels == (num_levels or 4)
+    for ly in head.transformer.decoder.layers:
+        assert ly.attentions[0].attn.num_heads == (num_heads or 8)
+    for m in (head.rf_multihead_attn, head.rf_multihead_attn2, head.rf_multihead_attn3):
+        assert m.num_heads == 8
+    assert head.num_classes == head.cls_out_channels == (num_classes or 10)
     sd = synth.make_state_dict(seed=3, **kw)
     ref_keys = {k: tuple(v.shape) for k, v in head.state_dict().items()}
     my_keys = {k: tuple(v.shape) for k, v in sd.items()}
     assert ref_keys == my_keys, (set(ref_keys) ^ set(my_keys))
+    assert sd['final_cls3.6.weight'].shape == (num_classes or 10, 256)
+    assert sd['cls_branches.5.6.bias'].shape == (num_classes or 10,)
     for i in range(6):
         w = sd['transformer.decoder.layers.%d.attentions.1.attention_weights.weight' % i]
         assert w.shape[0] == 6 * (num_points or 1) * (num_levels or 4) and np.abs(w).min() > 0 and w.std() > 0.01
@@ -139,7 +151,9 @@ def run_head(head, feats, l2i, frame):
     return outs, cap, tcap
 
 
-def g345_head(head, ref, shapes, tag):
+def g345_head(head, ref, shapes, tag, num_classes=None, hs_stride=16):
+    """G5 (with G3's and G4's intermediates): Detr3DHead.forward in two passes and the coder's decode at num_classes
+    (None: the configs' 10).  hs_rows keeps every hs_stride-th query; the stride is stored where it is not 16."""
     feats = synth.make_feats(shapes, seed=1, smooth=SMOOTH)
     l2i = synth.make_lidar2img()
     # pass 1: uniform radar, to learn where the decoder puts its boxes
@@ -161,10 +175,12 @@ def g345_head(head, ref, shapes, tag):
         m = cap['mask%d' % i].numpy()
         hit_counts.append((~m).sum(1).astype(np.int32))     # per selected row
     dec = ref.CODER.NMSFreeCoder(**{k: v for k, v in
-                                    configs.pts_bbox_head['bbox_coder'].items()
+                                    configs.head_cfg(num_classes=num_classes)['bbox_coder'].items()
                                     if k != 'type'})
+    assert dec.num_classes == (num_classes or 10)
     preds = dec.decode({'all_cls_scores': outs['all_cls_scores'],
                         'all_bbox_preds': outs['all_bbox_preds']})[0]
+    assert int(preds['labels'].max()) > 15 or dec.num_classes <= 16
     bb = preds['bboxes'].clone()
     bb[:, 2] = bb[:, 2] - bb[:, 5] * 0.5                    # HEAD:1018
     hs = tcap['hs'].numpy()                                  # [6,Q,1,C]
@@ -173,7 +189,7 @@ def g345_head(head, ref, shapes, tag):
          all_bbox_preds=outs['all_bbox_preds'].numpy(),
          inter_refs=tcap['inter_refs'].numpy(),
          init_ref=tcap['init_ref'].numpy(),
-         hs_rows=hs[:, ::16, 0, :],
+         hs_rows=hs[:, ::hs_stride, 0, :], **({} if hs_stride == 16 else {'hs_stride': hs_stride}),
          hs_sum=hs.astype(np.float64).sum(axis=(1, 2, 3)),
          radar_centres=centres,
          radar_tokens=tokens[:fill_in], fill_in=fill_in,
@@ -182,7 +198,8 @@ def g345_head(head, ref, shapes, tag):
          hit_counts2=hit_counts[2],
          dec_boxes=bb.numpy(), dec_scores=preds['scores'].numpy(),
          dec_labels=preds['labels'].numpy(), **level_shapes_of(shapes))
-    print(tag, 'fill_in', fill_in, 'Lq', [cap['Lq%d' % i] for i in range(3)])
+    print(tag, 'fill_in', fill_in, 'Lq', [cap['Lq%d' % i] for i in range(3)],
+          'labels > 15 among the decoded:', int((preds['labels'] > 15).sum()))
 
 
 def g4_radar_empty(head):
@@ -260,14 +277,17 @@ def g8_train_grads(tag='tiny', suffix='', shapes=None, radar_seed=2, **variant):
     tools/train.py:245-252.  Stored as write_g8 says.
 
     suffix, variant: of another head variant (fixture g5_head_<tag><suffix>.npz holds the centres); shapes: its level
-    shapes where they are not the four of `tag`; radar_seed: another radar frame than G5's, stored with the shapes."""
+    shapes where they are not the four of `tag`; radar_seed: another radar frame than G5's, stored in the fixture.  A
+    variant's num_classes is also the ground truth's (synth.make_gt)."""
+    num_classes = variant.get('num_classes') or 10
     head = ref_head(train=True, **variant)
     freeze_like_train_py(head)
     g5 = np.load(os.path.join(HERE, 'g5_head_%s%s.npz' % (tag, suffix)))
     feats = synth.make_feats(shapes or tag, seed=1, smooth=SMOOTH)
     l2i = synth.make_lidar2img()
     frame = synth.make_radar_frame(seed=radar_seed, n_per_radar=51, centres=g5['radar_centres'])
-    boxes, labels = synth.make_gt(seed=7, n=24)
+    boxes, labels = synth.make_gt(seed=7, n=24, num_classes=num_classes)
+    assert labels.max() < num_classes
     with torch.enable_grad():
         outs, cap, _ = run_head(head, feats, l2i, frame)
         if radar_seed == 2:
@@ -276,7 +296,15 @@ def g8_train_grads(tag='tiny', suffix='', shapes=None, radar_seed=2, **variant):
         losses = head.loss([RH.GtBoxes(torch.from_numpy(boxes))], [torch.from_numpy(labels)], outs)
         total = sum(v for k, v in losses.items() if 'loss' in k)
         total.backward()
-    extra = dict(level_shapes_of(shapes), radar_seed=radar_seed) if shapes else {}
+    if num_classes > 16:
+        # labels above 15 are matched in every fusion level: their columns of the class head see a positive target
+        gt = RH.GtBoxes(torch.from_numpy(boxes))
+        gc = torch.cat((gt.gravity_center, gt.tensor[:, 3:]), 1)
+        for i in range(3):
+            inds = head.assigner.assign(outs['all_bbox_preds'][i, 0].detach(), outs['all_cls_scores'][i, 0].detach(), gc,
+                                        torch.from_numpy(labels)).gt_inds.numpy()
+            assert (labels[inds[inds > 0] - 1] > 15).sum() >= 1
+    extra = dict(level_shapes_of(shapes or tag), **({} if radar_seed == 2 else {'radar_seed': radar_seed}))
     write_g8('g8_train_grads%s%s.npz' % ('' if tag == 'tiny' else '_' + tag, suffix), head, outs, cap, losses, total,
              **extra)
 

@@ -2,7 +2,9 @@
 """Fixtures of the head's variants beside the TransCAR configs' (4 levels, num_points 1, box refinement), from the
 REFERENCE's own code (oracle/ref_harness.py) with make_golden.py's functions and rigs (G2's inputs; G5's two passes,
 radar near the predicted centres; G8's iteration).  Run only in the authoring container:
-    python tests/golden/make_golden_variants.py [points] [levels] [norefine]          (none named: all three)
+    python tests/golden/make_golden_variants.py [points] [levels] [norefine] [heads] [classes] [decoder_outputs]
+                                                                                       (none named: all six)
+    python tests/golden/make_golden_variants.py seeds                (prints; see "classes" below)
 
 points -- Detr3DCrossAtten(num_points > 1):
   g2_cross_atten_p5.npz                Detr3DCrossAtten.forward at P = 5
@@ -23,14 +25,43 @@ norefine -- Detr3DHead(with_box_refine=False): one cls and one reg branch shared
   g5_head_tiny_p5_norefine.npz         ... at num_points 5
   g8_train_grads_norefine.npz          one training iteration's gradients, tiny shapes
   g9_norefine_state_dict.json          the reference head's state_dict keys and shapes
+heads -- a decoder self-attention of 4 or 16 heads (attn_cfgs[0].num_heads; the TransCAR configs: 8).  The state dict
+does not depend on the head count (same keys, same shapes: loaded strictly), and the radar fusion attention keeps the 8
+heads the reference builds it with (HEAD:129-171) -- both asserted by make_golden.ref_head:
+  g5_head_tiny_h{4,16}.npz             Detr3DHead.forward, tiny maps (self-attention never sees the maps), 900 queries
+  g8_train_grads_h4.npz                one training iteration's gradients, tiny shapes, 4 heads
+classes -- a head with 23 classes (the raw nuScenes annotation categories; the configs: the benchmark's 10 merged
+ones).  23 classes put seven columns of every class head into the second 16-column sub-tile of the row chains' narrow
+step, and the ground truth (synth.make_gt(seed=7, n=24, num_classes=23)) matches labels above 15 (asserted):
+  g5_head_tiny_c23.npz                 Detr3DHead.forward, tiny maps, 900 queries; decoded with NMSFreeCoder(num_classes=23).
+                                       hs_rows keeps every 32nd query (the other G5 fixtures: every 16th; `hs_stride`):
+                                       with 23 logits a row the file would otherwise pass the largest fixture committed
+  g8_train_grads_c23.npz               one training iteration's gradients, tiny shapes, ground-truth labels 0 .. 22, the
+                                       radar frame of seed G8_C23_RADAR_SEED
+decoder_outputs -- the class scores and boxes of the six DETR3D decoder levels (HEAD:277-298) from the reference's own
+arithmetic, on g5_head_tiny's rig (feature maps seed 1 with SMOOTH, state dict seed 3; the decoder reads no radar):
+  g10_decoder_outputs_tiny{,_norefine}.npz
+The reference computes these outputs and drops them (HEAD:607-608 reset the lists), so its return value cannot be
+recorded.  Forward hooks on each distinct module of head.cls_branches / head.reg_branches keep the OUTPUT TENSORS
+THEMSELVES (no clone): HEAD:287-293 edits `tmp` in place after the module returned, so after the forward a kept
+reg-branch output IS outputs_coord of its level.  With box refinement the decoder calls every reg branch once more
+(XFMR:191); the head's calls are the last six recorded.  The generator asserts that its inter_references equal the g5
+fixture's bit for bit: the fixtures describe the same run.
 
-A radar gate decision that sits next to its radius flips between two fp32 evaluation orders, and a flipped row of the
-third fusion layer moves its attention's gradients by ~1 % (G5-L2's radar frame, seed 2: query 880, 2.1e-4 m from the
-radius).  The two-level gradient fixture takes the radar frame whose closest gate decision, in all three fusion layers,
-is the farthest from its radius among seeds 3 .. 39 (seed 13: 8.9e-4 m, measured with the oracle)."""
+The radar seeds 13 / 14 / 16.  A radar gate decision that sits next to its radius flips between two fp32 evaluation
+orders, and a flipped row of the third fusion layer moves its attention's gradients by ~1 % (G5-L2's radar frame, seed
+2: query 880, 2.1e-4 m from the radius; G5-C23's, seed 2: one 3.8e-5 m from it).  A gradient fixture so affected takes
+the radar frame whose closest gate decision, in all three fusion layers, is the farthest from its radius, measured with
+the oracle: the two-level one among seeds 3 .. 39 (G8_L2_RADAR_SEED = 13: 8.9e-4 m), the 23-class one among seeds
+2 .. 39 (G8_C23_RADAR_SEED = 14: 8.9e-4 m; `seeds` prints the distance per seed, at 23 classes on G5-C23's centres).
+The 32-class training frame of tests/test_gpu_num_classes.py, which has no fixture, was chosen the same way around the
+centres the oracle's own decoder predicts (num_classes_rig.C32_RADAR_SEED = 16: 8.6e-4 m)."""
 import json
 import os
 import sys
+
+import numpy as np
+import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
@@ -38,8 +69,12 @@ sys.path.insert(0, HERE)
 import make_golden as MG                                 # noqa: E402
 from make_golden import g2_cross_atten, g345_head, g8_train_grads, ref_head      # noqa: E402
 
-TINY, RES101 = MG.configs.LEVEL_SHAPES['tiny'], MG.configs.LEVEL_SHAPES['res101']
+from oracle import transcar_oracle as O                  # noqa: E402
+from transcar_amd import configs, synth                  # noqa: E402
+
+TINY, RES101 = configs.LEVEL_SHAPES['tiny'], configs.LEVEL_SHAPES['res101']
 G8_L2_RADAR_SEED = 13
+NC, G8_C23_RADAR_SEED = 23, 14
 
 
 def points(ref):
@@ -76,9 +111,79 @@ def norefine(ref):
     g8_train_grads(suffix='_norefine', with_box_refine=False)
 
 
+def heads(ref):
+    for H in (4, 16):
+        g345_head(ref_head(num_heads=H), ref, 'tiny', 'tiny_h%d' % H)
+    g8_train_grads(suffix='_h4', num_heads=4)
+
+
+def classes(ref):
+    g345_head(ref_head(num_classes=NC), ref, 'tiny', 'tiny_c%d' % NC, num_classes=NC, hs_stride=32)
+    g8_train_grads(suffix='_c%d' % NC, radar_seed=G8_C23_RADAR_SEED, num_classes=NC)
+
+
+def decoder_outputs(ref):
+    for refine, tag in ((True, 'tiny'), (False, 'tiny_norefine')):
+        head = ref_head(with_box_refine=refine)
+        calls = {'cls': [], 'reg': []}
+        hooks = []
+        for kind, branches in (('cls', head.cls_branches), ('reg', head.reg_branches)):
+            for m in {id(m): m for m in branches}.values():        # without refinement: one module under every index
+                hooks.append(m.register_forward_hook(lambda mod, inp, out, kind=kind: calls[kind].append(out)))
+        feats = synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)
+        _, _, tcap = MG.run_head(head, feats, synth.make_lidar2img(), synth.make_radar_frame(seed=2, n_per_radar=51))
+        for h in hooks:
+            h.remove()
+        L = 6
+        assert len(calls['cls']) == L and len(calls['reg']) == (2 * L if refine else L), (len(calls['cls']), len(calls['reg']))
+        g5 = np.load(os.path.join(HERE, 'g5_head_%s.npz' % tag))
+        assert np.array_equal(tcap['inter_refs'].numpy(), g5['inter_refs']), 'not the run of g5_head_' + tag
+        dec_cls = torch.stack(calls['cls']).numpy()
+        dec_box = torch.stack(calls['reg'][-L:]).numpy()
+        assert dec_cls.shape == (L, 1, 900, 10) and dec_box.shape == (L, 1, 900, 10), (dec_cls.shape, dec_box.shape)
+        assert dec_cls.dtype == np.float32 and dec_box.dtype == np.float32
+        MG.save('g10_decoder_outputs_%s.npz' % tag, dec_cls=dec_cls, dec_box=dec_box)
+
+
+def gate_margins(seeds):
+    """Per radar seed: min over the three fusion layers, the queries, the three circles and the tokens of
+    |distance - radius| (metres), from the oracle at NC classes on G5-C23's centres."""
+    g5 = np.load(os.path.join(HERE, 'g5_head_tiny_c%d.npz' % NC))
+    sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_classes=NC))
+    feats = [torch.from_numpy(f) for f in synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)]
+    l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
+    seen = []
+
+    def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
+        length = length_log.exp()
+        radii = torch.clamp((length / 2.0).reshape(-1, 1), min=rmin, max=rmax)
+        live = radar_xy[0, :, 0] != 500.0                  # the padding tokens sit far outside every circle
+        for sign in (0.0, 0.25, -0.25):
+            c = centre_xy.clone()
+            c[..., 0] = c[..., 0] + sign * length * -rot_sin
+            c[..., 1] = c[..., 1] + sign * length * -rot_cos
+            seen.append(float((torch.cdist(c, radar_xy, p=2.0)[0][:, live] - radii).abs().min()))
+
+    out = {}
+    for seed in seeds:
+        del seen[:]
+        frame = synth.make_radar_frame(seed=seed, n_per_radar=51, centres=g5['radar_centres'])
+        O.head_forward(sd, feats, l2i, configs.IMG_SHAPE[:2], O.build_radar_features(frame), configs.point_cloud_range,
+                       gate_probe=probe)
+        assert len(seen) == 9
+        out[seed] = min(seen)
+        print('radar seed %2d: closest gate decision %.2e m from its radius' % (seed, out[seed]))
+    return out
+
+
 def main():
+    if 'seeds' in sys.argv[1:]:
+        m = gate_margins(range(2, 40))
+        best = max(m, key=m.get)
+        print('largest: seed %d, %.2e m' % (best, m[best]))
+        return
     ref = MG.RH.load_reference()
-    for make in (points, levels, norefine):
+    for make in (points, levels, norefine, heads, classes, decoder_outputs):
         if make.__name__ in sys.argv[1:] or not sys.argv[1:]:
             make(ref)
 

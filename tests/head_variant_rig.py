@@ -1,7 +1,12 @@
-"""The rig the GPU tests of the head's variants share (num_points > 1, num_levels < 4, with_box_refine=False and
-decoder layer 0's fold): heads and frames, the CPU oracle's forward, and the checks every variant repeats -- against
-the oracle, against the reference's fixtures, the train-mode decoder with read-back dropout masks, a training iteration
-against the reference's gradients, the plugin graphs, FramePipeline and a frame inside a nine-frame launch.
+"""The rig the tests of the head's variants share (num_points > 1, num_levels < 4, with_box_refine=False, num_heads 4 /
+16, num_classes up to 32, num_query, the decoder levels' own outputs and decoder layer 0's fold): heads and frames, the
+CPU oracle's forward, and the checks every variant repeats -- against the oracle, against the reference's fixtures, the
+train-mode decoder with read-back dropout masks, a training iteration against the reference's gradients, the plugin
+graphs, FramePipeline and a frame inside a nine-frame launch.
+
+A variant is keyword arguments named as CONFIGS' keys; what a key reaches differs (variant_kw, state_dict_kw,
+oracle_kw): the state dict does not depend on num_heads, and the oracle reads num_levels, num_points, num_classes and
+num_query off the state dict and the maps.
 
 A plain helper module (as adverse_rig.py): the test modules import the fixtures `T` and `no_grad` by name.  The
 checkers take torch tensors on any device; tests/test_head_variant_rig.py pins their caps on the CPU."""
@@ -27,7 +32,10 @@ E2E_TOL = 1e-3          # test_gpu_parity.test_head_end_to_end
 HS_TOL_F16X2 = 2e-3
 REFS_TOL = 5e-5         # inter_references against the oracle and the reference
 MAX_GATE_ROWS = 6       # rows whose radar gate decisions (hit counts) may differ: the gate is discontinuous
-CONFIGS = dict(num_levels=4, num_points=1, with_box_refine=True)      # the TransCAR configs' variant
+BOX_TOL = 5e-5          # metres: fp32 spacing at 50 m is 3.8e-6, the reference and the oracle order add / sigmoid / scale differently
+# the TransCAR configs' variant
+CONFIGS = dict(num_levels=4, num_points=1, with_box_refine=True, num_heads=8, num_classes=10, num_query=900)
+HEADS = (4, 16)         # num_heads beside the configs' 8: head dimension 64 and 16
 
 
 @pytest.fixture(autouse=True)
@@ -58,18 +66,38 @@ def gold(name):
 
 # ---- heads and frames ---------------------------------------------------------------------------------------------------
 def variant_kw(**variant):
-    """The arguments of configs.head_cfg / synth.make_state_dict that leave the configs' values."""
+    """The arguments of configs.head_cfg that leave the configs' values."""
     assert set(variant) <= set(CONFIGS), variant
     return {k: v for k, v in variant.items() if v != CONFIGS[k]}
+
+
+def state_dict_kw(**variant):
+    """variant_kw for synth.make_state_dict: the state dict does not depend on the head count."""
+    return {k: v for k, v in variant_kw(**variant).items() if k != 'num_heads'}
+
+
+def oracle_kw(**variant):
+    """What the oracle cannot read off the state dict and the maps (their defaults spelled out)."""
+    variant_kw(**variant)
+    return {k: variant.get(k, CONFIGS[k]) for k in ('with_box_refine', 'num_heads')}
+
+
+def variant_key(**variant):
+    return tuple(sorted(variant_kw(**variant).items()))
 
 
 def make_head(T, *, seed=3, shared_branches=False, **variant):
     """A fresh eval-mode head of the variant with seeded weights, and those weights as the oracle takes them.
     shared_branches: the weights of with_box_refine=False (one cls / reg branch under every index) whatever the head."""
-    kw = variant_kw(**variant)
-    sd_np = synth.make_state_dict(seed=seed, **(dict(kw, with_box_refine=False) if shared_branches else kw))
-    h = T.build_head(configs.head_cfg(**kw))
+    sd_kw = state_dict_kw(**variant)
+    if shared_branches:
+        sd_kw['with_box_refine'] = False
+    sd_np = synth.make_state_dict(seed=seed, **sd_kw)
+    h = T.build_head(configs.head_cfg(**variant_kw(**variant)))
     h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
+    want = dict(CONFIGS, **variant)
+    assert h.weights_struct().num_heads == want['num_heads']
+    assert h.weights_struct().num_classes == h.bbox_coder.num_classes == want['num_classes']
     return h.to(dev()).eval(), O.to_torch_sd(sd_np)
 
 
@@ -78,7 +106,7 @@ _HEADS = {}
 
 def shared_head(T, **variant):
     """make_head(T, **variant), one per variant for the tests that leave it as they found it."""
-    key = tuple(sorted(variant_kw(**variant).items()))
+    key = variant_key(**variant)
     if key not in _HEADS:
         _HEADS[key] = make_head(T, **variant)
     return _HEADS[key]
@@ -86,42 +114,76 @@ def shared_head(T, **variant):
 
 def train_head(**variant):
     import transcar_amd as T_
-    kw = variant_kw(**variant)
-    cfg = configs.head_cfg(**kw)
+    cfg = configs.head_cfg(**variant_kw(**variant))
     cfg['train_cfg'] = configs.train_cfg_pts
     h = T_.build_head(cfg)
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(3, **kw).items()})
+    h.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(3, **state_dict_kw(**variant)).items()})
     return h.to(dev()).freeze_decoder().set_dropout(0.0)
 
 
-def g8_frame(g5_name, shapes='tiny', radar_seed=2):
-    """The frame of a gradient fixture: G5's maps, the radar near the centres that fixture `g5_name` stores, G7's
-    ground truth."""
-    feats = synth.make_feats(shapes, seed=1, smooth=SMOOTH)
+def g8_frame(g5_name, shapes='tiny', radar_seed=2, num_classes=10, centres=None):
+    """The frame of a gradient fixture: G5's maps, the radar of `radar_seed` near `centres` (None: those fixture
+    `g5_name` stores), G7's ground truth drawn from `num_classes` classes.  -> the host side (feats_np, l2i_np, frame,
+    boxes, labels) and, where there is a GPU, the device side (feats, metas, gt, gt_labels)."""
+    feats_np = synth.make_feats(shapes, seed=1, smooth=SMOOTH)
     l2i = synth.make_lidar2img()
-    frame = synth.make_radar_frame(seed=radar_seed, n_per_radar=51, centres=gold(g5_name)['radar_centres'])
-    boxes, labels = synth.make_gt(seed=7, n=24)
-    metas = synth.make_img_metas(1, l2i)
-    metas[0]['radar'] = frame
-    gt = torch.from_numpy(boxes).clone()
-    gt[:, 2] += gt[:, 5] * 0.5
-    return [gpu(f) for f in feats], metas, gt.to(dev()), torch.from_numpy(labels).to(dev()), feats, l2i
+    frame = synth.make_radar_frame(seed=radar_seed, n_per_radar=51,
+                                   centres=gold(g5_name)['radar_centres'] if centres is None else centres)
+    boxes, labels = synth.make_gt(seed=7, n=24, num_classes=num_classes)
+    assert labels.max() > 15 or num_classes <= 16
+    f = dict(feats_np=feats_np, l2i_np=l2i, frame=frame, boxes=boxes, labels=labels)
+    if torch.cuda.is_available():
+        metas = synth.make_img_metas(1, l2i)
+        metas[0]['radar'] = frame
+        gt = torch.from_numpy(boxes).clone()
+        gt[:, 2] += gt[:, 5] * 0.5
+        f.update(feats=[gpu(x) for x in feats_np], metas=metas, gt=gt.to(dev()), gt_labels=torch.from_numpy(labels).to(dev()))
+    return f
 
 
 _ORACLE = {}
 
 
-def oracle_head(sd, feats_np, frame, with_box_refine=True, key=None):
-    """The oracle's head_forward with its debug dict.  key: keep the result under it (one forward for the parametrised
-    cases that share weights, maps and radar frame)."""
+def oracle_head(sd, feats_np, frame, key=None, **variant):
+    """The oracle's head_forward of the variant with its debug dict.  key: keep the result under it and the variant (one
+    forward for the parametrised cases that share weights, maps and radar frame)."""
+    key = None if key is None else (key, variant_key(**variant))
     if key is None or key not in _ORACLE:
         l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
         res = O.head_forward(sd, [torch.from_numpy(f) for f in feats_np], l2i, HW, O.build_radar_features(frame), PCR,
-                             return_debug=True, with_box_refine=with_box_refine)
+                             return_debug=True, **oracle_kw(**variant))
         if key is None:
             return res
         _ORACLE[key] = res
     return _ORACLE[key]
+
+
+_TRACE, _OUT = {}, {}
+
+
+def oracle_trace(**variant):
+    """The oracle's decoder on the g5_head_tiny rig (feature maps seed 1, state dict seed 3), once per variant:
+    -> (sd, hs [L,B,Q,C], init_ref [B,Q,3], inter_refs [L,B,Q,3])."""
+    key = variant_key(**variant)
+    if key not in _TRACE:
+        sd = O.to_torch_sd(synth.make_state_dict(seed=3, **state_dict_kw(**variant)))
+        feats = synth.make_feats('tiny', seed=1, smooth=SMOOTH)
+        l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
+        with torch.no_grad():
+            hs, init_ref, inter_refs, _ = O.transformer(sd, [torch.from_numpy(f) for f in feats], PCR, l2i, HW,
+                                                        **oracle_kw(**variant))
+        _TRACE[key] = (sd, hs.permute(0, 2, 1, 3).contiguous(), init_ref, inter_refs)
+    return _TRACE[key]
+
+
+def oracle_outputs(**variant):
+    """O.decoder_outputs on oracle_trace(**variant), computed once and shared: (cls, box) as numpy arrays"""
+    key = variant_key(**variant)
+    if key not in _OUT:
+        with torch.no_grad():
+            cls, box = O.decoder_outputs(*oracle_trace(**variant), PCR)
+        _OUT[key] = (cls.numpy(), box.numpy())
+    return _OUT[key]
 
 
 def run_head(head, feats_np, frame, **options):
@@ -241,7 +303,7 @@ def check_train_mode_decoder(frame, rows, matrix, refs_atol=2e-4, **variant):
     p, seed = 0.1, 0x5EED1234ABCD
     h = train_head(**variant)
     h.set_decoder_dropout(p)
-    feats, metas, _, _, feats_np, l2i_np = frame
+    feats, metas = frame['feats'], frame['metas']
     nhwc = ops.to_nhwc_levels(feats)
     l2i = ops.lidar2img_tensor(metas, dev())
     img_hw = metas[0]['img_shape'][0][:2]
@@ -252,40 +314,70 @@ def check_train_mode_decoder(frame, rows, matrix, refs_atol=2e-4, **variant):
     b = h.forward_nhwc(nhwc, l2i, img_hw, tokens, pad_mult, aux=True, _allow_train=True, options=head_options(**opts))
     hs = a['aux']['inter_states']
     assert torch.equal(hs, b['aux']['inter_states'])                 # same seed, same masks
-    refine = variant.get('with_box_refine', True)
-    if not refine:
+    okw = oracle_kw(**variant)
+    if not okw['with_box_refine']:
         refs_are_initial(a['aux'])
     want_hs, init_ref, want_refs, _ = O.transformer(
-        O.to_torch_sd(synth.make_state_dict(3, **variant_kw(**variant))), [torch.from_numpy(f) for f in feats_np], PCR,
-        torch.from_numpy(l2i_np).float()[None], HW, dec_drop=decoder_dropout_masks(p, seed, h.num_query),
-        with_box_refine=refine)
+        O.to_torch_sd(synth.make_state_dict(3, **state_dict_kw(**variant))), [torch.from_numpy(f) for f in frame['feats_np']],
+        PCR, torch.from_numpy(frame['l2i_np']).float()[None], HW,
+        dec_drop=decoder_dropout_masks(p, seed, h.num_query, H=okw['num_heads']), **okw)
     np.testing.assert_allclose(a['aux']['init_reference'].cpu().numpy(), init_ref.numpy(), atol=1e-6, rtol=0)
     np.testing.assert_allclose(a['aux']['inter_references'].cpu().numpy(), want_refs.numpy(), atol=refs_atol, rtol=0)
     np.testing.assert_allclose(hs.cpu().numpy()[:, 0], want_hs[:, :, 0].numpy(), atol=2e-3, rtol=0)
 
 
-def check_training_iteration(frame, g8_name, what, **variant):
-    """One FusionTrainer iteration (frozen decoder -> radar stack -> loss -> backward) against the reference's losses
-    and gradients (a G8 fixture), 2e-3 as test_training's oracle-vs-reference check.  frame: g8_frame(...)."""
-    from test_training import check_grads_against_g8, trainable
+class GradStats(dict):
+    """Gradients {name: tensor or None} in the layout of a G8 fixture (make_golden.write_g8): the reference side of
+    test_training.check_grads_against_g8 where no fixture exists."""
+    def __init__(self, grads):
+        super().__init__()
+        for k, g in grads.items():
+            key = k.replace('.', '__')
+            if g is None:
+                self[key + '__none'] = np.zeros(1)
+                continue
+            g = g.detach().double().flatten().cpu()
+            self[key + '__stats'] = np.array([g.sum(), g.abs().sum(), g.norm()], np.float64)
+            self[key + '__head'] = g[:16].float().numpy()
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def trainer_iteration(frame, **kw):
+    """One FusionTrainer.step_fused_nhwc(update=False) (frozen decoder -> radar stack -> loss -> backward) of a fresh
+    head.  frame: g8_frame(...); kw: the variant, and what is no variant key goes to FusionTrainer.
+    -> (losses {name: float}, {name: gradient or None} of the trainable parameters)"""
+    from test_training import trainable
     from transcar_amd import ops
     from transcar_amd.trainer import FusionTrainer
-    g8 = gold(g8_name)
+    variant = {k: kw.pop(k) for k in list(kw) if k in CONFIGS}
     h = train_head(**variant)
-    feats, metas, gt, labels, _, _ = frame
-    nhwc = [ops.to_nhwc(f) for f in feats]
+    metas = frame['metas']
+    nhwc = [ops.to_nhwc(f) for f in frame['feats']]
     l2i = ops.lidar2img_tensor(metas, dev())
     tokens, pad_mult = h.radar_tokens(metas, dev())
-    tr = FusionTrainer(h, dropout=0.0)
+    tr = FusionTrainer(h, dropout=0.0, **kw)
     with torch.enable_grad():
-        losses = tr.step_fused_nhwc(nhwc, l2i, metas[0]['img_shape'][0][:2], tokens, pad_mult, [gt], [labels],
-                                    update=False)
-    for k, v in losses.items():
-        ref = float(g8['loss__' + k.replace('.', '_')])
-        assert abs(float(v) - ref) < 2e-3 * max(1.0, abs(ref)), (k, float(v), ref)
+        losses = tr.step_fused_nhwc(nhwc, l2i, metas[0]['img_shape'][0][:2], tokens, pad_mult, [frame['gt']],
+                                    [frame['gt_labels']], update=False)
+    torch.cuda.synchronize()
     used = {n for n, _ in h.trainable_parameters()}
     grads = {k: (p.grad.clone() if (p.grad is not None and k in used) else None)
              for k, p in h.named_parameters() if trainable(k)}
+    return {k: float(v) for k, v in losses.items()}, grads
+
+
+def check_training_iteration(frame, g8_name, what, **variant):
+    """trainer_iteration against the reference's losses and gradients (a G8 fixture), 2e-3 as test_training's
+    oracle-vs-reference check."""
+    from test_training import check_grads_against_g8
+    g8 = gold(g8_name)
+    losses, grads = trainer_iteration(frame, **variant)
+    for k, v in losses.items():
+        ref = float(g8['loss__' + k.replace('.', '_')])
+        assert abs(v - ref) < 2e-3 * max(1.0, abs(ref)), (k, v, ref)
     assert check_grads_against_g8(grads, g8, 2e-3, what) == 98
 
 

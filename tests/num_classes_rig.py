@@ -1,22 +1,19 @@
 """What the tests of the head's class count (num_classes 17 .. 32: a second 16-column sub-tile in the class heads of
-the row chains; the configs: 10) add to head_variant_rig.py: heads built with configs.head_cfg(num_classes=NC) and
-synth.make_state_dict(num_classes=NC), the small two-sample case the fused radar chain is fed, the frames of the
-gradient fixture, and the oracle's training iteration with the loss composed per level (oracle.loss fixes 10 classes).
+the row chains; the configs: 10) add to head_variant_rig.py, whose heads, frames and trainer iteration they use with
+num_classes=NC: the fixtures' names and seeds, the small two-sample case the fused radar chain is fed, and the oracle's
+training iteration.  The oracle's class heads take their width from the state dict; its loss takes num_classes.
 
-The oracle needs no steering: its class heads take their width from the state dict.
-
-A plain helper module (as num_heads_rig.py); the checkers it runs are head_variant_rig's and teacher_forced_checks' own,
-by import.  Everything computed on the CPU is computed once per class count and kept."""
+A plain helper module.  Everything computed on the CPU is computed once per class count and kept."""
 import numpy as np
 import torch
 
 import head_variant_rig as R
 from oracle import transcar_oracle as O
-from transcar_amd import configs, synth
+from transcar_amd import synth
 
-NC_FIXTURE = 23                  # tests/golden/make_golden_classes.py
+NC_FIXTURE = 23                  # tests/golden/make_golden_variants.py `classes`
 G5_C23, G8_C23 = 'g5_head_tiny_c23.npz', 'g8_train_grads_c23.npz'
-G8_C23_RADAR_SEED = 14           # make_golden_classes.G8_C23_RADAR_SEED (the fixture stores it: asserted by the tests)
+G8_C23_RADAR_SEED = 14           # make_golden_variants.G8_C23_RADAR_SEED (the fixture stores it: asserted by the tests)
 # the 32-class training frame (no fixture): chosen the same way, with the oracle at 32 classes around the centres its
 # own decoder predicts -- of seeds 2 .. 39 the one whose closest gate decision is farthest from its radius (8.6e-4 m)
 C32_RADAR_SEED = 16
@@ -35,42 +32,8 @@ KERNEL_SEEDS = (2, 4)
 MIN_HIT_ROWS = 10
 
 
-def state_dict(NC, num_query=900, seed=3):
-    return synth.make_state_dict(seed=seed, num_classes=NC, **({} if num_query == 900 else dict(num_query=num_query)))
-
-
-def make_head(T, NC, num_query=900, seed=3, **head_kw):
-    """A fresh eval-mode head of NC classes with seeded weights, and those weights as the oracle takes them."""
-    sd_np = state_dict(NC, num_query, seed)
-    h = T.build_head(dict(configs.head_cfg(num_query=num_query, num_classes=NC), **head_kw))
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
-    assert h.weights_struct().num_classes == NC and h.bbox_coder.num_classes == NC
-    return h.to(R.dev()).eval(), O.to_torch_sd(sd_np)
-
-
-_HEADS = {}
-
-
-def shared_head(T, NC, num_query=900):
-    """make_head(T, NC, num_query), one per shape for the tests that leave it as they found it."""
-    if (NC, num_query) not in _HEADS:
-        _HEADS[NC, num_query] = make_head(T, NC, num_query)
-    return _HEADS[NC, num_query]
-
-
-def train_head(NC):
-    import transcar_amd as T_
-    cfg = configs.head_cfg(num_classes=NC)
-    cfg['train_cfg'] = configs.train_cfg_pts
-    h = T_.build_head(cfg)
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in state_dict(NC).items()})
-    return h.to(R.dev()).freeze_decoder().set_dropout(0.0)
-
-
-def _head_forward(sd, feats_np, frame):
-    l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
-    return O.head_forward(sd, [torch.from_numpy(f) for f in feats_np], l2i, R.HW, O.build_radar_features(frame), R.PCR,
-                          return_debug=True)
+def state_dict(NC, num_query=900):
+    return synth.make_state_dict(seed=3, **R.state_dict_kw(num_classes=NC, num_query=num_query))
 
 
 def centres_of(dbg):
@@ -92,12 +55,12 @@ def kernel_case(NC, seeds=None):
             sd_np = state_dict(NC, KQ)
             sd = O.to_torch_sd(sd_np)
             feats_np = synth.make_feats('tiny', seed=1, smooth=R.SMOOTH)
-            _, dbg0 = _head_forward(sd, feats_np, synth.make_radar_frame(seed=2, n_per_radar=12))
+            _, dbg0 = R.oracle_head(sd, feats_np, synth.make_radar_frame(seed=2, n_per_radar=12))
             centres = centres_of(dbg0)
             samples = []
             for s in (seeds or KERNEL_SEEDS):
                 frame = synth.make_radar_frame(seed=s, n_per_radar=12, centres=centres)
-                want, dbg = _head_forward(sd, feats_np, frame)
+                want, dbg = R.oracle_head(sd, feats_np, frame)
                 samples.append((want, dbg, O.build_radar_features(frame)))
         _KERNEL[key] = dict(sd_np=sd_np, feats_np=feats_np, samples=samples)
     return _KERNEL[key]
@@ -109,61 +72,12 @@ def hit_rows(case):
 
 
 # ---- training ------------------------------------------------------------------------------------------------------------
-def train_frame(NC, centres, radar_seed):
-    """head_variant_rig.g8_frame with the ground truth drawn from NC classes: G5's maps, the radar of `radar_seed` near
-    `centres`, synth.make_gt(seed=7, n=24, num_classes=NC).  -> (device side as g8_frame, host side for the oracle)"""
-    feats = synth.make_feats('tiny', seed=1, smooth=R.SMOOTH)
-    l2i = synth.make_lidar2img()
-    frame = synth.make_radar_frame(seed=radar_seed, n_per_radar=51, centres=centres)
-    boxes, labels = synth.make_gt(seed=7, n=24, num_classes=NC)
-    assert labels.max() > 15 or NC <= 16
-    host = dict(feats=feats, frame=frame, boxes=boxes, labels=labels)
-    if not torch.cuda.is_available():
-        return None, host
-    metas = synth.make_img_metas(1, l2i)
-    metas[0]['radar'] = frame
-    gt = torch.from_numpy(boxes).clone()
-    gt[:, 2] += gt[:, 5] * 0.5
-    return ([R.gpu(f) for f in feats], metas, gt.to(R.dev()), torch.from_numpy(labels).to(R.dev())), host
-
-
-def oracle_loss(outs, gt_boxes_bottom, gt_labels, code_weights, NC):
-    """oracle.loss (HEAD:919-1001, B = 1) with loss_single called per level at NC classes."""
-    g = gt_boxes_bottom.clone()
-    g[:, 2] = g[:, 2] + g[:, 5] * 0.5
-    per = [O.loss_single(outs['all_cls_scores'][i, 0], outs['all_bbox_preds'][i, 0], g, gt_labels, code_weights,
-                         num_classes=NC) for i in range(outs['all_cls_scores'].shape[0])]
-    res = {'loss_cls': per[-1][0], 'loss_bbox': per[-1][1]}
-    for i, (lc, lb, _) in enumerate(per[:-1]):
-        res['d%d.loss_cls' % i], res['d%d.loss_bbox' % i] = lc, lb
-    return res, [p[2] for p in per]
-
-
-class GradStats(dict):
-    """Gradients {name: tensor or None} in the layout of a G8 fixture (make_golden.write_g8): the reference side of
-    test_training.check_grads_against_g8 where no fixture exists."""
-    def __init__(self, grads):
-        super().__init__()
-        for k, g in grads.items():
-            key = k.replace('.', '__')
-            if g is None:
-                self[key + '__none'] = np.zeros(1)
-                continue
-            g = g.detach().double().flatten().cpu()
-            self[key + '__stats'] = np.array([g.sum(), g.abs().sum(), g.norm()], np.float64)
-            self[key + '__head'] = g[:16].float().numpy()
-
-    @property
-    def files(self):
-        return list(self)
-
-
 _TRAIN = {}
 
 
 def oracle_training(NC, host):
-    """One training iteration of the oracle (autograd) on train_frame's host side: -> (outs, losses {name: float},
-    matched gt per level, {name: gradient or None} of the trainable parameters).  Kept per class count."""
+    """One training iteration of the oracle (autograd) on the host side of a head_variant_rig.g8_frame: -> (outs, losses
+    {name: float}, matched gt per level, {name: gradient or None} of the trainable parameters).  Kept per class count."""
     from test_training import trainable
     if NC not in _TRAIN:
         sd = O.to_torch_sd(state_dict(NC))
@@ -171,33 +85,12 @@ def oracle_training(NC, host):
             if trainable(k):
                 v.requires_grad_(True)
         with torch.enable_grad():
-            outs = O.head_forward(sd, [torch.from_numpy(f) for f in host['feats']],
+            outs = O.head_forward(sd, [torch.from_numpy(f) for f in host['feats_np']],
                                   torch.from_numpy(synth.make_lidar2img()).float()[None], R.HW,
                                   O.build_radar_features(host['frame']), R.PCR)
-            res, matches = oracle_loss(outs, torch.from_numpy(host['boxes']), torch.from_numpy(host['labels']),
-                                       sd['code_weights'], NC)
+            res, matches = O.loss(outs, torch.from_numpy(host['boxes']), torch.from_numpy(host['labels']),
+                                  sd['code_weights'], num_classes=NC)
             sum(res.values()).backward()
         _TRAIN[NC] = ({k: v.detach() for k, v in outs.items() if v is not None}, {k: float(v.detach()) for k, v in res.items()},
                       matches, {k: v.grad for k, v in sd.items() if trainable(k)})
     return _TRAIN[NC]
-
-
-def trainer_iteration(NC, dev_frame, **trainer_kw):
-    """One FusionTrainer.step_fused_nhwc(update=False) of a fresh NC-class head: -> (losses, {name: gradient or None})."""
-    from test_training import trainable
-    from transcar_amd import ops
-    from transcar_amd.trainer import FusionTrainer
-    h = train_head(NC)
-    feats, metas, gt, labels = dev_frame
-    nhwc = [ops.to_nhwc(f) for f in feats]
-    l2i = ops.lidar2img_tensor(metas, R.dev())
-    tokens, pad_mult = h.radar_tokens(metas, R.dev())
-    tr = FusionTrainer(h, dropout=0.0, **trainer_kw)
-    with torch.enable_grad():
-        losses = tr.step_fused_nhwc(nhwc, l2i, metas[0]['img_shape'][0][:2], tokens, pad_mult, [gt], [labels],
-                                    update=False)
-    torch.cuda.synchronize()
-    used = {n for n, _ in h.trainable_parameters()}
-    grads = {k: (p.grad.clone() if (p.grad is not None and k in used) else None)
-             for k, p in h.named_parameters() if trainable(k)}
-    return {k: float(v) for k, v in losses.items()}, grads

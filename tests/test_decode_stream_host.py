@@ -1,21 +1,13 @@
 """The box decode's second kernel on the host side: the entries that name a kernel are exported and bound, the ABI
 version is what it was, the caps of the header and of the binding agree, and the refusals that need no launch.  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 
+from parity_util import header_define
 from transcar_amd import _lib as L
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'transcar_hip.h')
 PCR = (ctypes.c_float * 6)(-61.2, -61.2, -10.0, 61.2, 61.2, 10.0)
-
-
-def header_define(name):
-    m = re.search(r'^#define %s\s+(.+?)\s*$' % name, open(HEADER).read(), flags=re.M)
-    assert m, name
-    return int(eval(m.group(1), {'__builtins__': {}}))         # an integer expression: 12288, (1 << 20)
 
 
 def test_path_entries_are_exported_and_bound():

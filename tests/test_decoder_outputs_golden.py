@@ -1,5 +1,5 @@
-"""The decoder levels' own outputs (HEAD:277-298): the oracle helper tests/decoder_outputs_oracle.py against the
-fixtures tests/golden/make_golden_decoder_outputs.py recorded from the reference's own arithmetic.  No GPU.
+"""The decoder levels' own outputs (HEAD:277-298): the oracle's decoder_outputs against the fixtures
+tests/golden/make_golden_variants.py `decoder_outputs` recorded from the reference's own arithmetic.  No GPU.
 
 Measured where the fixtures were made, on the reference's own decoder states: logits differ by 0, boxes by 7.6e-6 m
 (fp32 spacing at 50 m: 3.8e-6; the oracle orders add / sigmoid / scale differently); the centres against the
@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-import decoder_outputs_oracle as DO
+import head_variant_rig as R
+from oracle import transcar_oracle as O
 
 CLS_ULPS = 8
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -32,10 +33,10 @@ def test_helper_matches_the_references_decoder_levels(refine):
     g5 = np.load(os.path.join(GOLDEN, FIXTURES[refine][1]))
     assert g10['dec_cls'].shape == (6, 1, 900, 10) and g10['dec_box'].shape == (6, 1, 900, 10)
     assert g10['dec_cls'].dtype == np.float32 and g10['dec_box'].dtype == np.float32
-    sd = DO.oracle_trace(refine)[0]
+    sd = R.oracle_trace(with_box_refine=refine)[0]
     with torch.no_grad():
-        cls, box = DO.decoder_outputs(sd, torch.from_numpy(g5['hs_rows'])[:, None], torch.from_numpy(g5['init_ref'])[:, ::16],
-                                      torch.from_numpy(g5['inter_refs'])[:, :, ::16])
+        cls, box = O.decoder_outputs(sd, torch.from_numpy(g5['hs_rows'])[:, None], torch.from_numpy(g5['init_ref'])[:, ::16],
+                                     torch.from_numpy(g5['inter_refs'])[:, :, ::16], R.PCR)
     d_cls = np.abs(cls.numpy() - g10['dec_cls'][:, :, ::16]).max()
     d_box = np.abs(box.numpy() - g10['dec_box'][:, :, ::16]).max()
     print('refine=%s, reference states: max|helper - reference| logits %.3g, boxes %.3g m' % (refine, d_cls, d_box))
@@ -43,15 +44,15 @@ def test_helper_matches_the_references_decoder_levels(refine):
         bound = CLS_ULPS * float(np.spacing(np.float32(4.0)))        # 3.8e-6; the logits reach |4|
         print('refine=%s: logits NOT bit-equal on this CPU: max %.3g, bound %.3g' % (refine, d_cls, bound))
         assert d_cls <= bound, (d_cls, bound)
-    assert d_box <= DO.BOX_TOL, d_box
+    assert d_box <= R.BOX_TOL, d_box
     # columns 0, 1, 4 of level l against the g5 fixture's reference points of level l, in metres
     centre = g10['dec_box'][..., [0, 1, 4]]
-    refs_m = DO.denormalised_refs(torch.from_numpy(g5['inter_refs'])).numpy()
+    refs_m = O.denormalised_refs(torch.from_numpy(g5['inter_refs']), R.PCR).numpy()
     d_ref = np.abs(centre - refs_m).max()
     print('refine=%s: max|box centre - denormalised inter_references| = %.3g m' % (refine, d_ref))
     if refine:
         # the refined reference point of level l IS the box centre of level l (XFMR:195-203, HEAD:287-293)
-        assert d_ref <= DO.BOX_TOL, d_ref
+        assert d_ref <= R.BOX_TOL, d_ref
     else:
         # no refinement: the references stay the initial ones, the boxes move -- an implementation that quietly
         # refines fails here
@@ -66,7 +67,7 @@ def test_helper_on_the_oracles_own_trace(refine):
     the library to both on the GPU."""
     from head_variant_rig import E2E_TOL, assert_all_but_two_queries
     g10 = np.load(os.path.join(GOLDEN, FIXTURES[refine][0]))
-    cls, box = DO.oracle_outputs(refine)
+    cls, box = R.oracle_outputs(with_box_refine=refine)
     print('refine=%s, oracle trace: max|oracle - reference| logits %.3g, boxes %.3g m'
           % (refine, np.abs(cls - g10['dec_cls']).max(), np.abs(box - g10['dec_box']).max()))
     assert_all_but_two_queries(cls[:, 0], g10['dec_cls'][:, 0], E2E_TOL, 'logits: oracle vs reference')

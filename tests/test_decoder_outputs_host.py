@@ -2,17 +2,16 @@
 side: declarations, bindings, the unchanged ABI, every refusal and its message.  No GPU: each call below fails on its
 argument check before anything is launched."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
 import transcar_amd as T
+from parity_util import header_text
 from transcar_amd import _lib as L
 from transcar_amd import configs, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ('tc_decoder_heads_packed_bytes', 'tc_decoder_heads_pack', 'tc_decoder_outputs_fwd')
 
 
@@ -24,7 +23,7 @@ def _head(refine=True, **kw):
 
 
 def test_entries_are_declared_exported_and_bound():
-    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'transcar_hip.h')).read(), flags=re.S)
+    text = header_text(comments=False)
     dll = ctypes.CDLL(L.LIB_PATH)
     for name in ENTRIES:
         assert re.search(r'\b%s\s*\(' % name, text), name

@@ -12,7 +12,6 @@ import numpy as np
 import pytest
 import torch
 
-import decoder_outputs_oracle as DO
 import head_variant_rig as R
 from head_variant_rig import T, no_grad           # noqa: F401 (fixtures)
 from oracle import transcar_oracle as O
@@ -54,7 +53,7 @@ def heads_struct(sd_gpu, levels, ncls, code):
     h = L.tc_decoder_heads()
     h.abi_version, h.num_levels, h.embed_dims, h.num_classes, h.code_size = L.TC_ABI_VERSION, levels, 256, ncls, code
     for i in range(6):
-        h.pc_range[i] = float(DO.PCR[i])
+        h.pc_range[i] = float(R.PCR[i])
 
     def lin(key):
         return L.tc_linear(sd_gpu[key + '.weight'].data_ptr(), sd_gpu[key + '.bias'].data_ptr())
@@ -74,8 +73,8 @@ def stream():
 
 def normalised(box):
     """columns 0, 1, 4 of boxes in metres -> (0, 1)"""
-    lo = box.new_tensor(DO.PCR[:3])
-    hi = box.new_tensor(DO.PCR[3:])
+    lo = box.new_tensor(R.PCR[:3])
+    hi = box.new_tensor(R.PCR[3:])
     return (box[..., [0, 1, 4]] - lo) / (hi - lo)
 
 
@@ -98,8 +97,8 @@ def test_kernel_against_fp64_at_every_tile_height_and_path(T, ncls, code):
     t = lambda a, dt: torch.from_numpy(a).to(dt)            # noqa: E731
     sd64 = {k: t(v, torch.float64) for k, v in sd.items()}
     sd32 = {k: t(v, torch.float32) for k, v in sd.items()}
-    want_cls, want_box = DO.decoder_outputs(sd64, t(hs, torch.float64), t(init_ref, torch.float64), t(inter_refs, torch.float64))
-    o32_cls, o32_box = DO.decoder_outputs(sd32, t(hs, torch.float32), t(init_ref, torch.float32), t(inter_refs, torch.float32))
+    want_cls, want_box = O.decoder_outputs(sd64, t(hs, torch.float64), t(init_ref, torch.float64), t(inter_refs, torch.float64), R.PCR)
+    o32_cls, o32_box = O.decoder_outputs(sd32, t(hs, torch.float32), t(init_ref, torch.float32), t(inter_refs, torch.float32), R.PCR)
     other = [j for j in range(code) if j not in (0, 1, 4)]
     dev32 = dict(cls=float((o32_cls.double() - want_cls).abs().max()),
                  box=float((o32_box.double() - want_box)[..., other].abs().max()),
@@ -206,7 +205,7 @@ def run(head, outputs, matrix_path=None, radar=None, aux=True):
 def test_camera_outputs_against_reference_and_oracle(T, refine, matrix_path):
     head, _ = R.shared_head(T, with_box_refine=refine)
     fixture = R.gold(FIXTURES[refine])
-    o_cls, o_box = DO.oracle_outputs(refine)
+    o_cls, o_box = R.oracle_outputs(with_box_refine=refine)
     outs = run(head, 'camera', matrix_path)
     assert outs['enc_cls_scores'] is None and outs['enc_bbox_preds'] is None
     aux = outs['aux']

@@ -1,7 +1,7 @@
 """Heads of 17 .. 32 classes on the MI355X: the fusion layers' class head takes a second 16-column sub-tile (chain.hip,
 K_NARROW of the radar programs).  The fused radar chain on the smallest shapes where that can go wrong, at every tile
 height and matrix path, against the CPU oracle; the whole 23-class head against the oracle and the reference's fixtures
-(tests/golden/make_golden_classes.py); outputs='all'; a training iteration at 23 classes against the reference's
+(tests/golden/make_golden_variants.py `classes`); outputs='all'; a training iteration at 23 classes against the reference's
 gradients and at 32 against the oracle's autograd; the replay paths; last_level_cls_only.  The shared checks are
 head_variant_rig.py's and teacher_forced_checks.py's, by import.  pytest -m gpu"""
 import numpy as np
@@ -13,6 +13,7 @@ import num_classes_rig as NC
 from head_variant_rig import SMOOTH, T, gpu, no_grad  # noqa: F401  (T, no_grad: fixtures)
 from parity_util import assert_rows_match
 from teacher_forced_checks import LAYER_TOL, hit_aware
+from oracle import transcar_oracle as O
 from test_training import check_grads_against_g8
 from transcar_amd import radar as RD, synth
 
@@ -65,7 +66,7 @@ def test_radar_chain_class_counts(T, ncls, path):
     from transcar_amd.detr3d_head import head_options
     case = NC.kernel_case(ncls)
     assert min(min(r) for r in NC.hit_rows(case)) >= NC.MIN_HIT_ROWS, NC.hit_rows(case)
-    head, _ = NC.shared_head(T, ncls, NC.KQ)
+    head, _ = R.shared_head(T, num_classes=ncls, num_query=NC.KQ)
     hs5, ref5, tmp, tokens, pad_mult, want, want_hits = _kernel_inputs(case)
     assert hs5.shape == (2, NC.KQ, 256) and tokens.shape == (2, NC.KT, 36)
     cls, box, hits = ops.radar_fusion(head, hs5, ref5, tmp, tokens, pad_mult, 0, 3, options=head_options(**NC.PATHS[path]))
@@ -82,7 +83,7 @@ def test_operator_by_operator_path_class_counts(T, ncls):
     from transcar_amd import ops
     from transcar_amd.detr3d_head import head_options
     case = NC.kernel_case(ncls)
-    head, _ = NC.shared_head(T, ncls, NC.KQ)
+    head, _ = R.shared_head(T, num_classes=ncls, num_query=NC.KQ)
     feats = [gpu(np.concatenate([f, f], 0)) for f in case['feats_np']]
     tok_np, pad_mult = RD.pack_tokens([f36 for _, _, f36 in case['samples']], T=NC.KT)
     metas = synth.make_img_metas(2, synth.make_lidar2img())
@@ -107,7 +108,7 @@ def _g5_frame():
 @pytest.mark.parametrize('path', sorted(NC.PATHS))
 def test_head_23_classes_paths_oracle_and_golden(T, path):
     gold, feats_np, frame = _g5_frame()
-    head, sd = NC.shared_head(T, 23)
+    head, sd = R.shared_head(T, num_classes=23)
     want, dbg = R.oracle_head(sd, feats_np, frame, key='num_classes 23 golden')      # (the paths share one oracle forward)
     outs = R.run_head(head, feats_np, frame, **NC.PATHS[path])
     assert outs['all_cls_scores'].shape == (3, 1, 900, 23) and torch.isfinite(outs['all_cls_scores']).all()
@@ -123,9 +124,8 @@ def test_get_bboxes_23_classes(T):
     """get_bboxes of the reference's outputs is the reference's decode (NMSFreeCoder(num_classes=23): labels above 15
     among them), up to neighbours swapping at near-tied scores (test_gpu_parity.test_box_decode_vs_oracle); and
     get_bboxes of the head's own forward is the oracle's decode of the same tensors."""
-    from oracle import transcar_oracle as O
     gold, feats_np, frame = _g5_frame()
-    head, _ = NC.shared_head(T, 23)
+    head, _ = R.shared_head(T, num_classes=23)
     got = head.get_bboxes({'all_cls_scores': gpu(gold['all_cls_scores']), 'all_bbox_preds': gpu(gold['all_bbox_preds'])},
                           synth.make_img_metas(1))[0]
     np.testing.assert_allclose(got[1].cpu().numpy(), gold['dec_scores'], atol=1e-6, rtol=0)
@@ -144,7 +144,7 @@ def test_get_bboxes_23_classes(T):
 # ---- 3. outputs='all' ----------------------------------------------------------------------------------------------------
 def test_all_outputs_23_classes(T):
     _, feats_np, frame = _g5_frame()
-    head, _ = NC.make_head(T, 23)
+    head, _ = R.make_head(T, num_classes=23)
     fusion = R.run_head(head, feats_np, frame)
     head.outputs = 'all'
     try:
@@ -167,10 +167,10 @@ def c23():
     """One fused iteration at 23 classes on the gradient fixture's frame."""
     g8 = R.gold(NC.G8_C23)
     assert int(g8['radar_seed']) == NC.G8_C23_RADAR_SEED
-    dev_frame, _ = NC.train_frame(23, R.gold(NC.G5_C23)['radar_centres'], NC.G8_C23_RADAR_SEED)
+    frame = R.g8_frame(NC.G5_C23, radar_seed=NC.G8_C23_RADAR_SEED, num_classes=23)
     with torch.no_grad():
-        losses, grads = NC.trainer_iteration(23, dev_frame)
-    return g8, dev_frame, losses, grads
+        losses, grads = R.trainer_iteration(frame, num_classes=23)
+    return g8, frame, losses, grads
 
 
 def test_training_iteration_23_classes_gradients_match_reference(T, c23):
@@ -183,22 +183,22 @@ def test_training_iteration_32_classes_gradients_match_oracle_autograd(T):
     """32 classes (the full second sub-tile, no fixture): the oracle's autograd on the CPU is the reference side.  The
     radar frame: G5's rig around the centres the oracle's decoder predicts, the seed chosen as G8-C23's."""
     with torch.no_grad():
-        sd = NC.O.to_torch_sd(NC.state_dict(32))
-        _, dbg0 = NC._head_forward(sd, synth.make_feats('tiny', seed=1, smooth=SMOOTH),
-                                   synth.make_radar_frame(seed=2, n_per_radar=51))
-    dev_frame, host = NC.train_frame(32, NC.centres_of(dbg0), NC.C32_RADAR_SEED)
-    _, want_losses, matches, want_grads = NC.oracle_training(32, host)
+        sd = O.to_torch_sd(NC.state_dict(32))
+        _, dbg0 = R.oracle_head(sd, synth.make_feats('tiny', seed=1, smooth=SMOOTH),
+                                synth.make_radar_frame(seed=2, n_per_radar=51))
+    frame = R.g8_frame(None, radar_seed=NC.C32_RADAR_SEED, num_classes=32, centres=NC.centres_of(dbg0))
+    _, want_losses, matches, want_grads = NC.oracle_training(32, frame)
     for m in matches:
-        assert (host['labels'][m[m > 0].numpy() - 1] > 15).sum() >= 1
-    losses, grads = NC.trainer_iteration(32, dev_frame)
+        assert (frame['labels'][m[m > 0].numpy() - 1] > 15).sum() >= 1
+    losses, grads = R.trainer_iteration(frame, num_classes=32)
     _losses_close(losses, want_losses, 'fused c32')
-    assert check_grads_against_g8(grads, NC.GradStats(want_grads), 2e-3, 'fused c32 vs oracle') == 98
+    assert check_grads_against_g8(grads, R.GradStats(want_grads), 2e-3, 'fused c32 vs oracle') == 98
 
 
 def test_deterministic_backward_23_classes_twice(T, c23):
-    g8, dev_frame, _, _ = c23
-    a = NC.trainer_iteration(23, dev_frame, deterministic=True)
-    b = NC.trainer_iteration(23, dev_frame, deterministic=True)
+    g8, frame, _, _ = c23
+    a = R.trainer_iteration(frame, num_classes=23, deterministic=True)
+    b = R.trainer_iteration(frame, num_classes=23, deterministic=True)
     assert check_grads_against_g8(a[1], g8, 2e-3, 'deterministic c23') == 98
     for k, g in a[1].items():
         assert (g is None) == (b[1][k] is None) and (g is None or torch.equal(g, b[1][k])), k
@@ -207,31 +207,31 @@ def test_deterministic_backward_23_classes_twice(T, c23):
 def test_operator_training_path_agrees_with_the_fused_one_23_classes(T, c23):
     """tc_radar_train_fwd / _bwd (the operator-by-operator training path) against the reference's gradients and the
     fused path's at 2e-3."""
-    g8, dev_frame, fused_losses, fused = c23
-    losses, grads = NC.trainer_iteration(23, dev_frame, chain_forward=False, chain_backward=False)
+    g8, frame, fused_losses, fused = c23
+    losses, grads = R.trainer_iteration(frame, num_classes=23, chain_forward=False, chain_backward=False)
     _losses_close(losses, fused_losses, 'operators vs fused c23')
     assert check_grads_against_g8(grads, g8, 2e-3, 'operators c23') == 98
-    assert check_grads_against_g8(grads, NC.GradStats(fused), 2e-3, 'operators vs fused c23') == 98
+    assert check_grads_against_g8(grads, R.GradStats(fused), 2e-3, 'operators vs fused c23') == 98
 
 
 # ---- 5. the replay paths ---------------------------------------------------------------------------------------------------
 def test_plugin_graph_replay_23_classes_is_the_eager_entry(T):
-    R.check_plugin_graph_replay(NC.make_head(T, 23)[0], NC.make_head(T, 23)[0])
+    R.check_plugin_graph_replay(R.make_head(T, num_classes=23)[0], R.make_head(T, num_classes=23)[0])
 
 
 def test_frame_pipeline_23_classes_equals_forward_nhwc(T):
-    R.check_frame_pipeline(NC.shared_head(T, 23)[0], 2)
+    R.check_frame_pipeline(R.shared_head(T, num_classes=23)[0], 2)
 
 
 def test_frame_of_nine_23_classes_is_its_own(T):
-    R.check_frame_of_nine(NC.shared_head(T, 23)[0])
+    R.check_frame_of_nine(R.shared_head(T, num_classes=23)[0])
 
 
 # ---- 6. last_level_cls_only ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('path', ['f32-4', 'f16x2-32'])
 def test_last_level_cls_only_23_classes(T, path):
     _, feats_np, frame = _g5_frame()
-    head, _ = NC.shared_head(T, 23)
+    head, _ = R.shared_head(T, num_classes=23)
     full = R.run_head(head, feats_np, frame, **NC.PATHS[path])
     fast = R.run_head(head, feats_np, frame, last_level_cls_only=True, **NC.PATHS[path])
     assert torch.equal(full['all_bbox_preds'], fast['all_bbox_preds'])

@@ -1,14 +1,13 @@
 """The decoder self-attention with 4 and 16 heads (head dimension 64 and 16; the configs: 8 heads of 32) on the MI355X:
 both attention cores against float64, the entry points that take the head dimension, the operator, and the whole head
-on its chain paths against the steered CPU oracle and the reference's fixtures (tests/golden/make_golden_heads.py);
-train mode, a training iteration, and the bit-identity checks.  The shared checks are head_variant_rig.py's, run under
-num_heads_rig.py.  pytest -m gpu"""
+on its chain paths against the CPU oracle at num_heads=H and the reference's fixtures (tests/golden/make_golden_variants.py
+`heads`); train mode, a training iteration, and the bit-identity checks.  The shared checks are head_variant_rig.py's,
+called with num_heads=H.  pytest -m gpu"""
 import numpy as np
 import pytest
 import torch
 
 import head_variant_rig as R
-import num_heads_rig as NH
 from head_variant_rig import SMOOTH, TINY, T, gpu, no_grad  # noqa: F401  (T, no_grad: fixtures)
 from transcar_amd import synth
 
@@ -65,7 +64,7 @@ def _check_sdpa(q, k, v, H, matrix, what):
 
 @pytest.mark.parametrize('matrix', ['f32', 'f16x2'])
 @pytest.mark.parametrize('case', ['ramp_up', 'ramp_down', 'huge_negative_start', 'spikes', 'short_ragged'])
-@pytest.mark.parametrize('H', NH.HEADS)
+@pytest.mark.parametrize('H', R.HEADS)
 def test_sdpa_heads_extreme_scores(T, H, case, matrix):
     """Both cores at head dimension 64 and 16 on the score sequences that stress the lazy re-centring.  (B, Q) =
     (2, 300): two whole 128-query groups of the staged core plus a ragged one, nine key pairs plus a ragged one (and 18
@@ -100,7 +99,7 @@ def test_sdpa_head_dim_32_is_the_8_head_entry_point(T, matrix):
 
 
 # ---- 3. the operator ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('H', NH.HEADS)
+@pytest.mark.parametrize('H', R.HEADS)
 def test_self_attn_heads_vs_torch(T, H):
     """tc_self_attn_fwd with 4 / 16 heads against torch.nn.MultiheadAttention on the CPU, same weights, with the
     tolerance of test_gpu_parity.test_self_attn_vs_oracle."""
@@ -128,16 +127,16 @@ PATHS = {'auto': {}, 'f16x2-16': dict(tile_rows=16, matrix_path='f16x2'), 'f32-1
 
 
 @pytest.mark.parametrize('path', sorted(PATHS))
-@pytest.mark.parametrize('H', NH.HEADS)
+@pytest.mark.parametrize('H', R.HEADS)
 def test_head_heads_paths_oracle_and_golden(T, H, path):
     """The whole head with a 4- / 16-head decoder, free-running through all nine layers on the fixture's frame: against
-    the steered oracle (every decoder state: layer 0's starts from the pack-time evaluation of its attention, which runs
+    the oracle at H heads (every decoder state: layer 0's starts from the pack-time evaluation of its attention, which runs
     the fp32 core at H heads) and against the reference's outputs (G5-H4 / -H16)."""
     gold = R.gold('g5_head_tiny_h%d.npz' % H)
-    head, sd = NH.shared_head(T, H)
+    head, sd = R.shared_head(T, num_heads=H)
     frame = synth.make_radar_frame(seed=2, n_per_radar=51, centres=gold['radar_centres'])
     feats_np = synth.make_feats('tiny', seed=1, smooth=SMOOTH)
-    want, dbg = NH.oracle_head(H, sd, feats_np, frame, key='golden')          # (the paths share one oracle forward)
+    want, dbg = R.oracle_head(sd, feats_np, frame, key='golden', num_heads=H)          # (the paths share one oracle forward)
     outs = R.run_head(head, feats_np, frame, **PATHS[path])
     R.check_against_oracle(outs, want, dbg, R.E2E_TOL)
     R.check_against_fixture(outs, want, dbg, gold)
@@ -147,54 +146,52 @@ def test_the_head_count_reaches_the_kernels(T):
     """The 4-head and the 16-head head part by O(1) on the same frame and weights: neither runs the other's split."""
     feats_np = synth.make_feats('tiny', seed=1, smooth=SMOOTH)
     frame = synth.make_radar_frame(seed=2, n_per_radar=51)
-    a = R.run_head(NH.shared_head(T, 4)[0], feats_np, frame)['aux']['inter_states']
-    b = R.run_head(NH.shared_head(T, 16)[0], feats_np, frame)['aux']['inter_states']
+    a = R.run_head(R.shared_head(T, num_heads=4)[0], feats_np, frame)['aux']['inter_states']
+    b = R.run_head(R.shared_head(T, num_heads=16)[0], feats_np, frame)['aux']['inter_states']
     assert float((a - b).abs().max()) > 0.1
 
 
 # ---- 5. one combined variant ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('path', ['auto', 'f16x2-32'])
 def test_head_16_heads_two_levels_three_points_no_refinement(T, path):
-    variant = dict(num_levels=2, num_points=3, with_box_refine=False)
-    head, sd = NH.make_head(T, 16, **variant)
+    variant = dict(num_heads=16, num_levels=2, num_points=3, with_box_refine=False)
+    head, sd = R.make_head(T, **variant)
     frame = synth.make_radar_frame(seed=2, n_per_radar=51)
     feats_np = synth.make_feats(TINY[:2], seed=1, smooth=SMOOTH)
-    want, dbg = NH.oracle_head(16, sd, feats_np, frame, with_box_refine=False, key='combined')
+    want, dbg = R.oracle_head(sd, feats_np, frame, key='combined', **variant)
     outs = R.run_head(head, feats_np, frame, **PATHS[path])
     R.check_against_oracle(outs, want, dbg, R.HS_TOL_F16X2 if path == 'f16x2-32' else R.E2E_TOL, refs_initial=True)
 
 
 # ---- 6. / 7. train mode and training -------------------------------------------------------------------------------------
 @pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (32, 'f16x2')])
-@pytest.mark.parametrize('H', NH.HEADS)
+@pytest.mark.parametrize('H', R.HEADS)
 def test_train_mode_decoder_heads_matches_reference_formula(T, H, rows, matrix):
     """The DROP instantiations of both cores at head dimension 64 / 16: the masks on the probabilities are read back as
-    [H, Q, Q] per layer and handed to the steered oracle's decoder."""
-    with NH.steered(H):
-        R.check_train_mode_decoder(R.g8_frame('g5_head_tiny_h%d.npz' % H), rows, matrix)
+    [H, Q, Q] per layer and handed to the oracle's decoder at H heads."""
+    R.check_train_mode_decoder(R.g8_frame('g5_head_tiny_h%d.npz' % H), rows, matrix, num_heads=H)
 
 
 def test_training_iteration_4_heads_gradients_match_reference(T):
-    with NH.steered(4):
-        R.check_training_iteration(R.g8_frame('g5_head_tiny_h4.npz'), 'g8_train_grads_h4.npz', 'fused h4')
+    R.check_training_iteration(R.g8_frame('g5_head_tiny_h4.npz'), 'g8_train_grads_h4.npz', 'fused h4', num_heads=4)
 
 
 # ---- 8. bit-identity with a 4-head head ---------------------------------------------------------------------------------
 def test_heads_frame_of_nine_is_its_own(T):
-    R.check_frame_of_nine(NH.shared_head(T, 4)[0])
+    R.check_frame_of_nine(R.shared_head(T, num_heads=4)[0])
 
 
 def test_frame_pipeline_heads_equals_forward_nhwc(T):
-    R.check_frame_pipeline(NH.shared_head(T, 4)[0], 2)
+    R.check_frame_pipeline(R.shared_head(T, num_heads=4)[0], 2)
 
 
 def test_plugin_graph_replay_heads_is_the_eager_entry(T):
-    R.check_plugin_graph_replay(NH.make_head(T, 4)[0], NH.make_head(T, 4)[0])
+    R.check_plugin_graph_replay(R.make_head(T, num_heads=4)[0], R.make_head(T, num_heads=4)[0])
 
 
 def test_cam_pregather_heads_is_bit_identical(T):
     """The pre-gather workgroups ride in the staged core's launch whatever its head dimension."""
-    head = NH.shared_head(T, 4)[0]
+    head = R.shared_head(T, num_heads=4)[0]
     feats_np = synth.make_feats('tiny', seed=1, smooth=SMOOTH)
     frame = synth.make_radar_frame(seed=2, n_per_radar=51)
     a = R.run_head(head, feats_np, frame, tile_rows=32, matrix_path='f16x2')

@@ -1,5 +1,6 @@
-"""The caps of head_variant_rig.py's checkers, on small synthetic tensors (CPU; no oracle forward, no reference): the
-GPU tests of every head variant go through these checkers, so a loosened cap here would loosen all of them."""
+"""The caps of head_variant_rig.py's checkers, on small synthetic tensors (CPU; no reference): the GPU tests of every
+head variant go through these checkers, so a loosened cap here would loosen all of them.  And the variant keys: what
+each reaches, and that the oracle's arguments for them default to the configs' head (37 queries on the tiny maps)."""
 import numpy as np
 import pytest
 import torch
@@ -137,3 +138,58 @@ def test_refs_are_initial_rejects_one_ulp():
         R.check_against_oracle(outs, want, dbg, refs_initial=True)
     with pytest.raises(AssertionError):
         R.check_against_fixture(outs, want, dbg, fixture, refs_initial=True)
+
+
+# ---- the variant keys, and the oracle's arguments for them ---------------------------------------------------------------
+def test_variant_kw_takes_the_configs_keys_and_refuses_others():
+    assert R.CONFIGS == dict(num_levels=4, num_points=1, with_box_refine=True, num_heads=8, num_classes=10, num_query=900)
+    assert R.variant_kw(**R.CONFIGS) == {} and R.variant_key(**R.CONFIGS) == ()
+    kw = dict(num_heads=4, num_classes=23, num_query=37)
+    assert R.variant_kw(num_points=1, **kw) == kw
+    assert R.state_dict_kw(**kw) == dict(num_classes=23, num_query=37)         # the state dict has no head count
+    assert R.oracle_kw(**kw) == dict(with_box_refine=True, num_heads=4)
+    assert R.variant_key(num_heads=4, num_classes=10) != R.variant_key(num_heads=16)
+    for fn in (R.variant_kw, R.state_dict_kw, R.oracle_kw, R.variant_key):
+        with pytest.raises(AssertionError):
+            fn(num_head=4)
+
+
+@pytest.fixture(scope='module')
+def tiny():
+    """The tiny maps, 37 queries and 60 radar points: the oracle's inputs and its head_forward with every default."""
+    from oracle import transcar_oracle as O
+    from transcar_amd import synth
+    sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_query=37))
+    args = (sd, [torch.from_numpy(f) for f in synth.make_feats('tiny', seed=1, smooth=R.SMOOTH)],
+            torch.from_numpy(synth.make_lidar2img()).float()[None], R.HW,
+            O.build_radar_features(synth.make_radar_frame(seed=2, n_per_radar=12)), R.PCR)
+    with torch.no_grad():
+        return O, sd, args, O.head_forward(*args, return_debug=True)
+
+
+def test_oracle_defaults_are_8_heads_and_10_classes(tiny):
+    O, sd, args, (outs, dbg) = tiny
+    with torch.no_grad():
+        outs8, dbg8 = O.head_forward(*args, return_debug=True, num_heads=8)
+    for k in ('all_cls_scores', 'all_bbox_preds'):
+        assert torch.equal(outs[k], outs8[k]), k
+    for k in ('hs', 'inter_refs', 'tmp'):
+        assert torch.equal(dbg[k], dbg8[k]), k
+    from transcar_amd import synth
+    boxes, labels = (torch.from_numpy(a) for a in synth.make_gt(seed=7, n=24))
+    with torch.no_grad():
+        a, ma = O.loss(outs, boxes, labels, sd['code_weights'])
+        b, mb = O.loss(outs, boxes, labels, sd['code_weights'], num_classes=10)
+    assert set(a) == set(b) and len(a) == 6
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    for x, y in zip(ma, mb):
+        assert torch.equal(x, y)
+
+
+def test_oracle_head_count_reaches_the_decoder_self_attention(tiny):
+    O, sd, args, (_, dbg) = tiny
+    feats, l2i, hw = args[1], args[2], args[3]
+    with torch.no_grad():
+        hs4 = O.transformer(sd, feats, R.PCR, l2i, hw, num_heads=4)[0]
+    assert float((hs4.permute(0, 2, 1, 3) - dbg['hs']).abs().max()) > 0.1      # (dbg: the default, 8 heads)

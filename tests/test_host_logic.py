@@ -2,7 +2,6 @@
 radar ingest, C-ABI surface, frame sharding (gloo, world size 2)."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -12,6 +11,7 @@ import torch
 
 import transcar_amd as T
 from oracle import transcar_oracle as O
+from parity_util import header_functions
 from transcar_amd import _lib, configs, radar, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -115,14 +115,8 @@ def test_pack_tokens_padding_and_multiplicity():
         assert pads_in_T - 1 + (1500 - 256 + 1) == 1500 - n
 
 
-def _header_functions():
-    text = open(os.path.join(ROOT, 'include', 'transcar_hip.h')).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(tc_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_c_abi_exports_every_declared_symbol():
-    names = _header_functions()
+    names = header_functions()
     assert len(names) >= 15
     dll = ctypes.CDLL(_lib.LIB_PATH)
     for n in names:

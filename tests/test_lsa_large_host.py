@@ -2,25 +2,18 @@
 exported and bound under the unchanged ABI version, the caps and path constants of the header and of the binding
 agree, the workspace query answers without a device, and the gate of device_loss.py states the same caps.  No GPU."""
 import ctypes
-import os
 import re
 
 import pytest
 
+from parity_util import header_define, header_text
 from transcar_amd import _lib as L
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'transcar_hip.h')
 ENTRIES = ('tc_lsa_workspace_bytes', 'tc_lsa_assign_ws')
 
 
-def header_define(name):
-    m = re.search(r'^#define %s\s+(.+?)\s*$' % name, open(HEADER).read(), flags=re.M)
-    assert m, name
-    return int(eval(m.group(1), {'__builtins__': {}}))
-
-
 def test_entries_are_declared_exported_and_bound_under_abi_13():
-    text = open(HEADER).read()
+    text = header_text()
     dll = ctypes.CDLL(L.LIB_PATH)
     for name in ENTRIES:
         assert re.search(r'\b%s\(' % name, text), name

@@ -1,6 +1,6 @@
 """The CPU oracle at 23 classes against the fixtures the REFERENCE produced with a 23-class head
-(tests/golden/make_golden_classes.py), with the bounds of tests/test_num_heads_golden.py, and the oracle's autograd
-gradients -- the loss composed per level, oracle.loss fixes 10 classes -- against the reference's at 2e-3.  CPU; the
+(tests/golden/make_golden_variants.py `classes`), with the bounds of tests/test_num_heads_golden.py, and the oracle's autograd
+gradients (oracle.loss with num_classes=23) against the reference's at 2e-3.  CPU; the
 fixtures are committed, so the reference itself is not needed."""
 import numpy as np
 import pytest
@@ -32,7 +32,7 @@ def forward(g5):
         frame = synth.make_radar_frame(seed=2, n_per_radar=51, centres=g5['radar_centres'])
         f36 = O.build_radar_features(frame)
         np.testing.assert_allclose(f36.astype(np.float32), g5['radar_tokens'], atol=1e-6, rtol=0)
-        return NC._head_forward(sd, synth.make_feats('tiny', seed=1, smooth=R.SMOOTH), frame)
+        return R.oracle_head(sd, synth.make_feats('tiny', seed=1, smooth=R.SMOOTH), frame)
 
 
 def _all_but_two(got, want, what):
@@ -73,14 +73,14 @@ def test_g5_decode_uses_the_coder_modulus(g5):
 def test_g8_forward_is_the_oracle_head(g5, g8):
     """The gradient fixture's forward (the radar frame of the seed it stores) is the oracle's head at 23 classes."""
     assert np.isfinite(g8['total_loss']) and int(g8['radar_seed']) == NC.G8_C23_RADAR_SEED
-    _, host = NC.train_frame(23, g5['radar_centres'], NC.G8_C23_RADAR_SEED)
+    host = R.g8_frame(NC.G5_C23, radar_seed=NC.G8_C23_RADAR_SEED, num_classes=23)
     outs, _, _, _ = NC.oracle_training(23, host)
     for k in ('all_cls_scores', 'all_bbox_preds'):
         _all_but_two(outs[k].numpy(), g8[k], k)
 
 
 def test_oracle_backward_matches_reference_23_classes(g5, g8):
-    _, host = NC.train_frame(23, g5['radar_centres'], NC.G8_C23_RADAR_SEED)
+    host = R.g8_frame(NC.G5_C23, radar_seed=NC.G8_C23_RADAR_SEED, num_classes=23)
     _, losses, matches, grads = NC.oracle_training(23, host)
     # matched labels lie above 15 in every level: the second sub-tile's columns see positive targets
     for m in matches:

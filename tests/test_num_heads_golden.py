@@ -1,5 +1,5 @@
-"""The CPU oracle, steered to a decoder self-attention of 4 and of 16 heads (tests/num_heads_rig.py), against the
-fixtures the REFERENCE produced with those head counts (tests/golden/make_golden_heads.py), with the tolerances of
+"""The CPU oracle with a decoder self-attention of 4 and of 16 heads (head_forward(num_heads=H)) against the fixtures
+the REFERENCE produced with those head counts (tests/golden/make_golden_variants.py `heads`), with the tolerances of
 tests/test_num_levels_golden.py.  CPU; the fixtures are committed, so the reference itself is not needed."""
 import os
 
@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-import num_heads_rig as NH
+from head_variant_rig import HEADS
 from oracle import transcar_oracle as O
 from transcar_amd import configs, synth
 
@@ -34,11 +34,10 @@ def _forward(g, H):
     np.testing.assert_allclose(f36.astype(np.float32), g['radar_tokens'], atol=1e-6, rtol=1e-6)
     if H is None:
         return O.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True)
-    with NH.steered(H):
-        return O.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True)
+    return O.head_forward(sd, feats, l2i, HW, f36, PCR, return_debug=True, num_heads=H)
 
 
-@pytest.mark.parametrize('H', NH.HEADS)
+@pytest.mark.parametrize('H', HEADS)
 def test_g5_head_heads(golden_dir, H):
     g = _g(golden_dir, 'g5_head_tiny_h%d.npz' % H)
     outs, dbg = _forward(g, H)
@@ -56,22 +55,15 @@ def test_g5_head_heads(golden_dir, H):
 
 def test_the_head_count_matters(golden_dir):
     """An oracle that ignored the head count could not pass: on the H = 4 fixture's frame the 8-head oracle is O(1) away
-    in the decoder states, and the steering is undone on the way out of the context."""
+    in the decoder states."""
     g = _g(golden_dir, 'g5_head_tiny_h4.npz')
-    keep = O.multihead_attention
     _, dbg = _forward(g, None)
-    assert O.multihead_attention is keep
     hs = dbg['hs'].permute(0, 2, 1, 3).numpy()
     assert np.abs(hs[:, ::16, 0, :] - g['hs_rows']).max() > 0.1
-    with pytest.raises(ZeroDivisionError):
-        with NH.steered(4):
-            assert O.multihead_attention is not keep
-            1 / 0
-    assert O.multihead_attention is keep
 
 
 def test_g8_forward_is_the_oracle_head(golden_dir):
-    """The gradient fixture's forward (4 heads, G5-H4's frame) is the steered oracle's head."""
+    """The gradient fixture's forward (4 heads, G5-H4's frame) is the oracle's head at 4 heads."""
     g8, g5 = _g(golden_dir, 'g8_train_grads_h4.npz'), _g(golden_dir, 'g5_head_tiny_h4.npz')
     assert np.isfinite(g8['total_loss'])
     outs, _ = _forward(g5, 4)

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 #: and is never the product.
 LIB_PATH = os.environ.get('TRANSCAR_HIP_LIB') or os.path.join(_HERE, 'lib', 'libtranscar_hip.so')
 
-TC_MAX_LEVELS = 4
+TC_MAX_LEVELS = 4      # FPN levels of tc_feats_nhwc / Detr3DCrossAtten.num_levels (include/transcar_hip.h)
 TC_MAX_LAYERS = 8
 TC_MAX_RADAR_LAYERS = 3
 TC_ABI_VERSION = 13
@@ -40,10 +40,6 @@ def check_num_points(num_points, num_cams, num_levels):
             'Detr3DCrossAtten(HIP): num_points=%r is not supported (num_points >= 1 and '
             'num_cams * num_levels * num_points = %d * %d * num_points <= %d)'
             % (num_points, num_cams, num_levels, TC_MAX_CAM_LOGITS))
-
-
-# FPN levels of tc_feats_nhwc / Detr3DCrossAtten.num_levels (include/transcar_hip.h)
-TC_MAX_LEVELS = 4
 
 
 def check_num_levels(num_levels):
