@@ -122,7 +122,7 @@ typedef struct {
    * The radar fusion attention does not read it: it has TC_RADAR_HEADS heads. */
   int num_query, embed_dims, num_heads, ffn_dims, num_layers;
   int num_cams, num_levels, num_classes, code_size;   /* num_levels: 1 .. TC_MAX_LEVELS */
-  int radar_in_dims, num_radar_layers, num_radar_tokens_ref; /* 36, 3, 1500   */
+  int radar_in_dims, num_radar_layers, num_radar_tokens_ref; /* 36, 1..3, 1500 (0: camera only) */
   float pc_range[6];
   const float* query_embedding;     /* [Q, 2C]: (query_pos | query) XFMR:119  */
   tc_linear reference_points;       /* transformer.reference_points [3,C]     */
@@ -179,9 +179,9 @@ typedef struct {
   int unfused;              /* 1: operator-by-operator launch sequence (~160 launches), the
                                in-tree cross-check of the fused chains */
   int last_level_cls_only;  /* 1 (inference opt-in): final_cls / final_cls2 are not evaluated --
-                               get_bboxes decodes level 3 only (HEAD:1003-1023) and levels 1-2
-                               feed only their BOX to the next gate; all_cls_scores[0:2] are
-                               left untouched.  0 keeps the reference's [3,B,Q,10] output */
+                               get_bboxes decodes the last level (N = num_radar_layers, 1..3) only
+                               (HEAD:1003-1023) and the levels before feed only their BOX to the next gate;
+                               all_cls_scores[0:N-1] are left untouched.  0 keeps the reference's [N,B,Q,10] output */
   int reuse_radar_kv;       /* tc_radar_fusion_fwd only: 1 = skip the radar encoders, the K/V
                                projections of the previous call in the same workspace are reused
                                (timing the fusion chain on its own) */
@@ -535,7 +535,7 @@ int tc_box_decode_kept_path(const float* cls_scores, const float* bbox_preds, in
  *   radar_tokens [B,T,36]: rows of the 36 hand-built features (HEAD:499-510),
  *                padded with 500.0 rows (HEAD:527); T <= 1500
  *   pad_mult     see tc_radar_gated_xattn_fwd
- *   all_cls_scores / all_bbox_preds [3,B,Q,10] */
+ *   all_cls_scores / all_bbox_preds [num_radar_layers (1..3),B,Q,10] */
 size_t tc_head_workspace_bytes(const tc_head_weights* w, int B, int T);
 /* scratch of tc_head_options.cam_pregather = 1 (ABI 12): B * Q * (num_cams * num_levels * C floats + one int) */
 size_t tc_cam_pregather_workspace_bytes(const tc_head_weights* w, int B);
@@ -606,7 +606,7 @@ int tc_decoder_outputs_fwd(const tc_decoder_heads* packed_view,
 /* ======================================================================
  * Training.  tools/train.py:245-252
  * freezes the DETR3D decoder, so one iteration differentiates the radar
- * encoders, the three gated radar fusion layers and final_cls* / final_reg*
+ * encoders, the 1..3 gated radar fusion layers and final_cls* / final_reg*
  * (HEAD:531-729).  The frozen decoder runs through tc_head_forward (aux gives
  * hs, references, last_box); the trainable stack runs operator by operator so
  * that the host autograd (the reference's own boundary for training: plain
@@ -693,7 +693,7 @@ int tc_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float 
                   float grad_scale, float max_norm, const float* sq_norm, tc_stream_t stream);
 
 
-/* The trainable stack (radar encoders + three fusion layers + final_cls / final_reg,
+/* The trainable stack (radar encoders + 1..3 fusion layers (num_radar_layers) + final_cls / final_reg,
  * HEAD:531-729) as two calls: the forward keeps its activations on a caller-provided
  * tape (tc_radar_train_tape_bytes), the backward walks it and ADDS the parameter
  * gradients into `grads`, a tc_head_weights whose pointers are the gradient buffers
@@ -715,7 +715,7 @@ int tc_radar_train_fwd(const tc_head_weights* w, const float* hs_last, const flo
                        float* all_cls_scores, float* all_bbox_preds, void* tape, size_t tape_bytes,
                        float dropout_p, unsigned long long dropout_seed, tc_stream_t stream);
 /* tc_radar_train_fwd as launches of the fused row chains: ONE launch for the encoders + K|V (token rows), ONE for
- * the three fusion layers (query rows; the dropout sites in the epilogues / the attention core, every tape tensor
+ * the 1..3 fusion layers (query rows; the dropout sites in the epilogues / the attention core, every tape tensor
  * stored as it is produced) + the reference set-up.  Same tape, same outputs (to fp32 rounding of the different
  * summation order), same (seed, site, index) dropout masks: tc_radar_train_bwd takes either tape.
  * `packed_view`: the head's packed weights holding the CURRENT parameters (after an optimizer step:
@@ -729,7 +729,7 @@ int tc_radar_train_bwd(const tc_head_weights* w, const tc_head_weights* grads, c
                        const float* all_bbox_preds, const float* d_all_cls, const float* d_all_box,
                        void* tape, size_t tape_bytes, float dropout_p, unsigned long long dropout_seed,
                        tc_stream_t stream);
-/* tc_radar_train_bwd with the query side of all three fusion layers as ONE launch of the backward row chain
+/* tc_radar_train_bwd with the query side of all 1..3 fusion layers as ONE launch of the backward row chain
  * (data gradients are row-local; every dY a weight gradient needs is stored as it is produced; LayerNorm
  * parameter gradients leave as one atomic per channel and workgroup), the token side (dK|dV -> encoders) as a
  * handful of launches, and EVERY weight / bias gradient in one grouped GEMM launch (two: a scalar variant for
@@ -754,8 +754,8 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
                                 float dropout_p, unsigned long long dropout_seed, const float* layer_losses,
                                 float* layer_losses_clean, int flags, tc_stream_t stream);
 /* ABI 12 (round 6): the weight gradients of one chunk after tc_radar_train_bwd_fused_ex(flags bit 1) on the same stream,
- * same tape / workspace: group 0 .. TC_MAX_RADAR_LAYERS - 1 = fusion layers from the TOP one down (the order a layer-wise
- * backward finishes them, the order DDP's buckets fill in the reference: tools/train.py:253-260), TC_MAX_RADAR_LAYERS =
+ * same tape / workspace: group 0 .. num_radar_layers - 1 = fusion layers from the TOP one down (the order a layer-wise
+ * backward finishes them, the order DDP's buckets fill in the reference: tools/train.py:253-260), num_radar_layers =
  * the radar encoders.  Every group is one grouped launch (two with the 10-wide heads); together they add exactly what the
  * single grouped launch of tc_radar_train_bwd_fused_ex adds. */
 int tc_radar_train_bwd_weights(const tc_head_weights* w, const tc_head_weights* grads, const float* hs_last,
@@ -770,7 +770,7 @@ int tc_radar_train_bwd_weights(const tc_head_weights* w, const tc_head_weights* 
  * bit-identical gradients from identical inputs, on any schedule.  (tools/train.py:238-260 trains with torch's float
  * atomics, i.e. without this guarantee; FusionTrainer(deterministic=True) and the tests that compare runs use it.)
  * grad_base / grad_elems: the span that holds EVERY tensor of `grads` (the flat bucket); shadow: shadow_elems >= grad_elems +
- * 3 * B * T * 2 * embed_dims + 8 64-bit words; the first grad_elems + 3 B T 2 embed_dims must be zero on entry -- the
+ * N * B * T * 2 * embed_dims + 8 64-bit words (N = num_radar_layers, 1..3); the first grad_elems + N B T 2 embed_dims must be zero on entry -- the
  * call leaves them zero -- and the LAST 8 words of the buffer (shadow[shadow_elems - 8 ..]) are scratch, wherever (B, T)
  * put the end of the sums: one buffer sized for the longest frame serves every shorter one (round 6).  A partial sum the
  * fixed-point word cannot hold (NaN, inf, |v| >= 2^23) is added to the float target itself: non-finite or exploding
@@ -784,7 +784,7 @@ int tc_radar_train_bwd_fused_det(const tc_head_weights* w, const tc_head_weights
                                  long long* shadow, size_t shadow_elems, tc_stream_t stream);
 /* One launch for BOTH weight layouts a fused training iteration needs from the current parameters: the 4x4x1 packed
  * copy of the trainable weights inside `packed_view` (tc_head_repack_trainable_ex(w, view, 1)) and the transposed
- * packed weights of the three fusion layers inside the backward's workspace (tc_radar_train_bwd_workspace_bytes(w, B,
+ * packed weights of the 1..3 fusion layers inside the backward's workspace (tc_radar_train_bwd_workspace_bytes(w, B,
  * T)); call it once after the optimizer step, then tc_radar_train_fwd_fused and tc_radar_train_bwd_fused_ex(flags 1). */
 int tc_radar_train_repack(const tc_head_weights* w, tc_head_weights* packed_view, void* bwd_workspace,
                           size_t bwd_workspace_bytes, int B, int T, tc_stream_t stream);

@@ -98,6 +98,18 @@ def check_num_classes(num_classes):
             'Detr3DHead(HIP): num_classes=%r is not supported (1 .. %d classes)' % (num_classes, TC_MAX_CLASSES))
 
 
+def check_num_fusion_layers(num_fusion_layers):
+    """The library's limit on the depth of the radar fusion stack (1 .. TC_MAX_RADAR_LAYERS
+    layers; the reference builds 3), checked before anything is built, packed or launched.
+    Returns the depth.  No fusion layer at all is what ``outputs='camera'`` is for."""
+    n = num_fusion_layers
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= TC_MAX_RADAR_LAYERS:
+        raise TransCARHipError(
+            "Detr3DHead(HIP): num_fusion_layers=%r is not supported (1 .. %d radar fusion layers; a head without "
+            "the fusion stack is outputs='camera')" % (n, TC_MAX_RADAR_LAYERS))
+    return n
+
+
 def cam_pregather_supported(embed_dims, num_levels, num_cams):
     """The shapes the camera pre-gather (tc_head_options.cam_pregather) runs:
     C = 256, 4 levels, at most 8 cameras.  Others take the chain's own gather,

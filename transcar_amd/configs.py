@@ -76,7 +76,8 @@ IMG_SHAPE = (928, 1600, 3)
 
 
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
-             num_levels=None, num_heads=None, num_classes=None):
+             num_levels=None, num_heads=None, num_classes=None,
+             num_fusion_layers=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -87,7 +88,8 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     or 16 -- the radar fusion attention keeps its 8, HEAD:129-171);
     num_classes sets the head's and the bbox_coder's (the configs: 10, CFG:54
     and :89; 1 .. 32 -- the coder's is the modulus that turns a score index
-    into a label, CODER:54-55)."""
+    into a label, CODER:54-55); num_fusion_layers sets the depth of the radar
+    fusion stack (the reference builds 3, HEAD:129-171; 1 .. 3)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -109,4 +111,7 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
         check_num_classes(num_classes)
         cfg['num_classes'] = num_classes
         cfg['bbox_coder']['num_classes'] = num_classes
+    if num_fusion_layers is not None:
+        from ._lib import check_num_fusion_layers
+        cfg['num_fusion_layers'] = check_num_fusion_layers(num_fusion_layers)
     return cfg

@@ -2721,6 +2721,10 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
     table = k.l0_seq == 1 ? PROG_DECODER_L0_T : PROG_DECODER_L0GEN_T;
     nsteps = (int)((k.l0_seq == 1 ? sizeof(PROG_DECODER_L0_T) : sizeof(PROG_DECODER_L0GEN_T)) / sizeof(StepDesc)) - 1;
   }
+  // the encoder programs end with the K/V projections of the fusion layers (pairs 7 + r, ascending): a head with fewer
+  // layers runs a shorter sequence of the same records -- the kernels see only another `total`
+  if (prog_is_enc_full(PROG) || PROG == PROG_RADAR_ENC_A || PROG == PROG_RADAR_ENC_B)
+    while (nsteps > 0 && table[nsteps - 1].kind == K_LINEAR && table[nsteps - 1].wp >= 7 + k.nlayers) --nsteps;
   const int nrep = (prog_is_radar(PROG) || PROG == PROG_RADAR_BWD) ? k.nlayers : 1;
   const int total = nsteps * nrep;
   memset(out, 0, sizeof(StepAllT<NW>) * rec_cap(PROG));
@@ -3222,8 +3226,11 @@ int launch_decoder_chain(const DecoderChainArgs& a, hipStream_t s) {
 
 static int make_radar_enc_k(const RadarEncodeArgs& a, ChainK& k, int part = 0) {
   TC_REQUIRE(a.RI <= 64 && (a.RI & 3) == 0, "radar_encode: radar_in_dims=%d", a.RI);
-  TC_REQUIRE(a.nlayers == TC_MAX_RADAR_LAYERS, "radar_encode: %d radar layers (3 supported)", a.nlayers);
+  TC_REQUIRE(a.nlayers >= 1 && a.nlayers <= TC_MAX_RADAR_LAYERS, "radar_encode: %d radar layers (1 .. %d supported)", a.nlayers,
+             TC_MAX_RADAR_LAYERS);
+  TC_REQUIRE(part != 2 || a.nlayers > 1, "radar_encode: half B has no K/V projection to run with %d radar layer", a.nlayers);
   init_k(k);
+  k.nlayers = a.nlayers;
   k.program = part == 1 ? PROG_RADAR_ENC_A : part == 2 ? PROG_RADAR_ENC_B : PROG_RADAR_ENC;
   if (a.tape != nullptr) {
     TC_REQUIRE(part == 0, "radar_encode: the training forward runs the whole encoder program");
@@ -3236,7 +3243,7 @@ static int make_radar_enc_k(const RadarEncodeArgs& a, ChainK& k, int part = 0) {
   k.g[G_RFEAT] = a.radar_feat; k.g_ld[G_RFEAT] = 256;
   k.pairs[0] = a.rpe.l0; k.pairs[1] = tc_linear{a.rpe.n1.g, a.rpe.n1.b}; k.pairs[2] = a.rpe.l3;
   k.pairs[3] = tc_linear{a.rpe.n4.g, a.rpe.n4.b}; k.pairs[4] = a.f0; k.pairs[5] = a.f2; k.pairs[6] = a.f4;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  for (int r = 0; r < a.nlayers; ++r) {
     k.pairs[7 + r] = a.kvproj[r];
     k.g[G_KV0 + r] = a.kv[r]; k.g_ld[G_KV0 + r] = 512;
   }
@@ -3351,7 +3358,7 @@ int launch_decoder_heads(const DecoderHeadsArgs& a, hipStream_t s) {
   return use_f16x2(k) ? launch_heads_r<16, 1>(a, s) : launch_heads_r<16, 0>(a, s);
 }
 
-// Backward of the three fusion layers for the query rows: one launch (PROG_RADAR_BWD).
+// Backward of the (1 .. 3) fusion layers for the query rows: one launch (PROG_RADAR_BWD).
 int launch_radar_chain_bwd(const RadarBwdChainArgs& a, hipStream_t s) {
   TC_REQUIRE(a.code <= 10 && a.ncls <= 32 && a.nlayers >= 1 && a.nlayers <= TC_MAX_RADAR_LAYERS,
              "radar_chain_bwd: code=%d ncls=%d nlayers=%d", a.code, a.ncls, a.nlayers);

@@ -115,7 +115,7 @@ static int check_dims(const tc_head_weights* w) {
              w->embed_dims, w->num_heads);
   TC_REQUIRE(w->num_layers >= 1 && w->num_layers <= TC_MAX_LAYERS, "num_layers=%d", w->num_layers);
   TC_REQUIRE(w->num_radar_layers >= 0 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
-             "num_radar_layers=%d", w->num_radar_layers);
+             "num_radar_layers=%d (0 .. %d supported)", w->num_radar_layers, TC_MAX_RADAR_LAYERS);
   TC_REQUIRE(w->num_levels >= 1 && w->num_levels <= TC_MAX_LEVELS, "num_levels=%d (1 .. %d supported)", w->num_levels,
              TC_MAX_LEVELS);
   TC_REQUIRE(w->num_points >= 0 && w->num_cams * w->num_levels * head_points(w) <= TC_MAX_CAM_LOGITS,
@@ -321,7 +321,9 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
     }
     // the radar encoders ride in two launches, half each (all in layer 0 when there is only one layer)
     if (radar && !ddrop && lid == enc_first) TC_TRY(launch_decoder_chain_with_encoders(d, re, L > 1 ? 1 : 0, s));
-    else if (radar && !ddrop && L > 1 && lid == enc_first + 1) TC_TRY(launch_decoder_chain_with_encoders(d, re, 2, s));
+    // (half B is the K/V of fusion layers 1 and 2: a one-layer fusion head has none, its second launch is the plain chain)
+    else if (radar && !ddrop && L > 1 && lid == enc_first + 1 && w->num_radar_layers > 1)
+      TC_TRY(launch_decoder_chain_with_encoders(d, re, 2, s));
     else TC_TRY(launch_decoder_chain(d, s));
   }
   if (opt.phase == 1) return 0;

@@ -45,13 +45,14 @@ size_t tape_layout(const tc_head_weights* w, int B, int T, void* base, size_t ca
   const size_t C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
   Arena a(base, cap);
   Tape t;
+  memset(&t, 0, sizeof(t));          // (the layers a shallower head does not have stay null)
   t.xyz4 = a.take<float>(rt * 4); t.w0p = a.take<float>(C * 4);
   t.u0 = a.take<float>(rt * C); t.u1 = a.take<float>(rt * C); t.u2 = a.take<float>(rt * C);
   t.pos = a.take<float>(rt * C);
   t.f0 = a.take<float>(rt * 64); t.f1 = a.take<float>(rt * 128); t.f2 = a.take<float>(rt * C);
   t.mem = a.take<float>(rt * C);
   t.cxy = a.take<float>(rows * 2); t.addref = a.take<float>(rows * 3);
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  for (int r = 0; r < w->num_radar_layers; ++r) {
     LayerTape& l = t.L[r];
     l.qp = a.take<float>(rows * C); l.kv = a.take<float>(rt * 2 * C); l.ao = a.take<float>(rows * C);
     l.x1 = a.take<float>(rows * C); l.x2 = a.take<float>(rows * C); l.h = a.take<float>(rows * F);
@@ -146,13 +147,17 @@ RadarAttnArgs core_args(const tc_head_weights* w, int r, const Tape& t, const fl
   return ra;
 }
 
+// distance between the tape tensors / hit counts of consecutive fusion layers (a one-layer head: no second layer, 0)
+size_t layer_stride(const tc_head_weights* w, const Tape& t) { return w->num_radar_layers > 1 ? (size_t)(t.L[1].qp - t.L[0].qp) : 0; }
+size_t hits_stride(const tc_head_weights* w, const Tape& t) { return w->num_radar_layers > 1 ? (size_t)(t.L[1].hits - t.L[0].hits) : 0; }
+
 int check(const tc_head_weights* w, int B, int T) {
   TC_REQUIRE(w != nullptr && w->abi_version == TC_ABI_VERSION, "radar_train: bad weights struct");
   // (num_heads is the decoder self-attention's; the fusion attention trained here has TC_RADAR_HEADS heads)
-  TC_REQUIRE(w->embed_dims == 256 && heads_ok(w->num_heads) &&
-                 w->num_radar_layers == TC_MAX_RADAR_LAYERS,
-             "radar_train: embed_dims=%d num_heads=%d radar layers=%d", w->embed_dims, w->num_heads,
-             w->num_radar_layers);
+  TC_REQUIRE(w->embed_dims == 256 && heads_ok(w->num_heads), "radar_train: embed_dims=%d num_heads=%d", w->embed_dims,
+             w->num_heads);
+  TC_REQUIRE(w->num_radar_layers >= 1 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
+             "radar_train: num_radar_layers=%d (1 .. %d supported)", w->num_radar_layers, TC_MAX_RADAR_LAYERS);
   TC_REQUIRE(B >= 1 && T >= 1 && (w->radar_in_dims & 3) == 0, "radar_train: B=%d T=%d", B, T);
   return 0;
 }
@@ -203,7 +208,7 @@ int tc_radar_train_fwd(const tc_head_weights* w, const float* hs_last, const flo
   }
   TS_TRY(launch_radar_ref_l1(ref_last, w->pc_range, t.cxy, t.addref, rows, s));
   const float* qin = hs_last;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  for (int r = 0; r < w->num_radar_layers; ++r) {
     const tc_radar_layer& rl = w->radar[r];
     LayerTape& l = t.L[r];
     float* cls_out = all_cls_scores + (size_t)r * rows * ncls;
@@ -281,7 +286,7 @@ int tc_radar_train_fwd_fused(const tc_head_weights* packed_view, const float* hs
   re.tokens = radar_tokens; re.RI = RI; re.M = rt;
   re.rpe = w->radar_position_encoder; re.f0 = w->radar_feat0; re.f2 = w->radar_feat2; re.f4 = w->radar_feat4;
   re.nlayers = w->num_radar_layers;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {          // (layers the head does not have: null weights, null tape)
     const tc_mha& m = w->radar[r].attn;
     re.kvproj[r] = tc_linear{m.in_proj.w ? m.in_proj.w + (size_t)C * C : nullptr, m.in_proj.b ? m.in_proj.b + C : nullptr};
     re.kv[r] = t.L[r].kv;
@@ -298,8 +303,7 @@ int tc_radar_train_fwd_fused(const tc_head_weights* packed_view, const float* hs
   for (int i = 0; i < 6; ++i) rc.pc[i] = w->pc_range[i];
   rc.all_cls = all_cls_scores; rc.all_box = all_bbox_preds; rc.hits = t.L[0].hits;
   rc.tape = slots;
-  rc.tape_stride = (size_t)(t.L[1].qp - t.L[0].qp);
-  rc.hits_stride = (size_t)(t.L[1].hits - t.L[0].hits);
+  rc.tape_stride = layer_stride(w, t); rc.hits_stride = hits_stride(w, t);
   rc.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
   return launch_radar_chain(rc, s);
 }
@@ -324,7 +328,7 @@ int tc_radar_train_bwd(const tc_head_weights* w, const tc_head_weights* grads, c
   TS_HIP(hipMemsetAsync(t.dmem, 0, (size_t)rt * C * 4, s));
   bool have_dqin = false;                       // gradient w.r.t. this layer's output from the layer above
   bool have_dbox_next = false;
-  for (int r = TC_MAX_RADAR_LAYERS - 1; r >= 0; --r) {
+  for (int r = w->num_radar_layers - 1; r >= 0; --r) {
     const tc_radar_layer& rl = w->radar[r];
     const tc_radar_layer& gl = grads->radar[r];
     LayerTape& l = t.L[r];
@@ -433,7 +437,8 @@ size_t bwd_ws_layout(const tc_head_weights* w, int B, int T, void* base, size_t 
   Arena a(base, cap);
   BwdWs b;
   memset(&b, 0, sizeof(b));
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  const int NR = w->num_radar_layers;
+  for (int r = 0; r < NR; ++r) {
     tc_radar_layer& l = b.wT[r];
     l.attn.in_proj.w = a.take<float>(packed_floats((int)C, (int)C));
     l.attn.out_proj.w = a.take<float>(packed_floats((int)C, (int)C));
@@ -447,7 +452,7 @@ size_t bwd_ws_layout(const tc_head_weights* w, int B, int T, void* base, size_t 
     l.final_reg.l4.w = a.take<float>(packed_floats((int)C, (int)code));
   }
   float* first = nullptr;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  for (int r = 0; r < NR; ++r) {
     float* s0 = a.take<float>(rows * code);
     if (r == 0) { first = s0; b.dy[DY_DBOX] = s0; }
     float* p1 = a.take<float>(rows * C); float* p2 = a.take<float>(rows * C); float* p3 = a.take<float>(rows * C);
@@ -461,7 +466,7 @@ size_t bwd_ws_layout(const tc_head_weights* w, int B, int T, void* base, size_t 
     }
     if (r == 1) b.dy_stride = (size_t)(s0 - first);
   }
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) b.dkv[r] = a.take<float>(rt * 2 * C);   // contiguous with dmem: one memset
+  for (int r = 0; r < NR; ++r) b.dkv[r] = a.take<float>(rt * 2 * C);   // contiguous with dmem: one memset
   b.dmem = a.take<float>(rt * C);
   b.du0 = a.take<float>(rt * C);     // its own slice: a tape scratch sized by the QUERY rows overran for T > 2 Q
   if (out) *out = b;
@@ -478,7 +483,7 @@ static int transposed_jobs(const tc_head_weights* w, const BwdWs& ws, PackJob* j
     j.W = W; j.P = P; j.P16 = nullptr; j.N = N_out; j.K = K_in; j.transpose = 1; j.ldw = N_out;
     jobs[n++] = j;
   };
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  for (int r = 0; r < w->num_radar_layers; ++r) {
     const tc_radar_layer& rl = w->radar[r];
     const tc_radar_layer& lt = ws.wT[r];
     // forward W is [N_fwd][K_fwd] (row stride K_fwd); the chain computes dx[K_fwd] = dy[N_fwd] W, i.e. a linear
@@ -501,7 +506,7 @@ int radar_train_transposed_jobs(const tc_head_weights* w, int B, int T, void* wo
                                 PackJob* jobs, int cap) {
   if (check(w, B, T) != 0) return -1;
   BwdWs ws;
-  if (workspace == nullptr || bwd_ws_layout(w, B, T, workspace, workspace_bytes, &ws) > workspace_bytes || cap < 10 * TC_MAX_RADAR_LAYERS) {
+  if (workspace == nullptr || bwd_ws_layout(w, B, T, workspace, workspace_bytes, &ws) > workspace_bytes || cap < 10 * w->num_radar_layers) {
     set_error("radar_train_repack: backward workspace too small");
     return -1;
   }
@@ -514,9 +519,9 @@ size_t tc_radar_train_bwd_workspace_bytes(const tc_head_weights* w, int B, int T
 }
 
 // The weight gradients dW = dY^T X (+ bias column sums) of the trainable stack from the tape and the dY tensors the backward
-// chain / the token side stored.  group -1: all 38 in one grouped launch; 0 .. TC_MAX_RADAR_LAYERS - 1: the jobs of fusion
-// layer (TC_MAX_RADAR_LAYERS - 1 - group) -- the top layer first, the order in which a layer-wise backward would finish
-// them --; TC_MAX_RADAR_LAYERS: the token side (radar encoders).
+// chain / the token side stored.  N = num_radar_layers; group -1: all 11 N + 5 in one grouped launch; 0 .. N - 1: the jobs of
+// fusion layer (N - 1 - group) -- the top layer first, the order in which a layer-wise backward would finish them --; N: the
+// token side (radar encoders).
 static int weight_gradients(const tc_head_weights* w, const tc_head_weights* grads, const float* hs_last,
                             const float* radar_tokens, int B, int T, const Tape& t, const BwdWs& ws, int group, hipStream_t s) {
   const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
@@ -534,8 +539,9 @@ static int weight_gradients(const tc_head_weights* w, const tc_head_weights* gra
     j.ldx = ldx;
     jobs[n++] = j;
   };
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
-    if (group >= 0 && r != TC_MAX_RADAR_LAYERS - 1 - group) continue;
+  const int NR = w->num_radar_layers;
+  for (int r = 0; r < NR; ++r) {
+    if (group >= 0 && r != NR - 1 - group) continue;
     const tc_radar_layer& gl = grads->radar[r];
     const LayerTape& l = t.L[r];
     const size_t off = (size_t)r * ws.dy_stride;
@@ -552,7 +558,7 @@ static int weight_gradients(const tc_head_weights* w, const tc_head_weights* gra
     job(l.t0, ws.dy[DY_DT1] + off, gl.final_reg.l2, rows, C, C);
     job(l.t1, ws.dy[DY_DBOX] + off, gl.final_reg.l4, rows, C, code);
   }
-  if (group < 0 || group == TC_MAX_RADAR_LAYERS) {
+  if (group < 0 || group == NR) {
     job(t.f1, ws.dmem, grads->radar_feat4, rt, 128, C, t.f2);
     job(t.f0, t.dt128, grads->radar_feat2, rt, 64, 128);
     job(radar_tokens, t.dt64, grads->radar_feat0, rt, RI, 64);
@@ -590,7 +596,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
     TS_TRY(launch_pack_group(jobs, n, s));
   }
   // 2. accumulators
-  TS_HIP(hipMemsetAsync(ws.dkv[0], 0, (size_t)((char*)(ws.dmem + (size_t)rt * C) - (char*)ws.dkv[0]), s));   // dK|dV x 3 + dmem
+  TS_HIP(hipMemsetAsync(ws.dkv[0], 0, (size_t)((char*)(ws.dmem + (size_t)rt * C) - (char*)ws.dkv[0]), s));   // dK|dV x N + dmem
   // 3. the query side of all three layers: one launch
   float* slots[TS_COUNT];
   memset(slots, 0, sizeof(slots));
@@ -599,18 +605,19 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   slots[TS_SUM] = l0.ff; slots[TS_X3] = l0.x3; slots[TS_C0] = l0.c0; slots[TS_C1] = l0.c1; slots[TS_C2] = l0.c2;
   slots[TS_C3] = l0.c3; slots[TS_T0] = l0.t0; slots[TS_T1] = l0.t1; slots[TS_TREG] = l0.treg;
   RadarBwdChainArgs a;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
+  const int NR = w->num_radar_layers;
+  for (int r = 0; r < NR; ++r) {
     a.wT[r] = ws.wT[r]; a.w[r] = w->radar[r]; a.grads[r] = grads->radar[r];
     a.kv[r] = t.L[r].kv; a.dkv[r] = ws.dkv[r];
     const float* box_prev = r == 0 ? last_box : all_bbox_preds + (size_t)(r - 1) * rows * code;
     a.cxy[r] = r == 0 ? t.cxy : box_prev; a.ld_c[r] = r == 0 ? 2 : code; a.box[r] = box_prev;
   }
-  a.tape = slots; a.tape_stride = (size_t)(t.L[1].qp - t.L[0].qp);
-  a.hits = t.L[0].hits; a.hits_stride = (size_t)(t.L[1].hits - t.L[0].hits);
+  a.tape = slots; a.tape_stride = layer_stride(w, t);
+  a.hits = t.L[0].hits; a.hits_stride = hits_stride(w, t);
   a.dy = ws.dy; a.dy_stride = ws.dy_stride;
   a.d_cls = d_all_cls; a.d_box = d_all_box; a.loss_vals = layer_losses; a.loss_out = layer_losses_clean;
   a.tokens = radar_tokens; a.RI = RI; a.T = T; a.pad_mult = pad_mult;
-  a.nlayers = TC_MAX_RADAR_LAYERS; a.Q = Q; a.M = rows; a.code = code; a.ncls = ncls;
+  a.nlayers = NR; a.Q = Q; a.M = rows; a.code = code; a.ncls = ncls;
   a.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   a.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
   {
@@ -627,7 +634,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   // (deterministic mode: the chain's dK | dV sums sit in their shadow; the token side reads dK | dV next)
   TS_TRY(launch_det_flush(current_det(), 1, s));
   // 4. the token side: dmem = sum_r dkv_r Wkv_r, then the encoders (data gradients only; weights below)
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r)
+  for (int r = 0; r < NR; ++r)
     TS_TRY(launch_linear_bwd_data(ws.dkv[r], nullptr, nullptr, w->radar[r].attn.in_proj.w + (size_t)C * C, nullptr, ws.dmem,
                                   rt, C, 2 * C, 1.0f, 1, s));
   const tc_pos_encoder& pe = w->radar_position_encoder;
@@ -657,7 +664,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
 // the attention backward's dK | dV -- becomes an integer atomic on a 2^-40 fixed-point shadow (common.hpp DetAcc), the
 // split reductions of the token side run unsplit, and two flush launches add the shadows back.  Two calls on the same
 // inputs give bit-identical gradients.  grad_base / grad_elems: the span that holds every tensor of `grads` (the flat
-// bucket); shadow: shadow_elems >= grad_elems + 3 * B * T * 2 * embed_dims + 8 64-bit words, the first grad_elems + 3 B T 2 C of
+// bucket); shadow: shadow_elems >= grad_elems + N * B * T * 2 * embed_dims + 8 64-bit words (N = num_radar_layers), the first grad_elems + N B T 2 C of
 // them ZERO on entry (the call leaves them zero); the LAST 8 words of the buffer (shadow + shadow_elems - 8 ...) are
 // scratch -- they hold the device copy of the ranges, at a place that does not depend on (B, T): one buffer sized for the
 // longest frame serves every shorter one (round 6; until then the copy sat right behind the dK | dV shadows and a
@@ -674,12 +681,12 @@ int tc_radar_train_bwd_fused_det(const tc_head_weights* w, const tc_head_weights
   BwdWs ws;
   TC_REQUIRE(bwd_ws_layout(w, B, T, workspace, workspace_bytes, &ws) <= workspace_bytes,
              "radar_train_bwd_fused_det: workspace too small");
-  const size_t dkv_elems = (size_t)TC_MAX_RADAR_LAYERS * B * T * 2 * w->embed_dims;
+  const size_t dkv_elems = (size_t)w->num_radar_layers * B * T * 2 * w->embed_dims;
   constexpr size_t kTail = 8;                                 // a device copy of the ranges in the buffer's last words
   static_assert(sizeof(DetAcc) <= kTail * 8, "the device copy of the ranges fits the tail");
   TC_REQUIRE(shadow_elems >= grad_elems + dkv_elems + kTail, "radar_train_bwd_fused_det: shadow holds %zu words, %zu needed",
              shadow_elems, grad_elems + dkv_elems + kTail);
-  TC_REQUIRE(ws.dkv[TC_MAX_RADAR_LAYERS - 1] + (size_t)B * T * 2 * w->embed_dims == ws.dkv[0] + dkv_elems,
+  TC_REQUIRE(ws.dkv[w->num_radar_layers - 1] + (size_t)B * T * 2 * w->embed_dims == ws.dkv[0] + dkv_elems,
              "radar_train_bwd_fused_det: the dK | dV accumulators are not contiguous");
   DetAcc d;
   d.lo[0] = grad_base; d.hi[0] = grad_base + grad_elems; d.shadow[0] = shadow;
@@ -702,14 +709,14 @@ int tc_radar_train_bwd_fused(const tc_head_weights* w, const tc_head_weights* gr
 }
 
 // Round 6: the weight gradients of ONE chunk (tc_radar_train_bwd_fused_ex with flags bit 1 left them out): group 0 ..
-// TC_MAX_RADAR_LAYERS - 1 = fusion layers top-down, TC_MAX_RADAR_LAYERS = the radar encoders.  Same tape / workspace as
+// num_radar_layers - 1 = fusion layers top-down, num_radar_layers = the radar encoders.  Same tape / workspace as
 // the backward call it follows on the same stream.
 int tc_radar_train_bwd_weights(const tc_head_weights* w, const tc_head_weights* grads, const float* hs_last,
                                const float* radar_tokens, int B, int T, void* tape, size_t tape_bytes, void* workspace,
                                size_t workspace_bytes, int group, tc_stream_t stream) {
   TS_TRY(check(w, B, T));
   TC_REQUIRE(grads != nullptr && workspace != nullptr && tape != nullptr, "radar_train_bwd_weights: null argument");
-  TC_REQUIRE(group >= 0 && group <= TC_MAX_RADAR_LAYERS, "radar_train_bwd_weights: group=%d (0..%d)", group, TC_MAX_RADAR_LAYERS);
+  TC_REQUIRE(group >= 0 && group <= w->num_radar_layers, "radar_train_bwd_weights: group=%d (0..%d)", group, w->num_radar_layers);
   Tape t;
   TC_REQUIRE(tape_layout(w, B, T, tape, tape_bytes, &t) <= tape_bytes, "radar_train_bwd_weights: tape too small");
   BwdWs ws;

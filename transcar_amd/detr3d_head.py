@@ -82,6 +82,10 @@ def head_options(tile_rows=None, unfused=None, last_level_cls_only=False,
     return o
 
 
+#: module-name suffixes of fusion layer 1, 2, 3: (rf_linear* / rf_norm* / rf_dropout*, rf_multihead_attn* / final_*)
+FUSION_SUFFIXES = (('', ''), ('_2', '2'), ('_3', '3'))
+
+
 def _cls_branch(embed, ncls):
     return nn.Sequential(
         nn.Linear(embed, embed), nn.LayerNorm(embed), nn.ReLU(inplace=True),
@@ -122,11 +126,15 @@ class Detr3DHead(BaseModule):
                  positional_encoding=None, loss_cls=None, loss_bbox=None,
                  loss_iou=None, train_cfg=None, test_cfg=None, init_cfg=None,
                  with_box_refine=False, as_two_stage=False, bbox_coder=None,
-                 num_cls_fcs=2, code_weights=None, outputs='fusion', **kwargs):
+                 num_cls_fcs=2, code_weights=None, outputs='fusion', num_fusion_layers=3, **kwargs):
         super().__init__(init_cfg)
+        #: depth N of the radar fusion stack, 1 .. 3 (the reference builds 3): only the first N sets of rf_* / final_*
+        #: modules exist, every output has N fusion levels.  Level k reads layers <= k only, so an N-layer head with the
+        #: first N layers' weights computes levels [0:N] of the three-layer head
+        self.num_fusion_layers = L.check_num_fusion_layers(num_fusion_layers)
         if outputs not in OUTPUTS:
             raise ValueError("Detr3DHead: outputs=%r (one of 'fusion', 'camera', 'all')" % (outputs,))
-        #: what ``forward`` returns as all_cls_scores / all_bbox_preds: 'fusion' the three radar fusion levels (the
+        #: what ``forward`` returns as all_cls_scores / all_bbox_preds: 'fusion' the radar fusion levels (three by default; the
         #: reference's return value), 'camera' the L decoder levels of the DETR3D camera detector alone (HEAD:277-298;
         #: radar is neither read nor required), 'all' the decoder levels followed by the fusion levels (the reference
         #: with HEAD:607-608 commented out).  A plain attribute: it may be changed between forwards.
@@ -167,11 +175,11 @@ class Detr3DHead(BaseModule):
             torch.tensor(code_weights, requires_grad=False),
             requires_grad=False)
         E, F = self.embed_dims, 512
-        for sfx in ('', '2', '3'):
+        for sfx in ('', '2', '3')[:self.num_fusion_layers]:
             setattr(self, 'final_cls' + sfx,
                     _cls_branch(E, self.cls_out_channels))
             setattr(self, 'final_reg' + sfx, _reg_branch(E, self.code_size))
-        for sfx, asfx in (('', ''), ('_2', '2'), ('_3', '3')):
+        for sfx, asfx in FUSION_SUFFIXES[:self.num_fusion_layers]:
             setattr(self, 'rf_multihead_attn' + asfx,
                     nn.MultiheadAttention(E, 8, dropout=0.1))
             setattr(self, 'rf_linear1' + sfx, nn.Linear(E, F))
@@ -189,7 +197,8 @@ class Detr3DHead(BaseModule):
             nn.Linear(36, 64), nn.ReLU(inplace=True),
             nn.Linear(64, 128), nn.ReLU(inplace=True),
             nn.Linear(128, E), nn.ReLU(inplace=True))
-        # constructed but never used by the reference forward (HEAD:191-195)
+        # constructed but never used by the reference forward (HEAD:191-195); kept at every fusion depth, so that the
+        # reference's checkpoint minus the absent layers' keys loads strictly
         self.attention_weights2 = nn.Linear(E, 6 * 4)
         self.attention_weights3 = nn.Linear(E, 6 * 4)
         self.output_proj2 = nn.Linear(E, E)
@@ -328,7 +337,8 @@ class Detr3DHead(BaseModule):
         L.check_num_points(w.num_points, w.num_cams, w.num_levels)
         L.check_num_classes(self.cls_out_channels)
         w.num_classes, w.code_size = self.cls_out_channels, self.code_size
-        w.radar_in_dims, w.num_radar_layers = radar.NUM_FEATURES, 3
+        w.radar_in_dims = radar.NUM_FEATURES
+        w.num_radar_layers = L.check_num_fusion_layers(self.num_fusion_layers)
         w.num_radar_tokens_ref = radar.NUM_RADAR_TOKENS
         for i in range(6):
             w.pc_range[i] = float(self.pc_range[i])
@@ -361,7 +371,7 @@ class Detr3DHead(BaseModule):
         w.radar_feat0 = _lin(self.radar_feat_encoder[0])
         w.radar_feat2 = _lin(self.radar_feat_encoder[2])
         w.radar_feat4 = _lin(self.radar_feat_encoder[4])
-        for r, (sfx, asfx) in enumerate((('', ''), ('_2', '2'), ('_3', '3'))):
+        for r, (sfx, asfx) in enumerate(FUSION_SUFFIXES[:w.num_radar_layers]):
             rl = w.radar[r]
             rl.attn = mha_view(getattr(self, 'rf_multihead_attn' + asfx))
             rl.norm2 = _ln(getattr(self, 'rf_norm2' + sfx))
@@ -641,12 +651,13 @@ class Detr3DHead(BaseModule):
             options = own
         ws = self._workspace[key]
         Q, ncls, code = self.num_query, self.cls_out_channels, self.code_size
+        NF = self.num_fusion_layers
         # one allocation, two views (_out: a static buffer of a captured graph, transcar_amd/plugin_graph.py)
-        out = _out if _out is not None else torch.empty(3 * B * Q * (ncls + code), dtype=torch.float32, device=dev)
-        if out.numel() != 3 * B * Q * (ncls + code) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise L.TransCARHipError('forward_nhwc: _out must be a contiguous fp32 buffer of %d elements' % (3 * B * Q * (ncls + code)))
-        cls = out[:3 * B * Q * ncls].view(3, B, Q, ncls)
-        box = out[3 * B * Q * ncls:].view(3, B, Q, code)
+        out = _out if _out is not None else torch.empty(NF * B * Q * (ncls + code), dtype=torch.float32, device=dev)
+        if out.numel() != NF * B * Q * (ncls + code) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise L.TransCARHipError('forward_nhwc: _out must be a contiguous fp32 buffer of %d elements' % (NF * B * Q * (ncls + code)))
+        cls = out[:NF * B * Q * ncls].view(NF, B, Q, ncls)
+        box = out[NF * B * Q * ncls:].view(NF, B, Q, code)
         fv = ops.feats_view(feats_nhwc)
         aux_s, aux_t = None, None
         if aux == 'train':
@@ -667,7 +678,7 @@ class Detr3DHead(BaseModule):
                                            device=dev),
                 inter_references=torch.empty((Lyr, B, Q, 3),
                                              dtype=torch.float32, device=dev),
-                radar_hit_counts=torch.empty((3, B, Q), dtype=torch.int32,
+                radar_hit_counts=torch.empty((NF, B, Q), dtype=torch.int32,
                                              device=dev),
                 last_box=torch.empty((B, Q, code), dtype=torch.float32,
                                      device=dev),
@@ -714,7 +725,7 @@ class Detr3DHead(BaseModule):
 
     def forward(self, mlvl_feats, img_metas, aux=False):
         """HEAD:248-261: mlvl_feats list of [B,N,C,H,W]; img_metas list[dict]
-        -> dict(all_cls_scores [3,B,Q,10], all_bbox_preds [3,B,Q,10], enc_*)."""
+        -> dict(all_cls_scores [N,B,Q,10], all_bbox_preds [N,B,Q,10], enc_*), N = num_fusion_layers (3)."""
         self.check_feature_levels(len(mlvl_feats))
         self._check_outputs()
         dev = mlvl_feats[0].device
@@ -779,7 +790,7 @@ class Detr3DHead(BaseModule):
 
         tools/train.py:245-252 freezes transformer / cls_branches /
         reg_branches / query_embedding, so gradients are only needed in the
-        radar encoders, the three fusion layers and final_cls*/final_reg*
+        radar encoders, the fusion layers and final_cls*/final_reg*
         (HEAD:531-729).  The frozen decoder runs through tc_head_forward; its
         last state, last reference and last box (``aux``) feed the radar stack,
         which is recomputed here node by node (transcar_amd/autograd_ops.py)
@@ -831,7 +842,7 @@ class Detr3DHead(BaseModule):
         mem = pos + f
 
         all_cls, all_box = [], []
-        for r, (sfx, asfx) in enumerate((('', ''), ('_2', '2'), ('_3', '3'))):
+        for r, (sfx, asfx) in enumerate(FUSION_SUFFIXES[:self.num_fusion_layers]):
             attn = getattr(self, 'rf_multihead_attn' + asfx)
             p_attn = float(attn.dropout)
             p_ffn = float(getattr(self, 'rf_dropout' + sfx).p)
@@ -909,7 +920,7 @@ class Detr3DHead(BaseModule):
         """p of every dropout site of the radar fusion layers (HEAD:129-171 build
         them with 0.1) and, with ``decoder``, of the frozen decoder layers
         (CFG:68-80, XFMR:378): 0.0 = the deterministic training forward."""
-        for asfx, sfx in (('', ''), ('2', '_2'), ('3', '_3')):
+        for sfx, asfx in FUSION_SUFFIXES[:self.num_fusion_layers]:
             getattr(self, 'rf_multihead_attn' + asfx).dropout = float(p)
             for name in ('rf_dropout', 'rf_dropout1', 'rf_dropout2', 'rf_dropout3'):
                 getattr(self, name + sfx).p = float(p)

@@ -287,11 +287,15 @@ def decoder_layer_tail(packed_layer, packed_next_in_proj, feats_nhwc, attn_o, x_
 
 
 def radar_fusion(head, hs_last, ref_last, prev_box, tokens, pad_mult, first_layer=0,
-                 num_layers=3, options=None, ws=None):
+                 num_layers=None, options=None, ws=None):
     """The radar part of the head from given decoder outputs (tc_radar_fusion_fwd):
-    encoders + fusion layers [first_layer, first_layer + num_layers).  Returns
-    (all_cls [3,B,Q,ncls], all_box [3,B,Q,code], hits [3,B,Q]); only the slices of
-    the layers that ran are written (the rest is NaN / -1)."""
+    encoders + fusion layers [first_layer, first_layer + num_layers); num_layers=None:
+    up to the head's last one.  Returns (all_cls [N,B,Q,ncls], all_box [N,B,Q,code],
+    hits [N,B,Q]), N = head.num_fusion_layers; only the slices of the layers that ran are
+    written (the rest is NaN / -1)."""
+    NF = head.num_fusion_layers
+    if num_layers is None:
+        num_layers = NF - int(first_layer)
     head.head_weights()
     head.sync_packed_weights()
     pv = head._packed_view
@@ -303,9 +307,9 @@ def radar_fusion(head, hs_last, ref_last, prev_box, tokens, pad_mult, first_laye
     nbytes = L.lib().tc_head_workspace_bytes(C.byref(pv), B, T)
     if ws is None:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    cls = torch.full((3, B, Q, head.cls_out_channels), float('nan'), dtype=torch.float32, device=dev)
-    box = torch.full((3, B, Q, head.code_size), float('nan'), dtype=torch.float32, device=dev)
-    hits = torch.full((3, B, Q), -1, dtype=torch.int32, device=dev)
+    cls = torch.full((NF, B, Q, head.cls_out_channels), float('nan'), dtype=torch.float32, device=dev)
+    box = torch.full((NF, B, Q, head.code_size), float('nan'), dtype=torch.float32, device=dev)
+    hits = torch.full((NF, B, Q), -1, dtype=torch.int32, device=dev)
     L.check(L.lib().tc_radar_fusion_fwd(
         C.byref(pv), _p(hs_last), _p(ref_last), _p(prev_box), _p(tokens), B, T, int(pad_mult),
         int(first_layer), int(num_layers), _p(cls), _p(box), _p(hits),

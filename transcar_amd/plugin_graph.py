@@ -128,10 +128,11 @@ class PluginGraphs:
         e.stage = ops.RadarRawStage(B, cap, dev)
         e.status_host = torch.zeros(1 + B, dtype=torch.int32).pin_memory()
         Q, ncls, code, mx = h.num_query, h.cls_out_channels, h.code_size, h.bbox_coder.max_num
+        NF = e.NF = h.num_fusion_layers
         e.Q, e.ncls, e.code = Q, ncls, code
         # ONE static result buffer: labels (int64) first, then class scores | boxes (forward_nhwc's own layout), then
         # the decoded boxes and scores
-        n_lab, n_out, n_box, n_sc = B * mx * 2, 3 * B * Q * (ncls + code), B * mx * 9, B * mx
+        n_lab, n_out, n_box, n_sc = B * mx * 2, NF * B * Q * (ncls + code), B * mx * 9, B * mx
         e.sizes = (n_lab, n_out, n_box, n_sc)
         side = torch.cuda.Stream(device=dev)
         h.sync_packed_weights()
@@ -181,12 +182,12 @@ class PluginGraphs:
     @staticmethod
     def _views(flat, e):
         n_lab, n_out, n_box, n_sc = e.sizes
-        B, Q, ncls, code = e.B, e.Q, e.ncls, e.code
+        B, Q, ncls, code, NF = e.B, e.Q, e.ncls, e.code, e.NF
         lab = flat[:n_lab].view(torch.int64)
         out = flat[n_lab:n_lab + n_out]
         boxes = flat[n_lab + n_out:n_lab + n_out + n_box]
         scores = flat[n_lab + n_out + n_box:]
-        return dict(out=out, cls=out[:3 * B * Q * ncls].view(3, B, Q, ncls), box=out[3 * B * Q * ncls:].view(3, B, Q, code),
+        return dict(out=out, cls=out[:NF * B * Q * ncls].view(NF, B, Q, ncls), box=out[NF * B * Q * ncls:].view(NF, B, Q, code),
                     labels=lab.view(B, -1), boxes=boxes.view(B, -1, 9), scores=scores.view(B, -1))
 
     def _replay(self, e, img_metas):

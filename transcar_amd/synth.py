@@ -103,6 +103,20 @@ def state_dict_spec(num_query=900, embed=256, ffn=512, num_layers=6,
     return s
 
 
+#: per-layer module stems of the radar fusion stack; layer 1 has no suffix, layers 2 / 3 carry '2' / '3' resp. '_2' / '_3'
+_FUSION_STEMS = (('final_cls', 'final_reg', 'rf_multihead_attn'), ('rf_linear1', 'rf_linear2', 'rf_norm1', 'rf_norm2', 'rf_norm3'))
+
+
+def fusion_layer_of(key):
+    """0-based radar fusion layer a ``pts_bbox_head.*`` state_dict key belongs to, None for every other key."""
+    mod = key.split('.', 1)[0]
+    for stems, sfxs in zip(_FUSION_STEMS, (('', '2', '3'), ('', '_2', '_3'))):
+        for stem in stems:
+            if mod.startswith(stem) and mod[len(stem):] in sfxs:
+                return sfxs.index(mod[len(stem):])
+    return None
+
+
 def make_state_dict(seed=3, **dims):
     """Seeded weights as {key: float32 ndarray}.
 
@@ -117,7 +131,13 @@ def make_state_dict(seed=3, **dims):
 
     ``with_box_refine=False``: the head shares ONE cls and ONE reg branch
     across the decoder layers (HEAD:223-231); its state_dict still carries
-    them under every index, so the seeded branch ``.0`` is written under all."""
+    them under every index, so the seeded branch ``.0`` is written under all.
+
+    ``num_fusion_layers=N`` (1 .. 3): the three-layer dict minus the keys of the
+    fusion layers a shallower head does not build; what remains keeps the values
+    it has in the three-layer dict (nothing is drawn again)."""
+    from ._lib import check_num_fusion_layers
+    num_fusion_layers = check_num_fusion_layers(dims.pop('num_fusion_layers', 3))
     reg_out_scale = dims.pop('reg_out_scale', 0.1)
     with_box_refine = dims.pop('with_box_refine', True)
     rng = np.random.RandomState(seed)
@@ -149,6 +169,10 @@ def make_state_dict(seed=3, **dims):
                 if key.startswith(stem):
                     rest = key[len(stem):].split('.', 1)[1]
                     sd[key] = sd[stem + '0.' + rest].copy()
+    for key in list(sd):
+        layer = fusion_layer_of(key)
+        if layer is not None and layer >= num_fusion_layers:
+            del sd[key]
     return sd
 
 

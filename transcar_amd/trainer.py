@@ -24,22 +24,21 @@ import torch.distributed as dist
 from . import _lib as L
 
 
-def exchange_chunk_of(name):
+def exchange_chunk_of(name, num_fusion_layers=3):
     """Chunk of the gradient exchange a trainable parameter of the fusion stack belongs to, in the order the backward
-    finishes the weight gradients (tc_radar_train_bwd_weights): 0 / 1 / 2 = fusion layer 3 / 2 / 1 (HEAD:129-171: the
-    modules with suffix `3` / `_3`, `2` / `_2`, none), 3 = the radar encoders and anything else."""
+    finishes the weight gradients (tc_radar_train_bwd_weights).  With N = num_fusion_layers: 0 .. N - 1 = fusion layer
+    N .. 1 (HEAD:129-171: the modules with suffix `3` / `_3`, `2` / `_2`, none), N = the radar encoders and anything else
+    -- N + 1 chunks.  The default depth of 3: 0 / 1 / 2 = fusion layer 3 / 2 / 1, 3 = the encoders."""
+    n = L.check_num_fusion_layers(num_fusion_layers)
     head = name.split('.')[0]
     stems = ('final_cls', 'final_reg', 'rf_multihead_attn', 'rf_linear1', 'rf_linear2', 'rf_norm1', 'rf_norm2', 'rf_norm3')
     for stem in stems:
         if head.startswith(stem):
             tail = head[len(stem):]
-            if tail in ('3', '_3'):
-                return 0
-            if tail in ('2', '_2'):
-                return 1
-            if tail == '':
-                return 2
-    return 3
+            layer = 2 if tail in ('3', '_3') else 1 if tail in ('2', '_2') else 0 if tail == '' else None
+            if layer is not None and layer < n:
+                return n - 1 - layer
+    return n
 
 
 class FlatBucket:
@@ -154,7 +153,8 @@ def grad_table(head):
     rpe, rfe = head.radar_position_encoder, head.radar_feat_encoder
     g.radar_position_encoder = L.tc_pos_encoder(lin(rpe[0]), ln(rpe[1]), lin(rpe[3]), ln(rpe[4]))
     g.radar_feat0, g.radar_feat2, g.radar_feat4 = lin(rfe[0]), lin(rfe[2]), lin(rfe[4])
-    for r, (sfx, asfx) in enumerate((('', ''), ('_2', '2'), ('_3', '3'))):
+    g.num_radar_layers = head.num_fusion_layers
+    for r, (sfx, asfx) in enumerate((('', ''), ('_2', '2'), ('_3', '3'))[:head.num_fusion_layers]):
         rl = g.radar[r]
         attn = getattr(head, 'rf_multihead_attn' + asfx)
         rl.attn = L.tc_mha(L.tc_linear(_g(attn.in_proj_weight), _g(attn.in_proj_bias)),
@@ -187,14 +187,16 @@ class FusionTrainer:
             raise ValueError('FusionTrainer(deterministic=True) needs the fused backward (chain_backward=True): the '
                              'per-operator backward (tc_radar_train_bwd) accumulates with float atomics')
         self._shadow = None
-        # Round 6: the bucket is laid out in EXCHANGE CHUNKS -- fusion layer 3, 2, 1, radar encoders,
+        # Round 6: the bucket is laid out in EXCHANGE CHUNKS -- fusion layer N, .., 1, radar encoders
+        # (N = head.num_fusion_layers: N + 1 chunks),
         # the order in which the backward finishes their weight gradients -- and with more than one rank an iteration
         # launches the weight gradients chunk by chunk (tc_radar_train_bwd_weights) with one asynchronous all-reduce
         # behind each: chunk k travels while chunk k + 1 is computed (`chunked_exchange`; tools/train.py:253-260: DDP's
         # buckets).  One rank, or deterministic=True (the order-free backward flushes its shadow once, behind ONE grouped
         # launch): the single grouped launch and the single all-reduce of round 5.
         self.chunked_exchange = True
-        self.bucket = FlatBucket(head.trainable_parameters(), chunk_of=exchange_chunk_of)
+        depth = head.num_fusion_layers
+        self.bucket = FlatBucket(head.trainable_parameters(), chunk_of=lambda name: exchange_chunk_of(name, depth))
         head.refresh_weights()                      # parameter addresses moved into the bucket
         self.m = torch.zeros_like(self.bucket.params)
         self.v = torch.zeros_like(self.bucket.params)
@@ -406,8 +408,9 @@ class FusionTrainer:
             self._tape_key = key
         tape = self._tape
         Q = head.num_query
-        all_cls = torch.empty((3, B, Q, head.cls_out_channels), dtype=torch.float32, device=tokens.device)
-        all_box = torch.empty((3, B, Q, head.code_size), dtype=torch.float32, device=tokens.device)
+        NF = head.num_fusion_layers
+        all_cls = torch.empty((NF, B, Q, head.cls_out_channels), dtype=torch.float32, device=tokens.device)
+        all_box = torch.empty((NF, B, Q, head.code_size), dtype=torch.float32, device=tokens.device)
         self._wT_ready = False
         if self.chain_forward:
             # the packed (4x4x1) copy of the trainable weights for the CURRENT parameters -- and, when the backward is
@@ -478,7 +481,7 @@ class FusionTrainer:
             flags = (1 if self._wT_ready else 0) | (2 if chunked else 0)
             common = common + (flags,)
             if self.deterministic:
-                need = self.bucket.numel + 3 * B * T * 2 * head.embed_dims + 8
+                need = self.bucket.numel + NF * B * T * 2 * head.embed_dims + 8
                 if self._shadow is None or self._shadow.numel() < need or self._shadow.device != tokens.device:
                     self._shadow = torch.zeros(need, dtype=torch.int64, device=tokens.device)   # the call leaves it zero
                 L.check(lib.tc_radar_train_bwd_fused_det(*common, self.bucket.grads.data_ptr(), self.bucket.numel,
@@ -540,9 +543,9 @@ class FusionTrainer:
 
     def _exchange_in_chunks(self, update=True):
         """Chunked weight-gradient launches + one all-reduce per chunk: only where there is an exchange to hide (more than
-        one rank), on the fused float-atomic backward, and only with the four chunks the C entry knows."""
+        one rank), on the fused float-atomic backward, and only with the N + 1 chunks the C entry knows (N fusion layers)."""
         return bool(update and self.chunked_exchange and self.chain_backward and not self.deterministic
-                    and len(self.bucket.chunk_ranges) == 4
+                    and len(self.bucket.chunk_ranges) == self.head.num_fusion_layers + 1
                     and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
 
     def _backward_workspace(self, lib, w, key, B, T, device):
