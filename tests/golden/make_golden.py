@@ -39,20 +39,28 @@ def save(name, **arrs):
     print('wrote %s (%.1f KB)' % (name, os.path.getsize(path) / 1024))
 
 
-def ref_head(num_levels=None, num_points=None, with_box_refine=True, num_heads=None, num_classes=None, train=False):
+def ref_head(num_levels=None, num_points=None, with_box_refine=True, num_heads=None, num_classes=None, train=False,
+             pc_range=None, post_center_range=None):
     """The REFERENCE's head of one variant (None: the configs' 4 levels / 1 point / 8 heads / 10 classes) in eval mode,
     with synth.make_state_dict's seeded weights: the same key set and shapes; attention_weights not the reference's zero
     init (XFMR:297-300: every sigmoid 0.5 would hide a wrong (camera, point, level) order of the logits); without box
     refinement ONE cls and ONE reg branch under every index (HEAD:223-231).  num_heads is the decoder self-attention's:
     the state dict does not depend on it, and the radar fusion attention keeps the 8 heads the reference builds it with
-    (HEAD:129-171)."""
+    (HEAD:129-171).  pc_range / post_center_range: configs.head_cfg's (the coder, every Detr3DCrossAtten, the assigner)."""
     kw = {k: v for k, v in dict(num_levels=num_levels, num_points=num_points, num_classes=num_classes).items()
           if v is not None}
     if not with_box_refine:
         kw['with_box_refine'] = False
-    cfg = configs.head_cfg(num_heads=num_heads, **kw)
+    cfg = configs.head_cfg(num_heads=num_heads, pc_range=pc_range, post_center_range=post_center_range, **kw)
     assert cfg['num_classes'] == cfg['bbox_coder']['num_classes'] == (num_classes or 10)
-    head = RH.build_reference_head(cfg, configs.train_cfg_pts if train else None)
+    train_cfg = cfg.pop('train_cfg', configs.train_cfg_pts)
+    head = RH.build_reference_head(cfg, train_cfg if train else None)
+    want_range = list(configs.point_cloud_range if pc_range is None else pc_range)
+    assert list(head.bbox_coder.pc_range) == list(head.pc_range) == want_range
+    for ly in head.transformer.decoder.layers:
+        assert list(ly.attentions[1].pc_range) == want_range
+    if train:
+        assert list(head.assigner.pc_range) == want_range
     assert bool(head.with_box_refine) == with_box_refine
     assert (head.reg_branches[0] is head.reg_branches[5]) == (head.cls_branches[0] is head.cls_branches[5]) \
         == (not with_box_refine)
@@ -102,12 +110,26 @@ def g1_feature_sampling(ref):
          sampled=sampled.numpy(), mask=mask.numpy())
 
 
-def g2_cross_atten(head, shapes='tiny', tag=''):
-    """Detr3DCrossAtten.forward (XFMR:302-378), C=256, Q=900, tiny maps (or the given level shapes)."""
+def cameras(geometry):
+    """(lidar2img, img_shape) of a geometry (tests/head_variant_rig.Geometry; None: the configs' image, the default
+    cameras)"""
+    if geometry is None:
+        return synth.make_lidar2img(), configs.IMG_SHAPE
+    return synth.make_lidar2img(focal=geometry.focal, pp=geometry.pp), geometry.img_shape
+
+
+def geometry_kw(geometry):
+    return {} if geometry is None else dict(pc_range=list(geometry.pc_range),
+                                            post_center_range=list(geometry.post_center_range))
+
+
+def g2_cross_atten(head, shapes='tiny', tag='', geometry=None):
+    """Detr3DCrossAtten.forward (XFMR:302-378), C=256, Q=900, tiny maps (or the given level shapes); geometry: the
+    cameras and the image size (the range is the head's)."""
     rng = np.random.RandomState(21)
     feats = synth.make_feats(shapes, seed=22)
-    l2i = synth.make_lidar2img()
-    metas = synth.make_img_metas(1, l2i)
+    l2i, img_shape = cameras(geometry)
+    metas = synth.make_img_metas(1, l2i, img_shape=img_shape)
     Q = 900
     query = rng.standard_normal((Q, 1, 256)).astype(np.float32)
     qpos = rng.standard_normal((Q, 1, 256)).astype(np.float32)
@@ -120,10 +142,10 @@ def g2_cross_atten(head, shapes='tiny', tag=''):
     save('g2_cross_atten%s.npz' % tag, out=out.numpy()[::4], **level_shapes_of(shapes))
 
 
-def run_head(head, feats, l2i, frame):
+def run_head(head, feats, l2i, frame, img_shape=None):
     RH.RADAR_FRAME.clear()
     RH.RADAR_FRAME.update(frame)
-    metas = synth.make_img_metas(1, l2i)
+    metas = synth.make_img_metas(1, l2i, img_shape=img_shape)
     cap = {}
 
     def hook_tokens(mod, inp):
@@ -151,23 +173,24 @@ def run_head(head, feats, l2i, frame):
     return outs, cap, tcap
 
 
-def g345_head(head, ref, shapes, tag, num_classes=None, hs_stride=16):
+def g345_head(head, ref, shapes, tag, num_classes=None, hs_stride=16, geometry=None):
     """G5 (with G3's and G4's intermediates): Detr3DHead.forward in two passes and the coder's decode at num_classes
-    (None: the configs' 10).  hs_rows keeps every hs_stride-th query; the stride is stored where it is not 16."""
+    (None: the configs' 10).  hs_rows keeps every hs_stride-th query; the stride is stored where it is not 16.
+    geometry: the cameras and the image size, and the ranges `head` was built with."""
     feats = synth.make_feats(shapes, seed=1, smooth=SMOOTH)
-    l2i = synth.make_lidar2img()
+    l2i, img_shape = cameras(geometry)
     # pass 1: uniform radar, to learn where the decoder puts its boxes
     frame0 = synth.make_radar_frame(seed=2, n_per_radar=51)
-    _, _, tcap = run_head(head, feats, l2i, frame0)
+    _, _, tcap = run_head(head, feats, l2i, frame0, img_shape)
     r = tcap['inter_refs'][-1][0].numpy().astype(np.float64)
-    pcr = configs.point_cloud_range
+    pcr = head.pc_range
     # centres are rounded to 1 cm and STORED in the fixture: they are an
     # input of pass 2, and must not depend on anyone's decoder arithmetic
     centres = np.round(np.stack([r[:, 0] * (pcr[3] - pcr[0]) + pcr[0],
                                  r[:, 1] * (pcr[4] - pcr[1]) + pcr[1]], 1), 2)
     # pass 2: 80 % of the radar returns near predicted centres
     frame = synth.make_radar_frame(seed=2, n_per_radar=51, centres=centres)
-    outs, cap, tcap = run_head(head, feats, l2i, frame)
+    outs, cap, tcap = run_head(head, feats, l2i, frame, img_shape)
     tokens = cap['tokens'][0].numpy()
     fill_in = int((tokens[:, 0] != 500.0).sum())
     hit_counts = []
@@ -175,7 +198,7 @@ def g345_head(head, ref, shapes, tag, num_classes=None, hs_stride=16):
         m = cap['mask%d' % i].numpy()
         hit_counts.append((~m).sum(1).astype(np.int32))     # per selected row
     dec = ref.CODER.NMSFreeCoder(**{k: v for k, v in
-                                    configs.head_cfg(num_classes=num_classes)['bbox_coder'].items()
+                                    configs.head_cfg(num_classes=num_classes, **geometry_kw(geometry))['bbox_coder'].items()
                                     if k != 'type'})
     assert dec.num_classes == (num_classes or 10)
     preds = dec.decode({'all_cls_scores': outs['all_cls_scores'],
@@ -270,7 +293,7 @@ def write_g8(name, head, outs, cap, losses, total, **extra):
           sum(p.numel() for p in head.parameters() if p.requires_grad), 'trainable scalars')
 
 
-def g8_train_grads(tag='tiny', suffix='', shapes=None, radar_seed=2, **variant):
+def g8_train_grads(tag='tiny', suffix='', shapes=None, radar_seed=2, geometry=None, **variant):
     """One training iteration's gradients from the reference: Detr3DHead.forward (tiny
     shapes -- or, tag 'res101', the ResNet-101 FPN shapes of BASELINE.json configs[2] -- radar near the G5 centres) -> loss() -> sum of the six losses (mmdet
     `_parse_losses`) -> backward, dropout off (eval mode), frozen groups as in
@@ -278,18 +301,19 @@ def g8_train_grads(tag='tiny', suffix='', shapes=None, radar_seed=2, **variant):
 
     suffix, variant: of another head variant (fixture g5_head_<tag><suffix>.npz holds the centres); shapes: its level
     shapes where they are not the four of `tag`; radar_seed: another radar frame than G5's, stored in the fixture.  A
-    variant's num_classes is also the ground truth's (synth.make_gt)."""
+    variant's num_classes is also the ground truth's (synth.make_gt).  geometry: the cameras, the image size and the
+    head's ranges."""
     num_classes = variant.get('num_classes') or 10
-    head = ref_head(train=True, **variant)
+    head = ref_head(train=True, **dict(variant, **geometry_kw(geometry)))
     freeze_like_train_py(head)
     g5 = np.load(os.path.join(HERE, 'g5_head_%s%s.npz' % (tag, suffix)))
     feats = synth.make_feats(shapes or tag, seed=1, smooth=SMOOTH)
-    l2i = synth.make_lidar2img()
+    l2i, img_shape = cameras(geometry)
     frame = synth.make_radar_frame(seed=radar_seed, n_per_radar=51, centres=g5['radar_centres'])
     boxes, labels = synth.make_gt(seed=7, n=24, num_classes=num_classes)
     assert labels.max() < num_classes
     with torch.enable_grad():
-        outs, cap, _ = run_head(head, feats, l2i, frame)
+        outs, cap, _ = run_head(head, feats, l2i, frame, img_shape)
         if radar_seed == 2:
             d = np.abs(outs['all_cls_scores'].detach().numpy() - g5['all_cls_scores']).max()
             assert d < 5e-4, d                      # same frame as fixture G5

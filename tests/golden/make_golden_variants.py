@@ -3,8 +3,8 @@
 REFERENCE's own code (oracle/ref_harness.py) with make_golden.py's functions and rigs (G2's inputs; G5's two passes,
 radar near the predicted centres; G8's iteration).  Run only in the authoring container:
     python tests/golden/make_golden_variants.py [points] [levels] [norefine] [heads] [classes] [decoder_outputs]
-                                                                                       (none named: all six)
-    python tests/golden/make_golden_variants.py seeds                (prints; see "classes" below)
+                                                [geometry]                             (none named: all seven)
+    python tests/golden/make_golden_variants.py seeds [geometry]     (prints; see "classes" and "geometry" below)
 
 points -- Detr3DCrossAtten(num_points > 1):
   g2_cross_atten_p5.npz                Detr3DCrossAtten.forward at P = 5
@@ -48,14 +48,30 @@ reg-branch output IS outputs_coord of its level.  With box refinement the decode
 (XFMR:191); the head's calls are the last six recorded.  The generator asserts that its inter_references equal the g5
 fixture's bit for bit: the fixtures describe the same run.
 
-The radar seeds 13 / 14 / 16.  A radar gate decision that sits next to its radius flips between two fp32 evaluation
+geometry -- the configs' head at a point-cloud range and an image size that are not the configs' (head_variant_rig.GEOM:
+pc_range [-30, -60, -4, 70, 36, 6] in the coder, every Detr3DCrossAtten and the assigner, post_center_range
+[-40, -70, -6, 80, 45, 8], images of 640 x 1152 with the principal point at their centre).  The configs' range has equal
+x and y intervals centred on 0, where an x / y swap or `2 * pc[3]` for `pc[3] - pc[0]` changes nothing:
+  g2_cross_atten_geom.npz              Detr3DCrossAtten.forward
+  g5_head_tiny_geom.npz                Detr3DHead.forward, tiny maps, 900 queries; decoded with post_center_range above.  The
+                                       radar filter's range is the reference's constant (HEAD:304), so the frame around
+                                       the predicted centres loses the points beyond +-51.2 m (asserted: at least 10 %)
+  g10_decoder_outputs_tiny_geom.npz    the six decoder levels of that run
+  g8_train_grads_geom.npz              one training iteration's gradients, the radar frame of seed G8_GEOM_RADAR_SEED
+  g6_decode_geom.npz                   NMSFreeCoder.decode_single with that post_center_range on seeded logits [1, 900, 10]
+                                       (make_golden_decode.py's grid) and box codes whose centres are uniform over the
+                                       range widened by an eighth on every side: each of its six faces rejects some of
+                                       the 300 candidates (asserted)
+
+The radar seeds 13 / 14 / 16 / 30.  A radar gate decision that sits next to its radius flips between two fp32 evaluation
 orders, and a flipped row of the third fusion layer moves its attention's gradients by ~1 % (G5-L2's radar frame, seed
 2: query 880, 2.1e-4 m from the radius; G5-C23's, seed 2: one 3.8e-5 m from it).  A gradient fixture so affected takes
 the radar frame whose closest gate decision, in all three fusion layers, is the farthest from its radius, measured with
 the oracle: the two-level one among seeds 3 .. 39 (G8_L2_RADAR_SEED = 13: 8.9e-4 m), the 23-class one among seeds
 2 .. 39 (G8_C23_RADAR_SEED = 14: 8.9e-4 m; `seeds` prints the distance per seed, at 23 classes on G5-C23's centres).
 The 32-class training frame of tests/test_gpu_num_classes.py, which has no fixture, was chosen the same way around the
-centres the oracle's own decoder predicts (num_classes_rig.C32_RADAR_SEED = 16: 8.6e-4 m)."""
+centres the oracle's own decoder predicts (num_classes_rig.C32_RADAR_SEED = 16: 8.6e-4 m).  The geometry's gradient
+fixture likewise, among seeds 2 .. 39 on G5-GEOM's centres (`seeds geometry`; G8_GEOM_RADAR_SEED = 30: 7.55e-4 m)."""
 import json
 import os
 import sys
@@ -65,6 +81,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))               # tests/: head_variant_rig names the geometry
 
 import make_golden as MG                                 # noqa: E402
 from make_golden import g2_cross_atten, g345_head, g8_train_grads, ref_head      # noqa: E402
@@ -72,7 +89,10 @@ from make_golden import g2_cross_atten, g345_head, g8_train_grads, ref_head     
 from oracle import transcar_oracle as O                  # noqa: E402
 from transcar_amd import configs, synth                  # noqa: E402
 
+from head_variant_rig import GEOM                        # noqa: E402
+
 TINY, RES101 = configs.LEVEL_SHAPES['tiny'], configs.LEVEL_SHAPES['res101']
+G8_GEOM_RADAR_SEED = 30
 G8_L2_RADAR_SEED = 13
 NC, G8_C23_RADAR_SEED = 23, 14
 
@@ -122,16 +142,17 @@ def classes(ref):
     g8_train_grads(suffix='_c%d' % NC, radar_seed=G8_C23_RADAR_SEED, num_classes=NC)
 
 
-def decoder_outputs(ref):
-    for refine, tag in ((True, 'tiny'), (False, 'tiny_norefine')):
-        head = ref_head(with_box_refine=refine)
+def decoder_outputs(ref, cases=((True, 'tiny', None), (False, 'tiny_norefine', None))):
+    for refine, tag, geometry in cases:
+        head = ref_head(with_box_refine=refine, **MG.geometry_kw(geometry))
         calls = {'cls': [], 'reg': []}
         hooks = []
         for kind, branches in (('cls', head.cls_branches), ('reg', head.reg_branches)):
             for m in {id(m): m for m in branches}.values():        # without refinement: one module under every index
                 hooks.append(m.register_forward_hook(lambda mod, inp, out, kind=kind: calls[kind].append(out)))
         feats = synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)
-        _, _, tcap = MG.run_head(head, feats, synth.make_lidar2img(), synth.make_radar_frame(seed=2, n_per_radar=51))
+        l2i, img_shape = MG.cameras(geometry)
+        _, _, tcap = MG.run_head(head, feats, l2i, synth.make_radar_frame(seed=2, n_per_radar=51), img_shape)
         for h in hooks:
             h.remove()
         L = 6
@@ -145,13 +166,52 @@ def decoder_outputs(ref):
         MG.save('g10_decoder_outputs_%s.npz' % tag, dec_cls=dec_cls, dec_box=dec_box)
 
 
-def gate_margins(seeds):
+def decode_geometry(ref):
+    """g6_decode_geom.npz: make_golden_decode.py's inputs at the head's 10 classes, the centres spread over and beyond
+    every face of GEOM's post_center_range."""
+    Q, NCLS, MAX_NUM, MIN_ULPS = 900, 10, 300, 16
+    rng = np.random.RandomState(27)
+    n = Q * NCLS
+    cls = np.linspace(-8.0, 4.0, n).astype(np.float32)[rng.permutation(n)].reshape(1, Q, NCLS)
+    top = np.sort(torch.from_numpy(cls).double().sigmoid().float().numpy().reshape(-1))[::-1][:MAX_NUM + 100]
+    assert np.diff(top[::-1].view(np.int32)).min() >= MIN_ULPS
+    post = np.asarray(GEOM.post_center_range, np.float64)
+    box = (rng.standard_normal((1, Q, 10)) * 0.3).astype(np.float32)
+    for col, ax in ((0, 0), (1, 1), (4, 2)):                  # cx, cy, cz of a box code
+        lo, hi = post[ax], post[ax + 3]
+        box[..., col] = rng.uniform(lo - (hi - lo) / 8, hi + (hi - lo) / 8, (1, Q)).astype(np.float32)
+    cfg = {k: v for k, v in configs.head_cfg(**MG.geometry_kw(GEOM))['bbox_coder'].items() if k != 'type'}
+    assert cfg['post_center_range'] == list(GEOM.post_center_range) and cfg['max_num'] == MAX_NUM
+    out = ref.CODER.NMSFreeCoder(**cfg).decode_single(torch.from_numpy(cls[0]), torch.from_numpy(box[0]))
+    assert MAX_NUM // 4 <= out['scores'].shape[0] < MAX_NUM
+    MG.save('g6_decode_geom.npz', cls=cls, box=box, post_center_range=np.asarray(cfg['post_center_range'], np.float32),
+            **{k: out[k].numpy() for k in ('bboxes', 'scores', 'labels')})
+
+
+def geometry(ref):
+    kw = MG.geometry_kw(GEOM)
+    head = ref_head(**kw)
+    g2_cross_atten(head, tag='_geom', geometry=GEOM)
+    g345_head(head, ref, 'tiny', 'tiny_geom', geometry=GEOM)
+    g5 = np.load(os.path.join(HERE, 'g5_head_tiny_geom.npz'))
+    assert 150 <= int(g5['fill_in']) <= 0.9 * 255, int(g5['fill_in'])      # the fixed radar range has work to do
+    decoder_outputs(ref, ((True, 'tiny_geom', GEOM),))
+    g8_train_grads(suffix='_geom', radar_seed=G8_GEOM_RADAR_SEED, geometry=GEOM)
+    decode_geometry(ref)
+
+
+def gate_margins(seeds, g5_name=None, geometry=None, **sd_kw):
     """Per radar seed: min over the three fusion layers, the queries, the three circles and the tokens of
-    |distance - radius| (metres), from the oracle at NC classes on G5-C23's centres."""
-    g5 = np.load(os.path.join(HERE, 'g5_head_tiny_c%d.npz' % NC))
-    sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_classes=NC))
+    |distance - radius| (metres), from the oracle at NC classes on G5-C23's centres -- or on fixture g5_name's, with
+    the state dict of sd_kw at the geometry."""
+    if g5_name is None:
+        g5_name, sd_kw = 'g5_head_tiny_c%d.npz' % NC, dict(num_classes=NC)
+    g5 = np.load(os.path.join(HERE, g5_name))
+    sd = O.to_torch_sd(synth.make_state_dict(seed=3, **sd_kw))
     feats = [torch.from_numpy(f) for f in synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)]
-    l2i = torch.from_numpy(synth.make_lidar2img()).float()[None]
+    l2i, img_shape = MG.cameras(geometry)
+    l2i = torch.from_numpy(l2i).float()[None]
+    pc_range = configs.point_cloud_range if geometry is None else list(geometry.pc_range)
     seen = []
 
     def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
@@ -168,8 +228,7 @@ def gate_margins(seeds):
     for seed in seeds:
         del seen[:]
         frame = synth.make_radar_frame(seed=seed, n_per_radar=51, centres=g5['radar_centres'])
-        O.head_forward(sd, feats, l2i, configs.IMG_SHAPE[:2], O.build_radar_features(frame), configs.point_cloud_range,
-                       gate_probe=probe)
+        O.head_forward(sd, feats, l2i, img_shape[:2], O.build_radar_features(frame), pc_range, gate_probe=probe)
         assert len(seen) == 9
         out[seed] = min(seen)
         print('radar seed %2d: closest gate decision %.2e m from its radius' % (seed, out[seed]))
@@ -178,12 +237,13 @@ def gate_margins(seeds):
 
 def main():
     if 'seeds' in sys.argv[1:]:
-        m = gate_margins(range(2, 40))
+        m = gate_margins(range(2, 40), 'g5_head_tiny_geom.npz', GEOM) if 'geometry' in sys.argv[1:] \
+            else gate_margins(range(2, 40))
         best = max(m, key=m.get)
         print('largest: seed %d, %.2e m' % (best, m[best]))
         return
     ref = MG.RH.load_reference()
-    for make in (points, levels, norefine, heads, classes, decoder_outputs):
+    for make in (points, levels, norefine, heads, classes, decoder_outputs, geometry):
         if make.__name__ in sys.argv[1:] or not sys.argv[1:]:
             make(ref)
 

@@ -5,7 +5,8 @@ of their constants, so that a rig cannot quietly be held to a looser standard th
 A ``rig`` is a dict with ``sd`` / ``sd64`` (the oracle's fp32 state dict and its .double() copy),
 ``head`` (the HIP head with the same weights, on the device), ``feats`` (host NCHW maps), ``nhwc``
 (the same maps channels-last on the device), ``l2i`` [1,N,4,4] and the fp32 oracle's trace of the
-decoder: ``hs`` [L,Q,1,C], ``init_ref``, ``inter_refs``.
+decoder: ``hs`` [L,Q,1,C], ``init_ref``, ``inter_refs``.  ``pcr`` / ``hw``: the rig's point-cloud range and image
+size where they are not the configs' (rig_pcr, rig_hw).
 
 Reference lines: XFMR:178-214 (decoder loop + refinement), XFMR:346-378 (cross attention),
 HEAD:538-729 (three fusion layers)."""
@@ -17,6 +18,7 @@ from oracle import transcar_oracle as O
 from transcar_amd import configs
 from transcar_amd.detr3d_head import MATRIX_PATHS
 
+# the configs' range and image size, for the rigs that name them; the checks read the rig's (rig_pcr, rig_hw)
 PCR = configs.point_cloud_range
 HW = configs.IMG_SHAPE[:2]
 # One layer on identical inputs; activations are LayerNorm outputs, |x| up to ~5.  On these
@@ -29,6 +31,14 @@ LAYER_MAX_TOL = 3e-4      # max |hip - fp64| (the fp32 oracle reaches 1.6e-4)
 LAYER_MEAN_TOL = 1e-5     # mean |hip - fp64| (the fp32 oracle: 4e-6)
 LAYER_TOL = 1e-4          # radar layers (no sampling: plain linear algebra on O(1) values)
 REF_TOL = 3e-5            # refined reference points (sigmoid of a full-xavier-scale MLP output; the fp32 oracle: 1.2e-5)
+
+
+def rig_pcr(rig):
+    return list(rig.get('pcr', configs.point_cloud_range))
+
+
+def rig_hw(rig):
+    return tuple(rig.get('hw', configs.IMG_SHAPE[:2]))
 
 
 def dev():
@@ -77,7 +87,7 @@ def decoder_layer_truth(rig, lid):
         ref_prev = rig['init_ref'] if lid == 0 else rig['inter_refs'][lid - 1]
         p = 'transformer.decoder.layers.%d.' % lid
         truth = O.decoder_layer(sd64, p, x_prev.permute(1, 0, 2).double(), pos.permute(1, 0, 2).double(),
-                                rig['_feats64'], ref_prev.double(), PCR, rig['l2i'].double(), HW).permute(1, 0, 2)
+                                rig['_feats64'], ref_prev.double(), rig_pcr(rig), rig['l2i'].double(), rig_hw(rig)).permute(1, 0, 2)
         tmp64 = O.reg_branch(sd64, 'reg_branches.%d' % lid, truth)
         new_ref = torch.zeros_like(ref_prev.double())
         new_ref[..., :2] = tmp64[..., :2] + O.inverse_sigmoid(ref_prev.double()[..., :2])
@@ -107,7 +117,7 @@ def decoder_layers_teacher_forced(rig, tile_rows, matrix, title):
         attn_o = ops.sdpa(gpu(q), gpu(k), gpu(vt), matrix_path='f16x2' if matrix == 'f16x2' else 'f32')
         nxt = pv.layers[lid + 1].self_attn.in_proj if lid + 1 < L else None
         hs, ref_out, qk_next, vt_next = ops.decoder_layer_tail(
-            pv.layers[lid], nxt, rig['nhwc'], attn_o, gpu(x_prev), gpu(qe), l2i, gpu(ref_prev), PCR, HW,
+            pv.layers[lid], nxt, rig['nhwc'], attn_o, gpu(x_prev), gpu(qe), l2i, gpu(ref_prev), rig_pcr(rig), rig_hw(rig),
             tile_rows=tile_rows, matrix_path=MATRIX_PATHS[matrix])
         # the same layer: fp32 oracle (from the rig's trace) and fp64 evaluation of the same formula
         truth, truth_ref = decoder_layer_truth(rig, lid)
@@ -201,7 +211,7 @@ def radar_layers_teacher_forced(rig, f36, tok_np, pad_mult, tile_rows, matrix, t
     prev_box = dbg['tmp']
     for r, (sa, sf, rmin, rmax) in enumerate((('', '', 1.0, 2.0), ('2', '_2', 1.0, 2.0), ('3', '_3', 0.5, 1.0))):
         if r == 0:
-            ref = dbg['inter_refs'][-1]
+            ref, PCR = dbg['inter_refs'][-1], rig_pcr(rig)
             cxy = torch.stack([ref[..., 0] * (PCR[3] - PCR[0]) + PCR[0],
                                ref[..., 1] * (PCR[4] - PCR[1]) + PCR[1]], -1)
         else:

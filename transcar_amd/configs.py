@@ -77,7 +77,7 @@ IMG_SHAPE = (928, 1600, 3)
 
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
              num_levels=None, num_heads=None, num_classes=None,
-             num_fusion_layers=None):
+             num_fusion_layers=None, pc_range=None, post_center_range=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -89,7 +89,13 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     num_classes sets the head's and the bbox_coder's (the configs: 10, CFG:54
     and :89; 1 .. 32 -- the coder's is the modulus that turns a score index
     into a label, CODER:54-55); num_fusion_layers sets the depth of the radar
-    fusion stack (the reference builds 3, HEAD:129-171; 1 .. 3)."""
+    fusion stack (the reference builds 3, HEAD:129-171; 1 .. 3); pc_range sets
+    the point-cloud range of the bbox_coder, of every Detr3DCrossAtten and of
+    the assigner together (the configs write one ``point_cloud_range`` into all
+    three, CFG:74, :85, :112; the result then carries ``train_cfg``, as
+    ``train_cfg(pc_range)`` gives it); post_center_range sets the coder's
+    (CFG:84).  The radar filter's range is no config value: the reference
+    writes it as a constant (HEAD:304)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -114,4 +120,29 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     if num_fusion_layers is not None:
         from ._lib import check_num_fusion_layers
         cfg['num_fusion_layers'] = check_num_fusion_layers(num_fusion_layers)
+    if pc_range is not None:
+        pc_range = _range6(pc_range, 'pc_range')
+        layers = cfg['transformer']['decoder']['transformerlayers']
+        layers['attn_cfgs'][1]['pc_range'] = list(pc_range)
+        cfg['bbox_coder']['pc_range'] = list(pc_range)
+        cfg['train_cfg'] = train_cfg(pc_range)
+    if post_center_range is not None:
+        cfg['bbox_coder']['post_center_range'] = _range6(post_center_range, 'post_center_range')
+    return cfg
+
+
+def _range6(r, what):
+    r = [float(v) for v in r]
+    if len(r) != 6 or not all(r[i] < r[i + 3] for i in range(3)):
+        raise ValueError('%s=%r: six values (x0, y0, z0, x1, y1, z1), each lower bound below its upper' % (what, r))
+    return r
+
+
+def train_cfg(pc_range=None):
+    """train_cfg_pts with ``pc_range`` (None: the configs') as its
+    point_cloud_range and the assigner's pc_range."""
+    cfg = copy.deepcopy(train_cfg_pts)
+    if pc_range is not None:
+        cfg['point_cloud_range'] = _range6(pc_range, 'pc_range')
+        cfg['assigner']['pc_range'] = _range6(pc_range, 'pc_range')
     return cfg

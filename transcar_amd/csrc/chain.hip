@@ -1833,7 +1833,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
             const float r = k.ref_last[(size_t)grow * 3 + c];
             const float* pc = k.cam.pc;
             // z stays normalised (HEAD:598 indexes an empty slice)
-            S.cen[row][c] = c < 2 ? __fadd_rn(__fmul_rn(r, pc[3 + c] - pc[c]), pc[c]) : r;
+            S.cen[row][c] = c < 2 ? mul_then_add_rn(r, pc[3 + c] - pc[c], pc[c]) : r;
           }
         }
       }

@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256) void radar_hit_flags_kernel(CompactK p) {
     const float* bx = p.box + row * p.code;
     if (p.cen_from_box) { cx[i] = bx[0]; cy[i] = bx[1]; }        // HEAD:615-617
     else {                                                       // HEAD:543-547
-      cx[i] = __fadd_rn(__fmul_rn(p.ref_last[row * 3 + 0], p.pc[3] - p.pc[0]), p.pc[0]);
-      cy[i] = __fadd_rn(__fmul_rn(p.ref_last[row * 3 + 1], p.pc[4] - p.pc[1]), p.pc[1]);
+      cx[i] = mul_then_add_rn(p.ref_last[row * 3 + 0], p.pc[3] - p.pc[0], p.pc[0]);
+      cy[i] = mul_then_add_rn(p.ref_last[row * 3 + 1], p.pc[4] - p.pc[1], p.pc[1]);
     }
     b3[i] = bx[3]; b6[i] = bx[6]; b7[i] = bx[7];
     any[i] = false;

@@ -448,6 +448,16 @@ __device__ __forceinline__ float sqrt_threshold(float rad) {
   }
   return c;        // not reached for rad in the clamp range [0.5, 2]
 }
+// a * b + c with two roundings (torch: mul, then add).  HIP's __fmul_rn / __fadd_rn are the plain operators, and hipcc
+// contracts a product and a sum into one v_fma_f32 (its default is -ffp-contract=fast-honor-pragmas) unless the pragma
+// forbids it here.  The gate centre of fusion layer 1 is computed with it at every site -- tc_radar_reference_l1 (the
+// operator path, the training stack, the centre the backward re-evaluates the gate from), the chain's radar prologue and
+// the compaction -- so that all of them gate on the same bits.
+__device__ __forceinline__ float mul_then_add_rn(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return p + c;
+}
 __device__ __forceinline__ float sqnorm2(float a, float b) {
   return __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
 }

@@ -177,9 +177,10 @@ __global__ void radar_ref_l1_kernel(const float* ref, Pc6 pcs, float* cxy, float
   const float* pc = pcs.v;
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= M) return;
-  // separate roundings (torch: mul, then add) -- these feed the distance gate
-  const float x = __fadd_rn(__fmul_rn(ref[(size_t)row * 3 + 0], pc[3] - pc[0]), pc[0]);
-  const float y = __fadd_rn(__fmul_rn(ref[(size_t)row * 3 + 1], pc[4] - pc[1]), pc[1]);
+  // separate roundings (torch: mul, then add) -- these feed the distance gate; the chain's radar prologue and the
+  // compaction compute the same centre with the same helper (the backward re-evaluates the forward's gate from this one)
+  const float x = mul_then_add_rn(ref[(size_t)row * 3 + 0], pc[3] - pc[0], pc[0]);
+  const float y = mul_then_add_rn(ref[(size_t)row * 3 + 1], pc[4] - pc[1], pc[1]);
   cxy[(size_t)row * 2 + 0] = x;
   cxy[(size_t)row * 2 + 1] = y;
   addref[(size_t)row * 3 + 0] = x;

@@ -166,6 +166,15 @@ class Detr3DHead(BaseModule):
         self.cls_out_channels = num_classes if use_sigmoid else num_classes + 1
         self.transformer = build_transformer(transformer)
         self.embed_dims = self.transformer.embed_dims
+        # The reference samples the cameras with Detr3DCrossAtten.pc_range (XFMR:366) and de-normalises the boxes with
+        # the coder's; the fused path packs ONE range for both, so a config in which they differ is refused rather than
+        # sampled with the coder's
+        for name, m in self.transformer.named_modules():
+            rng = getattr(m, 'pc_range', None)
+            if rng is not None and [float(v) for v in rng] != [float(v) for v in self.pc_range]:
+                raise ValueError('Detr3DHead: transformer.%s.pc_range %s differs from bbox_coder.pc_range %s; the fused '
+                                 'kernels take one point-cloud range for the camera sampling and the boxes'
+                                 % (name, list(rng), list(self.pc_range)))
         self.assigner = None
         if train_cfg and train_cfg.get('assigner') is not None:
             self.assigner = BBOX_ASSIGNERS.build(train_cfg['assigner'])

@@ -7,6 +7,8 @@ runs in the HIP library (fp32, eval mode).
   Detr3DTransformerDecoder  XFMR:142-214
   Detr3DCrossAtten          XFMR:217-378  (+ feature_sampling XFMR:381-422)
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -35,19 +37,37 @@ def reg_branch_forward(branch, x):
 
 
 class FeatureCache:
-    """NCHW -> NHWC conversion of the FPN maps, done once per forward and
-    shared by the 6 decoder layers (``value`` is the same list object)."""
+    """NCHW -> NHWC conversion of the FPN maps, done once per decoder forward
+    and shared by its 6 layers (``value`` is the same list object in all of
+    them).  Nothing is kept between forwards, and a Detr3DCrossAtten called on
+    its own converts the maps it is given: a key of addresses, versions and
+    shapes also matches the NEXT frame's maps whenever the allocator hands
+    out the same blocks again (or a captured backbone writes into the same
+    tensors), and the decoder then sampled the frame before."""
 
     def __init__(self):
-        self._key = None
+        self._depth = 0
+        self._src = None
         self._nhwc = None
 
+    @contextlib.contextmanager
+    def one_forward(self):
+        self._depth += 1
+        try:
+            yield
+        finally:
+            self._depth -= 1
+            if self._depth == 0:
+                self._src = self._nhwc = None
+
     def get(self, mlvl_feats):
-        key = tuple((f.data_ptr(), f._version, tuple(f.shape))
-                    for f in mlvl_feats)
-        if key != self._key:
+        if self._depth == 0:
+            return [ops.to_nhwc(f) for f in mlvl_feats]
+        # the tensors themselves are held until the forward ends: same objects, same maps
+        if self._src is None or len(self._src) != len(mlvl_feats) or \
+                any(a is not b for a, b in zip(self._src, mlvl_feats)):
             self._nhwc = [ops.to_nhwc(f) for f in mlvl_feats]
-            self._key = key
+            self._src = list(mlvl_feats)
         return self._nhwc
 
 
@@ -129,6 +149,11 @@ class Detr3DTransformerDecoder(TransformerLayerSequence):
 
     def forward(self, query, *args, reference_points=None, reg_branches=None,
                 **kwargs):
+        with _FEATS.one_forward():
+            return self._forward(query, *args, reference_points=reference_points, reg_branches=reg_branches, **kwargs)
+
+    def _forward(self, query, *args, reference_points=None, reg_branches=None,
+                 **kwargs):
         output = query
         intermediate, intermediate_reference_points = [], []
         for lid, layer in enumerate(self.layers):

@@ -259,13 +259,16 @@ def make_feats(level_shapes='res101', seed=1, batch=1, num_cams=6,
     return feats
 
 
-def make_img_metas(batch=1, lidar2img=None, radar=None):
+def make_img_metas(batch=1, lidar2img=None, radar=None, img_shape=None):
+    """img_shape: (H, W, 3) of every camera image (None: the configs' IMG_SHAPE)."""
+    if img_shape is None:
+        img_shape = IMG_SHAPE
     if lidar2img is None:
         lidar2img = make_lidar2img()
     metas = []
     for b in range(batch):
         m = dict(lidar2img=[lidar2img[i] for i in range(lidar2img.shape[0])],
-                 img_shape=[IMG_SHAPE] * lidar2img.shape[0],
+                 img_shape=[tuple(img_shape)] * lidar2img.shape[0],
                  sample_idx='synthetic-%d' % b,
                  box_type_3d=None)
         if radar is not None:
