@@ -172,10 +172,9 @@ typedef struct {
 
 /* per-call options of tc_head_forward (NULL = all defaults = the reference's eval forward) */
 typedef struct {
-  int chain_tile_rows;      /* rows of a workgroup's tile in the fused row chains: 0 = automatic
-                               (4 up to 1024 rows per launch, 8 up to 2048, 16 up to 4096, 32 beyond -- 16 when
-                               matrix_path is TC_MATRIX_F32), 4, 8, 16 or 32 (32: f16x2 matrix path only; one
-                               workgroup of 8 waves per CU, activations held in LDS as two f16 planes) */
+  int chain_tile_rows;      /* rows of a workgroup's tile in the fused row chains: 0 = automatic (by the rows of the
+                               launch and matrix_path: tc_chain_tile_rows answers), 4, 8, 16 or 32 (32: f16x2 matrix
+                               path only; one workgroup of 8 waves per CU, activations held in LDS as two f16 planes) */
   int unfused;              /* 1: operator-by-operator launch sequence (~160 launches), the
                                in-tree cross-check of the fused chains */
   int last_level_cls_only;  /* 1 (inference opt-in): final_cls / final_cls2 are not evaluated --
@@ -249,6 +248,10 @@ typedef struct {
 /* ---- library ---- */
 int tc_abi_version(void);
 const char* tc_last_error(void);
+/* The tile height (4, 8, 16 or 32) the row chains use for a launch over `rows` rows with chain_tile_rows = tile_rows and
+ * this matrix_path -- the one rule every chain launch and the choice of the attention core follow -- or a negative value
+ * with tc_last_error set for arguments a forward would refuse.  Host only: touches no device. */
+int tc_chain_tile_rows(int rows, int tile_rows, int matrix_path);
 /* number of HIP devices visible; does not initialise a context */
 int tc_device_count(void);
 

@@ -46,24 +46,44 @@ def centres_of(dbg):
 _KERNEL = {}
 
 
-def kernel_case(NC, seeds=None):
-    """The CPU side of the kernel case at NC classes: the oracle's head (KQ queries, tiny maps) on two radar frames of
-    60 points near the boxes its decoder predicts.  -> dict(sd_np, feats_np, samples=[(want, dbg, f36), (...)])."""
-    key = (NC, seeds)
+def _oracle_head(sd, feats_np, frame, num_layers):
+    if num_layers == 6:
+        return R.oracle_head(sd, feats_np, frame)
+    return O.head_forward(sd, [torch.from_numpy(f) for f in feats_np], torch.from_numpy(R.DEFAULT.lidar2img()).float()[None],
+                          R.HW, O.build_radar_features(frame), list(R.PCR), num_layers=num_layers, return_debug=True)
+
+
+def kernel_case(NC, seeds=None, num_layers=6, num_points=1):
+    """The CPU side of the kernel case at NC classes: the oracle's head (KQ queries, tiny maps, num_layers decoder layers,
+    num_points sampling points) on two radar frames of 60 points near the boxes its decoder predicts.
+    -> dict(sd_np, feats_np, samples=[(want, dbg, f36), (...)])."""
+    key = (NC, seeds, num_layers, num_points)
     if key not in _KERNEL:
         with torch.no_grad():
-            sd_np = state_dict(NC, KQ)
+            sd_np = synth.make_state_dict(seed=3, num_layers=num_layers, **R.state_dict_kw(num_classes=NC, num_query=KQ, num_points=num_points))
             sd = O.to_torch_sd(sd_np)
             feats_np = synth.make_feats('tiny', seed=1, smooth=R.SMOOTH)
-            _, dbg0 = R.oracle_head(sd, feats_np, synth.make_radar_frame(seed=2, n_per_radar=12))
+            _, dbg0 = _oracle_head(sd, feats_np, synth.make_radar_frame(seed=2, n_per_radar=12), num_layers)
             centres = centres_of(dbg0)
             samples = []
             for s in (seeds or KERNEL_SEEDS):
                 frame = synth.make_radar_frame(seed=s, n_per_radar=12, centres=centres)
-                want, dbg = R.oracle_head(sd, feats_np, frame)
+                want, dbg = _oracle_head(sd, feats_np, frame, num_layers)
                 samples.append((want, dbg, O.build_radar_features(frame)))
         _KERNEL[key] = dict(sd_np=sd_np, feats_np=feats_np, samples=samples)
     return _KERNEL[key]
+
+
+def one_layer_head(T, NC, num_points=1):
+    """The eval-mode head of NC classes and KQ queries with ONE decoder layer (its launch then carries the whole radar
+    encoder program, not a half), with kernel_case's seeded weights."""
+    from transcar_amd import configs
+    cfg = configs.head_cfg(**R.variant_kw(num_classes=NC, num_query=KQ, num_points=num_points))
+    cfg['transformer']['decoder']['num_layers'] = 1
+    h = T.build_head(cfg)
+    sd_np = kernel_case(NC, num_layers=1, num_points=num_points)['sd_np']
+    h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
+    return h.to(R.dev()).eval()
 
 
 def hit_rows(case):

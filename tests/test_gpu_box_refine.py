@@ -123,7 +123,7 @@ def test_training_iteration_norefine_gradients_match_reference(T):
     R.check_training_iteration(_g8_frame(), 'g8_train_grads_norefine.npz', 'fused norefine', with_box_refine=False)
 
 
-@pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (8, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
+@pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (8, 'f32'), (16, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
 def test_train_mode_decoder_norefine_matches_reference_formula(T, rows, matrix):
     """(the prologue's initial reference: the references are it to 1e-6, and bit for bit each other)"""
     R.check_train_mode_decoder(_g8_frame(), rows, matrix, refs_atol=1e-6, with_box_refine=False)

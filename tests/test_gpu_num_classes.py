@@ -105,8 +105,42 @@ def _g5_frame():
         synth.make_radar_frame(seed=2, n_per_radar=51, centres=gold['radar_centres'])
 
 
-@pytest.mark.parametrize('path', sorted(NC.PATHS))
+ONE_LAYER = 'one-decoder-layer-'
+
+
+def _one_layer_head_against_oracle(T, path):
+    """A fusion head with ONE decoder layer: that layer's launch carries the whole radar encoder program (chain.hip
+    launch_dual part 0), which no six-layer head asks for; 'p5-': with num_points = 5, the generic (MP) kernels.  The
+    kernel case (37 queries x 2 samples x 64 tokens: 74 rows), free-running, per sample against the oracle with
+    check_against_oracle's bounds (decoder states on the f16x2 path at P = 5: HS_TOL_F16X2, as test_head_points_paths)."""
+    from transcar_amd import ops
+    from transcar_amd.detr3d_head import head_options
+    P = 5 if path.startswith('p5-') else 1
+    path = path[3:] if P == 5 else path
+    case = NC.kernel_case(23, num_layers=1, num_points=P)
+    assert min(min(r) for r in NC.hit_rows(case)) >= NC.MIN_HIT_ROWS, NC.hit_rows(case)
+    head = NC.one_layer_head(T, 23, P)
+    assert head.weights_struct().num_points == P
+    assert head.weights_struct().num_layers == 1 and head.weights_struct().num_radar_layers == 3
+    feats = [gpu(np.concatenate([f, f], 0)) for f in case['feats_np']]
+    tok_np, pad_mult = RD.pack_tokens([f36 for _, _, f36 in case['samples']], T=NC.KT)
+    metas = synth.make_img_metas(2, synth.make_lidar2img())
+    outs = head.forward_nhwc(ops.to_nhwc_levels(feats), ops.lidar2img_tensor(metas, R.dev()), metas[0]['img_shape'][0][:2],
+                             gpu(tok_np), pad_mult, aux=True, options=head_options(**NC.PATHS[path]))
+    torch.cuda.synchronize()
+    assert outs['all_cls_scores'].shape == (3, 2, NC.KQ, 23) and outs['aux']['inter_states'].shape == (1, 2, NC.KQ, 256)
+    assert torch.isfinite(outs['all_cls_scores']).all() and torch.isfinite(outs['all_bbox_preds']).all()
+    for b, (want, dbg, _) in enumerate(case['samples']):
+        one = {k: outs[k][:, b:b + 1] for k in ('all_cls_scores', 'all_bbox_preds')}
+        one['aux'] = {k: outs['aux'][k][:, b:b + 1] for k in ('inter_references', 'inter_states', 'radar_hit_counts')}
+        R.check_against_oracle(one, want, dbg, R.HS_TOL_F16X2 if P == 5 and path.startswith('f16x2') else R.E2E_TOL)
+
+
+@pytest.mark.parametrize('path', sorted(NC.PATHS) + [ONE_LAYER + p for p in sorted(NC.PATHS)] +
+                         [ONE_LAYER + 'p5-' + p for p in sorted(NC.PATHS)])
 def test_head_23_classes_paths_oracle_and_golden(T, path):
+    if path.startswith(ONE_LAYER):
+        return _one_layer_head_against_oracle(T, path[len(ONE_LAYER):])
     gold, feats_np, frame = _g5_frame()
     head, sd = R.shared_head(T, num_classes=23)
     want, dbg = R.oracle_head(sd, feats_np, frame, key='num_classes 23 golden')      # (the paths share one oracle forward)

@@ -131,7 +131,7 @@ def test_training_iteration_points_gradients_match_reference(T):
     R.check_training_iteration(_g8_frame(), 'g8_train_grads_p5.npz', 'fused p5', num_points=5)
 
 
-@pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (8, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
+@pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (8, 'f32'), (16, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
 def test_train_mode_decoder_points_matches_reference_formula(T, rows, matrix):
     R.check_train_mode_decoder(_g8_frame(), rows, matrix, num_points=5)
 

@@ -168,6 +168,43 @@ def test_tuning_knob_validates_without_gpu():
     assert r.returncode != 0 and 'TRANSCAR_CHAIN_ROWS' in r.stderr
 
 
+#: tc_chain_tile_rows(rows, tile_rows, matrix_path), written out: rows -> tile_rows -> (AUTO, F32, F16X2); None = refused
+_X = None
+_TILE_ROWS = {
+    1:    {0: (4, 4, 4),    4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+    1024: {0: (4, 4, 4),    4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+    1025: {0: (8, 8, 8),    4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+    2048: {0: (8, 8, 8),    4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+    2049: {0: (16, 16, 16), 4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+    4096: {0: (16, 16, 16), 4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+    4097: {0: (32, 16, 32), 4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+    8100: {0: (32, 16, 32), 4: (4, 4, 4), 8: (8, 8, 8), 16: (16, 16, 16), 32: (32, _X, 32)},
+}
+
+
+def test_chain_tile_rows_is_the_one_rule_without_gpu():
+    """tc_chain_tile_rows: the tile height every chain launch (and the attention core's choice) follows, against the
+    table above; 32 rows on the f32 path, another tile_rows and another matrix_path are refused by name."""
+    lib = T.lib()
+    paths = (_lib.TC_MATRIX_AUTO, _lib.TC_MATRIX_F32, _lib.TC_MATRIX_F16X2)
+    assert paths == (0, 1, 2) and sorted(_TILE_ROWS) == [1, 1024, 1025, 2048, 2049, 4096, 4097, 8100]
+    for rows, by_opt in _TILE_ROWS.items():
+        assert sorted(by_opt) == [0, 4, 8, 16, 32]
+        for opt, want in by_opt.items():
+            for mp, w in zip(paths, want):
+                got = lib.tc_chain_tile_rows(rows, opt, mp)
+                if w is None:
+                    assert got < 0 and b'f16x2' in lib.tc_last_error(), (rows, opt, mp, got)
+                else:
+                    assert got == w, (rows, opt, mp, got)
+    assert _TILE_ROWS[4097][0] == (32, 16, 32) and _TILE_ROWS[4096][0][0] == 16
+    assert lib.tc_chain_tile_rows(900, 5, 0) < 0 and b'tile_rows' in lib.tc_last_error()
+    assert lib.tc_chain_tile_rows(900, 0, 3) < 0 and b'matrix_path' in lib.tc_last_error()
+    assert _lib.chain_tile_rows(8100) == 32 and _lib.chain_tile_rows(8100, 0, _lib.TC_MATRIX_F32) == 16
+    with pytest.raises(_lib.TransCARHipError):
+        _lib.chain_tile_rows(900, 32, _lib.TC_MATRIX_F32)
+
+
 def test_entry_points_refuse_bad_arguments_without_gpu():
     """Error behaviour of the C ABI: every call below fails on its argument check -- before anything is launched, so
     no GPU is needed -- with a non-zero code and a message that names the argument (tc_last_error)."""

@@ -91,7 +91,7 @@ def main():
         lib.tc_debug_wg_spans.argtypes = [C.c_void_p]
         assert lib.tc_debug_wg_spans(wg.ctypes.data) == 0
         rows = batch * head.num_query
-        R = rows_env or (4 if rows <= 1024 else 8 if rows <= 2048 else 16)
+        R = L.chain_tile_rows(rows, rows_env)
         nb = min(-(-rows // R), 1024)
         w = wg[:nb]
         t0 = w[:, 0].min()

@@ -231,6 +231,7 @@ _i, _f, _sz, _vp = C.c_int, C.c_float, C.c_size_t, C.c_void_p
 SIGNATURES = {
     'tc_abi_version': (_i, []),
     'tc_last_error': (C.c_char_p, []),
+    'tc_chain_tile_rows': (_i, [_i, _i, _i]),
     'tc_device_count': (_i, []),
     'tc_nchw_to_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'tc_nchw_to_nhwc_levels': (_i, [_P(_vp), _P(_vp), _i, _i, _i, _P(_i), _P(_i), _vp]),
@@ -386,6 +387,14 @@ def check(rc, what):
     if rc != 0:
         msg = lib().tc_last_error().decode('utf-8', 'replace')
         raise TransCARHipError('%s failed (status %d): %s' % (what, rc, msg))
+
+
+def chain_tile_rows(rows, tile_rows=0, matrix_path=TC_MATRIX_AUTO):
+    """The tile height the row chains use for `rows` rows per launch (tc_chain_tile_rows: the library's one rule)."""
+    r = lib().tc_chain_tile_rows(int(rows), int(tile_rows), int(matrix_path))
+    if r < 0:
+        check(r, 'tc_chain_tile_rows')
+    return r
 
 
 def f6(values):

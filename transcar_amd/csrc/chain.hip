@@ -2870,19 +2870,33 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
   k.early_n = early;
 }
 
+// once per device: `kernel` may take `lds` bytes of dynamic LDS
+template <class Kernel>
+int allow_lds(DeviceOnce& once, Kernel kernel, size_t lds) {
+  if (const int dev = once.need(); dev >= 0) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { set_error("chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+    once.done(dev);
+  }
+  return 0;
+}
+
+// tiles of 16 rows and more read a weight copy of their own behind the packed view (resolve_program: w16_delta)
+int need_packed16(int R, size_t w16_delta, const char* what, const char* packer = "tc_head_pack_weights") {
+  TC_REQUIRE(R < 16 || w16_delta != 0, "%s: 16- / 32-row tiles need weights from a %s view (packed16_delta is 0)", what, packer);
+  return 0;
+}
+
+// a LayerNorm's parameters as a weight pair of the step tables
+tc_linear ln_pair(const tc_lnorm& n) { return tc_linear{n.g, n.b}; }
+
 template <int RA, int RB, int PROGB, int MM = 0, bool PRE = false, bool MP = false>
 int launch_dual_r(const ChainK& ka_, const ChainK& kb_, hipStream_t s, const char* what) {
   constexpr size_t lds = chain_lds_bytes<RA, PROG_DECODER>() > chain_lds_bytes<RB, PROGB>() ? chain_lds_bytes<RA, PROG_DECODER>() : chain_lds_bytes<RB, PROGB>();
   static DeviceOnce once;
-  if (const int once_dev = once.need(); once_dev >= 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_dual_kernel<RA, RB, PROGB, MM, PRE, MP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    once.done(once_dev);
-  }
+  if (const int rc = allow_lds(once, chain_dual_kernel<RA, RB, PROGB, MM, PRE, MP>, lds)) return rc;
   ChainK ka = ka_, kb = kb_;
-  TC_REQUIRE((RA < 16 || ka.w16_delta != 0) && (RB < 16 || kb.w16_delta != 0),
-             "%s: 16- / 32-row tiles need weights from a tc_head_pack_weights view (packed16_delta is 0)", what);
+  if (const int rc = need_packed16(RA, ka.w16_delta, what) | need_packed16(RB, kb.w16_delta, what)) return rc;
   Recs<rec_cap(PROG_DECODER), nw_of(RA)> ra;
   Recs<rec_cap(PROGB), nw_of(RB)> rb;
   resolve_program<RA, PROG_DECODER, MM>(ka, ra.s);
@@ -2895,20 +2909,13 @@ int launch_dual_r(const ChainK& ka_, const ChainK& kb_, hipStream_t s, const cha
 
 template <int R, int PROG, bool DROP = false, int MM = 0, bool PRE = false, bool MP = false>
 int launch_r(const ChainK& k_, hipStream_t s, const char* what) {
+  constexpr size_t lds = chain_lds_bytes<R, PROG>();
   static DeviceOnce once;
-  if (const int once_dev = once.need(); once_dev >= 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<R, PROG, DROP, MM, PRE, MP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)chain_lds_bytes<R, PROG>());
-    if (e != hipSuccess) { set_error("chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    once.done(once_dev);
-  }
+  if (const int rc = allow_lds(once, chain_kernel<R, PROG, DROP, MM, PRE, MP>, lds)) return rc;
   ChainK k = k_;
-  TC_REQUIRE(R < 16 || k.w16_delta != 0,
-             "%s: 16- / 32-row tiles need weights from a tc_head_pack_weights view (packed16_delta is 0)", what);
+  if (const int rc = need_packed16(R, k.w16_delta, what)) return rc;
   Recs<rec_cap(PROG), nw_of(R)> recs;
   resolve_program<R, PROG, MM>(k, recs.s);
-  constexpr size_t lds = chain_lds_bytes<R, PROG>();
   hipLaunchKernelGGL((chain_kernel<R, PROG, DROP, MM, PRE, MP>), dim3((k.M + R - 1) / R), dim3(nw_of(R) * 64), lds, s,
                      static_cast<const ChainDev&>(k), recs);
   return check_launch(what);
@@ -2925,61 +2932,44 @@ void init_k(ChainK& k) {
 #endif
 }
 
-// Row-tile height (measured, bench.py --pair 1/2/4/8): 4 rows while that gives about one
-// workgroup per CU (one frame: 225 workgroups), 8 rows up to two frames per launch, 16 beyond.
-// All three run two workgroups per CU: the 16-row tiles since round 2 (four LDS units = 76 KB,
-// one weight buffer refilled in place = 239 VGPRs; before: 120 KB / 304 VGPRs, one per CU, and
-// they lost to 8 rows everywhere).  4 frames per launch x 3 lanes: 4214 (8 rows) -> 4597 frames/s.
-// The height is a per-call argument (tc_head_options.chain_tile_rows / tile_rows of
-// tc_decoder_layer_tail_fwd): no process-global state.
-// Round 5: 32 rows (one workgroup of 8 waves per CU, activations as planes) once the 16-row tiles would need two
-// workgroups per CU (more than 4096 rows: five frames or more) and the matrix path is not pinned to f32: the CU then pulls
-// a layer's weights through its L2 port once per 32 rows without relying on two workgroups sharing the L1 in lockstep
-// (nine frames: decoder chain 110 -> 102 us, radar chain 233 -> 214 us; profiles/r5_*).
-int tile_rows(const ChainK& k) {
-  if (k.tile_rows) return k.tile_rows;
-  return k.M <= 1024 ? 4 : k.M <= 2048 ? 8 : (k.M > 4096 && k.matrix_path != TC_MATRIX_F32) ? 32 : 16;
+// a run-time variant as a compile-time one: f(std::integral_constant<int, variant>); tile_variant's refusal passes through
+template <class F>
+int with_variant(int v, F&& f) {
+  switch (v) {
+    case TV_4: return f(std::integral_constant<int, TV_4>{});
+    case TV_8: return f(std::integral_constant<int, TV_8>{});
+    case TV_16_F32: return f(std::integral_constant<int, TV_16_F32>{});
+    case TV_16_F16X2: return f(std::integral_constant<int, TV_16_F16X2>{});
+    case TV_32_F16X2: return f(std::integral_constant<int, TV_32_F16X2>{});
+    default: return -1;
+  }
 }
 
-// The matrix path of the 16-row tiles (tc_head_options.matrix_path): automatic = the two-plane f16 form on the
-// matrix cores (measured: DESIGN.md section 5 "Round 4"); TC_MATRIX_F32 keeps the exact fp32 FMA chains of
-// v_mfma_f32_16x16x4_f32.  4- and 8-row tiles always compute in fp32 (their item loops are bound by the weight
-// stream, and both copies are 4 bytes per weight).
-bool use_f16x2(const ChainK& k) { return k.matrix_path != TC_MATRIX_F32; }
-
+// PRE (the camera pre-gather, round 6) exists for the decoder program on the f16x2 path only: 16 and 32 rows
 template <int PROG, bool MP = false>
 int launch_rows(const ChainK& k, hipStream_t s, const char* what) {
-  const int rows = tile_rows(k);
-  if (rows == 4) return launch_r<4, PROG, false, 0, false, MP>(k, s, what);
-  if (rows == 8) return launch_r<8, PROG, false, 0, false, MP>(k, s, what);
-  if (rows == 32) {
-    TC_REQUIRE(use_f16x2(k), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
-    if constexpr (PROG == PROG_DECODER) { if (k.pre != nullptr) return launch_r<32, PROG, false, 1, true, MP>(k, s, what); }
-    return launch_r<32, PROG, false, 1, false, MP>(k, s, what);
-  }
-  if constexpr (PROG == PROG_DECODER) { if (k.pre != nullptr && use_f16x2(k)) return launch_r<16, PROG, false, 1, true, MP>(k, s, what); }
-  if (use_f16x2(k)) return launch_r<16, PROG, false, 1, false, MP>(k, s, what);
-  return launch_r<16, PROG, false, 0, false, MP>(k, s, what);
+  return with_variant(tile_variant(k.M, k.tile_rows, k.matrix_path, what), [&](auto V) {
+    constexpr int R = variant_rows(V), MM = variant_mm(V);
+    if constexpr (PROG == PROG_DECODER && MM == 1) { if (k.pre != nullptr) return launch_r<R, PROG, false, MM, true, MP>(k, s, what); }
+    return launch_r<R, PROG, false, MM, false, MP>(k, s, what);
+  });
 }
+
+// train-mode dropout of the decoder program has its own instantiations -- 4- and 8-row tiles, and the 16- / 32-row tiles
+// of the f16x2 path (several frames per launch: the trainer's batched look-ahead of the frozen decoder, round 4).
+// No f32 16-row dropout kernel: 8 rows.
+constexpr int drop_variant(int v) { return v == TV_16_F32 ? TV_8 : v; }
 
 // the decoder program; MP: num_points > 1 (chain_body)
 template <bool MP>
 int launch_decoder(const ChainK& k, hipStream_t s, const char* what) {
-  if (k.drop.thr != 0) {            // train-mode dropout: its own instantiations -- 4- and 8-row tiles, and the
-    //                                  16-row tiles of the f16x2 path (several frames per launch: the trainer's
-    //                                  batched look-ahead of the frozen decoder, round 4)
-    TC_REQUIRE((unsigned long long)(k.drop.rows_per_sample ? k.drop.rows_per_sample : k.M) * 512ull < (1ull << 32),
-               "decoder_chain: dropout index space");
-    const int rows = tile_rows(k);
-    if (rows == 32) {
-      TC_REQUIRE(use_f16x2(k), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
-      return launch_r<32, PROG_DECODER, true, 1, false, MP>(k, s, what);
-    }
-    if (rows == 16 && use_f16x2(k)) return launch_r<16, PROG_DECODER, true, 1, false, MP>(k, s, what);
-    return rows == 4 ? launch_r<4, PROG_DECODER, true, 0, false, MP>(k, s, what)
-                     : launch_r<8, PROG_DECODER, true, 0, false, MP>(k, s, what);
-  }
-  return launch_rows<PROG_DECODER, MP>(k, s, what);
+  if (k.drop.thr == 0) return launch_rows<PROG_DECODER, MP>(k, s, what);
+  TC_REQUIRE((unsigned long long)(k.drop.rows_per_sample ? k.drop.rows_per_sample : k.M) * 512ull < (1ull << 32),
+             "decoder_chain: dropout index space");
+  return with_variant(tile_variant(k.M, k.tile_rows, k.matrix_path, what), [&](auto V) {
+    constexpr int W = drop_variant(V);
+    return launch_r<variant_rows(W), PROG_DECODER, true, variant_mm(W), false, MP>(k, s, what);
+  });
 }
 
 // ---- PROG_DECODER_HEADS: levels x row tiles in one launch; workgroup (level, tile) walks the level's record sequence ----
@@ -2998,7 +2988,7 @@ ChainK heads_level_k(const DecoderHeadsArgs& a, int l) {
   k.program = PROG_DECODER_HEADS; k.M = a.M; k.Q = a.M; k.code = a.code; k.ncls = a.ncls; k.has_next = 1;
   k.w16_delta = a.w16_delta; k.matrix_path = a.matrix_path; k.range_status = a.range_status;
   const tc_cls_branch& c = a.cls[l]; const tc_reg_branch& g = a.reg[l];
-  k.pairs[0] = c.l0; k.pairs[1] = tc_linear{c.n1.g, c.n1.b}; k.pairs[2] = c.l3; k.pairs[3] = tc_linear{c.n4.g, c.n4.b};
+  k.pairs[0] = c.l0; k.pairs[1] = ln_pair(c.n1); k.pairs[2] = c.l3; k.pairs[3] = ln_pair(c.n4);
   k.pairs[4] = c.l6; k.pairs[5] = g.l0; k.pairs[6] = g.l2; k.pairs[7] = g.l4;
   k.g[G_HS] = const_cast<float*>(a.hs) + (size_t)l * a.M * 256; k.g_ld[G_HS] = 256;
   k.g[G_CLS] = a.all_cls + (size_t)l * a.M * a.ncls; k.g_ld[G_CLS] = a.ncls;
@@ -3013,13 +3003,8 @@ int launch_heads_r(const DecoderHeadsArgs& a, hipStream_t s) {
   const char* what = "chain(decoder heads)";
   constexpr size_t lds = chain_lds_bytes<R, PROG_DECODER_HEADS>();
   static DeviceOnce once;
-  if (const int once_dev = once.need(); once_dev >= 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_heads_kernel<R, MM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    once.done(once_dev);
-  }
-  TC_REQUIRE(R < 16 || a.w16_delta != 0, "%s: 16- / 32-row tiles need weights from a tc_decoder_heads_pack view", what);
+  if (const int rc = allow_lds(once, chain_heads_kernel<R, MM>, lds)) return rc;
+  if (const int rc = need_packed16(R, a.w16_delta, what, "tc_decoder_heads_pack")) return rc;
   HeadsRecs<nw_of(R)> recs;
   memset(&recs, 0, sizeof(recs));
   ChainK k0;
@@ -3039,26 +3024,52 @@ int launch(const ChainK& k, hipStream_t s, const char* what) {
     case PROG_DECODER:
       return generic_xattn(k) ? launch_decoder<true>(k, s, what) : launch_decoder<false>(k, s, what);
     case PROG_RADAR: return launch_rows<PROG_RADAR>(k, s, what);
-    // training forward: 4-row tiles up to 1024 rows (one frame per GPU, CFG:188), 8 beyond; always the DROP
-    // instantiation (thr 0 keeps everything)
+    // training forward and backward: 4- or 8-row tiles, set by launch_radar_chain / launch_radar_chain_bwd (one frame
+    // per GPU, CFG:188, runs 4); always the DROP instantiation (thr 0 keeps everything)
     case PROG_RADAR_TRAIN:
       TC_REQUIRE((unsigned long long)k.M * 512ull < (1ull << 32), "radar_train: dropout index space");
-      return tile_rows(k) == 4 ? launch_r<4, PROG_RADAR_TRAIN, true>(k, s, what)
-                               : launch_r<8, PROG_RADAR_TRAIN, true>(k, s, what);
+      return k.tile_rows == 4 ? launch_r<4, PROG_RADAR_TRAIN, true>(k, s, what)
+                              : launch_r<8, PROG_RADAR_TRAIN, true>(k, s, what);
     case PROG_RADAR_ENC_TRAIN: return launch_r<4, PROG_RADAR_ENC_TRAIN>(k, s, what);
     case PROG_RADAR_BWD:
       TC_REQUIRE((unsigned long long)k.M * 512ull < (1ull << 32), "radar_bwd: dropout index space");
-      return tile_rows(k) == 4 ? launch_r<4, PROG_RADAR_BWD, true>(k, s, what)
-                               : launch_r<8, PROG_RADAR_BWD, true>(k, s, what);
+      return k.tile_rows == 4 ? launch_r<4, PROG_RADAR_BWD, true>(k, s, what)
+                              : launch_r<8, PROG_RADAR_BWD, true>(k, s, what);
     // the prologue runs once per checkpoint on Q rows (tc_head_pack_weights); stand-alone radar
     // encoders take the fewest workgroups (16-row tiles): 225 + 64 workgroups of 4-row tiles
     // did not fit 256 CUs next to a decoder layer
     case PROG_PROLOGUE: return launch_r<4, PROG_PROLOGUE>(k, s, what);
-    default: return use_f16x2(k) ? launch_r<16, PROG_RADAR_ENC, false, 1>(k, s, what) : launch_r<16, PROG_RADAR_ENC>(k, s, what);
+    default: return k.matrix_path != TC_MATRIX_F32 ? launch_r<16, PROG_RADAR_ENC, false, 1>(k, s, what) : launch_r<16, PROG_RADAR_ENC>(k, s, what);
   }
 }
 
 }  // namespace
+
+// Row-tile height (measured, bench.py --pair 1/2/4/8): 4 rows while that gives about one
+// workgroup per CU (one frame: 225 workgroups), 8 rows up to two frames per launch, 16 beyond.
+// All three run two workgroups per CU: the 16-row tiles since round 2 (four LDS units = 76 KB,
+// one weight buffer refilled in place = 239 VGPRs; before: 120 KB / 304 VGPRs, one per CU, and
+// they lost to 8 rows everywhere).  4 frames per launch x 3 lanes: 4214 (8 rows) -> 4597 frames/s.
+// The height is a per-call argument (tc_head_options.chain_tile_rows / tile_rows of
+// tc_decoder_layer_tail_fwd): no process-global state.
+// Round 5: 32 rows (one workgroup of 8 waves per CU, activations as planes) once the 16-row tiles would need two
+// workgroups per CU (more than 4096 rows: five frames or more) and the matrix path is not pinned to f32: the CU then pulls
+// a layer's weights through its L2 port once per 32 rows without relying on two workgroups sharing the L1 in lockstep
+// (nine frames: decoder chain 110 -> 102 us, radar chain 233 -> 214 us; profiles/r5_*).
+// The matrix path of the 16-row tiles (tc_head_options.matrix_path): automatic = the two-plane f16 form on the
+// matrix cores (measured: DESIGN.md section 5 "Round 4"); TC_MATRIX_F32 keeps the exact fp32 FMA chains of
+// v_mfma_f32_16x16x4_f32.  4- and 8-row tiles always compute in fp32 (their item loops are bound by the weight
+// stream, and both copies are 4 bytes per weight).
+int tile_variant(int rows, int tile_rows, int matrix_path, const char* what) {
+  TC_REQUIRE(tile_rows == 0 || tile_rows == 4 || tile_rows == 8 || tile_rows == 16 || tile_rows == 32,
+             "%s: tile_rows=%d (0 = automatic, 4, 8, 16 or 32)", what, tile_rows);
+  TC_REQUIRE(matrix_path >= TC_MATRIX_AUTO && matrix_path <= TC_MATRIX_F16X2,
+             "%s: matrix_path=%d (0 automatic, 1 fp32 MFMA, 2 two-plane f16 MFMA)", what, matrix_path);
+  const bool f16x2 = matrix_path != TC_MATRIX_F32;
+  const int r = tile_rows ? tile_rows : rows <= 1024 ? 4 : rows <= 2048 ? 8 : (rows > 4096 && f16x2) ? 32 : 16;
+  TC_REQUIRE(r != 32 || f16x2, "%s: 32-row tiles exist on the f16x2 matrix path only", what);
+  return r == 4 ? TV_4 : r == 8 ? TV_8 : r == 32 ? TV_32_F16X2 : f16x2 ? TV_16_F16X2 : TV_16_F32;
+}
 
 #ifdef TC_CHAIN_STAMPS
 extern "C" int tc_debug_chain_stamps(long long* host_out) {
@@ -3106,6 +3117,16 @@ extern "C" int tc_debug_diag_build() { return 2; }
 
 void fill_camk(const CamSampleArgs& a, CamK& p);   // cam_sample.hip
 
+// the RADAR_PAIRS weight pairs of one fusion layer: linear weights from `w`, LayerNorm parameters from `n` (the backward
+// reads transposed linear weights and the forward's own LayerNorm parameters)
+static void fill_radar_pairs(tc_linear* p, const tc_radar_layer& w, const tc_radar_layer& n) {
+  p[0] = w.attn.in_proj; p[1] = w.attn.out_proj; p[2] = ln_pair(n.norm2);
+  p[3] = w.linear1; p[4] = w.linear2; p[5] = ln_pair(n.norm3);
+  p[6] = w.final_cls.l0; p[7] = ln_pair(n.final_cls.n1); p[8] = w.final_cls.l3;
+  p[9] = ln_pair(n.final_cls.n4); p[10] = w.final_cls.l6;
+  p[11] = w.final_reg.l0; p[12] = w.final_reg.l2; p[13] = w.final_reg.l4;
+}
+
 int launch_prologue(const PrologueArgs& a, hipStream_t s) {
   ChainK k;
   init_k(k);
@@ -3136,11 +3157,11 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   const tc_decoder_layer& w = *a.w;
   const tc_pos_encoder& pe = w.position_encoder;
   k.pairs[0] = w.self_attn.in_proj; k.pairs[1] = w.self_attn.out_proj;
-  k.pairs[2] = tc_linear{w.norm0.g, w.norm0.b};
+  k.pairs[2] = ln_pair(w.norm0);
   k.pairs[3] = w.attention_weights; k.pairs[4] = w.output_proj; k.pairs[5] = pe.l0;
-  k.pairs[6] = tc_linear{pe.n1.g, pe.n1.b}; k.pairs[7] = pe.l3; k.pairs[8] = tc_linear{pe.n4.g, pe.n4.b};
-  k.pairs[9] = tc_linear{w.norm1.g, w.norm1.b}; k.pairs[10] = w.ffn0; k.pairs[11] = w.ffn1;
-  k.pairs[12] = tc_linear{w.norm2.g, w.norm2.b};
+  k.pairs[6] = ln_pair(pe.n1); k.pairs[7] = pe.l3; k.pairs[8] = ln_pair(pe.n4);
+  k.pairs[9] = ln_pair(w.norm1); k.pairs[10] = w.ffn0; k.pairs[11] = w.ffn1;
+  k.pairs[12] = ln_pair(w.norm2);
   k.pairs[13] = w.reg.l0; k.pairs[14] = w.reg.l2; k.pairs[15] = w.reg.l4;
   // without a reg branch (no box refinement) the layer writes neither ref_out nor a box
   k.refine = w.reg.l0.w != nullptr;
@@ -3161,8 +3182,6 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   TC_REQUIRE(a.pre == nullptr || a.cam.feats.num_levels == 4,
              "decoder_chain: num_levels=%d (the camera pre-gather exists for 4 levels)", a.cam.feats.num_levels);
   k.pre = a.pre; k.premask = a.premask;
-  TC_REQUIRE(a.tile_rows == 0 || a.tile_rows == 4 || a.tile_rows == 8 || a.tile_rows == 16 || a.tile_rows == 32,
-             "decoder_chain: tile_rows=%d (0 = automatic, 4, 8, 16 or 32)", a.tile_rows);
   k.tile_rows = a.tile_rows;
   k.matrix_path = a.matrix_path;
   k.drop = a.drop;
@@ -3183,14 +3202,6 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
 // ---- layer 0's pack-time constants (PROG_DECODER_L0_T / PROG_DECODER_L0GEN_T) ----
 size_t decoder_l0_const_floats(int Q) { return 3 * (arena_slice((size_t)Q * 256, 4) / 4); }
 
-int decoder_l0_variant(int M, int tile_rows_opt, int matrix_path) {
-  ChainK k;
-  init_k(k);
-  k.M = M; k.tile_rows = tile_rows_opt; k.matrix_path = matrix_path;
-  const int rows = tile_rows(k);
-  return rows == 4 ? 0 : rows == 8 ? 1 : rows == 32 ? 4 : use_f16x2(k) ? 3 : 2;
-}
-
 // norm0's second output, x + query_pos (F_LN_XP: add4 of the fp32 result and the position row)
 __global__ void l0_xpos_kernel(const float* __restrict__ x, const float* __restrict__ qe, float* __restrict__ xp, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3198,8 +3209,6 @@ __global__ void l0_xpos_kernel(const float* __restrict__ x, const float* __restr
 }
 
 int launch_decoder_l0_consts(const DecoderChainArgs& a, int variant, float* consts, hipStream_t s) {
-  static const int rows_of[TC_L0_VARIANTS] = {4, 8, 16, 16, 32};
-  static const int path_of[TC_L0_VARIANTS] = {TC_MATRIX_F32, TC_MATRIX_F32, TC_MATRIX_F32, TC_MATRIX_F16X2, TC_MATRIX_F16X2};
   TC_REQUIRE(variant >= 0 && variant < TC_L0_VARIANTS && a.M == a.Q, "decoder_l0_consts: variant=%d M=%d Q=%d", variant, a.M, a.Q);
   ChainK k;
   int rc = make_decoder_k(a, k);
@@ -3207,7 +3216,7 @@ int launch_decoder_l0_consts(const DecoderChainArgs& a, int variant, float* cons
   TC_REQUIRE(!generic_xattn(k) && k.drop.thr == 0, "decoder_l0_consts: one-point, four-level eval-mode kernels only");
   const size_t plane = decoder_l0_const_floats(a.Q) / 3;
   k.l0_seq = 2; k.has_next = 0;
-  k.tile_rows = rows_of[variant]; k.matrix_path = path_of[variant];
+  k.tile_rows = variant_rows(variant); k.matrix_path = variant_mm(variant) ? TC_MATRIX_F16X2 : TC_MATRIX_F32;
   k.g[G_KV0] = consts; k.g_ld[G_KV0] = 256;
   k.g[G_KV1] = consts + 2 * plane; k.g_ld[G_KV1] = 256;
   rc = launch(k, s, "chain(layer-0 constants)");
@@ -3241,8 +3250,8 @@ static int make_radar_enc_k(const RadarEncodeArgs& a, ChainK& k, int part = 0) {
   k.w16_delta = a.w16_delta; k.matrix_path = a.matrix_path; k.range_status = a.range_status;
   TC_REQUIRE(part == 0 || a.radar_feat != nullptr, "radar_encode: split programs need the radar_feat buffer");
   k.g[G_RFEAT] = a.radar_feat; k.g_ld[G_RFEAT] = 256;
-  k.pairs[0] = a.rpe.l0; k.pairs[1] = tc_linear{a.rpe.n1.g, a.rpe.n1.b}; k.pairs[2] = a.rpe.l3;
-  k.pairs[3] = tc_linear{a.rpe.n4.g, a.rpe.n4.b}; k.pairs[4] = a.f0; k.pairs[5] = a.f2; k.pairs[6] = a.f4;
+  k.pairs[0] = a.rpe.l0; k.pairs[1] = ln_pair(a.rpe.n1); k.pairs[2] = a.rpe.l3;
+  k.pairs[3] = ln_pair(a.rpe.n4); k.pairs[4] = a.f0; k.pairs[5] = a.f2; k.pairs[6] = a.f4;
   for (int r = 0; r < a.nlayers; ++r) {
     k.pairs[7 + r] = a.kvproj[r];
     k.g[G_KV0 + r] = a.kv[r]; k.g_ld[G_KV0 + r] = 512;
@@ -3257,28 +3266,25 @@ int launch_radar_encode(const RadarEncodeArgs& a, hipStream_t s) {
   return launch(k, s, "chain(radar_encode)");
 }
 
+// part 0: the whole encoder program, 1 / 2: its halves (PROG_RADAR_ENC_A / _B)
+template <int R, int MM, bool PRE, bool MP>
+static int launch_dual_part(const ChainK& kd, const ChainK& ke, int part, hipStream_t s, const char* what) {
+  return part == 1   ? launch_dual_r<R, R, PROG_RADAR_ENC_A, MM, PRE, MP>(kd, ke, s, what)
+         : part == 2 ? launch_dual_r<R, R, PROG_RADAR_ENC_B, MM, PRE, MP>(kd, ke, s, what)
+                     : launch_dual_r<R, R, PROG_RADAR_ENC, MM, PRE, MP>(kd, ke, s, what);
+}
+
+// The encoder rows take the decoder's variant.  4-row decoder tiles run two workgroups per CU (256 VGPRs): a 16-row
+// encoder body in the same kernel would spill ~100 registers at that budget, and 225 + T/4 workgroups fit the chip at
+// two per CU.  PRE as in launch_rows.
 template <bool MP>
 static int launch_dual(const ChainK& kd, const ChainK& ke, int part, hipStream_t s) {
-  const int rows = tile_rows(kd);
   const char* what = "chain(decoder + radar_encode)";
-#define TC_DUAL(RA, RB, MM, PRE)                                                                      \
-  (part == 1 ? launch_dual_r<RA, RB, PROG_RADAR_ENC_A, MM, PRE, MP>(kd, ke, s, what)                  \
-   : part == 2 ? launch_dual_r<RA, RB, PROG_RADAR_ENC_B, MM, PRE, MP>(kd, ke, s, what)                \
-               : launch_dual_r<RA, RB, PROG_RADAR_ENC, MM, PRE, MP>(kd, ke, s, what))
-  // 4-row decoder tiles run two workgroups per CU (256 VGPRs): the encoder rows then use 4-row
-  // tiles too -- a 16-row body in the same kernel would spill ~100 registers at that budget,
-  // and 225 + T/4 workgroups fit the chip at two per CU
-  if (rows == 4) return TC_DUAL(4, 4, 0, false);
-  if (rows == 8) return TC_DUAL(8, 8, 0, false);
-  if (rows == 32) {
-    TC_REQUIRE(use_f16x2(kd), "%s: 32-row tiles exist on the f16x2 matrix path only", what);
-    if (kd.pre != nullptr) return TC_DUAL(32, 32, 1, true);
-    return TC_DUAL(32, 32, 1, false);
-  }
-  if (use_f16x2(kd) && kd.pre != nullptr) return TC_DUAL(16, 16, 1, true);
-  if (use_f16x2(kd)) return TC_DUAL(16, 16, 1, false);
-  return TC_DUAL(16, 16, 0, false);
-#undef TC_DUAL
+  return with_variant(tile_variant(kd.M, kd.tile_rows, kd.matrix_path, what), [&](auto V) {
+    constexpr int R = variant_rows(V), MM = variant_mm(V);
+    if constexpr (MM == 1) { if (kd.pre != nullptr) return launch_dual_part<R, MM, true, MP>(kd, ke, part, s, what); }
+    return launch_dual_part<R, MM, false, MP>(kd, ke, part, s, what);
+  });
 }
 
 // a decoder layer and (a part of) the radar encoders in one launch;
@@ -3306,12 +3312,7 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {
   k.has_next = 1;
   for (int r = 0; r < a.nlayers; ++r) {
     const tc_radar_layer& w = a.w[r];
-    tc_linear* p = &k.pairs[r * RADAR_PAIRS];
-    p[0] = w.attn.in_proj; p[1] = w.attn.out_proj; p[2] = tc_linear{w.norm2.g, w.norm2.b};
-    p[3] = w.linear1; p[4] = w.linear2; p[5] = tc_linear{w.norm3.g, w.norm3.b};
-    p[6] = w.final_cls.l0; p[7] = tc_linear{w.final_cls.n1.g, w.final_cls.n1.b}; p[8] = w.final_cls.l3;
-    p[9] = tc_linear{w.final_cls.n4.g, w.final_cls.n4.b}; p[10] = w.final_cls.l6;
-    p[11] = w.final_reg.l0; p[12] = w.final_reg.l2; p[13] = w.final_reg.l4;
+    fill_radar_pairs(&k.pairs[r * RADAR_PAIRS], w, w);
     k.rmin[r] = w.radius_min; k.rmax[r] = w.radius_max;
     k.g[G_KV0 + r] = const_cast<float*>(a.kv[r]);
   }
@@ -3323,8 +3324,6 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {
   TC_REQUIRE(a.cen_from_box || a.ref_last != nullptr, "radar_chain: ref_last is null");
   for (int i = 0; i < 6; ++i) k.cam.pc[i] = a.pc[i];
   k.all_box = a.all_box; k.hits = a.hits;
-  TC_REQUIRE(a.tile_rows == 0 || a.tile_rows == 4 || a.tile_rows == 8 || a.tile_rows == 16 || a.tile_rows == 32,
-             "radar_chain: tile_rows=%d (0 = automatic, 4, 8, 16 or 32)", a.tile_rows);
   k.tile_rows = a.tile_rows; k.last_cls_only = a.last_cls_only; k.matrix_path = a.matrix_path;
   k.range_status = a.range_status;
   if (a.tape != nullptr) {                    // forward of a training iteration: tape + dropout
@@ -3332,7 +3331,10 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {
     k.program = PROG_RADAR_TRAIN;
     for (int i = 0; i < T_COUNT; ++i) k.tape[i] = a.tape[i];
     k.tape_stride = a.tape_stride; k.hits_stride = a.hits_stride; k.rdrop = a.drop;
-    if (k.tile_rows >= 16 || (k.tile_rows == 0 && a.M > 2048)) k.tile_rows = 8;
+    // the rule's height, capped at 8 rows; asked without the matrix path: the training kernels are fp32 whatever it says
+    const int v = tile_variant(a.M, a.tile_rows, TC_MATRIX_AUTO, "radar_chain");
+    if (v < 0) return v;
+    k.tile_rows = v == TV_4 ? 4 : 8;
   }
   return launch(k, s, "chain(radar)");
 }
@@ -3343,20 +3345,12 @@ int launch_decoder_heads(const DecoderHeadsArgs& a, hipStream_t s) {
   TC_REQUIRE(a.levels >= 1 && a.levels <= TC_MAX_LAYERS && a.M >= 1, "decoder_heads: levels=%d M=%d", a.levels, a.M);
   TC_REQUIRE(a.code >= 1 && a.code <= 12 && a.ncls >= 1 && a.ncls <= 32, "decoder_heads: code=%d ncls=%d", a.code, a.ncls);
   TC_REQUIRE((long long)a.levels * a.M < (1ll << 24), "decoder_heads: %lld rows in one launch", (long long)a.levels * a.M);
-  TC_REQUIRE(a.tile_rows == 0 || a.tile_rows == 4 || a.tile_rows == 8 || a.tile_rows == 16 || a.tile_rows == 32,
-             "decoder_heads: tile_rows=%d (0 = automatic, 4, 8, 16 or 32)", a.tile_rows);
-  ChainK k;
-  init_k(k);
-  k.M = a.levels * a.M; k.tile_rows = a.tile_rows; k.matrix_path = a.matrix_path;
-  const int rows = tile_rows(k);
-  if (rows == 4) return launch_heads_r<4, 0>(a, s);
-  if (rows == 8) return launch_heads_r<8, 0>(a, s);
-  if (rows == 32) {
-    TC_REQUIRE(use_f16x2(k), "decoder_heads: 32-row tiles exist on the f16x2 matrix path only");
-    return launch_heads_r<32, 1>(a, s);
-  }
-  return use_f16x2(k) ? launch_heads_r<16, 1>(a, s) : launch_heads_r<16, 0>(a, s);
+  return with_variant(tile_variant(a.levels * a.M, a.tile_rows, a.matrix_path, "decoder_heads"),
+                      [&](auto V) { return launch_heads_r<variant_rows(V), variant_mm(V)>(a, s); });
 }
+
+// the rule's automatic tile height for a launch over `rows` rows (no option, no pinned path: never refused)
+static int auto_tile_rows(int rows) { return variant_rows(tile_variant(rows, 0, TC_MATRIX_AUTO, "chain")); }
 
 // Backward of the (1 .. 3) fusion layers for the query rows: one launch (PROG_RADAR_BWD).
 int launch_radar_chain_bwd(const RadarBwdChainArgs& a, hipStream_t s) {
@@ -3369,18 +3363,11 @@ int launch_radar_chain_bwd(const RadarBwdChainArgs& a, hipStream_t s) {
   k.program = PROG_RADAR_BWD; k.M = a.M; k.Q = a.Q; k.code = a.code; k.ncls = a.ncls; k.nlayers = a.nlayers;
   k.has_next = 1;
   for (int r = 0; r < a.nlayers; ++r) {
-    const tc_radar_layer& w = a.wT[r];             // transposed packed weights
     const tc_radar_layer& n = a.w[r];              // LayerNorm parameters (and radii) of the forward
     const tc_radar_layer& g = a.grads[r];
-    tc_linear* p = &k.pairs[r * RADAR_PAIRS];
+    fill_radar_pairs(&k.pairs[r * RADAR_PAIRS], a.wT[r], n);       // linear weights: the transposed packed copy
     tc_linear* gp = &k.gpairs[r * RADAR_PAIRS];
-    p[0] = w.attn.in_proj; p[1] = w.attn.out_proj; p[2] = tc_linear{n.norm2.g, n.norm2.b};
-    p[3] = w.linear1; p[4] = w.linear2; p[5] = tc_linear{n.norm3.g, n.norm3.b};
-    p[6] = w.final_cls.l0; p[7] = tc_linear{n.final_cls.n1.g, n.final_cls.n1.b}; p[8] = w.final_cls.l3;
-    p[9] = tc_linear{n.final_cls.n4.g, n.final_cls.n4.b}; p[10] = w.final_cls.l6;
-    p[11] = w.final_reg.l0; p[12] = w.final_reg.l2; p[13] = w.final_reg.l4;
-    gp[2] = tc_linear{g.norm2.g, g.norm2.b}; gp[5] = tc_linear{g.norm3.g, g.norm3.b};
-    gp[7] = tc_linear{g.final_cls.n1.g, g.final_cls.n1.b}; gp[9] = tc_linear{g.final_cls.n4.g, g.final_cls.n4.b};
+    gp[2] = ln_pair(g.norm2); gp[5] = ln_pair(g.norm3); gp[7] = ln_pair(g.final_cls.n1); gp[9] = ln_pair(g.final_cls.n4);
     k.rmin[r] = n.radius_min; k.rmax[r] = n.radius_max;
     k.g[G_KV0 + r] = const_cast<float*>(a.kv[r]);
     k.dkv[r] = a.dkv[r];
@@ -3395,7 +3382,9 @@ int launch_radar_chain_bwd(const RadarBwdChainArgs& a, hipStream_t s) {
   k.qscale = a.qscale; k.tokens = a.tokens; k.RI = a.RI; k.T = a.T; k.pad_mult = a.pad_mult;
   k.rdrop = a.drop;
   k.detp = a.det_device;
-  k.tile_rows = a.tile_rows == 8 || (a.tile_rows == 0 && a.M > 1024) ? 8 : 4;
+  // 8 rows when asked, or when the rule's automatic height for M rows is beyond 4; anything else runs 4.  Not the rule's
+  // cap: tile_rows = 16 or 32 means 8 to the forward and 4 here, and the trainer relies on neither.
+  k.tile_rows = a.tile_rows == 8 || (a.tile_rows == 0 && auto_tile_rows(a.M) > 4) ? 8 : 4;
   return launch(k, s, "chain(radar backward)");
 }
 

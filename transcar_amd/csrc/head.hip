@@ -253,7 +253,9 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
   const bool folded = !ddrop && w->l0_attn_out != nullptr && w->l0_init_reference != nullptr;
   // ... and so is everything in front of its camera sampling that reads no frame data: out_proj, norm0 and pe.3 come
   // as constants too, made by the kernel variant this forward selects (bit-identical to running them here)
-  const int l0_variant = folded && l0_foldable(w) ? decoder_l0_variant(rows, opt.chain_tile_rows, opt.matrix_path) : -1;
+  const int variant = tile_variant(rows, opt.chain_tile_rows, opt.matrix_path, "head_forward");
+  if (variant < 0) return variant;
+  const int l0_variant = folded && l0_foldable(w) ? variant : -1;
   if (!folded && opt.phase != 2) {
     PrologueArgs pa;
     pa.qe = w->query_embedding; pa.Q = Q; pa.M = rows; pa.refpts = w->reference_points;
@@ -295,15 +297,14 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
     d.code = code; d.M = rows; d.tile_rows = opt.chain_tile_rows; d.matrix_path = opt.matrix_path;
     d.range_status = opt.range_status;
     if (l0c && l0_variant >= 0) d.l0_consts = l0_consts_of(w, l0_variant);
-    // the attention core follows the chains' rule (chain.hip tile_rows / use_f16x2): launches that run 16-row tiles on
+    // the attention core follows the chains' variant (tile_variant): launches that run 16- / 32-row tiles on
     // the f16 matrix cores take the staged two-plane core (self_attn.hip, round 4) -- 4- / 8-row launches (one or two
     // frames: too few workgroups for a form without split keys) and TC_MATRIX_F32 the fp32 core.  A
     // frame's arithmetic is therefore fixed by (chain_tile_rows, matrix_path), not by how many frames share a launch.
     // Round 6 (opt-in, tc_head_options.cam_pregather): the staged core's launch also carries the camera gather of THIS
     // layer's chain (pre-gather workgroups: the layer's reference points are final since the previous chain).
     if (!l0c) {
-      const int trows = opt.chain_tile_rows ? opt.chain_tile_rows : (rows <= 1024 ? 4 : rows <= 2048 ? 8 : 16);   // (32 counts as 16 here)
-      if (trows >= 16 && opt.matrix_path != TC_MATRIX_F32) {
+      if (variant_mm(variant) == 1) {
         PreGatherArgs pga;
         const bool pre = !ddrop && opt.cam_pregather == 1;
         if (pre) {
@@ -424,6 +425,10 @@ using namespace tc;
 extern "C" {
 
 int tc_abi_version(void) { return TC_ABI_VERSION; }
+int tc_chain_tile_rows(int rows, int tile_rows, int matrix_path) {
+  const int v = tile_variant(rows, tile_rows, matrix_path, "chain_tile_rows");
+  return v < 0 ? v : variant_rows(v);
+}
 const char* tc_last_error(void) { return g_err; }
 
 int tc_device_count(void) {
@@ -672,18 +677,16 @@ static int read_options(const tc_head_options* options, tc_head_options& opt) {
   if (options != nullptr) opt = *options;
   TC_REQUIRE(opt.radar_row_order >= 0 && opt.radar_row_order <= 2, "options.radar_row_order=%d (0 automatic, 1 own order, 2 hits first)",
              opt.radar_row_order);
-  TC_REQUIRE(opt.chain_tile_rows == 0 || opt.chain_tile_rows == 4 || opt.chain_tile_rows == 8 ||
-                 opt.chain_tile_rows == 16 || opt.chain_tile_rows == 32,
-             "options.chain_tile_rows=%d (0 = automatic, 4, 8, 16 or 32)", opt.chain_tile_rows);
-  TC_REQUIRE(opt.chain_tile_rows != 32 || opt.matrix_path != TC_MATRIX_F32,
-             "options.chain_tile_rows=32 exists on the f16x2 matrix path only (matrix_path = f32 was asked for)");
+  if (tile_variant(0, opt.chain_tile_rows, opt.matrix_path, "the row chains") < 0) {   // the chains' rule says why
+    char why[200];
+    snprintf(why, sizeof(why), "%s", g_err);
+    TC_REQUIRE(false, "options.chain_tile_rows=%d, options.matrix_path=%d: %s", opt.chain_tile_rows, opt.matrix_path, why);
+  }
   TC_REQUIRE(opt.decoder_dropout_p >= 0.0f && opt.decoder_dropout_p < 1.0f, "options.decoder_dropout_p=%g",
              (double)opt.decoder_dropout_p);
   TC_REQUIRE(opt.phase >= 0 && opt.phase <= 2, "options.phase=%d (0 whole forward, 1 before the radar tokens, 2 the rest)",
              opt.phase);
   TC_REQUIRE(opt.phase == 0 || !opt.unfused, "options.phase=%d needs the fused path", opt.phase);
-  TC_REQUIRE(opt.matrix_path >= TC_MATRIX_AUTO && opt.matrix_path <= TC_MATRIX_F16X2,
-             "options.matrix_path=%d (0 automatic, 1 fp32 MFMA, 2 two-plane f16 MFMA)", opt.matrix_path);
   TC_REQUIRE(opt.cam_pregather == 0 || opt.cam_pregather == 1, "options.cam_pregather=%d (0 off, 1 on)", opt.cam_pregather);
   TC_REQUIRE(opt.cam_pregather == 0 || opt.cam_pregather_ws != nullptr, "options.cam_pregather needs cam_pregather_ws");
   return 0;

@@ -89,6 +89,15 @@ struct PrologueArgs {
 };
 int launch_prologue(const PrologueArgs& a, hipStream_t s);
 
+// The kernel variant of a row-chain launch: tile height and matrix path.  Which attention core runs, which layer-0
+// constants and which packed weight copy are read all follow it.  tile_variant (chain.hip) is the one rule that picks it.
+enum TileVariant { TV_4 = 0, TV_8, TV_16_F32, TV_16_F16X2, TV_32_F16X2, TV_COUNT };
+constexpr int variant_rows(int v) { return v == TV_4 ? 4 : v == TV_8 ? 8 : v == TV_32_F16X2 ? 32 : 16; }
+constexpr int variant_mm(int v) { return v >= TV_16_F16X2 ? 1 : 0; }       // the chains' MM template argument (1: f16x2)
+// rows of the launch, tile_rows (0 = automatic, 4, 8, 16 or 32), matrix_path (TC_MATRIX_*) -> TileVariant, or -1 with the
+// error set (prefixed by `what`)
+int tile_variant(int rows, int tile_rows, int matrix_path, const char* what);
+
 struct DecoderChainArgs {
   const float* attn_o;                       // [M,256]
   int attn_mod = 0, ref_mod = 0;             // attn_o / ref_in rows taken modulo this when > 0
@@ -101,8 +110,7 @@ struct DecoderChainArgs {
   float* hs; float* qk; float* vt; int qpad;
   CamSampleArgs cam;                         // feats, lidar2img, pc, img size (ref/logits/out unused)
   int code, M;
-  int tile_rows = 0;                         // 0: automatic (4 up to 1024 rows, 8 up to 2048, 16 beyond), 4, 8, 16
-  int matrix_path = 0;                       // 16-row tiles: TC_MATRIX_AUTO / _F32 / _F16X2 (tc_head_options.matrix_path)
+  int tile_rows = 0, matrix_path = 0;        // what tile_variant() takes: 0 automatic / 4, 8, 16, 32; TC_MATRIX_*
   // train-mode statistics of the frozen decoder (thr 0 = eval): drop.site is the site of THIS
   // layer's attention probabilities (16 + 8 * layer); the chain's four sites are drop.site + 1
   // (self-attention output), + 2 (cross-attention output, XFMR:378), + 3 (FFN hidden), + 4 (FFN output)
@@ -112,16 +120,15 @@ struct DecoderChainArgs {
   // (PreGatherArgs::out / mask of the SAME reference points) instead of gathering itself; null: gathers itself
   const float* pre = nullptr; const int* premask = nullptr;
   // layer 0 of an eval-mode forward: the constants launch_decoder_l0_consts made for the kernel variant this launch
-  // selects (decoder_l0_variant of M, tile_rows, matrix_path); attn_o / x_in are not read then.  null: the full chain
+  // selects (tile_variant of M, tile_rows, matrix_path); attn_o / x_in are not read then.  null: the full chain
   const float* l0_consts = nullptr;
 };
 int launch_decoder_chain(const DecoderChainArgs& a, hipStream_t s);
-// Layer 0's frame-independent steps, once per checkpoint and per kernel variant (tile height, matrix path) a forward can
-// select: 0: 4 rows, 1: 8 rows, 2: 16 rows f32, 3: 16 rows f16x2, 4: 32 rows.  A block of constants is
-// decoder_l0_const_floats(Q) floats: norm0's output, that + query_pos, pe.3's output ([Q, 256] each, 256-byte slices).
-constexpr int TC_L0_VARIANTS = 5;
+// Layer 0's frame-independent steps, once per checkpoint and per kernel variant a forward can select (TileVariant).
+// A block of constants is decoder_l0_const_floats(Q) floats: norm0's output, that + query_pos, pe.3's output ([Q, 256]
+// each, 256-byte slices).
+constexpr int TC_L0_VARIANTS = TV_COUNT;
 size_t decoder_l0_const_floats(int Q);
-int decoder_l0_variant(int M, int tile_rows, int matrix_path);
 // `a` as for the full chain of layer 0 on the Q query rows (M = Q; the camera part is not read); runs the variant's own
 // kernels on a truncated step sequence
 int launch_decoder_l0_consts(const DecoderChainArgs& a, int variant, float* consts, hipStream_t s);

@@ -119,13 +119,11 @@ class FramePipeline:
         self._capture()
 
     def _auto_tile_rows(self, rows):
-        """the library's automatic rule (chain.hip tile_rows()): 4 up to 1024 rows per launch, 8 up to 2048, 16 up to
-        4096, 32 beyond (16 when the matrix path is pinned to f32)"""
+        """the library's automatic choice for `rows` rows per launch (after the f16-range guard's fall-back: f32)"""
         mp = int(self.options.matrix_path)
-        f32 = mp == _L.TC_MATRIX_F32 or (mp == _L.TC_MATRIX_AUTO and self.head.matrix_fallback)
-        if rows > 4096 and not f32:
-            return 32
-        return 4 if rows <= 1024 else 8 if rows <= 2048 else 16
+        if mp == _L.TC_MATRIX_AUTO and self.head.matrix_fallback:
+            mp = _L.TC_MATRIX_F32
+        return _L.chain_tile_rows(rows, 0, mp)
 
     def tile_rows_of(self, n=None):
         """Row-tile height of a launch over n (default: all) frame slots of a lane."""

@@ -235,12 +235,13 @@ class FusionTrainer:
         # Round 5: a look-ahead of more than 4 096 rows (nine frames: 8 100) runs the 32-row tiles, like inference.
         self.prefetch_depth = max(1, int(prefetch_depth))
         rows = self.prefetch_depth * int(head.num_query)
-        self.decoder_tile_rows = (32 if rows > 4096 else 16) if self.prefetch_depth > 1 else None
+        self.decoder_tile_rows = max(16, L.chain_tile_rows(rows)) if self.prefetch_depth > 1 else None
 
     def _decoder_tile_rows_now(self):
-        """`decoder_tile_rows`, resolved at the call: 32-row tiles exist on the f16x2 matrix path only (chain.hip
-        tile_rows()), so with ``decoder_matrix_path = 'f32'`` -- or after the f16-range guard's fall-back -- a depth
-        that asks for 32 rows runs the f32 kernels' 16 (every look-ahead raised otherwise)."""
+        """`decoder_tile_rows`, resolved at the call: 32-row tiles exist on the f16x2 matrix path only, so with
+        ``decoder_matrix_path = 'f32'`` -- or after the f16-range guard's fall-back -- a depth that asks for 32 rows
+        runs the f32 kernels' 16 (every look-ahead raised otherwise).  A demotion, so not a question for
+        tc_chain_tile_rows: the library's rule refuses (32, f32), it does not lower it; no threshold is repeated here."""
         rows = self.decoder_tile_rows
         mp = getattr(self, 'decoder_matrix_path', None)
         if rows == 32 and (mp == 'f32' or (mp in (None, 'auto') and self.head.matrix_fallback)):
