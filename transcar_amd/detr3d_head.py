@@ -282,6 +282,30 @@ class Detr3DHead(BaseModule):
         self._dec_heads = None
         return super().load_state_dict(*a, **k)
 
+    def reload_state_dict(self, state_dict, strict=True):
+        """``load_state_dict`` into a head whose packed weights captured hipGraphs may point at (FusionTrainer.
+        load_checkpoint): torch copies the values into the parameters where they lie, the packed copies are written again
+        at once and in place, and ``refresh_weights`` compares the pointer table with the one from before the load --
+        only values changed, so ``buffers_generation`` stays and a FramePipeline keeps replaying.  -> torch's result."""
+        before, dec = self._weights, self._dec_heads
+        res = self.load_state_dict(state_dict, strict=strict)
+        if before is None:                       # nothing was packed yet: the first forward does it
+            return res
+        self._weights = before
+        generation = self.buffers_generation
+        w = self.refresh_weights()
+        if dec is not None and self.buffers_generation == generation:
+            # the packed cls / reg branches of the decoder levels: same buffer, new values (a buffer of their own, which
+            # decoder_heads() would allocate anew for the new pointer table while a captured graph reads the old one)
+            buf, view, _ = dec
+            h, lib = self.decoder_heads_struct(), L.lib()
+            if lib.tc_decoder_heads_packed_bytes(C.byref(h)) == buf.numel():
+                L.check(lib.tc_decoder_heads_pack(C.byref(h), buf.data_ptr(), buf.numel(), C.byref(view),
+                                                  C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)),
+                        'tc_decoder_heads_pack')
+                self._dec_heads = (buf, view, w)
+        return res
+
     def head_weights(self):
         """tc_head_weights over this module's parameters (cached; parameters
         updated in place keep their addresses)."""

@@ -201,6 +201,9 @@ class FusionTrainer:
         self.m = torch.zeros_like(self.bucket.params)
         self.v = torch.zeros_like(self.bucket.params)
         self.sq = self.bucket.sq               # zeroed with the gradients (FlatBucket.zero_grad)
+        # set by load_checkpoint alone, for a checkpoint of ANOTHER bucket layout: the clip's sum of squares is then taken
+        # over the gradients in the layout of the run that is continued (`_adopt_clip_order`)
+        self._clip_order = self._clip_index = self._clip_scratch = None
         self.lr, self.betas, self.eps = lr, betas, eps
         self.weight_decay, self.max_norm = weight_decay, max_norm
         self.iter = 0
@@ -538,9 +541,181 @@ class FusionTrainer:
             check_assign_status(self.head, wait=True)
 
     def state_dict(self):
-        """Checkpoint of the head's parameters (the reference's keys) + the optimizer state; `finish()` first."""
+        """The head's parameters (the reference's keys; they ALIAS the live bucket) + the flat optimizer state in the layout
+        of this bucket, without names; `finish()` first.  To write a run out and resume it: ``checkpoint()`` below."""
         self.finish()
         return dict(head=self.head.state_dict(), m=self.m.clone(), v=self.v.clone(), iter=self.iter)
+
+    # ------------------------------------------------------------------
+    # checkpoint / resume (transcar_amd/checkpoint.py: the format)
+    # ------------------------------------------------------------------
+    @staticmethod
+    def _world_size():
+        return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+    def _layout(self):
+        """(names, shapes, offsets) of the bucket, in the order of ``head.trainable_parameters()``."""
+        b = self.bucket
+        return b.names, [tuple(p.shape) for p in b.items], b.offsets
+
+    def _bucket_order(self):
+        """The parameter names in the order they lie in the bucket."""
+        b = self.bucket
+        return [b.names[i] for i in sorted(range(len(b.names)), key=lambda i: b.offsets[i])]
+
+    def _adopt_clip_order(self, order):
+        """The gradient clip is the one place where an iteration's arithmetic depends on the LAYOUT of the bucket: its
+        coefficient comes from a float sum of squares over the bucket in bucket order (tc_sq_norm: fixed workgroup
+        partials), and another order rounds differently -- in the last bit of the coefficient, and of every parameter.  A
+        run continued from a checkpoint of another layout therefore keeps summing in the order of the run it continues
+        (``order``: that run's parameter names as they lay in its bucket): the gradients are gathered into a scratch of
+        that layout (one index_select) and tc_sq_norm reads the scratch.  None, or this bucket's own order: nothing."""
+        b = self.bucket
+        if order is None or list(order) == self._bucket_order():
+            self._clip_order = self._clip_index = self._clip_scratch = None
+            return
+        where = dict(zip(b.names, zip(b.offsets, (p.numel() for p in b.items))))
+        index = torch.cat([torch.arange(where[n][0], where[n][0] + where[n][1], dtype=torch.int32) for n in order])
+        assert index.numel() == b.numel
+        self._clip_order = [str(n) for n in order]
+        self._clip_index = index.to(b.grads.device)
+        self._clip_scratch = torch.empty_like(b.grads)
+
+    def checkpoint(self, meta=None, to_cpu=True):
+        """Everything that decides the next iteration, as one dict ``torch.load(weights_only=True)`` reads back:
+        ``state_dict`` (the head's, the reference's keys, CLONED -- ``state_dict()['head']`` above aliases the live bucket),
+        ``optimizer`` (the Adam moments per parameter BY NAME, in the form torch.optim.AdamW loads), ``trainer`` (iteration,
+        hyper-parameters the optimizer entry does not hold, the dropout seed and the head's forward counter every mask is
+        derived from) and ``meta`` (the caller's: epoch, iteration, what ``cosine_lr`` needs).  `finish()` first.
+        to_cpu=False leaves the tensors on the device."""
+        from . import checkpoint as K
+        self.finish()
+        names, shapes, offsets = self._layout()
+        m, v = (self.m.cpu(), self.v.cpu()) if to_cpu else (self.m, self.v)
+        opt = K.pack_optimizer_state(names, shapes, offsets, m, v, self.iter,
+                                     dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay))
+        head = self.head
+        trainer = dict(iter=int(self.iter), seed=int(self.seed), dropout=float(self.dropout),
+                       decoder_dropout=float(self.decoder_dropout),
+                       max_norm=None if self.max_norm is None else float(self.max_norm),
+                       train_forwards=int(getattr(head, '_train_forwards', 0)),
+                       dropout_seed=int(getattr(head, 'dropout_seed', 0)),
+                       num_fusion_layers=int(head.num_fusion_layers), deterministic=bool(self.deterministic),
+                       prefetch_depth=int(self.prefetch_depth), world_size=int(self._world_size()),
+                       # the order the clip's sum of squares runs over the parameters (`_adopt_clip_order`)
+                       bucket_order=list(self._clip_order or self._bucket_order()))
+        return K.make_checkpoint(head.state_dict(), opt, trainer, meta, to_cpu)
+
+    def load_checkpoint(self, ckpt, strict=True):
+        """Continue from ``checkpoint()``'s dict: the head's weights (in place -- the parameters stay views of the bucket
+        and a FramePipeline captured on this head keeps replaying), the Adam moments scattered BY NAME into this bucket's
+        layout, the iteration, hyper-parameters, dropout seed and forward counter.  With ``deterministic=True`` the
+        iterations that follow are bit-identical to those of the run that was not interrupted.
+        Also read: a reference-style ``{'meta', 'state_dict', 'optimizer'}`` file (keys under ``pts_bbox_head.``, other
+        prefixes ignored; a positional optimizer entry must have this trainer's number of parameters) and the legacy
+        ``state_dict()`` dict -- its flat moments carry no names, so all that can be checked is their length: they are
+        right only if the bucket that wrote them had this bucket's layout (same ``num_fusion_layers``, same version).
+        Refused (TransCARHipError, nothing is changed): another ``num_fusion_layers``, another set of trainable parameters,
+        moments of another shape, amsgrad / maximize, steps that differ between parameters.  ``deterministic``,
+        ``prefetch_depth`` and the world size stay what the constructor / launcher made them: a difference is reported.
+        A checkpoint of another bucket LAYOUT (same names, other offsets) loads like any other; the clip's sum of squares
+        then keeps the order of the run that is continued (`_adopt_clip_order`), so that run too continues bit for bit.
+        -> dict(form, missing_keys, unexpected_keys, differed={key: (checkpoint's, this trainer's)}, not_restored=[keys],
+        clip_sum_order='bucket' | 'checkpoint')."""
+        from . import checkpoint as K
+        self.finish()
+        head, b = self.head, self.bucket
+        names, shapes, offsets = self._layout()
+        report = dict(form='named', missing_keys=[], unexpected_keys=[], differed={}, not_restored=[])
+        m_new, v_new = torch.empty_like(self.m), torch.empty_like(self.v)
+        if K.is_legacy(ckpt):
+            report['form'] = 'legacy'
+            if ckpt['m'].numel() != b.numel or ckpt['v'].numel() != b.numel:
+                raise L.TransCARHipError('legacy checkpoint: %d moments for a bucket of %d elements'
+                                         % (ckpt['m'].numel(), b.numel))
+            sd = K.clone_tensors(K.head_state_dict(ckpt['head']))     # (its tensors may alias this very bucket)
+            missing = [n for n in names if n not in sd]
+            if missing:
+                raise L.TransCARHipError('legacy checkpoint lacks trainable parameter(s) %s' % K._some(missing))
+            m_new.copy_(ckpt['m'].reshape(-1))
+            v_new.copy_(ckpt['v'].reshape(-1))
+            step, hyper, saved = int(ckpt['iter']), None, {}
+            report['not_restored'] = ['lr', 'betas', 'eps', 'weight_decay'] + [k for k in K.RESTORED if k != 'iter']
+        else:
+            sd = K.check_structure(ckpt, names, head.num_fusion_layers)
+            opt, saved = ckpt.get('optimizer'), dict(ckpt.get('trainer') or {})
+            if opt is None:
+                report['form'], step, hyper = 'weights', None, None
+                report['not_restored'] = ['optimizer']
+            else:
+                if opt.get('param_names') is None:
+                    report['form'] = 'positional'
+                step = K.unpack_optimizer_state(opt, names, shapes, offsets, m_new, v_new)
+                hyper = K.optimizer_hyper(opt)
+            if 'iter' in saved and step is not None and int(saved['iter']) != step:
+                raise L.TransCARHipError('checkpoint: trainer iteration %d, optimizer step %d' % (int(saved['iter']), step))
+            report['not_restored'] += [k for k in K.RESTORED if k not in saved and not (k == 'iter' and step is not None)]
+            if saved.get('bucket_order') is not None and sorted(saved['bucket_order']) != sorted(names):
+                raise L.TransCARHipError('checkpoint: bucket_order does not hold the trainable parameters once each')
+        own = head.state_dict()
+        bad = ['%s %s (the head: %s)' % (k, tuple(t.shape), tuple(own[k].shape)) for k, t in sd.items()
+               if k in own and tuple(t.shape) != tuple(own[k].shape)]
+        if strict:
+            bad = ['%s (missing)' % k for k in own if k not in sd] + ['%s (unexpected)' % k for k in sd if k not in own] + bad
+        if bad:
+            raise L.TransCARHipError('checkpoint state_dict does not fit the head: %s' % K._some(bad))
+        # -- nothing was changed so far, and nothing is refused from here on
+        if head.query_embedding.weight.is_cuda:
+            torch.cuda.synchronize(head.query_embedding.weight.device)    # replays / iterations in flight read the old values
+        res = head.reload_state_dict(sd, strict=strict)
+        report['missing_keys'], report['unexpected_keys'] = list(res.missing_keys), list(res.unexpected_keys)
+        if step is not None:
+            self.m.copy_(m_new)
+            self.v.copy_(v_new)
+            self.iter = int(step)
+            self._adopt_clip_order(saved.get('bucket_order'))
+            report['clip_sum_order'] = 'bucket' if self._clip_index is None else 'checkpoint'
+        if hyper is not None:
+            self.lr, self.betas, self.eps = hyper['lr'], hyper['betas'], hyper['eps']
+            self.weight_decay = hyper['weight_decay']
+        if 'seed' in saved:
+            self.seed = int(saved['seed'])
+        if 'dropout' in saved:
+            self.dropout = float(saved['dropout'])
+        if 'decoder_dropout' in saved:
+            self.decoder_dropout = float(saved['decoder_dropout'])
+        if 'max_norm' in saved:
+            self.max_norm = None if saved['max_norm'] is None else float(saved['max_norm'])
+        if 'dropout_seed' in saved:
+            head.dropout_seed = int(saved['dropout_seed'])
+        if 'train_forwards' in saved:
+            head._train_forwards = int(saved['train_forwards'])
+        mine = dict(deterministic=bool(self.deterministic), prefetch_depth=int(self.prefetch_depth),
+                    world_size=int(self._world_size()))
+        for k in K.COMPARED:
+            if k in saved and saved[k] != mine[k]:
+                report['differed'][k] = (saved[k], mine[k])
+        self.invalidate_lookahead()           # a pending look-ahead drew the masks of the old counter from the old weights
+        self._sq_clean = False
+        return report
+
+    def save_checkpoint(self, path, meta=None):
+        """``checkpoint(meta)`` to ``path``, atomically (written beside it, then renamed).  With a process group rank 0
+        writes and every rank waits for the file."""
+        import os
+        ckpt = self.checkpoint(meta)           # (every rank: finish() is this rank's own)
+        grouped = dist.is_available() and dist.is_initialized()
+        if not grouped or dist.get_rank() == 0:
+            tmp = str(path) + '.tmp'
+            torch.save(ckpt, tmp)
+            os.replace(tmp, str(path))
+        if grouped:
+            dist.barrier()
+
+    def load_checkpoint_file(self, path, map_location=None, strict=True):
+        """``load_checkpoint`` of a file ``save_checkpoint`` (or mmcv) wrote.  Every rank loads the same file: the
+        parameters agree, the dropout masks differ by rank as before (Detr3DHead.next_dropout_seed)."""
+        return self.load_checkpoint(torch.load(str(path), map_location=map_location, weights_only=True), strict=strict)
 
     def _exchange_in_chunks(self, update=True):
         """Chunked weight-gradient launches + one all-reduce per chunk: only where there is an exchange to hide (more than
@@ -581,7 +756,10 @@ class FusionTrainer:
         if not self._sq_clean:                 # (zeroed with the gradients in the fused iteration)
             self.sq.zero_()
         self._sq_clean = False
-        L.check(lib.tc_sq_norm(b.grads.data_ptr(), b.numel, self.sq.data_ptr(), self._stream()),
+        grads = b.grads
+        if self._clip_index is not None:       # a run continued from another bucket layout: its order of the float sum
+            grads = torch.index_select(b.grads, 0, self._clip_index, out=self._clip_scratch)
+        L.check(lib.tc_sq_norm(grads.data_ptr(), b.numel, self.sq.data_ptr(), self._stream()),
                 'tc_sq_norm')
         L.check(lib.tc_adamw_step(
             b.params.data_ptr(), b.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), b.numel,
