@@ -8,6 +8,8 @@ The HIP library is the product; there is no CPU fallback.  ``lib()`` raises
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 #: TRANSCAR_HIP_LIB selects another build of the same ABI.  The STAMPS debug build
 #: (`make STAMPS=1`: s_memtime stamps and the TRANSCAR_CHAIN_DBG timing switches, which
@@ -387,6 +389,24 @@ def check(rc, what):
     if rc != 0:
         msg = lib().tc_last_error().decode('utf-8', 'replace')
         raise TransCARHipError('%s failed (status %d): %s' % (what, rc, msg))
+
+
+def stream_ptr(device=None):
+    """The current HIP stream of `device` (None: of the current device) as the void* every tc_* entry takes last."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def size_query(query, *args):
+    """A tc_*_bytes query of the library; 0 is its refusal and raises with its message."""
+    nbytes = query(*args)
+    if nbytes == 0:
+        raise TransCARHipError(lib().tc_last_error().decode())
+    return nbytes
+
+
+def device_bytes(device, query, *args):
+    """A new byte buffer on `device` of the size ``query(*args)`` asks for (`size_query`)."""
+    return torch.empty(size_query(query, *args), dtype=torch.uint8, device=device)
 
 
 def chain_tile_rows(rows, tile_rows=0, matrix_path=TC_MATRIX_AUTO):

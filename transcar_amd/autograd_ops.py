@@ -12,7 +12,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
-from .ops import _chk, _p, _stream
+from .ops import _chk, _p
 
 
 def _c(t):
@@ -33,7 +33,7 @@ class _Linear(Function):
         M = x.numel() // K
         y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
         L.check(L.lib().tc_linear_fwd(_p(x), None, _p(weight), _p(bias), None, _p(y),
-                                      M, K, N, int(act), _stream()), 'tc_linear_fwd')
+                                      M, K, N, int(act), L.stream_ptr()), 'tc_linear_fwd')
         ctx.act = int(act)
         ctx.save_for_backward(x, weight, y if act else None)
         ctx.has_bias = bias is not None
@@ -51,13 +51,13 @@ class _Linear(Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             L.check(lib.tc_linear_bwd_data(_p(dy), _p(y), None, _p(weight), None, _p(dx),
-                                           M, K, N, 1.0, 0, _stream()), 'tc_linear_bwd_data')
+                                           M, K, N, 1.0, 0, L.stream_ptr()), 'tc_linear_bwd_data')
         if ctx.needs_input_grad[1]:
             dw = _zeros_like(weight)
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 db = torch.zeros(N, dtype=torch.float32, device=x.device)
             L.check(lib.tc_linear_bwd_weight(_p(x), _p(dy), _p(y), None, _p(dw), _p(db),
-                                             M, K, N, 1.0, _stream()), 'tc_linear_bwd_weight')
+                                             M, K, N, 1.0, L.stream_ptr()), 'tc_linear_bwd_weight')
         return dx, dw, db, None
 
 
@@ -71,7 +71,7 @@ class _GatedLinearResidual(Function):
         M = x.numel() // K
         y = torch.empty_like(res)
         L.check(L.lib().tc_linear_gated_fwd(_p(x), _p(weight), _p(bias), _p(res), _p(gate),
-                                            _p(y), M, K, N, _stream()), 'tc_linear_gated_fwd')
+                                            _p(y), M, K, N, L.stream_ptr()), 'tc_linear_gated_fwd')
         ctx.save_for_backward(x, weight, gate)
         return y
 
@@ -87,12 +87,12 @@ class _GatedLinearResidual(Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             L.check(lib.tc_linear_bwd_data(_p(dy), None, _p(gate), _p(weight), None, _p(dx),
-                                           M, K, N, 1.0, 0, _stream()), 'tc_linear_bwd_data')
+                                           M, K, N, 1.0, 0, L.stream_ptr()), 'tc_linear_bwd_data')
         if ctx.needs_input_grad[1]:
             dw = _zeros_like(weight)
             db = torch.zeros(N, dtype=torch.float32, device=x.device)
             L.check(lib.tc_linear_bwd_weight(_p(x), _p(dy), None, _p(gate), _p(dw), _p(db),
-                                             M, K, N, 1.0, _stream()), 'tc_linear_bwd_weight')
+                                             M, K, N, 1.0, L.stream_ptr()), 'tc_linear_bwd_weight')
         return dx, dw, db, (dy if ctx.needs_input_grad[3] else None), None
 
 
@@ -105,7 +105,7 @@ class _AddLayerNorm(Function):
         Cd = a.shape[-1]
         y = torch.empty_like(a)
         L.check(L.lib().tc_add_layernorm_fwd(_p(a), _p(b), _p(gamma), _p(beta), _p(y),
-                                             a.numel() // Cd, Cd, 1 if relu else 0, _stream()),
+                                             a.numel() // Cd, Cd, 1 if relu else 0, L.stream_ptr()),
                 'tc_add_layernorm_fwd')
         ctx.save_for_backward(a, b, gamma, y if relu else None)
         return y
@@ -121,7 +121,7 @@ class _AddLayerNorm(Function):
         dg = torch.zeros(Cd, dtype=torch.float32, device=a.device) if want_w else None
         dbt = torch.zeros(Cd, dtype=torch.float32, device=a.device) if want_w else None
         L.check(L.lib().tc_add_layernorm_bwd(_p(a), _p(b), _p(gamma), _p(dy), _p(y), _p(dz),
-                                             _p(dg), _p(dbt), a.numel() // Cd, Cd, _stream()),
+                                             _p(dg), _p(dbt), a.numel() // Cd, Cd, L.stream_ptr()),
                 'tc_add_layernorm_bwd')
         return (dz if ctx.needs_input_grad[0] else None,
                 dz if (b is not None and ctx.needs_input_grad[1]) else None, dg, dbt, None)
@@ -148,7 +148,7 @@ class _RadarAttnCore(Function):
         L.check(L.lib().tc_radar_attn_core_fwd(
             _p(qproj), scale, _p(kv), _p(centre), meta[1], _p(box), meta[2], _p(tokens), meta[3],
             B, Q, T, Cd, meta[8], meta[9], meta[10], meta[11], _p(out), _p(hits),
-            float(drop[0]), int(drop[1]), int(drop[2]), _stream()),
+            float(drop[0]), int(drop[1]), int(drop[2]), L.stream_ptr()),
             'tc_radar_attn_core_fwd')
         ctx.meta = meta
         ctx.drop = (float(drop[0]), int(drop[1]), int(drop[2]))
@@ -167,7 +167,7 @@ class _RadarAttnCore(Function):
         L.check(L.lib().tc_radar_attn_core_bwd(
             _p(qproj), scale, _p(kv), _p(centre), ld_c, _p(box), code, _p(tokens), ld_xy,
             B, Q, T, Cd, heads, pad_mult, rmin, rmax, _p(out), _p(d_out), _p(dq), _p(dkv),
-            ctx.drop[0], ctx.drop[1], ctx.drop[2], _stream()), 'tc_radar_attn_core_bwd')
+            ctx.drop[0], ctx.drop[1], ctx.drop[2], L.stream_ptr()), 'tc_radar_attn_core_bwd')
         return dq, dkv, None, None, None, None, None, None, None, None, None
 
 
@@ -182,7 +182,7 @@ class _Dropout(Function):
         out = torch.empty_like(x)
         ctx.args = (x.numel() // cols, cols, float(p), int(seed), int(site))
         L.check(L.lib().tc_dropout(_p(x), ctx.args[0], cols, ctx.args[2], ctx.args[3], ctx.args[4],
-                                   _p(out), _stream()), 'tc_dropout')
+                                   _p(out), L.stream_ptr()), 'tc_dropout')
         return out
 
     @staticmethod
@@ -191,7 +191,7 @@ class _Dropout(Function):
         dy = _c(dy)
         dx = torch.empty_like(dy)
         rows, cols, p, seed, site = ctx.args
-        L.check(L.lib().tc_dropout(_p(dy), rows, cols, p, seed, site, _p(dx), _stream()), 'tc_dropout')
+        L.check(L.lib().tc_dropout(_p(dy), rows, cols, p, seed, site, _p(dx), L.stream_ptr()), 'tc_dropout')
         return dx, None, None, None
 
 
@@ -213,7 +213,7 @@ class _BoxAddRef(Function):
             _chk(add_ref, 'add_ref')
             xy, ld_xy, z, ld_z = add_ref.data_ptr(), 3, add_ref.data_ptr() + 8, 3
         L.check(L.lib().tc_box_add_ref_fwd(_p(reg_out), code, C.c_void_p(xy), ld_xy,
-                                           C.c_void_p(z), ld_z, _p(box), M, _stream()),
+                                           C.c_void_p(z), ld_z, _p(box), M, L.stream_ptr()),
                 'tc_box_add_ref_fwd')
         ctx.with_prev = prev_box is not None
         return box
@@ -227,7 +227,7 @@ class _BoxAddRef(Function):
             code = d_box.shape[-1]
             d_prev = torch.zeros_like(d_box)
             L.check(L.lib().tc_box_add_ref_bwd(_p(d_box), code, _p(d_prev),
-                                               d_box.numel() // code, _stream()),
+                                               d_box.numel() // code, L.stream_ptr()),
                     'tc_box_add_ref_bwd')
         return d_box, d_prev, None
 
@@ -265,5 +265,5 @@ def radar_reference_l1(ref, pc_range):
     cxy = torch.empty(ref.shape[:-1] + (2,), dtype=torch.float32, device=ref.device)
     addref = torch.empty_like(ref)
     L.check(L.lib().tc_radar_reference_l1(_p(ref), L.f6(pc_range), _p(cxy), _p(addref), M,
-                                          _stream()), 'tc_radar_reference_l1')
+                                          L.stream_ptr()), 'tc_radar_reference_l1')
     return cxy, addref

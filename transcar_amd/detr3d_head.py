@@ -22,9 +22,11 @@ There is no CPU fallback.
 """
 import copy
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib as L
@@ -86,6 +88,42 @@ def head_options(tile_rows=None, unfused=None, last_level_cls_only=False,
 FUSION_SUFFIXES = (('', ''), ('_2', '2'), ('_3', '3'))
 
 
+def fusion_module_names(r):
+    """field -> attribute name of fusion layer r's modules (0-based; HEAD:129-171): the one place that knows the suffixes."""
+    sfx, asfx = FUSION_SUFFIXES[r]
+    names = dict(attn='rf_multihead_attn' + asfx, linear1='rf_linear1' + sfx, linear2='rf_linear2' + sfx,
+                 final_cls='final_cls' + asfx, final_reg='final_reg' + asfx, dropout='rf_dropout' + sfx)
+    for n in (1, 2, 3):
+        names['norm%d' % n] = 'rf_norm%d%s' % (n, sfx)
+        names['dropout%d' % n] = 'rf_dropout%d%s' % (n, sfx)
+    return names
+
+
+def fusion_modules(head, r):
+    """The modules of fusion layer r of `head` under their field names (``.attn``, ``.norm2``, ``.final_cls``, ...)."""
+    return SimpleNamespace(**{field: getattr(head, name) for field, name in fusion_module_names(r).items()})
+
+
+#: coefficient of the forward counter in `dropout_seed_of`: consecutive training forwards draw seeds this far apart
+SEED_STRIDE = 0x85EBCA77
+
+
+def dropout_seed_of(dropout_seed, rank, n):
+    """Seed of the counter-based dropout masks of a process's n-th training forward (n = 1 for the first)."""
+    return (int(dropout_seed) * 0x9E3779B1 + rank * 0xC2B2AE3D27D4EB4F + n * SEED_STRIDE + 1) & 0xFFFFFFFFFFFFFFFF
+
+
+def _rank():
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def radar_frames(img_metas):
+    """[img_metas[i]['radar']]; a frame without one is refused."""
+    if any('radar' not in m for m in img_metas):
+        raise KeyError("img_metas[i]['radar'] is required: raw sweeps (transcar_amd/radar.py) or an [n,36] feature array")
+    return [m['radar'] for m in img_metas]
+
+
 def _cls_branch(embed, ncls):
     return nn.Sequential(
         nn.Linear(embed, embed), nn.LayerNorm(embed), nn.ReLU(inplace=True),
@@ -100,21 +138,36 @@ def _reg_branch(embed, code, inplace=True):
         nn.Linear(embed, code))
 
 
-def _lin(m):
-    return ops.linear_view(m.weight, m.bias)
+def _lin(m, ptr=ops._p):
+    return L.tc_linear(ptr(m.weight), ptr(m.bias))
 
 
-def _ln(m):
-    return ops.lnorm_view(m.weight, m.bias)
+def _ln(m, ptr=ops._p):
+    return L.tc_lnorm(ptr(m.weight), ptr(m.bias))
 
 
-def cls_branch_view(seq):
-    return L.tc_cls_branch(_lin(seq[0]), _ln(seq[1]), _lin(seq[3]),
-                           _ln(seq[4]), _lin(seq[6]))
+def cls_branch_view(seq, ptr=ops._p):
+    return L.tc_cls_branch(_lin(seq[0], ptr), _ln(seq[1], ptr), _lin(seq[3], ptr), _ln(seq[4], ptr), _lin(seq[6], ptr))
 
 
-def reg_branch_view(seq):
-    return L.tc_reg_branch(_lin(seq[0]), _lin(seq[2]), _lin(seq[4]))
+def reg_branch_view(seq, ptr=ops._p):
+    return L.tc_reg_branch(_lin(seq[0], ptr), _lin(seq[2], ptr), _lin(seq[4], ptr))
+
+
+def radar_table(head, w, ptr=ops._p):
+    """Fill the radar stack's part of the tc_head_weights `w` (the two encoders, ``head.num_fusion_layers`` layers) with
+    ptr(tensor): the parameters' addresses (Detr3DHead.weights_struct) or their gradients' (trainer.grad_table)."""
+    rpe, rfe = head.radar_position_encoder, head.radar_feat_encoder
+    w.radar_position_encoder = L.tc_pos_encoder(_lin(rpe[0], ptr), _ln(rpe[1], ptr), _lin(rpe[3], ptr), _ln(rpe[4], ptr))
+    w.radar_feat0, w.radar_feat2, w.radar_feat4 = _lin(rfe[0], ptr), _lin(rfe[2], ptr), _lin(rfe[4], ptr)
+    w.num_radar_layers = L.check_num_fusion_layers(head.num_fusion_layers)
+    for r in range(w.num_radar_layers):
+        m, rl = fusion_modules(head, r), w.radar[r]
+        rl.attn = L.tc_mha(L.tc_linear(ptr(m.attn.in_proj_weight), ptr(m.attn.in_proj_bias)), _lin(m.attn.out_proj, ptr))
+        rl.norm2, rl.norm3 = _ln(m.norm2, ptr), _ln(m.norm3, ptr)
+        rl.linear1, rl.linear2 = _lin(m.linear1, ptr), _lin(m.linear2, ptr)
+        rl.final_cls, rl.final_reg = cls_branch_view(m.final_cls, ptr), reg_branch_view(m.final_reg, ptr)
+    return w
 
 
 @HEADS.register_module(export=True)
@@ -184,21 +237,19 @@ class Detr3DHead(BaseModule):
             torch.tensor(code_weights, requires_grad=False),
             requires_grad=False)
         E, F = self.embed_dims, 512
-        for sfx in ('', '2', '3')[:self.num_fusion_layers]:
-            setattr(self, 'final_cls' + sfx,
-                    _cls_branch(E, self.cls_out_channels))
-            setattr(self, 'final_reg' + sfx, _reg_branch(E, self.code_size))
-        for sfx, asfx in FUSION_SUFFIXES[:self.num_fusion_layers]:
-            setattr(self, 'rf_multihead_attn' + asfx,
-                    nn.MultiheadAttention(E, 8, dropout=0.1))
-            setattr(self, 'rf_linear1' + sfx, nn.Linear(E, F))
-            setattr(self, 'rf_linear2' + sfx, nn.Linear(F, E))
-            for n in (1, 2, 3):
-                setattr(self, 'rf_norm%d%s' % (n, sfx), nn.LayerNorm(E))
+        names = [fusion_module_names(r) for r in range(self.num_fusion_layers)]
+        for nm in names:
+            setattr(self, nm['final_cls'], _cls_branch(E, self.cls_out_channels))
+            setattr(self, nm['final_reg'], _reg_branch(E, self.code_size))
+        for nm in names:
+            setattr(self, nm['attn'], nn.MultiheadAttention(E, 8, dropout=0.1))
+            setattr(self, nm['linear1'], nn.Linear(E, F))
+            setattr(self, nm['linear2'], nn.Linear(F, E))
+            for n in ('norm1', 'norm2', 'norm3'):
+                setattr(self, nm[n], nn.LayerNorm(E))
             # HEAD:132, 138-140 (rf_dropout1* is constructed but never used there either)
-            setattr(self, 'rf_dropout' + sfx, nn.Dropout(0.1))
-            for n in (1, 2, 3):
-                setattr(self, 'rf_dropout%d%s' % (n, sfx), nn.Dropout(0.1))
+            for n in ('dropout', 'dropout1', 'dropout2', 'dropout3'):
+                setattr(self, nm[n], nn.Dropout(0.1))
         self.radar_position_encoder = nn.Sequential(
             nn.Linear(3, E), nn.LayerNorm(E), nn.ReLU(inplace=True),
             nn.Linear(E, E), nn.LayerNorm(E), nn.ReLU(inplace=True))
@@ -215,6 +266,11 @@ class Detr3DHead(BaseModule):
         self._weights = None
         self._workspace = {}
         self._packed = None
+        self._packed_view = None        # tc_head_weights over `_packed`, written by `_pack`
+        #: the dropout masks of a training forward: seed base (FusionTrainer(seed=)), training forwards so far, last seed
+        self.dropout_seed = 0
+        self._train_forwards = 0
+        self.last_dropout_seed = None
         #: cls_branches / reg_branches packed for tc_decoder_outputs_fwd: (buffer, view, key), built by the first
         #: forward with outputs != 'fusion', dropped whenever the packed weights are (refresh_weights, load_state_dict)
         self._dec_heads = None
@@ -301,8 +357,7 @@ class Detr3DHead(BaseModule):
             h, lib = self.decoder_heads_struct(), L.lib()
             if lib.tc_decoder_heads_packed_bytes(C.byref(h)) == buf.numel():
                 L.check(lib.tc_decoder_heads_pack(C.byref(h), buf.data_ptr(), buf.numel(), C.byref(view),
-                                                  C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)),
-                        'tc_decoder_heads_pack')
+                                                  L.stream_ptr(buf.device)), 'tc_decoder_heads_pack')
                 self._dec_heads = (buf, view, w)
         return res
 
@@ -323,9 +378,7 @@ class Detr3DHead(BaseModule):
         return self._pack(w, L.lib())
 
     def _pack(self, w, lib):
-        nbytes = lib.tc_head_packed_bytes(C.byref(w))
-        if nbytes == 0:
-            raise L.TransCARHipError(lib.tc_last_error().decode())
+        nbytes = L.size_query(lib.tc_head_packed_bytes, C.byref(w))
         dev = self.query_embedding.weight.device
         # Re-pack IN PLACE when the buffer fits (load_state_dict / refresh_weights / a
         # FusionTrainer moving the parameters into its flat bucket): captured hipGraphs hold
@@ -334,11 +387,8 @@ class Detr3DHead(BaseModule):
             self._packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self.buffers_generation += 1
         self._packed_view = L.tc_head_weights()
-        L.check(lib.tc_head_pack_weights(
-            C.byref(w), self._packed.data_ptr(), nbytes,
-            C.byref(self._packed_view),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-            'tc_head_pack_weights')
+        L.check(lib.tc_head_pack_weights(C.byref(w), self._packed.data_ptr(), nbytes, C.byref(self._packed_view),
+                                         L.stream_ptr(dev)), 'tc_head_pack_weights')
         self._weights = w
         self._packed_dirty = False
         return w
@@ -371,7 +421,6 @@ class Detr3DHead(BaseModule):
         L.check_num_classes(self.cls_out_channels)
         w.num_classes, w.code_size = self.cls_out_channels, self.code_size
         w.radar_in_dims = radar.NUM_FEATURES
-        w.num_radar_layers = L.check_num_fusion_layers(self.num_fusion_layers)
         w.num_radar_tokens_ref = radar.NUM_RADAR_TOKENS
         for i in range(6):
             w.pc_range[i] = float(self.pc_range[i])
@@ -400,20 +449,9 @@ class Detr3DHead(BaseModule):
                 d.reg = reg_branch_view(self.reg_branches[i])
             else:
                 d.reg = L.tc_reg_branch()
-        w.radar_position_encoder = pos_encoder_view(self.radar_position_encoder)
-        w.radar_feat0 = _lin(self.radar_feat_encoder[0])
-        w.radar_feat2 = _lin(self.radar_feat_encoder[2])
-        w.radar_feat4 = _lin(self.radar_feat_encoder[4])
-        for r, (sfx, asfx) in enumerate(FUSION_SUFFIXES[:w.num_radar_layers]):
-            rl = w.radar[r]
-            rl.attn = mha_view(getattr(self, 'rf_multihead_attn' + asfx))
-            rl.norm2 = _ln(getattr(self, 'rf_norm2' + sfx))
-            rl.norm3 = _ln(getattr(self, 'rf_norm3' + sfx))
-            rl.linear1 = _lin(getattr(self, 'rf_linear1' + sfx))
-            rl.linear2 = _lin(getattr(self, 'rf_linear2' + sfx))
-            rl.final_cls = cls_branch_view(getattr(self, 'final_cls' + asfx))
-            rl.final_reg = reg_branch_view(getattr(self, 'final_reg' + asfx))
-            rl.radius_min, rl.radius_max = RADAR_RADII[r]
+        radar_table(self, w, ops._p)
+        for r in range(w.num_radar_layers):
+            w.radar[r].radius_min, w.radar[r].radius_max = RADAR_RADII[r]
         return w
 
     def decoder_heads_struct(self):
@@ -440,17 +478,52 @@ class Detr3DHead(BaseModule):
             return self._dec_heads[1]
         h = self.decoder_heads_struct()
         lib = L.lib()
-        nbytes = lib.tc_decoder_heads_packed_bytes(C.byref(h))
-        if nbytes == 0:
-            raise L.TransCARHipError(lib.tc_last_error().decode())
         dev = self.query_embedding.weight.device
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        buf = L.device_bytes(dev, lib.tc_decoder_heads_packed_bytes, C.byref(h))
         view = L.tc_decoder_heads()
-        L.check(lib.tc_decoder_heads_pack(C.byref(h), buf.data_ptr(), nbytes, C.byref(view),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+        L.check(lib.tc_decoder_heads_pack(C.byref(h), buf.data_ptr(), buf.numel(), C.byref(view), L.stream_ptr(dev)),
                 'tc_decoder_heads_pack')
         self._dec_heads = (buf, view, key)
         return view
+
+    # ------------------------------------------------------------------
+    # the f16-range guard's fall-back (`matrix_fallback`) and the options of one launch sequence
+    # ------------------------------------------------------------------
+    def effective_matrix_path(self, mp):
+        """The TC_MATRIX_* path a launch that asks for `mp` runs: f32 iff it asks for f32, or for the automatic path
+        after the f16-range guard fell back.  A pinned f16x2 is never touched."""
+        return L.TC_MATRIX_F32 if (mp == L.TC_MATRIX_AUTO and self.matrix_fallback) else mp
+
+    def effective_tile_rows(self, rows, mp, derived=False):
+        """The tile height next to `effective_matrix_path(mp)`: the 32-row tiles exist on the f16x2 path only, so a 32
+        becomes the f32 kernels' 16 where this head turned auto into f32.  An explicit (32, f32) stays, for the library
+        to refuse (tc_chain_tile_rows does not lower it) -- unless the rows are `derived` (FusionTrainer's, from its
+        look-ahead depth: nobody asked for 32 by name), which an explicit f32 demotes too."""
+        if rows == 32 and self.effective_matrix_path(mp) == L.TC_MATRIX_F32 and (derived or mp == L.TC_MATRIX_AUTO):
+            return 16
+        return rows
+
+    def _options_for(self, options, dev, w, key):
+        """The tc_head_options to hand tc_head_forward for the caller's `options`: the f16-range guard's status word
+        filled in, the fall-back applied and the camera pre-gather's scratch (one per workspace `key`, sized for the
+        weights `w`) where it is asked for without one.  The caller's struct stays as it is; no copy if nothing changes."""
+        mp = self.effective_matrix_path(options.matrix_path)
+        scratch = options.cam_pregather and not options.cam_pregather_ws
+        if options.range_status and mp == options.matrix_path and not scratch:
+            return options
+        own = L.tc_head_options()
+        C.memmove(C.byref(own), C.byref(options), C.sizeof(own))
+        if not own.range_status:
+            own.range_status = self.status_buffer(dev).data_ptr()
+        if mp != own.matrix_path:
+            own.chain_tile_rows = self.effective_tile_rows(own.chain_tile_rows, own.matrix_path)
+            own.matrix_path = mp
+        if scratch:
+            pk = ('pregather',) + key
+            if pk not in self._workspace:
+                self._workspace[pk] = L.device_bytes(dev, L.lib().tc_cam_pregather_workspace_bytes, C.byref(w), key[0])
+            own.cam_pregather_ws, own.cam_pregather_bytes = self._workspace[pk].data_ptr(), self._workspace[pk].numel()
+        return own
 
     def decoder_outputs(self, aux_t, options=None):
         """cls_branches[l] / reg_branches[l] of every decoder level (HEAD:277-298) from the decoder's kept states and
@@ -464,19 +537,15 @@ class Detr3DHead(BaseModule):
         out = torch.empty(Lyr * B * Q * (ncls + code), dtype=torch.float32, device=dev)
         cls = out[:Lyr * B * Q * ncls].view(Lyr, B, Q, ncls)
         box = out[Lyr * B * Q * ncls:].view(Lyr, B, Q, code)
-        own = L.tc_head_options()
         src = options if options is not None else (self.forward_options if self.forward_options is not None
                                                    else head_options())
-        own.chain_tile_rows, own.matrix_path = src.chain_tile_rows, src.matrix_path
+        own = L.tc_head_options()          # (of a forward's options this launch takes these three alone)
+        own.chain_tile_rows = self.effective_tile_rows(src.chain_tile_rows, src.matrix_path)
+        own.matrix_path = self.effective_matrix_path(src.matrix_path)
         own.range_status = src.range_status or self.status_buffer(dev).data_ptr()
-        if self.matrix_fallback and own.matrix_path == L.TC_MATRIX_AUTO:
-            own.matrix_path = L.TC_MATRIX_F32
-            if own.chain_tile_rows == 32:
-                own.chain_tile_rows = 16
         L.check(L.lib().tc_decoder_outputs_fwd(
             C.byref(view), hs.data_ptr(), aux_t['init_reference'].data_ptr(), aux_t['inter_references'].data_ptr(),
-            B, Q, cls.data_ptr(), box.data_ptr(), C.byref(own),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'tc_decoder_outputs_fwd')
+            B, Q, cls.data_ptr(), box.data_ptr(), C.byref(own), L.stream_ptr(dev)), 'tc_decoder_outputs_fwd')
         return cls, box
 
     def _check_outputs(self):
@@ -555,16 +624,11 @@ class Detr3DHead(BaseModule):
             return self.head_weights()
         dev = self.query_embedding.weight.device
         if trainable_only:
-            L.check(L.lib().tc_head_repack_trainable(
-                C.byref(self._weights), C.byref(self._packed_view),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                'tc_head_repack_trainable')
+            L.check(L.lib().tc_head_repack_trainable(C.byref(self._weights), C.byref(self._packed_view),
+                                                     L.stream_ptr(dev)), 'tc_head_repack_trainable')
             return self._weights
-        L.check(L.lib().tc_head_pack_weights(
-            C.byref(self._weights), self._packed.data_ptr(),
-            self._packed.numel(), C.byref(self._packed_view),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-            'tc_head_pack_weights')
+        L.check(L.lib().tc_head_pack_weights(C.byref(self._weights), self._packed.data_ptr(), self._packed.numel(),
+                                             C.byref(self._packed_view), L.stream_ptr(dev)), 'tc_head_pack_weights')
         return self._weights
 
     # ------------------------------------------------------------------
@@ -579,14 +643,7 @@ class Detr3DHead(BaseModule):
         float64 arithmetic as HEAD:311-521, bit-equal to the host builder except the six rotated-velocity
         columns, which agree to 1 ulp); [n,36] feature arrays, or ``ingest='host'``, take the numpy route of
         the reference.  T: fixed token count (default: the smallest multiple of 64 that holds the frame)."""
-        raws = []
-        for m in img_metas:
-            if 'radar' not in m:
-                raise KeyError(
-                    "img_metas[i]['radar'] is required: raw sweeps "
-                    '(transcar_amd/radar.py) or an [n,36] feature array')
-            raws.append(m['radar'])
-        tokens, pad_mult, fill = self._radar_tokens_plan(raws, device, T, ingest)
+        tokens, pad_mult, fill = self._radar_tokens_plan(radar_frames(img_metas), device, T, ingest)
         if fill is not None:
             fill()
         return tokens, pad_mult
@@ -596,7 +653,7 @@ class Detr3DHead(BaseModule):
         ``fill()`` does the work (host packing of the raw rows, three H2D copies per sample, one launch) -- so that
         ``forward`` can enqueue the part of the decoder that does not read the tokens first
         (tc_head_options.phase).  Otherwise the tokens are ready and fill is None."""
-        mode = ingest or getattr(self, 'radar_ingest', 'device')
+        mode = ingest or self.radar_ingest
         if mode == 'device' and all(isinstance(r, dict) for r in raws):
             n_raw = [sum(int(np.asarray(r['points'][c]).shape[1]) for c in radar.RADAR_CHANNELS) for r in raws]
             if T is None:
@@ -654,35 +711,9 @@ class Detr3DHead(BaseModule):
         lib = L.lib()
         key = (B, T, str(dev), int(lane))
         if key not in self._workspace:
-            nbytes = lib.tc_head_workspace_bytes(C.byref(w), B, T)
-            if nbytes == 0:
-                raise L.TransCARHipError(lib.tc_last_error().decode())
-            self._workspace[key] = torch.empty(nbytes, dtype=torch.uint8,
-                                               device=dev)
-        if options is None:
-            options = head_options()
-        if (not options.range_status or (self.matrix_fallback and options.matrix_path == L.TC_MATRIX_AUTO)
-                or (options.cam_pregather and not options.cam_pregather_ws)):
-            own = L.tc_head_options()                  # (the caller's struct stays as it is)
-            C.memmove(C.byref(own), C.byref(options), C.sizeof(own))
-            if not own.range_status:
-                own.range_status = self.status_buffer(dev).data_ptr()
-            if self.matrix_fallback and own.matrix_path == L.TC_MATRIX_AUTO:
-                own.matrix_path = L.TC_MATRIX_F32
-                if own.chain_tile_rows == 32:
-                    own.chain_tile_rows = 16
-            if own.cam_pregather and not own.cam_pregather_ws:
-                # scratch of the pre-gather workgroups: one per (batch, device, lane), like the workspace
-                pk = ('pregather',) + key
-                if pk not in self._workspace:
-                    nb = lib.tc_cam_pregather_workspace_bytes(C.byref(w), B)
-                    if nb == 0:
-                        raise L.TransCARHipError(lib.tc_last_error().decode())
-                    self._workspace[pk] = torch.empty(nb, dtype=torch.uint8, device=dev)
-                own.cam_pregather_ws = self._workspace[pk].data_ptr()
-                own.cam_pregather_bytes = self._workspace[pk].numel()
-            options = own
+            self._workspace[key] = L.device_bytes(dev, lib.tc_head_workspace_bytes, C.byref(w), B, T)
         ws = self._workspace[key]
+        options = self._options_for(options if options is not None else head_options(), dev, w, key)
         Q, ncls, code = self.num_query, self.cls_out_channels, self.code_size
         NF = self.num_fusion_layers
         # one allocation, two views (_out: a static buffer of a captured graph, transcar_amd/plugin_graph.py)
@@ -693,31 +724,21 @@ class Detr3DHead(BaseModule):
         box = out[NF * B * Q * ncls:].view(NF, B, Q, code)
         fv = ops.feats_view(feats_nhwc)
         aux_s, aux_t = None, None
-        if aux == 'train':
-            # what a training iteration needs of the frozen decoder (FusionTrainer): its states / references / last box,
-            # written in place by the chains -- no init_reference copy, no pair counter (a zero fill + atomics)
-            Lyr = w.num_layers
-            aux_t = dict(
-                inter_states=torch.empty((Lyr, B, Q, self.embed_dims), dtype=torch.float32, device=dev),
-                inter_references=torch.empty((Lyr, B, Q, 3), dtype=torch.float32, device=dev),
-                last_box=torch.empty((B, Q, code), dtype=torch.float32, device=dev))
+        if aux:
+            # aux='train': what a training iteration needs of the frozen decoder (FusionTrainer), its states / references
+            # / last box, written in place by the chains -- no init_reference copy, no pair counter (a zero fill + atomics)
+            Lyr, full, f32 = w.num_layers, aux != 'train', dict(dtype=torch.float32, device=dev)
+            aux_t = dict(inter_states=torch.empty((Lyr, B, Q, self.embed_dims), **f32))
+            if full:
+                aux_t['init_reference'] = torch.empty((B, Q, 3), **f32)
+            aux_t['inter_references'] = torch.empty((Lyr, B, Q, 3), **f32)
+            if full:
+                aux_t['radar_hit_counts'] = torch.empty((NF, B, Q), dtype=torch.int32, device=dev)
+            aux_t['last_box'] = torch.empty((B, Q, code), **f32)
+            if full:
+                aux_t['sample_pairs'] = torch.zeros(1, dtype=torch.int64, device=dev)
             aux_s = L.tc_head_aux(**{k: t.data_ptr() for k, t in aux_t.items()})
-        elif aux:
-            Lyr = w.num_layers
-            aux_t = dict(
-                inter_states=torch.empty((Lyr, B, Q, self.embed_dims),
-                                         dtype=torch.float32, device=dev),
-                init_reference=torch.empty((B, Q, 3), dtype=torch.float32,
-                                           device=dev),
-                inter_references=torch.empty((Lyr, B, Q, 3),
-                                             dtype=torch.float32, device=dev),
-                radar_hit_counts=torch.empty((NF, B, Q), dtype=torch.int32,
-                                             device=dev),
-                last_box=torch.empty((B, Q, code), dtype=torch.float32,
-                                     device=dev),
-                sample_pairs=torch.zeros(1, dtype=torch.int64, device=dev))
-            aux_s = L.tc_head_aux(**{k: t.data_ptr()
-                                     for k, t in aux_t.items()})
+
         def call(opts):
             L.check(lib.tc_head_forward(
                 C.byref(w), C.byref(packed), C.byref(fv), B,
@@ -725,9 +746,7 @@ class Detr3DHead(BaseModule):
                 float(img_hw[0]), float(img_hw[1]), tokens.data_ptr(), T,
                 int(pad_mult), cls.data_ptr(), box.data_ptr(),
                 C.byref(aux_s) if aux_s is not None else None,
-                C.byref(opts), ws.data_ptr(), ws.numel(),
-                C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                'tc_head_forward')
+                C.byref(opts), ws.data_ptr(), ws.numel(), L.stream_ptr()), 'tc_head_forward')
         if fill_tokens is None:
             call(options)
         elif options.unfused or options.phase != 0:
@@ -768,11 +787,7 @@ class Detr3DHead(BaseModule):
                 '(got %s); transcar_amd has no CPU path' % dev)
         if self.outputs == 'camera':
             return self._forward_camera(mlvl_feats, img_metas, aux)
-        for m in img_metas:
-            if 'radar' not in m:
-                raise KeyError(
-                    "img_metas[i]['radar'] is required: raw sweeps "
-                    '(transcar_amd/radar.py) or an [n,36] feature array')
+        raws = radar_frames(img_metas)
         # round 6: a call signature seen before (same feature-map addresses, shapes, options) replays two captured
         # graphs instead of ~20 eager launches (transcar_amd/plugin_graph.py); anything else takes the eager path below
         if self._plugin_graphs is None:
@@ -785,13 +800,6 @@ class Detr3DHead(BaseModule):
         feats_nhwc = ops.to_nhwc_levels(mlvl_feats)       # one launch; channels_last levels zero-copy
         l2i = ops.lidar2img_tensor(img_metas, dev, staged=True)    # pinned ring, one async H2D (none if unchanged)
         img_hw = img_metas[0]['img_shape'][0][:2]           # XFMR:403-404
-        raws = []
-        for m in img_metas:
-            if 'radar' not in m:
-                raise KeyError(
-                    "img_metas[i]['radar'] is required: raw sweeps "
-                    '(transcar_amd/radar.py) or an [n,36] feature array')
-            raws.append(m['radar'])
         tokens, pad_mult, fill = self._radar_tokens_plan(raws, dev)
         if self.training:
             if fill is not None:
@@ -875,12 +883,11 @@ class Detr3DHead(BaseModule):
         mem = pos + f
 
         all_cls, all_box = [], []
-        for r, (sfx, asfx) in enumerate(FUSION_SUFFIXES[:self.num_fusion_layers]):
-            attn = getattr(self, 'rf_multihead_attn' + asfx)
+        for r in range(self.num_fusion_layers):
+            m = fusion_modules(self, r)
+            attn = m.attn
             p_attn = float(attn.dropout)
-            p_ffn = float(getattr(self, 'rf_dropout' + sfx).p)
-            p2 = float(getattr(self, 'rf_dropout2' + sfx).p)
-            p3 = float(getattr(self, 'rf_dropout3' + sfx).p)
+            p_ffn, p2, p3 = float(m.dropout.p), float(m.dropout2.p), float(m.dropout3.p)
             wq, bq = attn.in_proj_weight[:E], attn.in_proj_bias[:E]
             wkv, bkv = attn.in_proj_weight[E:], attn.in_proj_bias[E:]
             qp = A.linear(qf, wq, bq)
@@ -898,16 +905,12 @@ class Detr3DHead(BaseModule):
             else:
                 x = A.gated_linear_residual(ao, attn.out_proj.weight,
                                             attn.out_proj.bias, qf, hits)
-            n2 = getattr(self, 'rf_norm2' + sfx)
-            n3 = getattr(self, 'rf_norm3' + sfx)
-            l1 = getattr(self, 'rf_linear1' + sfx)
-            l2 = getattr(self, 'rf_linear2' + sfx)
+            n2, n3, l1, l2 = m.norm2, m.norm3, m.linear1, m.linear2
             x = A.add_layernorm(x, None, n2.weight, n2.bias)
             h = A.dropout(A.linear(x, l1.weight, l1.bias, act=1), p_ffn, seed, 4 * r + 2)
             ff = A.dropout(A.linear(h, l2.weight, l2.bias), p3, seed, 4 * r + 3)
             qf = A.add_layernorm(x, ff, n3.weight, n3.bias)
-            fc = getattr(self, 'final_cls' + asfx)
-            fr = getattr(self, 'final_reg' + asfx)
+            fc, fr = m.final_cls, m.final_reg
             c = A.linear(qf, fc[0].weight, fc[0].bias)
             c = A.add_layernorm(c, None, fc[1].weight, fc[1].bias, relu=True)
             c = A.linear(c, fc[3].weight, fc[3].bias)
@@ -928,11 +931,7 @@ class Detr3DHead(BaseModule):
     def peek_dropout_seed(self, ahead=1):
         """The seed `next_dropout_seed` will return on its `ahead`-th next call (nothing is advanced): a look-ahead of
         the frozen decoder draws the masks of the iterations that will consume it (FusionTrainer.prefetch_decoder)."""
-        import torch.distributed as dist
-        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-        n = getattr(self, '_train_forwards', 0) + int(ahead)
-        return (int(getattr(self, 'dropout_seed', 0)) * 0x9E3779B1 + rank * 0xC2B2AE3D27D4EB4F
-                + n * 0x85EBCA77 + 1) & 0xFFFFFFFFFFFFFFFF
+        return dropout_seed_of(self.dropout_seed, _rank(), self._train_forwards + int(ahead))
 
     def next_dropout_seed(self):
         """Seed of the counter-based dropout masks of ONE training forward: a function of
@@ -941,22 +940,19 @@ class Detr3DHead(BaseModule):
         from this one counter, so they are seed-compatible; ranks draw different masks as the
         reference's per-process RNG streams do; gradient-accumulation steps (no optimizer step
         in between) get fresh masks."""
-        import torch.distributed as dist
-        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-        self._train_forwards = getattr(self, '_train_forwards', 0) + 1
-        seed = (int(getattr(self, 'dropout_seed', 0)) * 0x9E3779B1 + rank * 0xC2B2AE3D27D4EB4F
-                + self._train_forwards * 0x85EBCA77 + 1) & 0xFFFFFFFFFFFFFFFF
-        self.last_dropout_seed = seed
+        self._train_forwards += 1
+        seed = self.last_dropout_seed = dropout_seed_of(self.dropout_seed, _rank(), self._train_forwards)
         return seed
 
     def set_dropout(self, p, decoder=True):
         """p of every dropout site of the radar fusion layers (HEAD:129-171 build
         them with 0.1) and, with ``decoder``, of the frozen decoder layers
         (CFG:68-80, XFMR:378): 0.0 = the deterministic training forward."""
-        for sfx, asfx in FUSION_SUFFIXES[:self.num_fusion_layers]:
-            getattr(self, 'rf_multihead_attn' + asfx).dropout = float(p)
-            for name in ('rf_dropout', 'rf_dropout1', 'rf_dropout2', 'rf_dropout3'):
-                getattr(self, name + sfx).p = float(p)
+        for r in range(self.num_fusion_layers):
+            m = fusion_modules(self, r)
+            m.attn.dropout = float(p)
+            for d in (m.dropout, m.dropout1, m.dropout2, m.dropout3):
+                d.p = float(p)
         if decoder:
             self.set_decoder_dropout(p)
         return self

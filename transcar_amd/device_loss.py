@@ -15,10 +15,6 @@ from scipy.optimize import linear_sum_assignment
 from . import _lib as L
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def gt_tensors(gt_bboxes_list, device):
     """mmdet3d LiDARInstance3DBoxes (gravity_center / tensor) or plain [n,9]
     gravity-centre tensors -> list of [n,9] fp32 tensors (HEAD:963-966)."""
@@ -76,7 +72,7 @@ def detr_loss_device(head, all_cls, all_box, gt_bboxes_list, gt_labels_list, bef
                 lab[b, :counts[b]] = l.to(device=dev, dtype=torch.int32)
         cnt = torch.from_numpy(np.asarray(counts, dtype=np.int32)).to(dev)
         gtn = torch.empty((B, Gmax, 10), dtype=torch.float32, device=dev)
-        L.check(lib.tc_normalize_bbox(gt9.data_ptr(), B * Gmax, gtn.data_ptr(), _stream()), 'tc_normalize_bbox')
+        L.check(lib.tc_normalize_bbox(gt9.data_ptr(), B * Gmax, gtn.data_ptr(), L.stream_ptr()), 'tc_normalize_bbox')
         cache = head._gt_cache = (key, counts, Gmax, lab, cnt, gtn, list(gt_bboxes_list), list(gt_labels_list))
     _, counts, Gmax, lab, cnt, gtn = cache[:6]
     a = head.assigner
@@ -85,7 +81,7 @@ def detr_loss_device(head, all_cls, all_box, gt_bboxes_list, gt_labels_list, bef
         all_cls.data_ptr(), all_box.data_ptr(), Lyr, B, Q, ncls, code, gtn.data_ptr(), lab.data_ptr(),
         cnt.data_ptr(), Gmax, float(a.cls_cost.weight), float(a.reg_cost.weight),
         float(getattr(a.cls_cost, 'alpha', 0.25)), float(getattr(a.cls_cost, 'gamma', 2.0)),
-        float(getattr(a.cls_cost, 'eps', 1e-12)), cost.data_ptr(), _stream()), 'tc_match_cost')
+        float(getattr(a.cls_cost, 'eps', 1e-12)), cost.data_ptr(), L.stream_ptr()), 'tc_match_cost')
     if before_sync is not None:        # work the device can do while the host waits and solves the assignment
         before_sync()
     if device_assign is None:
@@ -130,7 +126,7 @@ def detr_loss_device(head, all_cls, all_box, gt_bboxes_list, gt_labels_list, bef
         Gmax, asg.data_ptr(), avg.data_ptr(), head.code_weights.data_ptr(),
         float(lc.get('alpha', 0.25)), float(lc.get('gamma', 2.0)), float(lc.get('loss_weight', 1.0)),
         float(lb.get('loss_weight', 1.0)), losses.data_ptr(), d_cls.data_ptr(), d_box.data_ptr(),
-        _stream()), 'tc_detr_loss_fwd_bwd')
+        L.stream_ptr()), 'tc_detr_loss_fwd_bwd')
     # HEAD:915-916 zeroes a NaN loss (`loss[torch.isnan(loss)] = 0`); its gradient must not reach the flat
     # bucket / the Adam moments either: a layer whose loss is not finite contributes nothing
     if defer_guard:
@@ -164,7 +160,7 @@ def _loss_with_device_assignment(head, lib, all_cls, all_box, cost, cache, defer
         ws = head._lsa_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     L.check(lib.tc_lsa_assign_ws(cost.data_ptr(), cnt.data_ptr(), Lyr, B, Q, Gmax, asg.data_ptr(), num_pos.data_ptr(),
                                  status.data_ptr(), losses.data_ptr(), ws.data_ptr() if need else None,
-                                 ws.numel() if need else 0, L.TC_LSA_AUTO, _stream()), 'tc_lsa_assign_ws')
+                                 ws.numel() if need else 0, L.TC_LSA_AUTO, L.stream_ptr()), 'tc_lsa_assign_ws')
     # > 0: a sample had a non-finite cost.  scipy raises there (ASSIGN:117-125) and the reference stops; here the
     # output's losses are poisoned (NaN: the backward's guard then sends no gradient down) and the word travels to
     # the host without a synchronisation -- FusionTrainer raises at its next step (check_assign_status)
@@ -186,7 +182,7 @@ def _loss_with_device_assignment(head, lib, all_cls, all_box, cost, cache, defer
         Gmax, asg.data_ptr(), avg.data_ptr(), head.code_weights.data_ptr(),
         float(lc.get('alpha', 0.25)), float(lc.get('gamma', 2.0)), float(lc.get('loss_weight', 1.0)),
         float(lb.get('loss_weight', 1.0)), losses.data_ptr(), d_cls.data_ptr(), d_box.data_ptr(),
-        _stream()), 'tc_detr_loss_fwd_bwd_counts')
+        L.stream_ptr()), 'tc_detr_loss_fwd_bwd_counts')
     if defer_guard:
         return None, d_cls, d_box, asg, losses
     fin = torch.isfinite(losses)

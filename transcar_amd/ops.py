@@ -13,10 +13,6 @@ import torch
 from . import _lib as L
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _p(t):
     if t is None:
         return None
@@ -59,7 +55,7 @@ def to_nhwc(feat, out=None):
     if out is None:
         out = torch.empty((n, h, w, c), dtype=torch.float32,
                           device=feat.device)
-    L.check(L.lib().tc_nchw_to_nhwc(_p(feat), _p(out), n, c, h, w, _stream()),
+    L.check(L.lib().tc_nchw_to_nhwc(_p(feat), _p(out), n, c, h, w, L.stream_ptr()),
             'tc_nchw_to_nhwc')
     return out
 
@@ -95,7 +91,7 @@ def to_nhwc_levels(feats, out=None):
         hs = (C.c_int * k)(*[f.shape[2] for f, _ in todo])
         ws = (C.c_int * k)(*[f.shape[3] for f, _ in todo])
         L.check(L.lib().tc_nchw_to_nhwc_levels(src, dst, k, todo[0][0].shape[0],
-                                               todo[0][0].shape[1], hs, ws, _stream()),
+                                               todo[0][0].shape[1], hs, ws, L.stream_ptr()),
                 'tc_nchw_to_nhwc_levels')
     return res
 
@@ -127,7 +123,7 @@ def linear(x, weight, bias, x2=None, res=None, act=0):
     K, N = x.shape[-1], weight.shape[0]
     y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
     L.check(L.lib().tc_linear_fwd(_p(x), _p(x2), _p(weight), _p(bias), _p(res),
-                                  _p(y), M, K, N, act, _stream()),
+                                  _p(y), M, K, N, act, L.stream_ptr()),
             'tc_linear_fwd')
     return y
 
@@ -139,7 +135,7 @@ def add_layernorm(a, b, gamma, beta, relu=False):
     y = torch.empty_like(a)
     L.check(L.lib().tc_add_layernorm_fwd(_p(a), _p(b), _p(gamma), _p(beta),
                                          _p(y), a.numel() // Cdim, Cdim,
-                                         1 if relu else 0, _stream()),
+                                         1 if relu else 0, L.stream_ptr()),
             'tc_add_layernorm_fwd')
     return y
 
@@ -150,7 +146,7 @@ def refine_reference(reg_out, ref):
     new_ref = torch.empty_like(ref)
     L.check(L.lib().tc_refine_reference_fwd(
         _p(reg_out), reg_out.shape[-1], _p(ref), _p(new_ref),
-        ref.numel() // 3, _stream()), 'tc_refine_reference_fwd')
+        ref.numel() // 3, L.stream_ptr()), 'tc_refine_reference_fwd')
     return new_ref
 
 
@@ -171,12 +167,12 @@ def cam_sample_fuse(feats_nhwc, lidar2img, ref, attn_logits, pc_range, img_hw,
         L.check(L.lib().tc_cam_sample_fuse_fwd(
             C.byref(fv), B, Q, Cdim, num_cams, _p(lidar2img), _p(ref),
             _p(attn_logits), L.f6(pc_range), float(img_hw[0]), float(img_hw[1]),
-            _p(out), _p(vis), None, _stream()), 'tc_cam_sample_fuse_fwd')
+            _p(out), _p(vis), None, L.stream_ptr()), 'tc_cam_sample_fuse_fwd')
     else:
         L.check(L.lib().tc_cam_sample_fuse_points_fwd(
             C.byref(fv), B, Q, Cdim, num_cams, int(num_points), _p(lidar2img),
             _p(ref), _p(attn_logits), L.f6(pc_range), float(img_hw[0]),
-            float(img_hw[1]), _p(out), _p(vis), None, _stream()),
+            float(img_hw[1]), _p(out), _p(vis), None, L.stream_ptr()),
             'tc_cam_sample_fuse_points_fwd')
     return (out, vis) if return_mask else out
 
@@ -198,7 +194,7 @@ def cross_atten(aw, oproj, pe, feats_nhwc, query, query_pos, lidar2img, ref,
             C.byref(aw), C.byref(oproj), C.byref(pe), C.byref(fv), B, Q, Cdim,
             num_cams, _p(query), _p(query_pos), _p(lidar2img), _p(ref),
             L.f6(pc_range), float(img_hw[0]), float(img_hw[1]), _p(out), _p(ws),
-            nbytes, _stream()), 'tc_cross_atten_fwd')
+            nbytes, L.stream_ptr()), 'tc_cross_atten_fwd')
         return out
     nbytes = L.lib().tc_cross_atten_points_workspace_bytes(
         B, Q, Cdim, num_cams, fv.num_levels, int(num_points))
@@ -207,7 +203,7 @@ def cross_atten(aw, oproj, pe, feats_nhwc, query, query_pos, lidar2img, ref,
         C.byref(aw), C.byref(oproj), C.byref(pe), C.byref(fv), B, Q, Cdim,
         num_cams, int(num_points), _p(query), _p(query_pos), _p(lidar2img),
         _p(ref), L.f6(pc_range), float(img_hw[0]), float(img_hw[1]), _p(out),
-        _p(ws), nbytes, _stream()), 'tc_cross_atten_points_fwd')
+        _p(ws), nbytes, L.stream_ptr()), 'tc_cross_atten_points_fwd')
     return out
 
 
@@ -220,7 +216,7 @@ def self_attn(mha, x, pos, num_heads=8):
     out = torch.empty_like(x)
     L.check(L.lib().tc_self_attn_fwd(C.byref(mha), _p(x), _p(pos), _p(out), B,
                                      Q, Cdim, num_heads, _p(ws), nbytes,
-                                     _stream()), 'tc_self_attn_fwd')
+                                     L.stream_ptr()), 'tc_self_attn_fwd')
     return out
 
 
@@ -241,19 +237,19 @@ def sdpa(q, k, vt, num_heads=8, matrix_path='f32', head_dim=None):
                                      % (num_heads, head_dim, Cdim))
         if matrix_path == 'f16x2':
             L.check(L.lib().tc_sdpa_fwd_f16x2_hd(qk.data_ptr(), _p(vt), vt.shape[-1], _p(out), Cdim, B, Q, num_heads,
-                                                 int(head_dim), _stream()), 'tc_sdpa_fwd_f16x2_hd')
+                                                 int(head_dim), L.stream_ptr()), 'tc_sdpa_fwd_f16x2_hd')
         else:
             L.check(L.lib().tc_sdpa_fwd_hd(qk.data_ptr(), qk.data_ptr() + 4 * Cdim, 2 * Cdim, _p(vt), vt.shape[-1],
-                                           _p(out), Cdim, B, Q, num_heads, int(head_dim), _stream()),
+                                           _p(out), Cdim, B, Q, num_heads, int(head_dim), L.stream_ptr()),
                     'tc_sdpa_fwd_hd')
         return out
     if matrix_path == 'f16x2':
         ws = torch.empty(L.lib().tc_sdpa_f16x2_workspace_bytes(B, Q, num_heads), dtype=torch.uint8, device=q.device)
         L.check(L.lib().tc_sdpa_fwd_f16x2(qk.data_ptr(), _p(vt), vt.shape[-1], _p(out), Cdim, B, Q, num_heads,
-                                          ws.data_ptr(), ws.numel(), _stream()), 'tc_sdpa_fwd_f16x2')
+                                          ws.data_ptr(), ws.numel(), L.stream_ptr()), 'tc_sdpa_fwd_f16x2')
         return out
     L.check(L.lib().tc_sdpa_fwd(qk.data_ptr(), qk.data_ptr() + 4 * Cdim, 2 * Cdim, _p(vt),
-                                vt.shape[-1], _p(out), Cdim, B, Q, num_heads, _stream()),
+                                vt.shape[-1], _p(out), Cdim, B, Q, num_heads, L.stream_ptr()),
             'tc_sdpa_fwd')
     return out
 
@@ -282,7 +278,7 @@ def decoder_layer_tail(packed_layer, packed_next_in_proj, feats_nhwc, attn_o, x_
         C.byref(packed_layer), C.byref(packed_next_in_proj) if packed_next_in_proj is not None else None,
         C.byref(fv), B, Q, num_cams, code_size, _p(attn_o), _p(x_in), _p(query_embedding),
         _p(lidar2img), _p(ref_in), L.f6(pc_range), float(img_hw[0]), float(img_hw[1]), _p(hs),
-        _p(ref_out), _p(qk), _p(vt), qpad, int(tile_rows) | (int(matrix_path) << 8), _stream()), 'tc_decoder_layer_tail_fwd')
+        _p(ref_out), _p(qk), _p(vt), qpad, int(tile_rows) | (int(matrix_path) << 8), L.stream_ptr()), 'tc_decoder_layer_tail_fwd')
     return hs, ref_out, qk, vt
 
 
@@ -313,7 +309,7 @@ def radar_fusion(head, hs_last, ref_last, prev_box, tokens, pad_mult, first_laye
     L.check(L.lib().tc_radar_fusion_fwd(
         C.byref(pv), _p(hs_last), _p(ref_last), _p(prev_box), _p(tokens), B, T, int(pad_mult),
         int(first_layer), int(num_layers), _p(cls), _p(box), _p(hits),
-        C.byref(options) if options is not None else None, _p(ws), ws.numel() * ws.element_size(), _stream()),
+        C.byref(options) if options is not None else None, _p(ws), ws.numel() * ws.element_size(), L.stream_ptr()),
         'tc_radar_fusion_fwd')
     return cls, box, hits
 
@@ -335,7 +331,7 @@ def radar_gated_xattn(mha, query, centre_xy, box, radar_feat, radar_xy,
         C.byref(mha), _p(query), _p(centre_xy), _p(box), box.shape[-1],
         _p(radar_feat), _p(radar_xy), B, Q, T, Cdim, num_heads, int(pad_mult),
         float(rmin), float(rmax), _p(out), _p(hits), _p(ws), nbytes,
-        _stream()), 'tc_radar_gated_xattn_fwd')
+        L.stream_ptr()), 'tc_radar_gated_xattn_fwd')
     return out, hits
 
 
@@ -386,7 +382,7 @@ def radar_build_tokens(frame, T, device, out=None, point_range=None, check=False
     L.check(L.lib().tc_radar_build_tokens(
         _p(raw_d), _p(times_d), start.ctypes.data_as(C.POINTER(C.c_int)), len(R.RADAR_CHANNELS),
         rr.ctypes.data_as(C.POINTER(C.c_double)), lr.ctypes.data_as(C.POINTER(C.c_double)), pr,
-        _p(out), int(T), _p(count), _stream()), 'tc_radar_build_tokens')
+        _p(out), int(T), _p(count), L.stream_ptr()), 'tc_radar_build_tokens')
     if check:
         radar_check_fits(count, T)
     return out, count, R.NUM_RADAR_TOKENS - T + 1
@@ -507,7 +503,7 @@ class RadarRawStage:
                 or tokens.dtype != torch.float32:
             raise L.TransCARHipError('tokens must be a contiguous fp32 [>=%d,T,%d] tensor' % (n, R.NUM_FEATURES))
         L.check(L.lib().tc_radar_build_tokens_batch(_p(self.raw), _p(self.times), _p(self.desc), n, self.cap,
-                                                    _p(tokens), T, _p(self.count), _stream()),
+                                                    _p(tokens), T, _p(self.count), L.stream_ptr()),
                 'tc_radar_build_tokens_batch')
         return tokens, R.NUM_RADAR_TOKENS - T + 1
 
@@ -544,7 +540,7 @@ def box_decode_topk(cls_scores, bbox_preds, post_center_range, max_num=300, path
     L.check(L.lib().tc_box_decode_topk_path(
         _p(cls_scores), _p(bbox_preds), B, Q, ncls, bbox_preds.shape[-1],
         max_num, L.f6(post_center_range), _p(boxes), _p(scores), _p(labels),
-        _p(valid), None, 0, _stream(), int(path)), 'tc_box_decode_topk')
+        _p(valid), None, 0, L.stream_ptr(), int(path)), 'tc_box_decode_topk')
     return boxes, scores, labels, valid
 
 
@@ -572,7 +568,7 @@ def box_decode_kept(cls_scores, bbox_preds, post_center_range, max_num=300, scor
     L.check(L.lib().tc_box_decode_kept_path(
         _p(cls_scores), _p(bbox_preds), B, Q, ncls, bbox_preds.shape[-1], max_num, L.f6(post_center_range),
         float(score_threshold) if use_thr else 0.0, int(use_thr), int(bool(z_shift)),
-        _p(boxes), _p(scores), _p(labels), _p(count), _stream(), int(path)), 'tc_box_decode_kept')
+        _p(boxes), _p(scores), _p(labels), _p(count), L.stream_ptr(), int(path)), 'tc_box_decode_kept')
     return boxes, scores, labels, count
 
 

@@ -120,10 +120,7 @@ class FramePipeline:
 
     def _auto_tile_rows(self, rows):
         """the library's automatic choice for `rows` rows per launch (after the f16-range guard's fall-back: f32)"""
-        mp = int(self.options.matrix_path)
-        if mp == _L.TC_MATRIX_AUTO and self.head.matrix_fallback:
-            mp = _L.TC_MATRIX_F32
-        return _L.chain_tile_rows(rows, 0, mp)
+        return _L.chain_tile_rows(rows, 0, self.head.effective_matrix_path(int(self.options.matrix_path)))
 
     def tile_rows_of(self, n=None):
         """Row-tile height of a launch over n (default: all) frame slots of a lane."""
@@ -173,7 +170,7 @@ class FramePipeline:
     def _check_outputs(self):
         """The lanes capture the fusion outputs only.  ``Detr3DHead.outputs`` is a plain attribute that may change after
         the pipeline was built: checked at construction, at every capture and at every launch."""
-        if getattr(self.head, 'outputs', 'fusion') != 'fusion':
+        if self.head.outputs != 'fusion':
             raise TransCARHipError(
                 "FramePipeline: Detr3DHead.outputs=%r is not supported in a pipeline (its lanes capture the fusion "
                 "outputs only); use outputs='fusion' or the eager Detr3DHead.forward" % (self.head.outputs,))
@@ -246,7 +243,7 @@ class FramePipeline:
             raise TransCARHipError(
                 'FramePipeline: the head re-allocated device buffers (packed weights / workspaces) '
                 'after these graphs were captured; call recapture()')
-        if getattr(self.head, '_packed_dirty', False):
+        if self.head._packed_dirty:
             # an optimizer step since the last replay: the re-pack (current stream) overwrites the packed
             # buffer that EVERY lane's graph reads -- it must come after all replays still in flight
             cur = torch.cuda.current_stream()

@@ -22,6 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from .detr3d_head import MATRIX_PATHS, SEED_STRIDE, head_options, radar_table
 
 
 def exchange_chunk_of(name, num_fusion_layers=3):
@@ -142,37 +143,17 @@ def _g(t):
 def grad_table(head):
     """tc_head_weights whose pointers are the .grad buffers of the trainable stack's
     parameters (the table tc_radar_train_bwd adds into)."""
-    def lin(m):
-        return L.tc_linear(_g(m.weight), _g(m.bias))
-
-    def ln(m):
-        return L.tc_lnorm(_g(m.weight), _g(m.bias))
-
     g = L.tc_head_weights()
     g.abi_version = L.TC_ABI_VERSION
-    rpe, rfe = head.radar_position_encoder, head.radar_feat_encoder
-    g.radar_position_encoder = L.tc_pos_encoder(lin(rpe[0]), ln(rpe[1]), lin(rpe[3]), ln(rpe[4]))
-    g.radar_feat0, g.radar_feat2, g.radar_feat4 = lin(rfe[0]), lin(rfe[2]), lin(rfe[4])
-    g.num_radar_layers = head.num_fusion_layers
-    for r, (sfx, asfx) in enumerate((('', ''), ('_2', '2'), ('_3', '3'))[:head.num_fusion_layers]):
-        rl = g.radar[r]
-        attn = getattr(head, 'rf_multihead_attn' + asfx)
-        rl.attn = L.tc_mha(L.tc_linear(_g(attn.in_proj_weight), _g(attn.in_proj_bias)),
-                           lin(attn.out_proj))
-        rl.norm2, rl.norm3 = ln(getattr(head, 'rf_norm2' + sfx)), ln(getattr(head, 'rf_norm3' + sfx))
-        rl.linear1, rl.linear2 = lin(getattr(head, 'rf_linear1' + sfx)), lin(getattr(head, 'rf_linear2' + sfx))
-        fc, fr = getattr(head, 'final_cls' + asfx), getattr(head, 'final_reg' + asfx)
-        rl.final_cls = L.tc_cls_branch(lin(fc[0]), ln(fc[1]), lin(fc[3]), ln(fc[4]), lin(fc[6]))
-        rl.final_reg = L.tc_reg_branch(lin(fr[0]), lin(fr[2]), lin(fr[4]))
-    return g
+    return radar_table(head, g, _g)
 
 
 class FusionTrainer:
     """head: transcar_amd.Detr3DHead on the GPU, built with ``train_cfg``."""
 
-    #: coefficient of the forward counter in Detr3DHead.next_dropout_seed: consecutive training forwards draw
-    #: seeds this far apart, which is what lets ONE launch give every frame of a look-ahead batch its own masks
-    SEED_STRIDE = 0x85EBCA77
+    #: coefficient of the forward counter in Detr3DHead.next_dropout_seed (detr3d_head.dropout_seed_of): consecutive
+    #: training forwards draw seeds this far apart, which lets ONE launch give every frame of a look-ahead batch its masks
+    SEED_STRIDE = SEED_STRIDE
 
     def __init__(self, head, lr=1.5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01,
                  max_norm=35.0, device_loss=True, dropout=0.1, seed=0, decoder_dropout=None,
@@ -240,19 +221,29 @@ class FusionTrainer:
         rows = self.prefetch_depth * int(head.num_query)
         self.decoder_tile_rows = max(16, L.chain_tile_rows(rows)) if self.prefetch_depth > 1 else None
 
+        #: matrix path of the frozen decoder's forward (head_options(matrix_path=)): None / 'auto', 'f32', 'f16x2'
+        self.decoder_matrix_path = None
+        # the look-ahead: the batch in use and the one behind it (`prefetch_decoder`), its side stream; the head lane of
+        # the decoder forward in use, the generation of `invalidate_lookahead`, frames taken from a look-ahead so far
+        self._pre = self._pre_next = self._pre_stream = None
+        self._lane = self._generation = self.lookahead_hits = 0
+        # allocated anew when their key changes: tape and backward workspace (B, T), gradient table (bucket address)
+        self._tape = self._tape_key = self._bws = self._bws_key = self._gtab = self._gtab_key = None
+        self._wT_ready, self.last_dropout_seed = False, None
+        #: keep_last = True: `_last` holds the operands of the last backward call (tests).  The three lists, when set,
+        #: collect timing events (bench.py --full --train): per chunk's gradients, around the exchange wait, that per chunk
+        self.keep_last, self._last = False, None
+        self.chunk_events = self.exchange_events = self.exchange_chunk_events = None
+
     def _decoder_tile_rows_now(self):
         """`decoder_tile_rows`, resolved at the call: 32-row tiles exist on the f16x2 matrix path only, so with
         ``decoder_matrix_path = 'f32'`` -- or after the f16-range guard's fall-back -- a depth that asks for 32 rows
-        runs the f32 kernels' 16 (every look-ahead raised otherwise).  A demotion, so not a question for
-        tc_chain_tile_rows: the library's rule refuses (32, f32), it does not lower it; no threshold is repeated here."""
-        rows = self.decoder_tile_rows
-        mp = getattr(self, 'decoder_matrix_path', None)
-        if rows == 32 and (mp == 'f32' or (mp in (None, 'auto') and self.head.matrix_fallback)):
-            return 16
-        return rows
+        runs the f32 kernels' 16 (Detr3DHead.effective_tile_rows).  A number or an unknown name: left to the library."""
+        mp = MATRIX_PATHS.get(self.decoder_matrix_path)
+        return self.head.effective_tile_rows(self.decoder_tile_rows, mp, derived=True)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return L.stream_ptr()
 
     def backward_and_step(self, losses, lr=None):
         """losses: dict from head.loss(); every key containing 'loss' is summed
@@ -272,12 +263,11 @@ class FusionTrainer:
         b draws the masks of seed + b * SEED_STRIDE (the seed of the iteration that will take it).  An ordinary batch
         (B > 1 frames of ONE iteration) draws from one index space with the iteration's seed: with the stride, sample 1
         of iteration n would repeat the masks of sample 0 of iteration n + 1."""
-        from .detr3d_head import head_options
         with torch.no_grad():
             return self.head.forward_nhwc(feats_nhwc, lidar2img, img_hw, tokens, pad_mult, aux='train',
                                           _allow_train=True, decoder_only=True, lane=lane,
                                           options=head_options(tile_rows=self._decoder_tile_rows_now(),
-                                                               matrix_path=getattr(self, 'decoder_matrix_path', None),
+                                                               matrix_path=self.decoder_matrix_path,
                                                                decoder_dropout_p=self.decoder_dropout,
                                                                dropout_seed=seed,
                                                                dropout_seed_stride=self.SEED_STRIDE if lookahead else 0))
@@ -288,7 +278,7 @@ class FusionTrainer:
         # raw-pointer kernels (ops.to_nhwc into a preallocated buffer, RadarRawStage.build, FramePipeline write hooks,
         # any ctypes tc_* call) must call ``invalidate_lookahead()`` -- it bumps the generation, and a pending
         # look-ahead of the old contents is dropped instead of handing their decoder states to the new frame
-        return (int(getattr(self, '_generation', 0)),
+        return (self._generation,
                 tuple((int(f.data_ptr()), int(f._version), tuple(f.shape)) for f in feats_nhwc),
                 (int(lidar2img.data_ptr()), int(lidar2img._version)), (int(tokens.data_ptr()), int(tokens._version)),
                 int(pad_mult), tuple(tokens.shape))
@@ -296,7 +286,7 @@ class FusionTrainer:
     def invalidate_lookahead(self):
         """The tensors handed to ``prefetch_decoder`` / ``step_fused_nhwc(prefetch=...)`` were rewritten in place by
         something torch's version counters do not see: pending look-ahead frames are stale."""
-        self._generation = int(getattr(self, '_generation', 0)) + 1
+        self._generation += 1
         self._pre = self._pre_next = None
 
     def prefetch_decoder(self, feats_nhwc, lidar2img, img_hw, tokens, pad_mult, skip=0):
@@ -315,14 +305,14 @@ class FusionTrainer:
         if not head.training:
             head.train()
         cur = torch.cuda.current_stream()
-        if getattr(self, '_pre_stream', None) is None:
+        if self._pre_stream is None:
             self._pre_stream = torch.cuda.Stream()
         P = int(lidar2img.shape[0])
         ncam = feats_nhwc[0].shape[0] // P
-        counter0 = getattr(head, '_train_forwards', 0) + int(skip)
+        counter0 = head._train_forwards + int(skip)
         seed0 = head.peek_dropout_seed(1 + int(skip))          # the seed of the training forward that takes frame 0
-        pend = getattr(self, '_pre', None)
-        lane = 1 - (pend['lane'] if pend is not None else getattr(self, '_lane', 0))
+        pend = self._pre
+        lane = 1 - (pend['lane'] if pend is not None else self._lane)
         self._pre_stream.wait_stream(cur)                      # inputs written on the current stream are complete
         with torch.cuda.stream(self._pre_stream):
             base = self._decoder_forward(feats_nhwc, lidar2img, img_hw, tokens, pad_mult, seed0, lane, lookahead=True)
@@ -341,14 +331,13 @@ class FusionTrainer:
 
     def _take_prefetched(self, feats_nhwc, lidar2img, tokens, pad_mult):
         """-> (aux of this frame, its dropout seed) from the pending look-ahead, or None."""
-        pre = getattr(self, '_pre', None)
-        if pre is None and getattr(self, '_pre_next', None) is not None:
-            pre = self._pre = self._pre_next
-            self._pre_next = None
+        if self._pre is None:
+            self._pre, self._pre_next = self._pre_next, None
+        pre = self._pre
         if pre is None:
             return None
         head, i = self.head, pre['next']
-        ok = (i < pre['count'] and getattr(head, '_train_forwards', 0) == pre['counter0'] + i and
+        ok = (i < pre['count'] and head._train_forwards == pre['counter0'] + i and
               lidar2img.shape[0] == 1 and pre['keys'][i] == self._input_key(feats_nhwc, lidar2img, tokens, pad_mult))
         if not ok:
             self._pre = self._pre_next = None                  # stale: nothing was drawn from the seed counter for it
@@ -363,14 +352,14 @@ class FusionTrainer:
                    last_box=aux['last_box'][i:i + 1])
         pre['next'] = i + 1
         if pre['next'] >= pre['count']:
-            self._pre, self._pre_next = getattr(self, '_pre_next', None), None
-        self.lookahead_hits = getattr(self, 'lookahead_hits', 0) + 1
+            self._pre, self._pre_next = self._pre_next, None
+        self.lookahead_hits += 1
         return out, seed
 
     def lookahead_pending(self):
         """Frames of look-ahead batches not consumed yet."""
         n = 0
-        for pre in (getattr(self, '_pre', None), getattr(self, '_pre_next', None)):
+        for pre in (self._pre, self._pre_next):
             if pre is not None:
                 n += pre['count'] - pre['next']
         return n
@@ -397,18 +386,15 @@ class FusionTrainer:
         else:
             drop_seed = head.next_dropout_seed()   # (seed, rank, forward counter): shared with forward_train_nhwc
             aux = self._decoder_forward(feats_nhwc, lidar2img, img_hw, tokens, pad_mult, drop_seed,
-                                        getattr(self, '_lane', 0))['aux']
+                                        self._lane)['aux']
         w = head.head_weights()
         B, T = lidar2img.shape[0], tokens.shape[1]
         hs_last = aux['inter_states'][-1].contiguous()
         ref_last = aux['inter_references'][-1].contiguous()
         last_box = aux['last_box']
         key = (B, T)
-        if getattr(self, '_tape_key', None) != key:
-            nbytes = lib.tc_radar_train_tape_bytes(C.byref(w), B, T)
-            if nbytes == 0:
-                raise L.TransCARHipError(lib.tc_last_error().decode())
-            self._tape = torch.empty(nbytes, dtype=torch.uint8, device=tokens.device)
+        if self._tape_key != key:
+            self._tape = L.device_bytes(tokens.device, lib.tc_radar_train_tape_bytes, C.byref(w), B, T)
             self._tape_key = key
         tape = self._tape
         Q = head.num_query
@@ -424,21 +410,21 @@ class FusionTrainer:
             if self.chain_backward:
                 bws = self._backward_workspace(lib, w, key, B, T, tokens.device)
                 L.check(lib.tc_radar_train_repack(C.byref(w), C.byref(pv), bws.data_ptr(), bws.numel(), B, T,
-                                                  self._stream()), 'tc_radar_train_repack')
+                                                  L.stream_ptr()), 'tc_radar_train_repack')
                 self._wT_ready = True
             else:
-                L.check(lib.tc_head_repack_trainable_ex(C.byref(w), C.byref(pv), 1, self._stream()),
+                L.check(lib.tc_head_repack_trainable_ex(C.byref(w), C.byref(pv), 1, L.stream_ptr()),
                         'tc_head_repack_trainable_ex')
             head._packed_dirty = True                  # the 16x16x4 copy (inference at >= 3 frames) is stale
             L.check(lib.tc_radar_train_fwd_fused(
                 C.byref(pv), hs_last.data_ptr(), ref_last.data_ptr(), last_box.data_ptr(), tokens.data_ptr(),
                 B, T, int(pad_mult), all_cls.data_ptr(), all_box.data_ptr(), tape.data_ptr(), tape.numel(),
-                self.dropout, drop_seed, self._stream()), 'tc_radar_train_fwd_fused')
+                self.dropout, drop_seed, L.stream_ptr()), 'tc_radar_train_fwd_fused')
         else:
             L.check(lib.tc_radar_train_fwd(
                 C.byref(w), hs_last.data_ptr(), ref_last.data_ptr(), last_box.data_ptr(), tokens.data_ptr(),
                 B, T, int(pad_mult), all_cls.data_ptr(), all_box.data_ptr(), tape.data_ptr(), tape.numel(),
-                self.dropout, drop_seed, self._stream()), 'tc_radar_train_fwd')
+                self.dropout, drop_seed, L.stream_ptr()), 'tc_radar_train_fwd')
         raw_losses = None
         if self.device_loss:
             from .device_loss import detr_loss_device
@@ -448,7 +434,7 @@ class FusionTrainer:
             # ~1.2 ms of device work beside a 1 ms iteration, and the iteration that takes its first frame would wait
             # for all of it (measured: 1.70 instead of 0.96 ms once per batch)
             pend = self.lookahead_pending()
-            start = prefetch is not None and getattr(self, '_pre_next', None) is None and \
+            start = prefetch is not None and self._pre_next is None and \
                 pend <= (1 if self.prefetch_depth > 1 else 0)
             hook = (lambda: self.prefetch_decoder(skip=pend, **(prefetch(pend) if callable(prefetch) else prefetch))) \
                 if start else None
@@ -467,10 +453,10 @@ class FusionTrainer:
             total = sum(v for k, v in losses.items() if 'loss' in k)
             total.backward()                               # d loss / d outputs only
             d_cls, d_box = cls_leaf.grad.contiguous(), box_leaf.grad.contiguous()
-        self.bucket.zero_grad(check_views=getattr(self, '_gtab_key', None) is None)
+        self.bucket.zero_grad(check_views=self._gtab_key is None)
         # the gradient pointers are views into the flat bucket: they do not move between iterations
         gkey = self.bucket.grads.data_ptr()
-        if getattr(self, '_gtab_key', None) != gkey:
+        if self._gtab_key != gkey:
             self._gtab, self._gtab_key = grad_table(head), gkey
         g = self._gtab
         if self.chain_backward:
@@ -489,10 +475,10 @@ class FusionTrainer:
                 if self._shadow is None or self._shadow.numel() < need or self._shadow.device != tokens.device:
                     self._shadow = torch.zeros(need, dtype=torch.int64, device=tokens.device)   # the call leaves it zero
                 L.check(lib.tc_radar_train_bwd_fused_det(*common, self.bucket.grads.data_ptr(), self.bucket.numel,
-                                                         self._shadow.data_ptr(), self._shadow.numel(), self._stream()),
+                                                         self._shadow.data_ptr(), self._shadow.numel(), L.stream_ptr()),
                         'tc_radar_train_bwd_fused_det')
             else:
-                L.check(lib.tc_radar_train_bwd_fused_ex(*common, self._stream()), 'tc_radar_train_bwd_fused_ex')
+                L.check(lib.tc_radar_train_bwd_fused_ex(*common, L.stream_ptr()), 'tc_radar_train_bwd_fused_ex')
                 if chunked:
                     # the weight gradients chunk by chunk, each chunk's all-reduce started behind its launch: it travels
                     # (RCCL's stream) while the compute stream forms the next chunk
@@ -500,8 +486,8 @@ class FusionTrainer:
                     for gi in range(len(self.bucket.chunk_ranges)):
                         L.check(lib.tc_radar_train_bwd_weights(
                             C.byref(w), C.byref(g), hs_last.data_ptr(), tokens.data_ptr(), B, T, tape.data_ptr(),
-                            tape.numel(), bws.data_ptr(), bws.numel(), gi, self._stream()), 'tc_radar_train_bwd_weights')
-                        if getattr(self, 'chunk_events', None) is not None:
+                            tape.numel(), bws.data_ptr(), bws.numel(), gi, L.stream_ptr()), 'tc_radar_train_bwd_weights')
+                        if self.chunk_events is not None:
                             ev = torch.cuda.Event(enable_timing=True)
                             ev.record()
                             self.chunk_events.append((gi, ev))
@@ -513,10 +499,10 @@ class FusionTrainer:
             L.check(lib.tc_radar_train_bwd(
                 C.byref(w), C.byref(g), hs_last.data_ptr(), last_box.data_ptr(), tokens.data_ptr(), B, T,
                 int(pad_mult), all_box.data_ptr(), d_cls.data_ptr(), d_box.data_ptr(), tape.data_ptr(),
-                tape.numel(), self.dropout, drop_seed, self._stream()), 'tc_radar_train_bwd')
+                tape.numel(), self.dropout, drop_seed, L.stream_ptr()), 'tc_radar_train_bwd')
         self.last_dropout_seed = drop_seed
         self._sq_clean = True                  # bucket.zero_grad above cleared it and nothing has added to it since
-        if getattr(self, 'keep_last', False):        # tests: the operands of the backward call
+        if self.keep_last:        # tests: the operands of the backward call
             self._last = dict(w=w, g=g, hs_last=hs_last, last_box=last_box, tokens=tokens, B=B, T=T, pad_mult=int(pad_mult),
                               all_box=all_box, d_cls=d_cls, d_box=d_box, tape=tape, seed=drop_seed)
         if update:
@@ -525,7 +511,7 @@ class FusionTrainer:
             # how long the compute stream stood still between the backward's end and the optimizer's first kernel
             pending = chunk_pending if (self.chain_backward and chunked) else self.bucket.all_reduce_begin()
             ev = None
-            if getattr(self, 'exchange_events', None) is not None:
+            if self.exchange_events is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
             self._optimizer_step(lr, pending=pending, mark=ev)
@@ -598,8 +584,8 @@ class FusionTrainer:
         trainer = dict(iter=int(self.iter), seed=int(self.seed), dropout=float(self.dropout),
                        decoder_dropout=float(self.decoder_dropout),
                        max_norm=None if self.max_norm is None else float(self.max_norm),
-                       train_forwards=int(getattr(head, '_train_forwards', 0)),
-                       dropout_seed=int(getattr(head, 'dropout_seed', 0)),
+                       train_forwards=int(head._train_forwards),
+                       dropout_seed=int(head.dropout_seed),
                        num_fusion_layers=int(head.num_fusion_layers), deterministic=bool(self.deterministic),
                        prefetch_depth=int(self.prefetch_depth), world_size=int(self._world_size()),
                        # the order the clip's sum of squares runs over the parameters (`_adopt_clip_order`)
@@ -725,11 +711,8 @@ class FusionTrainer:
                     and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
 
     def _backward_workspace(self, lib, w, key, B, T, device):
-        if getattr(self, '_bws_key', None) != key:
-            nb = lib.tc_radar_train_bwd_workspace_bytes(C.byref(w), B, T)
-            if nb == 0:
-                raise L.TransCARHipError(lib.tc_last_error().decode())
-            self._bws = torch.empty(nb, dtype=torch.uint8, device=device)
+        if self._bws_key != key:
+            self._bws = L.device_bytes(device, lib.tc_radar_train_bwd_workspace_bytes, C.byref(w), B, T)
             self._bws_key = key
         return self._bws
 
@@ -744,7 +727,7 @@ class FusionTrainer:
                 e = torch.cuda.Event(enable_timing=True)
                 e.record()
                 evs.append(e)
-            if getattr(self, 'exchange_chunk_events', None) is not None:
+            if self.exchange_chunk_events is not None:
                 self.exchange_chunk_events.append(evs)
         else:
             world = self.bucket.all_reduce_end(pending) if pending is not None else self.bucket.all_reduce()
@@ -759,13 +742,13 @@ class FusionTrainer:
         grads = b.grads
         if self._clip_index is not None:       # a run continued from another bucket layout: its order of the float sum
             grads = torch.index_select(b.grads, 0, self._clip_index, out=self._clip_scratch)
-        L.check(lib.tc_sq_norm(grads.data_ptr(), b.numel, self.sq.data_ptr(), self._stream()),
+        L.check(lib.tc_sq_norm(grads.data_ptr(), b.numel, self.sq.data_ptr(), L.stream_ptr()),
                 'tc_sq_norm')
         L.check(lib.tc_adamw_step(
             b.params.data_ptr(), b.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), b.numel,
             float(self.lr if lr is None else lr), self.betas[0], self.betas[1], self.eps,
             self.weight_decay, self.iter, 1.0 / world, float(self.max_norm or 0.0),
-            self.sq.data_ptr(), self._stream()), 'tc_adamw_step')
+            self.sq.data_ptr(), L.stream_ptr()), 'tc_adamw_step')
         self.head.mark_trainable_dirty()      # re-packed lazily by the next inference forward / replay
 
     def step(self, mlvl_feats, img_metas, gt_bboxes_list, gt_labels_list, lr=None):
