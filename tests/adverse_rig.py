@@ -18,11 +18,21 @@ re-evaluated) are never compared with an independent reference.  This rig:
 * four radar frames (FRAMES) around the oracle's last reference points, one per regime.
 
 Everything here runs on the CPU; the oracle (fp32) and its evaluation on the .double() copy of
-the same state dict are the references."""
+the same state dict are the references.
+
+For the BACKWARD (test_adverse_backward_host.py, test_gpu_adverse_backward.py) the rig also holds the
+fp64 reference of the trainable radar stack's gradients: ``radar_stack`` (the three fusion layers composed
+from the oracle's functions, with GIVEN gate masks and dropout multipliers, in any dtype), ``relu_inputs`` /
+``tie_rows`` (the query rows whose gradient is not a continuous function of the rounding: a ReLU input
+within delta of zero) and ``reference_gradients`` (torch autograd in fp32 and in fp64)."""
+import contextlib
+
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from oracle import transcar_oracle as O
+from test_training import trainable
 from transcar_amd import configs, radar as R, synth
 
 PCR = configs.point_cloud_range
@@ -36,10 +46,10 @@ ATTENTIONS = ['transformer.decoder.layers.%d.attentions.0.attn' % l for l in ran
 # name -> (make_radar_frame arguments, points kept, (T, pad_mult) of the HIP launch,
 #          rows hit in fusion layers 1 / 2 / 3 and the largest hit count of a row: CPU measurements)
 FRAMES = {
-    'keep': (dict(n_per_radar=80, near_frac=0.9), 396, (448, 1053), (481, 401, 115), 17),
-    'mid': (dict(n_per_radar=140, near_frac=0.9), 692, (704, 797), (609, 540, 150), 27),
-    'truncated': (dict(n_per_radar=330), 1633, (1500, 1), (790, 714, 257), 48),
-    'all_hit': (dict(n_per_radar=300), 1497, (1500, 1), (900, 875, 241), 52),
+    'keep': (dict(n_per_radar=80, near_frac=0.9), 444, (448, 1053), (476, 392, 117), 33),
+    'mid': (dict(n_per_radar=140, near_frac=0.9), 700, (704, 797), (605, 536, 149), 39),
+    'truncated': (dict(n_per_radar=330), 1633, (1500, 1), (788, 712, 258), 52),
+    'all_hit': (dict(n_per_radar=300), 1497, (1500, 1), (900, 875, 242), 55),
 }
 
 
@@ -67,8 +77,9 @@ def build():
     refs = inter_refs[-1][0].double().numpy()
     centres = np.round(np.stack([refs[:, 0] * (PCR[3] - PCR[0]) + PCR[0],
                                  refs[:, 1] * (PCR[4] - PCR[1]) + PCR[1]], 1), 2)     # bench.make_inputs
+    last_box = O.decoder_box(sd, 5, hs.permute(0, 2, 1, 3)[5], inter_refs[4], PCR)     # HEAD:277-298, as head_forward
     return dict(sd_np=sd_np, sd=sd, sd64={k: v.double() for k, v in sd.items()}, feats_np=feats_np, feats=feats,
-                l2i=l2i, xfmr=xfmr, hs=hs, init_ref=init_ref, inter_refs=inter_refs, centres=centres)
+                l2i=l2i, xfmr=xfmr, hs=hs, init_ref=init_ref, inter_refs=inter_refs, centres=centres, last_box=last_box)
 
 
 def layer_inputs(rig, lid):
@@ -112,6 +123,75 @@ def recentring_share(scores, chunk=32, tau=8.0):
     return float(((cmax[..., 1:] - run[..., :-1]) > tau).any(-1).float().mean())
 
 
+# Rows with MANY hits (the backward's softmax statistics over several 64-token chunks of one row, dK | dV rows that many
+# queries add to): per frame at least MANY_HIT_ROWS rows of fusion layer 1 admit >= MANY_HITS returns.  The generator's
+# returns alone give 8 / 21 / 95 / 96 such rows, so radar_frame moves the returns that lie far from every query (the
+# 1 - near_frac share of make_radar_frame) -- and, on the two small frames, EXTRA_POINTS copies of them: T stays -- onto
+# sites several gates cover (query centres and a half-metre grid), until MANY_HIT_TARGET rows are there (a margin: the choice is made from all returns,
+# the launch keeps the first 1500).
+MANY_HITS, MANY_HIT_ROWS, MANY_HIT_TARGET = 8, 100, 125
+EXTRA_POINTS = {'keep': 48, 'mid': 8, 'truncated': 0, 'all_hit': 0}
+NEAR_FRAC_DEFAULT = 0.8           # synth.make_radar_frame
+
+
+def _gate_cover(rig, xy):
+    """bool [Q, n]: fusion layer 1's gate of query q (the fp32 oracle's, HEAD:549-571) admits a return at xy[n]."""
+    ref = rig['inter_refs'][-1]
+    cxy = torch.stack([ref[..., 0] * (PCR[3] - PCR[0]) + PCR[0], ref[..., 1] * (PCR[4] - PCR[1]) + PCR[1]], -1)
+    box = rig['last_box']
+    pts = torch.from_numpy(np.ascontiguousarray(xy)).float()[None]
+    return (~O.circle_mask(cxy, box[..., 3], box[..., 6], box[..., 7], pts, 1.0, 2.0)).numpy()
+
+
+def _cluster_far_returns(rig, frame, name):
+    """Moves the frame's far returns (and EXTRA_POINTS[name] copies of them, appended to the first channel) onto sites
+    that several gates cover, a few returns per site, chosen greedily: the site and the number of returns (1..MANY_HITS) that bring the
+    most rows to MANY_HITS hits per return spent, until MANY_HIT_TARGET rows have them or the returns run out."""
+    near_frac = FRAMES[name][0].get('near_frac', NEAR_FRAC_DEFAULT)
+    first = synth.RADAR_CHANNELS[0]
+    extra = EXTRA_POINTS[name]
+    slots = []
+    for chan in synth.RADAR_CHANNELS:
+        p = frame['points'][chan]
+        n = p.shape[1]
+        k = int(round(near_frac * n))
+        if chan == first and extra:
+            assert n - k >= 1
+            src = k + np.arange(extra) % (n - k)
+            frame['points'][chan] = p = np.concatenate([p, p[:, src]], 1)
+            frame['times'][chan] = np.concatenate([frame['times'][chan], frame['times'][chan][:, src]], 1)
+        slots += [(chan, i) for i in range(k, p.shape[1])]
+    moved = set(slots)
+    rest = np.array([[frame['points'][c][0, i], frame['points'][c][1, i]] for c in synth.RADAR_CHANNELS
+                     for i in range(frame['points'][c].shape[1]) if (c, i) not in moved])
+    rest = rest[(np.abs(rest) < PCR[3]).all(1)]                  # the reference's range filter (HEAD:304) on x, y
+    counts = _gate_cover(rig, rest).sum(1).astype(int)
+    g = np.arange(-50.0, 50.25, 0.5)
+    sites = np.concatenate([rig['centres'], np.stack(np.meshgrid(g, g), -1).reshape(-1, 2)])
+    cover = rig.get('_cover')                                   # a function of the rig alone: once for the four frames
+    if cover is None:
+        cover = _gate_cover(rig, sites)
+        dense = cover.sum(0) >= 6                               # only sites several gates cover can be chosen
+        cover = rig['_cover'] = (sites[dense], cover[:, dense])
+    sites, cover = cover
+    used = 0
+    while used < len(slots) and int((counts >= MANY_HITS).sum()) < MANY_HIT_TARGET:
+        best = None
+        for n in range(1, min(MANY_HITS, len(slots) - used) + 1):
+            gain = (((counts < MANY_HITS) & (counts + n >= MANY_HITS))[:, None] & cover).sum(0)
+            c = int(gain.argmax())
+            if gain[c] and (best is None or gain[c] / n > best[0]):
+                best = (gain[c] / n, c, n)
+        if best is None:
+            break
+        _, c, n = best
+        for chan, i in slots[used:used + n]:
+            frame['points'][chan][0, i], frame['points'][chan][1, i] = sites[c]
+        counts += n * cover[:, c]
+        used += n
+    return frame
+
+
 def radar_frame(rig, name):
     """The raw radar frame `name` of FRAMES (nuScenes-devkit layout, synth.make_radar_frame)."""
     frame = synth.make_radar_frame(seed=2, centres=rig['centres'], **FRAMES[name][0])
@@ -123,7 +203,7 @@ def radar_frame(rig, name):
             p[1, :180] = rig['centres'][k:k + 180, 1]
             k += 180
         assert k == rig['centres'].shape[0] == 900
-    return frame
+    return _cluster_far_returns(rig, frame, name)
 
 
 def radar_case(rig, name):
@@ -172,3 +252,180 @@ def radar_layer1_truth(rig, case):
     t64[..., 4:5] = t64[..., 4:5] + ref.double()[..., 2:3]
     return dict(cls=c64[0], box=t64[0], gate_flips=int((m32 != m64).sum()),
                 enc_dev=float((dbg['radar_feat'].double() - rf64).abs().max()))
+
+
+# --------------------------------------------------------------------------
+# the backward: fp64 reference of the trainable radar stack's gradients
+# --------------------------------------------------------------------------
+# (attention suffix, module suffix, gate radius clamp, cls / reg branch) of fusion layers 1 / 2 / 3 (HEAD:538-729)
+FUSION = (('', '', 1.0, 2.0, 'final_cls', 'final_reg'), ('2', '_2', 1.0, 2.0, 'final_cls2', 'final_reg2'),
+          ('3', '_3', 0.5, 1.0, 'final_cls3', 'final_reg3'))
+TOKEN_RELUS = 5         # radar_encode: two of the position encoder, three of the feature encoder
+QUERY_RELUS = 5         # per fusion layer: the FFN hidden, two of the cls branch, two of the reg branch
+MAX_EXCLUDED = 0.25     # of a layer's rows (tie_rows); see test_adverse_backward_host.py for the measured shares
+
+
+def radar_masks(rig, case, drop=None):
+    """The fp32 oracle's three gate masks [Q,1500] (True = masked) on this frame, as head_forward evaluates them: in eval
+    mode, or in train mode with the given dropout multipliers (layers 2 and 3 gate on the box of the layer before, which
+    the dropout moves)."""
+    if drop is not None or 'masks' not in case:
+        masks = []
+        O.head_forward(rig['sd'], rig['feats'], rig['l2i'], HW, case['f36'], PCR, decoder_trace=rig['xfmr'], drop=drop,
+                       gate_probe=lambda *args: masks.append(O.circle_mask(*args)))
+        assert len(masks) == 3 and np.array_equal((~masks[0]).sum(1).numpy(), case['hits'][0])
+        if drop is not None:
+            return masks
+        assert all(np.array_equal((~m).sum(1).numpy(), h) for m, h in zip(masks, case['hits']))
+        case['masks'] = masks
+    return case['masks']
+
+
+def radar_stack(sd, dtype, rig, case, masks, drop=None):
+    """The three fusion layers (HEAD:531-729) on the fp32 oracle's last decoder state, with GIVEN gate masks (the gate
+    is not differentiated: the reference's masks are boolean) and given dropout multipliers (``drop`` as
+    O.head_forward takes it: per layer probs [8,Q,1500], d2, ffn, d3; None = eval), composed from the oracle's
+    functions in ``dtype``.  sd: the state dict in ``dtype``; differentiable with respect to its entries.
+    -> (all_cls_scores [3,1,Q,ncls], all_bbox_preds [3,1,Q,code])."""
+    tokens, _ = O.radar_tokens_from_features(case['f36'])
+    radar_feat = O.radar_encode(sd, tokens.to(dtype)).permute(1, 0, 2)          # [K,1,C]
+    qf = rig['hs'].permute(0, 2, 1, 3)[-1].permute(1, 0, 2).to(dtype)           # HEAD:539, [Q,1,C]
+    reference = rig['inter_refs'][-1].to(dtype).clone()
+    reference[..., 0:1] = reference[..., 0:1] * (PCR[3] - PCR[0]) + PCR[0]      # HEAD:596-600: z stays normalised
+    reference[..., 1:2] = reference[..., 1:2] * (PCR[4] - PCR[1]) + PCR[1]
+    cls_out, box_out = [], []
+    for r, (sa, sf, _, _, cls_name, reg_name) in enumerate(FUSION):
+        d = None if drop is None else {k: v.to(dtype) for k, v in drop[r].items()}
+        qf, _ = O.radar_layer(sd, sa, sf, qf, radar_feat, masks[r], d)
+        qf_b = qf.permute(1, 0, 2)
+        c = O.cls_branch(sd, cls_name, qf_b)
+        t = O.reg_branch(sd, reg_name, qf_b)
+        t[..., 0:2] = t[..., 0:2] + reference[..., 0:2]
+        t[..., 4:5] = t[..., 4:5] + reference[..., 2:3]
+        cls_out.append(c)
+        box_out.append(t)
+        reference = torch.zeros_like(reference)                                 # HEAD:613-617 / 670-674
+        reference[..., :2] = t[..., :2]
+        reference[..., 2:3] = t[..., 4:5]
+    return torch.stack(cls_out), torch.stack(box_out)
+
+
+@contextlib.contextmanager
+def _relu_recorder():
+    """Every F.relu call inside records its input (the oracle's functions call F.relu and nothing else)."""
+    seen, real = [], F.relu
+
+    def relu(x, *a, **kw):
+        seen.append(x.detach())
+        return real(x, *a, **kw)
+    F.relu = relu
+    try:
+        yield seen
+    finally:
+        F.relu = real
+
+
+def relu_inputs(sd, dtype, rig, case, masks, drop=None):
+    """The inputs of every ReLU of radar_stack, in evaluation order: dict(token = the encoder's TOKEN_RELUS sites
+    [1500,*], query = per fusion layer its QUERY_RELUS sites [Q,*], outputs = radar_stack's)."""
+    with torch.no_grad(), _relu_recorder() as seen:
+        outputs = radar_stack(sd, dtype, rig, case, masks, drop)
+    assert len(seen) == TOKEN_RELUS + 3 * QUERY_RELUS
+    flat = [x.reshape(-1, x.shape[-1]) for x in seen]
+    query = [flat[TOKEN_RELUS + QUERY_RELUS * r:TOKEN_RELUS + QUERY_RELUS * (r + 1)] for r in range(3)]
+    return dict(token=flat[:TOKEN_RELUS], query=query, outputs=outputs)
+
+
+def relu_deviation(x32, x64, real_tokens):
+    """max |fp32 - fp64| of the ReLU inputs: (query side, token side over the first `real_tokens` rows)."""
+    dq = max(float((a.double() - b).abs().max()) for la, lb in zip(x32['query'], x64['query']) for a, b in zip(la, lb))
+    dt = max(float((a.double() - b)[:real_tokens].abs().max()) for a, b in zip(x32['token'], x64['token']))
+    return dq, dt
+
+
+def tie_rows(x64, masks, delta):
+    """bool [3,Q]: the (layer, query) pairs whose gradient may differ between two correct evaluations by more than
+    rounding -- a ReLU input within delta of zero (fp64 forward) lands on either side.  Row q is excluded from layer
+    l on (cumulative: layer l + 1 reads layer l's row) if one of layer l's QUERY_RELUS sites has |x| < delta[0] in row q,
+    or if layer l's gate admits a token with |x| < delta[1] at one of the encoder's TOKEN_RELUS sites.
+    delta: (query side, token side) of tie_delta."""
+    tok_tie = torch.zeros(masks[0].shape[1], dtype=torch.bool)
+    for x in x64['token']:
+        tok_tie |= (x.abs() < delta[1]).any(-1)
+    out = []
+    for r in range(3):
+        tie = ((~masks[r]) & tok_tie[None]).any(1)
+        for x in x64['query'][r]:
+            tie |= (x.abs() < delta[0]).any(-1)
+        out.append(tie.numpy())
+    return np.logical_or.accumulate(np.stack(out), 0)
+
+
+def tie_delta(x32, x64, real_tokens):
+    """(query side, token side) delta of tie_rows: a CONDITION, not a tolerance -- 3 x the largest deviation of the fp32
+    oracle's ReLU inputs from fp64, per side (the token side over the `real_tokens` rows a gate can admit: the pad rows,
+    inputs of 500, deviate by 1.9e-4 and are never hit).  The inference tests hold HIP's forward within 2 x the oracle's
+    deviation from fp64, so a value 3 deviations from zero has one sign in fp64, in the fp32 oracle and in HIP."""
+    dq, dt = relu_deviation(x32, x64, real_tokens)
+    return 3.0 * dq, 3.0 * dt
+
+
+def trainable_sd(sd):
+    """A copy of the state dict whose trainable entries (test_training.trainable) are autograd leaves."""
+    return {k: (v.detach().clone().requires_grad_(True) if trainable(k) and v.is_floating_point() else v)
+            for k, v in sd.items()}
+
+
+def reference_gradients(rig, case, drop, d_cls, d_box, keep, masks=None):
+    """Gradients of  sum(all_cls * d_cls * keep) + sum(all_box * d_box * keep)  through radar_stack with the fp32
+    oracle's masks, by torch autograd in fp32 and in fp64: (g32, g64), each {state-dict key: gradient} over the
+    trainable tensors the stack uses.  d_cls [3,1,Q,ncls], d_box [3,1,Q,code]: the cotangents; keep: bool [3,Q]; masks:
+    radar_masks(rig, case, drop) where the caller has them."""
+    masks = masks or radar_masks(rig, case, drop)
+    w = torch.from_numpy(np.ascontiguousarray(keep)).double()[:, None, :, None]
+    res = []
+    for dtype, base in ((torch.float32, rig['sd']), (torch.float64, rig['sd64'])):
+        sd = trainable_sd(base)
+        cls, box = radar_stack(sd, dtype, rig, case, masks, drop)
+        ((cls * (d_cls.double() * w).to(dtype)).sum() + (box * (d_box.double() * w).to(dtype)).sum()).backward()
+        res.append({k: v.grad.detach() for k, v in sd.items() if v.requires_grad and v.grad is not None})
+    return tuple(res)
+
+
+def host_dropout(p, Q, seed, Cd=256, Fd=512, H=8, K=1500):
+    """Dropout multipliers (0 | 1/(1-p), float32) as O.head_forward's ``drop`` takes them, drawn by torch on the host."""
+    g = torch.Generator().manual_seed(seed)
+    scale = np.float32(1.0) / np.float32(1.0 - p)
+
+    def m(*shape):
+        return (torch.rand(*shape, generator=g) >= p).float() * float(scale)
+    return [dict(probs=m(H, Q, K), d2=m(Q, Cd), ffn=m(Q, Fd), d3=m(Q, Cd)) for _ in range(3)]
+
+
+GROUPS = (('attention projections', ('rf_multihead_attn',)), ('FFN', ('rf_linear',)), ('norms', ('rf_norm',)),
+          ('cls / reg branches', ('final_cls', 'final_reg')),
+          ('radar encoders', ('radar_position_encoder', 'radar_feat_encoder')))
+
+
+def group_of(name):
+    for title, prefixes in GROUPS:
+        if name.startswith(prefixes):
+            return title
+    raise KeyError(name)
+
+
+def cotangents(seed, layers=3, B=1, Q=900, ncls=10, code=10):
+    """Unit-normal cotangents (d_cls [layers,B,Q,ncls], d_box [layers,B,Q,code]) of the stack's two outputs."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(layers, B, Q, ncls, generator=g), torch.randn(layers, B, Q, code, generator=g)
+
+
+def backward_case(rig, name, drop=None):
+    """What the backward tests need of frame `name` before any gradient: dict(case, masks, x32 / x64 = relu_inputs of the
+    fp32 / fp64 stack with the fp32 oracle's masks and the given multipliers, delta = tie_delta, ties = tie_rows [3,Q])."""
+    case = radar_case(rig, name)
+    masks = radar_masks(rig, case, drop)
+    x32 = relu_inputs(rig['sd'], torch.float32, rig, case, masks, drop)
+    x64 = relu_inputs(rig['sd64'], torch.float64, rig, case, masks, drop)
+    delta = tie_delta(x32, x64, min(case['f36'].shape[0], R.NUM_RADAR_TOKENS))
+    return dict(case=case, masks=masks, x32=x32, x64=x64, delta=delta, ties=tie_rows(x64, masks, delta))

@@ -17,10 +17,10 @@ rig of adverse_rig.py reaches the branches that workload never takes:
   which every row tile has a hit:
 
     frame      points kept  T, pad_mult   rows hit, layers 1/2/3   max hits per row
-    keep       396          448, 1053     481 / 401 / 115          17
-    mid        692          704, 797      609 / 540 / 150          27
-    truncated  1633         1500, 1       790 / 714 / 257          48
-    all_hit    1497         1500, 1       900 / 875 / 241          52
+    keep       444          448, 1053     476 / 392 / 117          33
+    mid        700          704, 797      605 / 536 / 149          39
+    truncated  1633         1500, 1       788 / 712 / 258          52
+    all_hit    1497         1500, 1       900 / 875 / 242          55
 
 CPU measurements of the rig (re-measured by the tests): the fp32 oracle deviates from the fp64
 evaluation of the same decoder layer by max 0.87e-4 - 1.55e-4, mean 3.9e-6 - 4.7e-6 (the bench's
@@ -74,22 +74,22 @@ of |hs - fp64| over 900 x 256 values, max |ref - fp64|; radar: max |d| of fusion
     layer 5: max 8.06e-05 / 8.14e-05   mean 3.30e-06 / 3.74e-06   ref 8.5e-06 / 9.2e-06   rows excluded []
   attention core alone, layer-3 operands, f32: max|o - fp64| hip 5.13e-06 / fp32 torch 6.05e-06
   attention core alone, layer-3 operands, f16x2: max|o - fp64| hip 3.83e-06 / fp32 torch 6.05e-06
-  radar layer 1, keep      tile_rows=0  matrix=None : cls 1.85e-06 / 1.75e-06   box 5.93e-06 / 2.60e-06
-  radar layer 1, keep      tile_rows=16 matrix=f16x2: cls 1.55e-06 / 1.75e-06   box 5.81e-06 / 2.60e-06
-  radar layer 1, keep      tile_rows=16 matrix=f32  : cls 2.18e-06 / 1.75e-06   box 5.87e-06 / 2.60e-06
-  radar layer 1, keep      tile_rows=32 matrix=f16x2: cls 1.56e-06 / 1.75e-06   box 5.80e-06 / 2.60e-06
-  radar layer 1, mid       tile_rows=0  matrix=None : cls 1.89e-06 / 2.02e-06   box 5.89e-06 / 2.63e-06
-  radar layer 1, mid       tile_rows=16 matrix=f16x2: cls 1.93e-06 / 2.02e-06   box 5.78e-06 / 2.63e-06
-  radar layer 1, mid       tile_rows=16 matrix=f32  : cls 2.59e-06 / 2.02e-06   box 5.98e-06 / 2.63e-06
-  radar layer 1, mid       tile_rows=32 matrix=f16x2: cls 1.40e-06 / 2.02e-06   box 5.95e-06 / 2.63e-06
-  radar layer 1, truncated tile_rows=0  matrix=None : cls 1.82e-06 / 2.32e-06   box 6.36e-06 / 2.70e-06
-  radar layer 1, truncated tile_rows=16 matrix=f16x2: cls 1.76e-06 / 2.32e-06   box 5.88e-06 / 2.70e-06
-  radar layer 1, truncated tile_rows=16 matrix=f32  : cls 2.63e-06 / 2.32e-06   box 6.02e-06 / 2.70e-06
-  radar layer 1, truncated tile_rows=32 matrix=f16x2: cls 1.49e-06 / 2.32e-06   box 6.02e-06 / 2.70e-06
-  radar layer 1, all_hit   tile_rows=0  matrix=None : cls 1.95e-06 / 2.19e-06   box 6.03e-06 / 2.62e-06
-  radar layer 1, all_hit   tile_rows=16 matrix=f16x2: cls 1.51e-06 / 2.19e-06   box 6.05e-06 / 2.62e-06
-  radar layer 1, all_hit   tile_rows=16 matrix=f32  : cls 2.86e-06 / 2.19e-06   box 6.19e-06 / 2.62e-06
-  radar layer 1, all_hit   tile_rows=32 matrix=f16x2: cls 1.66e-06 / 2.19e-06   box 6.03e-06 / 2.62e-06
+  radar layer 1, keep      tile_rows=0  matrix=None : cls 1.80e-06 / 1.75e-06   box 2.62e-06 / 2.60e-06
+  radar layer 1, keep      tile_rows=16 matrix=f16x2: cls 1.55e-06 / 1.75e-06   box 2.49e-06 / 2.60e-06
+  radar layer 1, keep      tile_rows=16 matrix=f32  : cls 2.13e-06 / 1.75e-06   box 2.63e-06 / 2.60e-06
+  radar layer 1, keep      tile_rows=32 matrix=f16x2: cls 1.73e-06 / 1.75e-06   box 2.53e-06 / 2.60e-06
+  radar layer 1, mid       tile_rows=0  matrix=None : cls 1.89e-06 / 2.02e-06   box 2.46e-06 / 2.63e-06
+  radar layer 1, mid       tile_rows=16 matrix=f16x2: cls 1.93e-06 / 2.02e-06   box 2.35e-06 / 2.63e-06
+  radar layer 1, mid       tile_rows=16 matrix=f32  : cls 2.59e-06 / 2.02e-06   box 2.79e-06 / 2.63e-06
+  radar layer 1, mid       tile_rows=32 matrix=f16x2: cls 1.68e-06 / 2.02e-06   box 2.80e-06 / 2.63e-06
+  radar layer 1, truncated tile_rows=0  matrix=None : cls 1.82e-06 / 2.32e-06   box 2.55e-06 / 2.70e-06
+  radar layer 1, truncated tile_rows=16 matrix=f16x2: cls 1.76e-06 / 2.32e-06   box 2.48e-06 / 2.70e-06
+  radar layer 1, truncated tile_rows=16 matrix=f32  : cls 2.63e-06 / 2.32e-06   box 2.72e-06 / 2.70e-06
+  radar layer 1, truncated tile_rows=32 matrix=f16x2: cls 1.49e-06 / 2.32e-06   box 2.48e-06 / 2.70e-06
+  radar layer 1, all_hit   tile_rows=0  matrix=None : cls 1.95e-06 / 2.05e-06   box 2.52e-06 / 2.62e-06
+  radar layer 1, all_hit   tile_rows=16 matrix=f16x2: cls 1.51e-06 / 2.05e-06   box 2.29e-06 / 2.62e-06
+  radar layer 1, all_hit   tile_rows=16 matrix=f32  : cls 2.81e-06 / 2.05e-06   box 3.24e-06 / 2.62e-06
+  radar layer 1, all_hit   tile_rows=32 matrix=f16x2: cls 1.66e-06 / 2.05e-06   box 2.37e-06 / 2.62e-06
 """
 import numpy as np
 import pytest
