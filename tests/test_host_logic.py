@@ -252,6 +252,61 @@ def test_entry_points_refuse_bad_arguments_without_gpu():
     assert lib.tc_dropout_mask(1.0, 1, 0, 16, None, None) != 0            # p = 1 drops everything: refused
 
 
+def _fusion_head_struct(packed=True):
+    """A tc_head_weights of the default fusion head that passes the dimension checks; `packed`: it looks like a view of
+    tc_head_pack_weights (l0_attn_out set -- to a host buffer nothing reads: the calls below fail before any launch)."""
+    w = _lib.tc_head_weights()
+    w.abi_version = _lib.TC_ABI_VERSION
+    w.num_query, w.embed_dims, w.num_heads, w.ffn_dims = 900, 256, 8, 512
+    w.num_layers, w.num_cams, w.num_levels = 6, 6, 4
+    w.num_classes, w.code_size, w.radar_in_dims, w.num_radar_layers = 10, 10, 36, 3
+    keep = (ctypes.c_float * 4)()
+    if packed:
+        w.l0_attn_out = ctypes.cast(keep, dict(_lib.tc_head_weights._fields_)['l0_attn_out'])
+    return w, keep
+
+
+def test_radar_fusion_refuses_bad_layers_and_unpacked_view_without_gpu():
+    """tc_radar_fusion_fwd names the layer range it was asked for and the argument that is no packed view."""
+    lib = T.lib()
+    w, keep = _fusion_head_struct()
+    buf = ctypes.cast(keep, ctypes.c_void_p)
+
+    def fusion(view, first, n):
+        return lib.tc_radar_fusion_fwd(ctypes.byref(view), buf, buf, buf, buf, 1, 64, 1, first, n, buf, buf, None, None, None, 0, None)
+    assert fusion(w, 2, 2) != 0
+    assert b'radar_fusion' in lib.tc_last_error() and b'layers [2, 4) of 3' in lib.tc_last_error()
+    assert fusion(w, 0, 0) != 0 and b'layers [0, 0) of 3' in lib.tc_last_error()
+    raw, _ = _fusion_head_struct(packed=False)
+    assert fusion(raw, 0, 3) != 0 and b'packed_view' in lib.tc_last_error()
+
+
+def test_training_entry_points_name_themselves_when_the_tape_is_too_small_without_gpu():
+    """Every training entry point lays out its tape (and the fused backward its workspace) before it launches anything;
+    a buffer that is too small is refused with a message that begins with the entry point's own name."""
+    lib = T.lib()
+    w, keep = _fusion_head_struct()
+    g, _ = _fusion_head_struct()
+    buf = ctypes.cast(keep, ctypes.c_void_p)
+    B, Tk = 1, 64
+    wp, gp = ctypes.byref(w), ctypes.byref(g)
+    calls = {
+        'radar_train_fwd': lambda: lib.tc_radar_train_fwd(wp, buf, buf, buf, buf, B, Tk, 1, buf, buf, buf, 0, 0.0, 0, None),
+        'radar_train_fwd_fused': lambda: lib.tc_radar_train_fwd_fused(wp, buf, buf, buf, buf, B, Tk, 1, buf, buf, buf, 0, 0.0, 0, None),
+        'radar_train_bwd': lambda: lib.tc_radar_train_bwd(wp, gp, buf, buf, buf, B, Tk, 1, buf, buf, buf, buf, 0, 0.0, 0, None),
+        'radar_train_bwd_fused': lambda: lib.tc_radar_train_bwd_fused(wp, gp, buf, buf, buf, B, Tk, 1, buf, buf, buf, buf, 0, buf, 0,
+                                                                     0.0, 0, None, None, None),
+        'radar_train_bwd_weights': lambda: lib.tc_radar_train_bwd_weights(wp, gp, buf, buf, B, Tk, buf, 0, buf, 0, 0, None),
+    }
+    for name, call in calls.items():
+        assert call() != 0, name
+        assert lib.tc_last_error() == name.encode() + b': tape too small', (name, lib.tc_last_error())
+    tape_bytes = lib.tc_radar_train_tape_bytes(wp, B, Tk)
+    assert tape_bytes > 0 and lib.tc_radar_train_bwd_workspace_bytes(wp, B, Tk) > 0
+    rc = lib.tc_radar_train_bwd_fused(wp, gp, buf, buf, buf, B, Tk, 1, buf, buf, buf, buf, tape_bytes, buf, 0, 0.0, 0, None, None, None)
+    assert rc != 0 and lib.tc_last_error() == b'radar_train_bwd_fused: workspace too small', lib.tc_last_error()
+
+
 _WORKER = r'''
 import os, sys
 sys.path.insert(0, %r)

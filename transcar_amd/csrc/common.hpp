@@ -21,6 +21,19 @@ int check_launch(const char* what);   // hipGetLastError -> message; returns cod
       return -1;                                    \
     }                                               \
   } while (0)
+#define TC_TRY(expr)          \
+  do {                        \
+    int _rc = (expr);         \
+    if (_rc != 0) return _rc; \
+  } while (0)
+#define TC_HIP(expr)                                          \
+  do {                                                        \
+    hipError_t _e = (expr);                                   \
+    if (_e != hipSuccess) {                                   \
+      tc::set_error("%s: %s", #expr, hipGetErrorString(_e)); \
+      return (int)_e;                                         \
+    }                                                         \
+  } while (0)
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -9,7 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "kernels.hpp"
+#include "chain_args.hpp"
 
 namespace tc {
 
@@ -31,24 +31,8 @@ int check_launch(const char* what) {
   return 0;
 }
 
-#define TC_TRY(expr)          \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-
-#define TC_HIP(expr)                                          \
-  do {                                                        \
-    hipError_t _e = (expr);                                   \
-    if (_e != hipSuccess) {                                   \
-      tc::set_error("%s: %s", #expr, hipGetErrorString(_e)); \
-      return (int)_e;                                         \
-    }                                                         \
-  } while (0)
-
-static int linear(const float* x, int ldx, const tc_linear& w, int M, int K, int N, int act,
-                  float* y, int ldy, hipStream_t s, const float* x2 = nullptr,
-                  const float* res = nullptr, int ldr = 0, const int* rowgate = nullptr) {
+int linear(const float* x, int ldx, const tc_linear& w, int M, int K, int N, int act, float* y, int ldy, hipStream_t s,
+           const float* x2, const float* res, int ldr, const int* rowgate) {
   GemmArgs g;
   g.X = x; g.ldx = ldx; g.X2 = x2; g.x2_cols = x2 ? ((N + 15) / 16) * 16 : 0;
   g.W = w.w; g.ldw = K; g.bias = w.b; g.R = res; g.ldr = ldr; g.rowgate = rowgate;
@@ -56,11 +40,14 @@ static int linear(const float* x, int ldx, const tc_linear& w, int M, int K, int
   return launch_gemm(g, s);
 }
 
-static int layernorm(const float* a, const tc_lnorm& n, float* y, int M, int relu, hipStream_t s) {
+int layernorm(const float* a, const tc_lnorm& n, float* y, int M, int relu, hipStream_t s, const float* b) {
   LnArgs l;
-  l.a = a; l.gamma = n.g; l.beta = n.b; l.y = y; l.M = M; l.relu = relu;
+  l.a = a; l.b = b; l.gamma = n.g; l.beta = n.b; l.y = y; l.M = M; l.relu = relu;
   return launch_ln256(l, s);
 }
+
+// q * log2(e)/sqrt(head_dim): the decoder's attention cores exponentiate with 2^x
+static float decoder_qscale(int C, int H) { return 1.4426950408889634f / sqrtf((float)(C / H)); }
 
 // mmcv MultiheadAttention wrapper for decoder self-attention:
 // out = x + out_proj(MHA(q = k = x + pos, v = x))
@@ -73,11 +60,45 @@ static int self_attn(const tc_mha& w, const float* x, const float* pos, float* o
   g.Y = qk; g.ldy = 2 * C;
   g.Yt = vt; g.t_col0 = 2 * C; g.t_ld = qpad; g.t_rows_per_batch = Q;
   g.M = rows; g.K = C; g.N = 3 * C;
-  // q * log2(e)/sqrt(head_dim): the attention core exponentiates with 2^x
-  g.scale = 1.4426950408889634f / sqrtf((float)(C / H)); g.scale_cols = C;
+  g.scale = decoder_qscale(C, H); g.scale_cols = C;
   TC_TRY(launch_gemm(g, s));
   TC_TRY(launch_self_attn_core(qk, qk + C, 2 * C, vt, qpad, attn_o, C, B, Q, H, C / H, s));
   return linear(attn_o, C, w.out_proj, rows, C, C, 0, out, C, s, nullptr, x, C);
+}
+
+// Detr3DCrossAtten.num_points of a head (0 in a struct that does not set it: 1)
+static int head_points(const tc_head_weights* w) { return w->num_points > 0 ? w->num_points : 1; }
+
+// the camera sampling of B frames of Q queries, by explicit dimensions (pc null: the range stays zero) ...
+static CamSampleArgs cam_args(const tc_feats_nhwc& feats, int B, int Q, int C, int num_cams, int num_points,
+                              const float* lidar2img, const float* ref, const float* pc, float img_h, float img_w,
+                              unsigned long long* pair_counter = nullptr, const float* logits = nullptr,
+                              float* out = nullptr, unsigned char* vis = nullptr) {
+  CamSampleArgs c;
+  c.feats = feats; c.B = B; c.Q = Q; c.C = C; c.num_cams = num_cams; c.num_points = num_points;
+  c.lidar2img = lidar2img; c.ref = ref; c.logits = logits;
+  if (pc != nullptr) copy_pc(c.pc, pc);
+  c.img_h = img_h; c.img_w = img_w; c.out = out; c.vis = vis; c.pair_counter = pair_counter;
+  return c;
+}
+// ... and by a head's, as the decoder chains take it (they sample from their own logits into their own rows)
+static CamSampleArgs cam_args(const tc_head_weights* w, const tc_feats_nhwc& feats, int B, const float* lidar2img,
+                              const float* ref, float img_h, float img_w, unsigned long long* pair_counter) {
+  return cam_args(feats, B, w->num_query, w->embed_dims, w->num_cams, head_points(w), lidar2img, ref, w->pc_range, img_h,
+                  img_w, pair_counter);
+}
+
+// one decoder layer's chain on the rows of `cam` (ref_in = cam.ref); the caller adds what only some launches have
+// (row modulos, box_m, dropout, tile options, the pre-gather, layer 0's constants)
+static DecoderChainArgs decoder_layer_args(const tc_decoder_layer* layer, const tc_linear* next_in_proj,
+                                           const CamSampleArgs& cam, int code, float qscale, const float* attn_o,
+                                           const float* x_in, int x_ld, const float* qe, float* hs, float* ref_out,
+                                           float* qk, float* vt, int qpad) {
+  DecoderChainArgs d;
+  d.attn_o = attn_o; d.x_in = x_in; d.x_ld = x_ld; d.qe = qe; d.Q = cam.Q;
+  d.ref_in = cam.ref; d.ref_out = ref_out; d.w = layer; d.next_in_proj = next_in_proj; d.qscale = qscale;
+  d.hs = hs; d.qk = qk; d.vt = vt; d.qpad = qpad; d.cam = cam; d.code = code; d.M = cam.B * cam.Q;
+  return d;
 }
 
 struct CrossWs { float *logits, *sampled, *t0, *pe0, *pe1; };
@@ -93,19 +114,11 @@ static int cross_atten_parts(const tc_linear& aw, const tc_linear& oproj, const 
   const int rows = B * Q;
   const int NL = ncams * feats->num_levels * np;       // attention_weights: N * P * L columns (XFMR:362-363)
   TC_TRY(linear(query, C, aw, rows, C, NL, 0, ws.logits, NL, s, pos));
-  CamSampleArgs c;
-  c.feats = *feats; c.B = B; c.Q = Q; c.C = C; c.num_cams = ncams; c.num_points = np;
-  c.lidar2img = l2i; c.ref = ref; c.logits = ws.logits;
-  for (int i = 0; i < 6; ++i) c.pc[i] = pc[i];
-  c.img_h = img_h; c.img_w = img_w; c.out = ws.sampled; c.vis = nullptr; c.pair_counter = pair_counter;
-  TC_TRY(launch_cam_sample(c, s));
+  TC_TRY(launch_cam_sample(cam_args(*feats, B, Q, C, ncams, np, l2i, ref, pc, img_h, img_w, pair_counter, ws.logits, ws.sampled), s));
   TC_TRY(linear(ws.sampled, C, oproj, rows, C, C, 0, ws.t0, C, s, nullptr, query, C));
   TC_TRY(launch_posenc_l1(ref, 3, 1, pe.l0.w, pe.l0.b, pe.n1.g, pe.n1.b, ws.pe0, rows, s));
   return linear(ws.pe0, C, pe.l3, rows, C, C, 0, ws.pe1, C, s);
 }
-
-// Detr3DCrossAtten.num_points of a head (0 in a struct that does not set it: 1)
-static int head_points(const tc_head_weights* w) { return w->num_points > 0 ? w->num_points : 1; }
 
 static int check_dims(const tc_head_weights* w) {
   TC_REQUIRE(w != nullptr, "weights pointer is null");
@@ -199,15 +212,132 @@ static const float* l0_consts_of(const tc_head_weights* packed_view, int variant
 }
 
 // ---- fused path: 12 launches per frame (chain.hip) ---------------------------
+// The attention core in front of a decoder chain follows the chains' variant (tile_variant): launches that run 16- / 32-row
+// tiles on the f16 matrix cores take the staged two-plane core (self_attn.hip, round 4) -- 4- / 8-row launches (one or two
+// frames: too few workgroups for a form without split keys) and TC_MATRIX_F32 the fp32 core.  A frame's arithmetic is
+// therefore fixed by (chain_tile_rows, matrix_path), not by how many frames share a launch.
+// Round 6 (opt-in, tc_head_options.cam_pregather): the staged core's launch also carries the camera gather of THIS layer's
+// chain `d` (pre-gather workgroups: the layer's reference points are final since the previous chain).
+static int launch_layer_attn_core(const tc_head_weights* w, int B, const tc_head_options& opt, const HeadWs& h, int variant,
+                                  DecoderChainArgs& d, hipStream_t s) {
+  const int Q = w->num_query, C = w->embed_dims, H = w->num_heads, rows = B * Q;
+  const DropK* drop = opt.decoder_dropout_p > 0.0f ? &d.drop : nullptr;
+  if (variant_mm(variant) != 1)
+    return launch_self_attn_core(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, C / H, s, drop);
+  PreGatherArgs pga;
+  const bool pre = drop == nullptr && opt.cam_pregather == 1;
+  if (pre) {
+    // scratch: [rows][num_cams][levels][C] level values (only the visible pairs' 4 KiB are ever touched), [rows] masks
+    float* pbuf = static_cast<float*>(opt.cam_pregather_ws);
+    int* pmask = reinterpret_cast<int*>(pbuf + (size_t)rows * w->num_cams * w->num_levels * C);
+    pga.cam = d.cam; pga.M = rows; pga.ref_mod = d.ref_mod; pga.out = pbuf; pga.mask = pmask;
+    d.pre = pbuf; d.premask = pmask;
+  }
+  return launch_self_attn_core_x(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, C / H, s, drop, pre ? &pga : nullptr);
+}
+
+// Phase 1, the decoder layers of this call (all of them, or options.phase's share).  re: the radar encoders, null without
+// a radar part.  folded: layer 0 up to its attention output comes from the packed view.
+static int fused_decoder_layers(const tc_head_weights* w, const tc_feats_nhwc* feats, int B, const float* lidar2img,
+                                float img_h, float img_w, const RadarEncodeArgs* re, unsigned long long* pairs,
+                                const tc_head_options& opt, const HeadWs& h, bool refine, bool folded, hipStream_t s) {
+  const int Q = w->num_query, C = w->embed_dims, L = w->num_layers, H = w->num_heads, rows = B * Q;
+  const float* qe = w->query_embedding;
+  // the radar encoders and K/V projections do not depend on the decoder: they ride in the launches of two
+  // decoder layers as extra workgroups (chain_dual_kernel): layers 0 and 1 in the one-call forward; the LAST
+  // two when the forward comes in two phases (options.phase) -- their K/V feed only the fusion stack, and a
+  // caller that still has to build the tokens does so while the device runs the layers before
+  const int enc_first = opt.phase != 0 && L > 1 ? L - 2 : 0;
+  const int lid_begin = opt.phase == 2 ? enc_first : 0, lid_end = opt.phase == 1 ? enc_first : L;
+  // train-mode statistics of the frozen decoder: five dropout sites per layer (sites 16 + 8 l + 0..4)
+  const bool ddrop = opt.decoder_dropout_p > 0.0f;
+  TC_REQUIRE(!ddrop || (unsigned long long)(opt.dropout_seed_stride ? 1 : B) * H * Q * Q < (1ull << 32),
+             "decoder dropout: B*H*Q*Q exceeds 32 bits");
+  if (re != nullptr && ddrop && opt.phase != 1) TC_TRY(launch_radar_encode(*re, s));     // no ride in the decoder launches then
+  // everything in front of layer 0's camera sampling that reads no frame data is a constant too (out_proj, norm0, pe.3),
+  // made by the kernel variant this forward selects (bit-identical to running them here)
+  const int variant = tile_variant(rows, opt.chain_tile_rows, opt.matrix_path, "head_forward");
+  if (variant < 0) return variant;
+  const int l0_variant = folded && l0_foldable(w) ? variant : -1;
+  if (!folded && opt.phase != 2) {
+    PrologueArgs pa;
+    pa.qe = qe; pa.Q = Q; pa.M = rows; pa.refpts = w->reference_points;
+    pa.in_proj = w->layers[0].self_attn.in_proj; pa.init_ref = h.init_ref; pa.qk = h.qk; pa.vt = h.vt;
+    pa.qpad = h.qpad; pa.qscale = decoder_qscale(C, H); pa.w16_delta = w->packed16_delta;
+    TC_TRY(launch_prologue(pa, s));
+  }
+  for (int lid = lid_begin; lid < lid_end; ++lid) {
+    const bool l0c = folded && lid == 0;
+    // without box refinement every layer samples at the initial reference points (the folded one when layer 0 is) ...
+    const bool init_in = lid == 0 || !refine;
+    const float* ref_in = init_in ? (folded ? w->l0_init_reference : h.init_ref)
+                                  : h.inter_refs + (size_t)(lid - 1) * rows * 3;
+    // ... and only the last layer has a reg branch (its box); the point it refines is not used (h.addref: the
+    // operator-by-operator path's scratch), every level's reference is filled after the layers
+    float* ref_out = refine ? h.inter_refs + (size_t)lid * rows * 3 : h.addref;
+    DecoderChainArgs d = decoder_layer_args(
+        &w->layers[lid], lid + 1 < L ? &w->layers[lid + 1].self_attn.in_proj : nullptr,
+        cam_args(w, *feats, B, lidar2img, ref_in, img_h, img_w, pairs), w->code_size, decoder_qscale(C, H),
+        l0c ? w->l0_attn_out : h.attn_o, lid == 0 ? qe + C : h.hs + (size_t)(lid - 1) * rows * C, lid == 0 ? 2 * C : C, qe,
+        h.hs + (size_t)lid * rows * C, ref_out, h.qk, h.vt, h.qpad);
+    d.attn_mod = l0c ? Q : 0; d.ref_mod = folded && init_in ? Q : 0; d.x_mod = lid == 0 ? Q : 0;
+    d.box_m = lid == L - 1 ? h.box_m : nullptr;
+    if (ddrop) {
+      d.drop = make_drop(opt.decoder_dropout_p, opt.dropout_seed, 16u + 8u * (unsigned)lid, 0u);
+      if (opt.dropout_seed_stride != 0) { d.drop.seed_stride = opt.dropout_seed_stride; d.drop.rows_per_sample = (unsigned)Q; }
+    }
+    d.tile_rows = opt.chain_tile_rows; d.matrix_path = opt.matrix_path; d.range_status = opt.range_status;
+    if (l0c && l0_variant >= 0) d.l0_consts = l0_consts_of(w, l0_variant);
+    if (!l0c) TC_TRY(launch_layer_attn_core(w, B, opt, h, variant, d, s));
+    // the radar encoders ride in two launches, half each (all in layer 0 when there is only one layer)
+    if (re != nullptr && !ddrop && lid == enc_first) TC_TRY(launch_decoder_chain_with_encoders(d, *re, L > 1 ? 1 : 0, s));
+    // (half B is the K/V of fusion layers 1 and 2: a one-layer fusion head has none, its second launch is the plain chain)
+    else if (re != nullptr && !ddrop && L > 1 && lid == enc_first + 1 && w->num_radar_layers > 1)
+      TC_TRY(launch_decoder_chain_with_encoders(d, *re, 2, s));
+    else TC_TRY(launch_decoder_chain(d, s));
+  }
+  return 0;
+}
+
+// Phase 2, the references behind the last decoder layer: what the radar part reads and what the caller asked for
+static int fused_references(const tc_head_weights* w, int B, const tc_head_aux* aux, const HeadWs& h, bool refine,
+                            bool folded, hipStream_t s) {
+  const int Q = w->num_query, rows = B * Q;
+  if (!refine)   // inter_references[l] = init_reference (XFMR:183-203 with reg_branches=None): what the radar part reads
+    TC_TRY(launch_ref_broadcast(folded ? w->l0_init_reference : h.init_ref, folded ? Q : 0, h.inter_refs, rows, w->num_layers, s));
+  if (aux == nullptr || aux->init_reference == nullptr) return 0;
+  if (!folded) {
+    TC_HIP(hipMemcpyAsync(aux->init_reference, h.init_ref, (size_t)rows * 3 * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  for (int b = 0; b < B; ++b)
+    TC_HIP(hipMemcpyAsync(aux->init_reference + (size_t)b * Q * 3, w->l0_init_reference, (size_t)Q * 3 * 4,
+                          hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// Phase 3, the fusion layers of `rc` on the B frames, then their hit counts into hit_counts (may be null).  The one place
+// that decides the row order: queries with a radar return inside their first gate go first (the other tiles skip the gated
+// part) when asked (radar_row_order 2) or, left to the library (0), with more than 1024 rows.
+static int launch_fusion_chain(RadarChainArgs rc, int B, const tc_head_options& opt, const HeadWs& h, int* hit_counts,
+                               hipStream_t s) {
+  if (opt.radar_row_order == 2 || (opt.radar_row_order == 0 && rc.M > 1024)) {
+    TC_TRY(launch_radar_compact(rc.ref_last, rc.box_m, rc.code, rc.cen_from_box, rc.pc, rc.tokens, rc.RI, B, rc.Q, rc.T,
+                                rc.w[0].radius_min, rc.w[0].radius_max, h.hitflag, h.perm, s));
+    rc.row_perm = h.perm;
+  }
+  TC_TRY(launch_radar_chain(rc, s));
+  if (hit_counts != nullptr)
+    TC_HIP(hipMemcpyAsync(hit_counts, h.hits, (size_t)rc.nlayers * rc.M * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
 static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* feats, int B,
                               const float* lidar2img, float img_h, float img_w,
                               const float* radar_tokens, int T, int pad_mult, float* all_cls_scores,
                               float* all_bbox_preds, const tc_head_aux* aux, const tc_head_options& opt,
                               const HeadWs& h_, hipStream_t s) {
-  const int Q = w->num_query, C = w->embed_dims, L = w->num_layers, H = w->num_heads;
-  const int code = w->code_size, ncls = w->num_classes;
-  const int rows = B * Q, rt = B * T;
-  const float attn_qscale = 1.4426950408889634f / sqrtf((float)(C / H));   // 2^x softmax
+  const int C = w->embed_dims, L = w->num_layers, rows = B * w->num_query;
   // the caller's aux tensors ARE the buffers the chains write (and read back for the next layer): no copies
   // at the end of the forward (round 2: four device-to-device copies per forward with aux, e.g. every training
   // iteration)
@@ -217,153 +347,23 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
     if (aux->inter_references) h.inter_refs = aux->inter_references;
     if (aux->last_box) h.box_m = aux->last_box;
   }
-  unsigned long long* pairs = aux ? aux->sample_pairs : nullptr;
   const bool radar = w->num_radar_layers > 0;
   bool refine = true;
   TC_TRY(decoder_refines(w, &refine));
-
-  // the radar encoders and K/V projections do not depend on the decoder: they ride in the launches of two
-  // decoder layers as extra workgroups (chain_dual_kernel): layers 0 and 1 in the one-call forward; the LAST
-  // two when the forward comes in two phases (options.phase) -- their K/V feed only the fusion stack, and a
-  // caller that still has to build the tokens does so while the device runs the layers before
-  const int enc_first = opt.phase != 0 && L > 1 ? L - 2 : 0;
-  const int lid_begin = opt.phase == 2 ? enc_first : 0, lid_end = opt.phase == 1 ? enc_first : L;
   RadarEncodeArgs re;
-  if (radar) {
-    re.tokens = radar_tokens; re.RI = w->radar_in_dims; re.M = rt;
-    re.rpe = w->radar_position_encoder; re.f0 = w->radar_feat0; re.f2 = w->radar_feat2;
-    re.f4 = w->radar_feat4; re.nlayers = w->num_radar_layers;
-    for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
-      const tc_mha& m = w->radar[r].attn;
-      re.kvproj[r] = tc_linear{m.in_proj.w ? m.in_proj.w + (size_t)C * C : nullptr,
-                               m.in_proj.b ? m.in_proj.b + C : nullptr};
-      re.kv[r] = h.kv3[r];
-    }
-    re.radar_feat = h.radar_feat;
-    re.w16_delta = w->packed16_delta; re.matrix_path = opt.matrix_path; re.range_status = opt.range_status;
-  }
-
-  // train-mode statistics of the frozen decoder: five dropout sites per layer (sites 16 + 8 l + 0..4)
-  const bool ddrop = opt.decoder_dropout_p > 0.0f;
-  TC_REQUIRE(!ddrop || (unsigned long long)(opt.dropout_seed_stride ? 1 : B) * H * Q * Q < (1ull << 32),
-             "decoder dropout: B*H*Q*Q exceeds 32 bits");
-  if (radar && ddrop && opt.phase != 1) TC_TRY(launch_radar_encode(re, s));     // no ride in the decoder launches then
+  if (radar) re = radar_encode_args(w, radar_tokens, B * T, h.kv3, h.radar_feat, opt.matrix_path, opt.range_status);
   // layer 0 up to its attention output is a constant of the checkpoint (pack time) -- in eval
   // mode: with dropout on the attention probabilities it is not
-  const bool folded = !ddrop && w->l0_attn_out != nullptr && w->l0_init_reference != nullptr;
-  // ... and so is everything in front of its camera sampling that reads no frame data: out_proj, norm0 and pe.3 come
-  // as constants too, made by the kernel variant this forward selects (bit-identical to running them here)
-  const int variant = tile_variant(rows, opt.chain_tile_rows, opt.matrix_path, "head_forward");
-  if (variant < 0) return variant;
-  const int l0_variant = folded && l0_foldable(w) ? variant : -1;
-  if (!folded && opt.phase != 2) {
-    PrologueArgs pa;
-    pa.qe = w->query_embedding; pa.Q = Q; pa.M = rows; pa.refpts = w->reference_points;
-    pa.in_proj = w->layers[0].self_attn.in_proj; pa.init_ref = h.init_ref; pa.qk = h.qk; pa.vt = h.vt;
-    pa.qpad = h.qpad; pa.qscale = attn_qscale; pa.w16_delta = w->packed16_delta;
-    TC_TRY(launch_prologue(pa, s));
-  }
-  for (int lid = lid_begin; lid < lid_end; ++lid) {
-    const bool l0c = folded && lid == 0;
-    // without box refinement every layer samples at the initial reference points (the folded one when layer 0 is)
-    const bool init_in = lid == 0 || !refine;
-    const float* ref_in = init_in ? (folded ? w->l0_init_reference : h.init_ref)
-                                  : h.inter_refs + (size_t)(lid - 1) * rows * 3;
-    DecoderChainArgs d;
-    if (ddrop) {
-      d.drop = make_drop(opt.decoder_dropout_p, opt.dropout_seed, 16u + 8u * (unsigned)lid, 0u);
-      if (opt.dropout_seed_stride != 0) { d.drop.seed_stride = opt.dropout_seed_stride; d.drop.rows_per_sample = (unsigned)Q; }
-    }
-    d.attn_o = l0c ? w->l0_attn_out : h.attn_o;
-    d.attn_mod = l0c ? Q : 0; d.ref_mod = folded && init_in ? Q : 0;
-    if (lid == 0) { d.x_in = w->query_embedding + C; d.x_ld = 2 * C; d.x_mod = Q; }
-    else { d.x_in = h.hs + (size_t)(lid - 1) * rows * C; d.x_ld = C; d.x_mod = 0; }
-    d.qe = w->query_embedding; d.Q = Q;
-    d.ref_in = ref_in; d.ref_out = h.inter_refs + (size_t)lid * rows * 3;
-    d.box_m = lid == L - 1 ? h.box_m : nullptr;
-    // without box refinement only the last layer has a reg branch (its box); the point it refines is not used
-    // (h.addref: the operator-by-operator path's scratch), every level's reference is filled below
-    if (!refine) d.ref_out = h.addref;
-    d.w = &w->layers[lid];
-    d.next_in_proj = lid + 1 < L ? &w->layers[lid + 1].self_attn.in_proj : nullptr;
-    d.qscale = attn_qscale;
-    d.hs = h.hs + (size_t)lid * rows * C; d.qk = h.qk; d.vt = h.vt; d.qpad = h.qpad;
-    d.cam.feats = *feats; d.cam.B = B; d.cam.Q = Q; d.cam.C = C; d.cam.num_cams = w->num_cams;
-    d.cam.num_points = head_points(w);
-    d.cam.lidar2img = lidar2img; d.cam.ref = ref_in; d.cam.logits = nullptr;
-    for (int i = 0; i < 6; ++i) d.cam.pc[i] = w->pc_range[i];
-    d.cam.img_h = img_h; d.cam.img_w = img_w; d.cam.out = nullptr; d.cam.vis = nullptr;
-    d.cam.pair_counter = pairs;
-    d.code = code; d.M = rows; d.tile_rows = opt.chain_tile_rows; d.matrix_path = opt.matrix_path;
-    d.range_status = opt.range_status;
-    if (l0c && l0_variant >= 0) d.l0_consts = l0_consts_of(w, l0_variant);
-    // the attention core follows the chains' variant (tile_variant): launches that run 16- / 32-row tiles on
-    // the f16 matrix cores take the staged two-plane core (self_attn.hip, round 4) -- 4- / 8-row launches (one or two
-    // frames: too few workgroups for a form without split keys) and TC_MATRIX_F32 the fp32 core.  A
-    // frame's arithmetic is therefore fixed by (chain_tile_rows, matrix_path), not by how many frames share a launch.
-    // Round 6 (opt-in, tc_head_options.cam_pregather): the staged core's launch also carries the camera gather of THIS
-    // layer's chain (pre-gather workgroups: the layer's reference points are final since the previous chain).
-    if (!l0c) {
-      if (variant_mm(variant) == 1) {
-        PreGatherArgs pga;
-        const bool pre = !ddrop && opt.cam_pregather == 1;
-        if (pre) {
-          // scratch: [rows][num_cams][levels][C] level values (only the visible pairs' 4 KiB are ever touched), [rows] masks
-          float* pbuf = static_cast<float*>(opt.cam_pregather_ws);
-          int* pmask = reinterpret_cast<int*>(pbuf + (size_t)rows * w->num_cams * w->num_levels * C);
-          pga.cam = d.cam; pga.M = rows; pga.ref_mod = d.ref_mod; pga.out = pbuf; pga.mask = pmask;
-          d.pre = pbuf; d.premask = pmask;
-        }
-        TC_TRY(launch_self_attn_core_x(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, C / H, s, ddrop ? &d.drop : nullptr,
-                                       pre ? &pga : nullptr));
-      } else {
-        TC_TRY(launch_self_attn_core(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, C / H, s, ddrop ? &d.drop : nullptr));
-      }
-    }
-    // the radar encoders ride in two launches, half each (all in layer 0 when there is only one layer)
-    if (radar && !ddrop && lid == enc_first) TC_TRY(launch_decoder_chain_with_encoders(d, re, L > 1 ? 1 : 0, s));
-    // (half B is the K/V of fusion layers 1 and 2: a one-layer fusion head has none, its second launch is the plain chain)
-    else if (radar && !ddrop && L > 1 && lid == enc_first + 1 && w->num_radar_layers > 1)
-      TC_TRY(launch_decoder_chain_with_encoders(d, re, 2, s));
-    else TC_TRY(launch_decoder_chain(d, s));
-  }
+  const bool folded = !(opt.decoder_dropout_p > 0.0f) && w->l0_attn_out != nullptr && w->l0_init_reference != nullptr;
+  TC_TRY(fused_decoder_layers(w, feats, B, lidar2img, img_h, img_w, radar ? &re : nullptr, aux ? aux->sample_pairs : nullptr,
+                              opt, h, refine, folded, s));
   if (opt.phase == 1) return 0;
-  if (!refine)   // inter_references[l] = init_reference (XFMR:183-203 with reg_branches=None): what the radar part reads
-    TC_TRY(launch_ref_broadcast(folded ? w->l0_init_reference : h.init_ref, folded ? Q : 0, h.inter_refs, rows, L, s));
-  if (aux) {
-    if (aux->init_reference) {
-      if (folded) {
-        for (int b = 0; b < B; ++b)
-          TC_HIP(hipMemcpyAsync(aux->init_reference + (size_t)b * Q * 3, w->l0_init_reference,
-                                (size_t)Q * 3 * 4, hipMemcpyDeviceToDevice, s));
-      } else {
-        TC_HIP(hipMemcpyAsync(aux->init_reference, h.init_ref, (size_t)rows * 3 * 4, hipMemcpyDeviceToDevice, s));
-      }
-    }
-  }
+  TC_TRY(fused_references(w, B, aux, h, refine, folded, s));
   if (!radar) return 0;
-  RadarChainArgs rc;
-  rc.qf = h.hs + (size_t)(L - 1) * rows * C;
-  rc.ref_last = h.inter_refs + (size_t)(L - 1) * rows * 3;
-  rc.box_m = h.box_m; rc.tokens = radar_tokens; rc.RI = w->radar_in_dims;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) { rc.kv[r] = h.kv3[r]; rc.w[r] = w->radar[r]; }
-  rc.nlayers = w->num_radar_layers; rc.Q = Q; rc.T = T; rc.pad_mult = pad_mult; rc.code = code;
-  rc.ncls = ncls; rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
-  for (int i = 0; i < 6; ++i) rc.pc[i] = w->pc_range[i];
-  rc.all_cls = all_cls_scores; rc.all_box = all_bbox_preds; rc.hits = h.hits;
-  rc.tile_rows = opt.chain_tile_rows; rc.last_cls_only = opt.last_level_cls_only; rc.matrix_path = opt.matrix_path;
-  rc.range_status = opt.range_status;
-  if (opt.radar_row_order == 2 || (opt.radar_row_order == 0 && rows > 1024)) {
-    // queries with a radar return inside their first gate go first: the other tiles skip the gated part
-    TC_TRY(launch_radar_compact(rc.ref_last, rc.box_m, code, 0, w->pc_range, radar_tokens, w->radar_in_dims, B, Q, T,
-                                w->radar[0].radius_min, w->radar[0].radius_max, h.hitflag, h.perm, s));
-    rc.row_perm = h.perm;
-  }
-  TC_TRY(launch_radar_chain(rc, s));
-  if (aux && aux->radar_hit_counts)
-    TC_HIP(hipMemcpyAsync(aux->radar_hit_counts, h.hits, (size_t)w->num_radar_layers * rows * 4,
-                          hipMemcpyDeviceToDevice, s));
-  return 0;
+  return launch_fusion_chain(radar_chain_args(w, 0, w->num_radar_layers, h.kv3, h.hs + (size_t)(L - 1) * rows * C,
+                                              h.inter_refs + (size_t)(L - 1) * rows * 3, h.box_m, radar_tokens, B, T, pad_mult,
+                                              all_cls_scores, all_bbox_preds, h.hits, &opt),
+                             B, opt, h, aux ? aux->radar_hit_counts : nullptr, s);
 }
 
 // ---- packed weights for the fused chains (pack.hip) --------------------------
@@ -417,6 +417,28 @@ static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, Pack
   return n;
 }
 constexpr int MAX_PACK_ITEMS = 1 + 10 * TC_MAX_LAYERS + 4 + 10 * TC_MAX_RADAR_LAYERS;
+
+// The re-pack jobs of the trainable weights after an optimizer step, copies = 1 (the 4x4x1 copy) or 3 (+ the 16x16x4 and
+// the f16 ones): the same item order as tc_head_pack_weights; the decoder's items (frozen under tools/train.py:245-252)
+// and the layer-0 constants keep their packed contents.  For ONE launch (round 2: one launch per weight, 28 launches
+// after every optimizer step).  Returns the job count, -1 with the error set (prefixed by `who`).
+static int trainable_pack_jobs(const char* who, const tc_head_weights* w, const tc_head_weights* packed_view, int copies,
+                               PackJob* jobs) {
+  tc_head_weights scratch = *packed_view;
+  PackItem items[MAX_PACK_ITEMS];
+  const int n = collect_pack_items(w, &scratch, items);
+  const size_t delta = packed_view->packed16_delta;
+  int nj = 0;
+  for (int i = 1 + 10 * w->num_layers; i < n; ++i) {
+    TC_REQUIRE(items[i].src != nullptr, "%s: weight %d is null", who, i);
+    if (items[i].narrow) continue;                     // read in place by the chains
+    // scratch is a copy of the packed view: its slot still holds the packed destination
+    float* dst = const_cast<float*>(*items[i].slot);
+    jobs[nj] = PackJob{items[i].src, dst, copies == 3 ? dst + delta : nullptr, items[i].N, items[i].K};
+    jobs[nj++].PH = copies == 3 ? dst + 2 * delta : nullptr;
+  }
+  return nj;
+}
 
 }  // namespace tc
 
@@ -485,13 +507,8 @@ int tc_cam_sample_fuse_fwd(const tc_feats_nhwc* feats, int B, int Q, int C, int 
                            const float* pc_range, float img_h, float img_w, float* out,
                            unsigned char* vis_mask, unsigned long long* pair_counter,
                            tc_stream_t stream) {
-  TC_REQUIRE(feats != nullptr, "feats is null");
-  CamSampleArgs c;
-  c.feats = *feats; c.B = B; c.Q = Q; c.C = C; c.num_cams = num_cams;
-  c.lidar2img = lidar2img; c.ref = ref; c.logits = attn_logits;
-  for (int i = 0; i < 6; ++i) c.pc[i] = pc_range[i];
-  c.img_h = img_h; c.img_w = img_w; c.out = out; c.vis = vis_mask; c.pair_counter = pair_counter;
-  return launch_cam_sample(c, as_stream(stream));
+  return tc_cam_sample_fuse_points_fwd(feats, B, Q, C, num_cams, 1, lidar2img, ref, attn_logits, pc_range, img_h, img_w, out,
+                                       vis_mask, pair_counter, stream);
 }
 
 int tc_cam_sample_fuse_points_fwd(const tc_feats_nhwc* feats, int B, int Q, int C, int num_cams, int num_points,
@@ -500,12 +517,8 @@ int tc_cam_sample_fuse_points_fwd(const tc_feats_nhwc* feats, int B, int Q, int 
                                   unsigned char* vis_mask, unsigned long long* pair_counter,
                                   tc_stream_t stream) {
   TC_REQUIRE(feats != nullptr, "feats is null");
-  CamSampleArgs c;
-  c.feats = *feats; c.B = B; c.Q = Q; c.C = C; c.num_cams = num_cams; c.num_points = num_points;
-  c.lidar2img = lidar2img; c.ref = ref; c.logits = attn_logits;
-  for (int i = 0; i < 6; ++i) c.pc[i] = pc_range[i];
-  c.img_h = img_h; c.img_w = img_w; c.out = out; c.vis = vis_mask; c.pair_counter = pair_counter;
-  return launch_cam_sample(c, as_stream(stream));
+  return launch_cam_sample(cam_args(*feats, B, Q, C, num_cams, num_points, lidar2img, ref, pc_range, img_h, img_w, pair_counter,
+                                    attn_logits, out, vis_mask), as_stream(stream));
 }
 
 size_t tc_cross_atten_points_workspace_bytes(int B, int Q, int C, int num_cams, int num_levels, int num_points) {
@@ -590,19 +603,11 @@ int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* ne
   TC_REQUIRE(layer != nullptr && feats != nullptr, "decoder_layer_tail: null argument");
   TC_REQUIRE(feats->num_levels == 4, "decoder_layer_tail: num_levels=%d (4 supported; heads with fewer levels run "
              "through tc_head_forward)", feats->num_levels);
-  const int C = 256;
-  DecoderChainArgs d;
-  d.attn_o = attn_o; d.x_in = x_in; d.x_ld = C; d.x_mod = 0;
-  d.qe = query_embedding; d.Q = Q; d.ref_in = ref_in; d.ref_out = ref_out; d.box_m = nullptr;
-  d.w = layer; d.next_in_proj = next_in_proj;
-  d.qscale = 1.4426950408889634f / sqrtf(32.0f);
-  d.hs = hs; d.qk = qk; d.vt = vt; d.qpad = qpad;
-  d.cam.feats = *feats; d.cam.B = B; d.cam.Q = Q; d.cam.C = C; d.cam.num_cams = num_cams;
-  d.cam.lidar2img = lidar2img; d.cam.ref = ref_in; d.cam.logits = nullptr;
-  for (int i = 0; i < 6; ++i) d.cam.pc[i] = pc_range[i];
-  d.cam.img_h = img_h; d.cam.img_w = img_w; d.cam.out = nullptr; d.cam.vis = nullptr;
-  d.cam.pair_counter = nullptr;
-  d.code = code_size; d.M = B * Q; d.tile_rows = TC_TILE_ROWS(tile_rows); d.matrix_path = TC_TILE_MATRIX(tile_rows);
+  const int C = 256, H = 8;            // (the layer of the default head: one sampling point, head dimension 32)
+  DecoderChainArgs d = decoder_layer_args(layer, next_in_proj, cam_args(*feats, B, Q, C, num_cams, 1, lidar2img, ref_in, pc_range,
+                                                                         img_h, img_w), code_size, decoder_qscale(C, H),
+                                          attn_o, x_in, C, query_embedding, hs, ref_out, qk, vt, qpad);
+  d.tile_rows = TC_TILE_ROWS(tile_rows); d.matrix_path = TC_TILE_MATRIX(tile_rows);
   TC_REQUIRE(d.matrix_path <= TC_MATRIX_F16X2 && (tile_rows >> 10) == 0, "decoder_layer_tail: tile_rows=0x%x", tile_rows);
   TC_TRY(launch_decoder_chain(d, as_stream(stream)));
   if (layer->reg.l0.w == nullptr)      // no reg branch (a decoder without box refinement): the reference stays
@@ -655,19 +660,14 @@ int tc_radar_gated_xattn_fwd(const tc_mha* w, const float* query, const float* c
   float* qproj = a.take<float>((size_t)rows * C);
   float* rattn = a.take<float>((size_t)rows * C);
   int* hits = hit_counts ? hit_counts : a.take<int>(rows);
-  tc_linear wkv{w->in_proj.w + (size_t)C * C, w->in_proj.b + C};
-  TC_TRY(linear(radar_feat, C, wkv, rt, C, 2 * C, 0, kv, 2 * C, s));
+  TC_TRY(linear(radar_feat, C, kv_half(*w, C), rt, C, 2 * C, 0, kv, 2 * C, s));
   GemmArgs g;
   g.X = query; g.ldx = C; g.W = w->in_proj.w; g.ldw = C; g.bias = w->in_proj.b;
   g.Y = qproj; g.ldy = C; g.M = rows; g.K = C; g.N = C;
   g.scale = 1.0f / sqrtf((float)(C / num_heads)); g.scale_cols = C;
   TC_TRY(launch_gemm(g, s));
-  RadarAttnArgs r;
-  r.qproj = qproj; r.ldq = C; r.kv = kv; r.ldkv = 2 * C; r.centre_xy = centre_xy; r.ld_c = 2;
-  r.box = box; r.code = code_size; r.radar_xy = radar_xy; r.ld_xy = 2;
-  r.B = B; r.Q = Q; r.T = T; r.C = C; r.H = num_heads; r.pad_mult = pad_mult;
-  r.rmin = radius_min; r.rmax = radius_max; r.attn_out = rattn; r.hit_counts = hits;
-  TC_TRY(launch_radar_attn(r, s));
+  TC_TRY(launch_radar_attn(radar_attn_args(qproj, kv, centre_xy, 2, box, code_size, radar_xy, 2, B, Q, T, C, num_heads, pad_mult,
+                                           radius_min, radius_max, rattn, hits), s));
   return linear(rattn, C, w->out_proj, rows, C, C, 0, out, C, s, nullptr, query, C, hits);
 }
 
@@ -711,45 +711,13 @@ int tc_radar_fusion_fwd(const tc_head_weights* packed_view, const float* hs_last
   const size_t need = head_ws_layout(w, B, T, workspace, workspace_bytes, &h);
   TC_REQUIRE(need <= workspace_bytes, "workspace too small: need %zu, have %zu", need, workspace_bytes);
   hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, rows = B * Q, rt = B * T;
-  const int code = w->code_size, ncls = w->num_classes;
-  // encoders + K/V projections of all layers (stand-alone encoder program)
-  RadarEncodeArgs re;
-  re.tokens = radar_tokens; re.RI = w->radar_in_dims; re.M = rt;
-  re.rpe = w->radar_position_encoder; re.f0 = w->radar_feat0; re.f2 = w->radar_feat2;
-  re.f4 = w->radar_feat4; re.nlayers = w->num_radar_layers;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {
-    const tc_mha& m = w->radar[r].attn;
-    re.kvproj[r] = tc_linear{m.in_proj.w ? m.in_proj.w + (size_t)C * C : nullptr,
-                             m.in_proj.b ? m.in_proj.b + C : nullptr};
-    re.kv[r] = h.kv3[r];
-  }
-  re.radar_feat = h.radar_feat;
-  re.w16_delta = w->packed16_delta; re.matrix_path = opt.matrix_path;
-  if (!opt.reuse_radar_kv) TC_TRY(launch_radar_encode(re, s));
-  RadarChainArgs rc;
-  rc.qf = hs_last; rc.ref_last = ref_last; rc.box_m = prev_box; rc.tokens = radar_tokens;
-  rc.RI = w->radar_in_dims;
-  for (int r = 0; r < num_layers; ++r) { rc.kv[r] = h.kv3[first_layer + r]; rc.w[r] = w->radar[first_layer + r]; }
-  rc.nlayers = num_layers; rc.Q = Q; rc.T = T; rc.pad_mult = pad_mult; rc.code = code; rc.ncls = ncls;
-  rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
-  for (int i = 0; i < 6; ++i) rc.pc[i] = w->pc_range[i];
-  rc.all_cls = all_cls_scores + (size_t)first_layer * rows * ncls;
-  rc.all_box = all_bbox_preds + (size_t)first_layer * rows * code;
-  rc.hits = h.hits; rc.tile_rows = opt.chain_tile_rows; rc.last_cls_only = opt.last_level_cls_only; rc.matrix_path = opt.matrix_path;
-  rc.range_status = opt.range_status;
-  rc.cen_from_box = first_layer > 0;
-  if (opt.radar_row_order == 2 || (opt.radar_row_order == 0 && rows > 1024)) {
-    TC_TRY(launch_radar_compact(ref_last, prev_box, code, rc.cen_from_box, w->pc_range, radar_tokens, w->radar_in_dims,
-                                B, Q, T, w->radar[first_layer].radius_min, w->radar[first_layer].radius_max,
-                                h.hitflag, h.perm, s));
-    rc.row_perm = h.perm;
-  }
-  TC_TRY(launch_radar_chain(rc, s));
-  if (hit_counts != nullptr)
-    TC_HIP(hipMemcpyAsync(hit_counts + (size_t)first_layer * rows, h.hits, (size_t)num_layers * rows * 4,
-                          hipMemcpyDeviceToDevice, s));
-  return 0;
+  // encoders + K/V projections of all layers (stand-alone encoder program).  As before the builders: this launch gets no
+  // range_status (the chain launch below does), so it never raises the sticky non-finite flag
+  if (!opt.reuse_radar_kv)
+    TC_TRY(launch_radar_encode(radar_encode_args(w, radar_tokens, B * T, h.kv3, h.radar_feat, opt.matrix_path, nullptr), s));
+  return launch_fusion_chain(radar_chain_args(w, first_layer, num_layers, h.kv3, hs_last, ref_last, prev_box, radar_tokens, B, T,
+                                              pad_mult, all_cls_scores, all_bbox_preds, h.hits, &opt),
+                             B, opt, h, hit_counts ? hit_counts + (size_t)first_layer * B * w->num_query : nullptr, s);
 }
 
 int tc_radar_gate_selfcheck(int n_radii, unsigned long long seed, unsigned long long* mismatches,
@@ -865,7 +833,7 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
     PrologueArgs pa;
     pa.qe = w->query_embedding; pa.Q = Q; pa.M = Q; pa.refpts = packed_view->reference_points;
     pa.in_proj = packed_view->layers[0].self_attn.in_proj; pa.init_ref = init_ref; pa.qk = qk; pa.vt = vt;
-    pa.qpad = qpad; pa.qscale = 1.4426950408889634f / sqrtf((float)(C / H));
+    pa.qpad = qpad; pa.qscale = decoder_qscale(C, H);
     pa.w16_delta = delta;
     TC_TRY(launch_prologue(pa, s));
     TC_TRY(launch_self_attn_core(qk, qk + C, 2 * C, vt, qpad, attn_o, C, 1, Q, H, C / H, s));
@@ -876,13 +844,13 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
     // constants overwrite qk / vt, which nothing reads after the attention core above (same stream).
     if (l0_foldable(w)) {
       static_assert(sizeof(float) == 4, "slices are counted in floats");
-      DecoderChainArgs d{};
-      d.attn_o = attn_o; d.x_in = w->query_embedding + C; d.x_ld = 2 * C; d.x_mod = Q;
-      d.qe = w->query_embedding; d.Q = Q; d.ref_in = init_ref;
-      d.w = &packed_view->layers[0]; d.qscale = pa.qscale; d.qpad = qpad;
-      d.cam.feats.num_levels = w->num_levels; d.cam.B = 1; d.cam.Q = Q; d.cam.C = C; d.cam.num_cams = w->num_cams;
-      d.cam.num_points = 1; d.cam.ref = init_ref;
-      d.code = w->code_size; d.M = Q;
+      tc_feats_nhwc no_feats = {};          // (the camera part is not read: the level count only selects the kernels)
+      no_feats.num_levels = w->num_levels;
+      DecoderChainArgs d = decoder_layer_args(&packed_view->layers[0], nullptr, cam_args(no_feats, 1, Q, C, w->num_cams, 1, nullptr,
+                                                                                          init_ref, nullptr, 0.0f, 0.0f),
+                                              w->code_size, pa.qscale, attn_o, w->query_embedding + C, 2 * C, w->query_embedding,
+                                              nullptr, nullptr, nullptr, nullptr, qpad);
+      d.x_mod = Q;
       for (int v = 0; v < TC_L0_VARIANTS; ++v)
         TC_TRY(launch_decoder_l0_consts(d, v, const_cast<float*>(l0_consts_of(packed_view, v)), s));
     }
@@ -896,25 +864,9 @@ int tc_head_repack_trainable_ex(const tc_head_weights* w, tc_head_weights* packe
   TC_REQUIRE(packed_view != nullptr && packed_view->l0_attn_out != nullptr,
              "repack_trainable: packed_view was not produced by tc_head_pack_weights");
   TC_REQUIRE(copies == 1 || copies == 3, "repack_trainable: copies=%d (1: the 4x4x1 copy, 3: both)", copies);
-  // the same item order as tc_head_pack_weights; the decoder's items (frozen under
-  // tools/train.py:245-252) and the layer-0 constants keep their packed contents.
-  // ONE launch for all of them (round 2: one launch per weight, 28 launches after every optimizer step).
-  tc_head_weights scratch = *packed_view;
-  PackItem items[MAX_PACK_ITEMS];
-  const int n = collect_pack_items(w, &scratch, items);
-  const int first = 1 + 10 * w->num_layers;
   PackJob jobs[MAX_PACK_ITEMS];
-  int nj = 0;
-  for (int i = first; i < n; ++i) {
-    TC_REQUIRE(items[i].src != nullptr, "repack_trainable: weight %d is null", i);
-    if (items[i].narrow) continue;                     // read in place by the chains
-    // scratch is a copy of the packed view: its slot still holds the packed destination
-    float* dst = const_cast<float*>(*items[i].slot);
-    jobs[nj] = PackJob{items[i].src, dst, copies == 3 ? dst + packed_view->packed16_delta : nullptr,
-                       items[i].N, items[i].K};
-    jobs[nj++].PH = copies == 3 ? dst + 2 * packed_view->packed16_delta : nullptr;
-  }
-  if (nj == 0) return 0;
+  const int nj = trainable_pack_jobs("repack_trainable", w, packed_view, copies, jobs);
+  if (nj <= 0) return nj;
   return launch_pack_group(jobs, nj, as_stream(stream));
 }
 
@@ -927,18 +879,10 @@ int tc_radar_train_repack(const tc_head_weights* w, tc_head_weights* packed_view
   TC_TRY(check_dims(w));
   TC_REQUIRE(packed_view != nullptr && packed_view->l0_attn_out != nullptr,
              "radar_train_repack: packed_view was not produced by tc_head_pack_weights");
-  tc_head_weights scratch = *packed_view;
-  PackItem items[MAX_PACK_ITEMS];
-  const int n = collect_pack_items(w, &scratch, items);
-  const int first = 1 + 10 * w->num_layers;
   PackJob jobs[MAX_PACK_ITEMS + 10 * TC_MAX_RADAR_LAYERS];
-  int nj = 0;
-  for (int i = first; i < n; ++i) {
-    TC_REQUIRE(items[i].src != nullptr, "radar_train_repack: weight %d is null", i);
-    if (items[i].narrow) continue;
-    jobs[nj++] = PackJob{items[i].src, const_cast<float*>(*items[i].slot), nullptr, items[i].N, items[i].K};
-  }
-  const int nt = radar_train_transposed_jobs(w, B, T, bwd_workspace, bwd_workspace_bytes, jobs + nj, 10 * TC_MAX_RADAR_LAYERS);
+  const int nj = trainable_pack_jobs("radar_train_repack", w, packed_view, 1, jobs);
+  if (nj < 0) return nj;
+  const int nt =radar_train_transposed_jobs(w, B, T, bwd_workspace, bwd_workspace_bytes, jobs + nj, 10 * TC_MAX_RADAR_LAYERS);
   if (nt < 0) return -1;
   return launch_pack_group(jobs, nj + nt, as_stream(stream));
 }
@@ -1064,26 +1008,18 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   // HEAD:543-547, 596-598
   TC_TRY(launch_radar_ref_l1(h.inter_refs + (size_t)(L - 1) * rows * 3, pc, h.cxy, h.addref, rows, s));
   const float* qf = h.hs + (size_t)(L - 1) * rows * C;
-  const float qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
   for (int r = 0; r < w->num_radar_layers; ++r) {
     const tc_radar_layer& rl = w->radar[r];
     float* cls_out = all_cls_scores + (size_t)r * rows * ncls;
     float* box_out = all_bbox_preds + (size_t)r * rows * code;
-    const float* box_prev = r == 0 ? h.box_m : all_bbox_preds + (size_t)(r - 1) * rows * code;
+    const float* box_prev = layer_box_prev(r, h.box_m, all_bbox_preds, rows, code);
     int* hits = h.hits + (size_t)r * rows;
-    tc_linear wkv{rl.attn.in_proj.w + (size_t)C * C, rl.attn.in_proj.b + C};
-    TC_TRY(linear(h.radar_feat, C, wkv, rt, C, 2 * C, 0, h.kv, 2 * C, s));
+    TC_TRY(linear(h.radar_feat, C, kv_half(rl.attn, C), rt, C, 2 * C, 0, h.kv, 2 * C, s));
     GemmArgs g;
     g.X = qf; g.ldx = C; g.W = rl.attn.in_proj.w; g.ldw = C; g.bias = rl.attn.in_proj.b;
-    g.Y = h.qproj; g.ldy = C; g.M = rows; g.K = C; g.N = C; g.scale = qscale; g.scale_cols = C;
+    g.Y = h.qproj; g.ldy = C; g.M = rows; g.K = C; g.N = C; g.scale = radar_qscale(C); g.scale_cols = C;
     TC_TRY(launch_gemm(g, s));
-    RadarAttnArgs ra;
-    ra.qproj = h.qproj; ra.ldq = C; ra.kv = h.kv; ra.ldkv = 2 * C;
-    ra.centre_xy = r == 0 ? h.cxy : box_prev; ra.ld_c = r == 0 ? 2 : code;
-    ra.box = box_prev; ra.code = code; ra.radar_xy = radar_tokens; ra.ld_xy = RI;
-    ra.B = B; ra.Q = Q; ra.T = T; ra.C = C; ra.H = TC_RADAR_HEADS; ra.pad_mult = pad_mult;
-    ra.rmin = rl.radius_min; ra.rmax = rl.radius_max; ra.attn_out = h.rattn; ra.hit_counts = hits;
-    TC_TRY(launch_radar_attn(ra, s));
+    TC_TRY(launch_radar_attn(radar_attn_args(w, r, h.qproj, h.kv, h.cxy, box_prev, radar_tokens, B, T, pad_mult, h.rattn, hits), s));
     // HEAD:581-586
     TC_TRY(linear(h.rattn, C, rl.attn.out_proj, rows, C, C, 0, h.t0, C, s, nullptr, qf, C, hits));
     TC_TRY(layernorm(h.t0, rl.norm2, h.t1, rows, 0, s));
@@ -1208,7 +1144,7 @@ int tc_decoder_outputs_fwd(const tc_decoder_heads* packed_view, const float* int
   a.hs = inter_states; a.init_ref = init_reference; a.inter_refs = inter_references;
   a.all_cls = all_cls_scores; a.all_box = all_bbox_preds;
   a.ncls = w->num_classes; a.code = w->code_size;
-  for (int i = 0; i < 6; ++i) a.pc[i] = w->pc_range[i];
+  copy_pc(a.pc, w->pc_range);
   a.tile_rows = opt.chain_tile_rows; a.matrix_path = opt.matrix_path; a.range_status = opt.range_status;
   return launch_decoder_heads(a, as_stream(stream));
 }
@@ -1256,20 +1192,6 @@ int tc_box_add_ref_bwd(const float* d_box, int code_size, float* d_prev_box, int
   return launch_box_ref_bwd(d_box, code_size, d_prev_box, M, as_stream(stream));
 }
 
-static RadarAttnArgs radar_core_args(const float* qproj, float q_scale, const float* kv,
-                                     const float* centre_xy, int ld_c, const float* box,
-                                     int code_size, const float* radar_xy, int ld_xy, int B, int Q,
-                                     int T, int C, int num_heads, int pad_mult, float radius_min,
-                                     float radius_max) {
-  RadarAttnArgs r;
-  r.qproj = qproj; r.ldq = C; r.kv = kv; r.ldkv = 2 * C; r.centre_xy = centre_xy; r.ld_c = ld_c;
-  r.box = box; r.code = code_size; r.radar_xy = radar_xy; r.ld_xy = ld_xy;
-  r.B = B; r.Q = Q; r.T = T; r.C = C; r.H = num_heads; r.pad_mult = pad_mult;
-  r.rmin = radius_min; r.rmax = radius_max; r.attn_out = nullptr; r.hit_counts = nullptr;
-  r.qscale = q_scale;
-  return r;
-}
-
 int tc_radar_attn_core_fwd(const float* qproj, float q_scale, const float* kv,
                            const float* centre_xy, int ld_c, const float* box, int code_size,
                            const float* radar_xy, int ld_xy, int B, int Q, int T, int C,
@@ -1278,9 +1200,8 @@ int tc_radar_attn_core_fwd(const float* qproj, float q_scale, const float* kv,
                            unsigned long long dropout_seed, int dropout_site, tc_stream_t stream) {
   TC_REQUIRE(attn_out != nullptr && hit_counts != nullptr, "radar_attn_core: NULL output");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core: dropout_p=%g", (double)dropout_p);
-  RadarAttnArgs r = radar_core_args(qproj, q_scale, kv, centre_xy, ld_c, box, code_size, radar_xy,
-                                    ld_xy, B, Q, T, C, num_heads, pad_mult, radius_min, radius_max);
-  r.attn_out = attn_out; r.hit_counts = hit_counts;
+  RadarAttnArgs r = radar_attn_args(qproj, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads, pad_mult,
+                                    radius_min, radius_max, attn_out, hit_counts, q_scale);
   r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, 1500u);
   return launch_radar_attn(r, as_stream(stream));
 }
@@ -1293,9 +1214,8 @@ int tc_radar_attn_core_bwd(const float* qproj, float q_scale, const float* kv,
                            float dropout_p, unsigned long long dropout_seed, int dropout_site,
                            tc_stream_t stream) {
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core_bwd: dropout_p=%g", (double)dropout_p);
-  RadarAttnArgs r = radar_core_args(qproj, 1.0f, kv, centre_xy, ld_c, box, code_size, radar_xy,
-                                    ld_xy, B, Q, T, C, num_heads, pad_mult, radius_min, radius_max);
-  r.attn_out = const_cast<float*>(attn_out);
+  RadarAttnArgs r = radar_attn_args(qproj, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads, pad_mult,
+                                    radius_min, radius_max, const_cast<float*>(attn_out), nullptr);     // (q_scale: the launch's)
   r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, 1500u);
   return launch_radar_attn_bwd(r, q_scale, d_attn, dq, dkv, as_stream(stream));
 }

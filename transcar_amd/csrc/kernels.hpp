@@ -21,6 +21,9 @@ struct GemmArgs {
   float scale = 1.0f; int scale_cols = 0;      // (acc+bias)*scale for cols < scale_cols
 };
 int launch_gemm(const GemmArgs& a, hipStream_t s);
+// y = act((x (+ x2)) W^T + b) (+ res, the linear term dropped where rowgate is 0): head.hip
+int linear(const float* x, int ldx, const tc_linear& w, int M, int K, int N, int act, float* y, int ldy, hipStream_t s,
+           const float* x2 = nullptr, const float* res = nullptr, int ldr = 0, const int* rowgate = nullptr);
 
 // ---- rowops.hip: wave-per-row kernels -------------------------------------
 // y = LN(a (+b gated by rowgate) (+ relu(LN(c; g2,b2))))*g + beta, optional relu
@@ -36,6 +39,7 @@ struct LnArgs {
   int d_relu = 0;                    // apply relu to d first
 };
 int launch_ln256(const LnArgs& a, hipStream_t s);
+int layernorm(const float* a, const tc_lnorm& n, float* y, int M, int relu, hipStream_t s, const float* b = nullptr);   // head.hip
 
 // y = relu(LN(W0 p + b0)), p = inverse_sigmoid(src[row,0:3]) or raw src[row*ld+0:3]
 int launch_posenc_l1(const float* src, int ld, int inv_sigmoid, const float* w0, const float* b0,
@@ -71,20 +75,20 @@ int launch_radar_ref_l1(const float* ref, const float* pc_range6_host, float* ce
 
 // ---- cam_sample.hip --------------------------------------------------------
 struct CamSampleArgs {
-  tc_feats_nhwc feats;
-  int B, Q, C, num_cams;
-  const float* lidar2img; const float* ref; const float* logits;
-  float pc[6]; float img_h, img_w;
-  float* out; unsigned char* vis; unsigned long long* pair_counter;
+  tc_feats_nhwc feats = {};
+  int B = 0, Q = 0, C = 0, num_cams = 0;
+  const float* lidar2img = nullptr; const float* ref = nullptr; const float* logits = nullptr;
+  float pc[6] = {0, 0, 0, 0, 0, 0}; float img_h = 0, img_w = 0;
+  float* out = nullptr; unsigned char* vis = nullptr; unsigned long long* pair_counter = nullptr;
   int num_points = 1;           // Detr3DCrossAtten.num_points: logits are [B*Q][num_cams][num_points][levels]
 };
 int launch_cam_sample(const CamSampleArgs& a, hipStream_t s);
 
 // ---- chain.hip: fused row-chain kernels (16 rows per workgroup) ------------
 struct PrologueArgs {
-  const float* qe; int Q, M;                 // query_embedding [Q,512]; M = B*Q rows
-  tc_linear refpts, in_proj;                 // transformer.reference_points, layer-0 in_proj
-  float* init_ref; float* qk; float* vt; int qpad; float qscale;
+  const float* qe = nullptr; int Q = 0, M = 0;   // query_embedding [Q,512]; M = B*Q rows
+  tc_linear refpts = {}, in_proj = {};       // transformer.reference_points, layer-0 in_proj
+  float* init_ref = nullptr; float* qk = nullptr; float* vt = nullptr; int qpad = 0; float qscale = 1.0f;
   size_t w16_delta = 0;                      // packed view's packed16_delta (16-row tiles read W + delta)
 };
 int launch_prologue(const PrologueArgs& a, hipStream_t s);
@@ -99,17 +103,17 @@ constexpr int variant_mm(int v) { return v >= TV_16_F16X2 ? 1 : 0; }       // th
 int tile_variant(int rows, int tile_rows, int matrix_path, const char* what);
 
 struct DecoderChainArgs {
-  const float* attn_o;                       // [M,256]
+  const float* attn_o = nullptr;             // [M,256]
   int attn_mod = 0, ref_mod = 0;             // attn_o / ref_in rows taken modulo this when > 0
-  const float* x_in; int x_ld, x_mod;        // layer input rows (row % x_mod when x_mod > 0)
-  const float* qe; int Q;
-  const float* ref_in; float* ref_out; float* box_m;
-  const tc_decoder_layer* w;
-  const tc_linear* next_in_proj;             // next layer's in_proj (null after the last layer)
-  float qscale;
-  float* hs; float* qk; float* vt; int qpad;
+  const float* x_in = nullptr; int x_ld = 0, x_mod = 0;   // layer input rows (row % x_mod when x_mod > 0)
+  const float* qe = nullptr; int Q = 0;
+  const float* ref_in = nullptr; float* ref_out = nullptr; float* box_m = nullptr;
+  const tc_decoder_layer* w = nullptr;
+  const tc_linear* next_in_proj = nullptr;   // next layer's in_proj (null after the last layer)
+  float qscale = 1.0f;
+  float* hs = nullptr; float* qk = nullptr; float* vt = nullptr; int qpad = 0;
   CamSampleArgs cam;                         // feats, lidar2img, pc, img size (ref/logits/out unused)
-  int code, M;
+  int code = 0, M = 0;
   int tile_rows = 0, matrix_path = 0;        // what tile_variant() takes: 0 automatic / 4, 8, 16, 32; TC_MATRIX_*
   // train-mode statistics of the frozen decoder (thr 0 = eval): drop.site is the site of THIS
   // layer's attention probabilities (16 + 8 * layer); the chain's four sites are drop.site + 1
@@ -134,10 +138,10 @@ size_t decoder_l0_const_floats(int Q);
 int launch_decoder_l0_consts(const DecoderChainArgs& a, int variant, float* consts, hipStream_t s);
 
 struct RadarEncodeArgs {
-  const float* tokens; int RI, M;            // [M, RI]
-  tc_pos_encoder rpe; tc_linear f0, f2, f4;
-  int nlayers; tc_linear kvproj[TC_MAX_RADAR_LAYERS]; float* kv[TC_MAX_RADAR_LAYERS];
-  float* radar_feat;                         // optional [M,256]
+  const float* tokens = nullptr; int RI = 0, M = 0;   // [M, RI]
+  tc_pos_encoder rpe = {}; tc_linear f0 = {}, f2 = {}, f4 = {};
+  int nlayers = 0; tc_linear kvproj[TC_MAX_RADAR_LAYERS] = {}; float* kv[TC_MAX_RADAR_LAYERS] = {};
+  float* radar_feat = nullptr;               // optional [M,256]
   size_t w16_delta = 0;
   float* const* tape = nullptr;              // training forward: tape tensors by TapeSlot (chain.hip TSel order)
   int matrix_path = 0;                       // as DecoderChainArgs (the stand-alone encoder program runs 16-row tiles)
@@ -149,13 +153,13 @@ int launch_decoder_chain_with_encoders(const DecoderChainArgs& d, const RadarEnc
                                        hipStream_t s);
 
 struct RadarChainArgs {
-  const float* qf; const float* ref_last; const float* box_m;
-  const float* tokens; int RI;
-  const float* kv[TC_MAX_RADAR_LAYERS];
-  tc_radar_layer w[TC_MAX_RADAR_LAYERS];
-  int nlayers, Q, T, pad_mult, code, ncls, M;
-  float qscale; float pc[6];
-  float* all_cls; float* all_box; int* hits;
+  const float* qf = nullptr; const float* ref_last = nullptr; const float* box_m = nullptr;
+  const float* tokens = nullptr; int RI = 0;
+  const float* kv[TC_MAX_RADAR_LAYERS] = {};
+  tc_radar_layer w[TC_MAX_RADAR_LAYERS] = {};
+  int nlayers = 0, Q = 0, T = 0, pad_mult = 0, code = 0, ncls = 0, M = 0;
+  float qscale = 1.0f; float pc[6] = {0, 0, 0, 0, 0, 0};
+  float* all_cls = nullptr; float* all_box = nullptr; int* hits = nullptr;
   int tile_rows = 0;
   int matrix_path = 0;                       // as DecoderChainArgs
   int last_cls_only = 0;                     // skip final_cls of all but the last layer (inference opt-in)
@@ -172,20 +176,20 @@ struct RadarChainArgs {
 // parameter gradients added into `grads`, dK | dV into dkv[r] (atomics; zero them first).
 enum DySlot { DY_DBOX = 0, DY_DT1, DY_DT0, DY_DC2, DY_DC0, DY_DFF, DY_DH, DY_DPROJ, DY_DQP, DY_DCLS, DY_COUNT };
 struct RadarBwdChainArgs {
-  tc_radar_layer wT[TC_MAX_RADAR_LAYERS];      // TRANSPOSED packed weights (pack.hip, PackJob::transpose)
-  tc_radar_layer w[TC_MAX_RADAR_LAYERS];       // the forward's parameters (LayerNorm gamma, radii)
-  tc_radar_layer grads[TC_MAX_RADAR_LAYERS];   // gradient destinations (LayerNorm g / b are used here)
-  const float* kv[TC_MAX_RADAR_LAYERS]; float* dkv[TC_MAX_RADAR_LAYERS];
-  const float* cxy[TC_MAX_RADAR_LAYERS]; int ld_c[TC_MAX_RADAR_LAYERS]; const float* box[TC_MAX_RADAR_LAYERS];
-  float* const* tape; size_t tape_stride, hits_stride; const int* hits;
-  float* const* dy; size_t dy_stride;
-  const float* d_cls; const float* d_box;      // [layers, M, ncls / code]
+  tc_radar_layer wT[TC_MAX_RADAR_LAYERS] = {};      // TRANSPOSED packed weights (pack.hip, PackJob::transpose)
+  tc_radar_layer w[TC_MAX_RADAR_LAYERS] = {};       // the forward's parameters (LayerNorm gamma, radii)
+  tc_radar_layer grads[TC_MAX_RADAR_LAYERS] = {};   // gradient destinations (LayerNorm g / b are used here)
+  const float* kv[TC_MAX_RADAR_LAYERS] = {}; float* dkv[TC_MAX_RADAR_LAYERS] = {};
+  const float* cxy[TC_MAX_RADAR_LAYERS] = {}; int ld_c[TC_MAX_RADAR_LAYERS] = {}; const float* box[TC_MAX_RADAR_LAYERS] = {};
+  float* const* tape = nullptr; size_t tape_stride = 0, hits_stride = 0; const int* hits = nullptr;
+  float* const* dy = nullptr; size_t dy_stride = 0;
+  const float* d_cls = nullptr; const float* d_box = nullptr;   // [layers, M, ncls / code]
   const float* loss_vals = nullptr;            // optional [layers, 2]: non-finite losses / elements send nothing down
   float* loss_out = nullptr;                   // optional [layers, 2]: loss_vals, NaN -> 0
-  const float* tokens; int RI, T, pad_mult;
-  int nlayers, Q, M, code, ncls;
-  float qscale;
-  DropK drop;
+  const float* tokens = nullptr; int RI = 0, T = 0, pad_mult = 0;
+  int nlayers = 0, Q = 0, M = 0, code = 0, ncls = 0;
+  float qscale = 1.0f;
+  DropK drop = DropK{0, 0, 1.0f, 0, 1500, 0, 0, 0};
   int tile_rows = 0;
   const DetAcc* det_device = nullptr;          // deterministic mode: a device copy of the thread's DetAcc (launch_det_store)
 };
@@ -198,14 +202,14 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s);
 // cls_branches[l] / reg_branches[l] of every decoder level on the stored decoder states (chain.hip PROG_DECODER_HEADS):
 // one launch, levels x row tiles.  cls / reg: a tc_decoder_heads_pack view (the last Linear of a branch unpacked).
 struct DecoderHeadsArgs {
-  int levels, M;                             // M = B * Q rows per level
-  tc_cls_branch cls[TC_MAX_LAYERS]; tc_reg_branch reg[TC_MAX_LAYERS];
+  int levels = 0, M = 0;                     // M = B * Q rows per level
+  tc_cls_branch cls[TC_MAX_LAYERS] = {}; tc_reg_branch reg[TC_MAX_LAYERS] = {};
   size_t w16_delta = 0;
-  const float* hs;                           // [levels, M, 256]
-  const float* init_ref;                     // [M, 3]: the reference points of level 0
-  const float* inter_refs;                   // [levels, M, 3]: level l > 0 reads slice l - 1
-  float* all_cls; float* all_box;            // [levels, M, ncls / code]
-  int ncls, code; float pc[6];
+  const float* hs = nullptr;                 // [levels, M, 256]
+  const float* init_ref = nullptr;           // [M, 3]: the reference points of level 0
+  const float* inter_refs = nullptr;         // [levels, M, 3]: level l > 0 reads slice l - 1
+  float* all_cls = nullptr; float* all_box = nullptr;   // [levels, M, ncls / code]
+  int ncls = 0, code = 0; float pc[6] = {0, 0, 0, 0, 0, 0};
   int tile_rows = 0, matrix_path = 0;
   int* range_status = nullptr;
 };
@@ -234,7 +238,7 @@ int launch_self_attn_core(const float* q, const float* k, int ld, const float* v
 // FOLLOWS (rowdev.hpp cam_pregather_rows): `cam` as for the chain (ref = that layer's reference points), out
 // [M][num_cams][num_levels][256] floats, mask [M] ints.  Eval launches only (drop == null / thr 0).
 struct PreGatherArgs {
-  CamSampleArgs cam; int M, ref_mod; float* out; int* mask;
+  CamSampleArgs cam; int M = 0, ref_mod = 0; float* out = nullptr; int* mask = nullptr;
 };
 int launch_self_attn_core_x(const float* q, const float* k, int ld, const float* vt, int ldt, float* out, int ldo,
                             int B, int Q, int H, int D, hipStream_t s, const DropK* drop = nullptr,
@@ -242,15 +246,15 @@ int launch_self_attn_core_x(const float* q, const float* k, int ld, const float*
 
 // ---- radar_attn.hip --------------------------------------------------------
 struct RadarAttnArgs {
-  const float* qproj; int ldq;         // [B*Q, C] projected+scaled queries
-  const float* kv; int ldkv;           // [B*T, 2C]: K | V
-  const float* centre_xy; int ld_c;    // centre at centre_xy[row*ld_c + {0,1}]
-  const float* box; int code;          // [B*Q,code]
-  const float* radar_xy; int ld_xy;    // token xy at radar_xy[(b*T+t)*ld_xy + {0,1}]
-  int B, Q, T, C, H, pad_mult;
-  float rmin, rmax;
-  float* attn_out;                     // [B*Q, C] (zero rows where no hit)
-  int* hit_counts;                     // [B*Q]
+  const float* qproj = nullptr; int ldq = 0;         // [B*Q, C] projected+scaled queries
+  const float* kv = nullptr; int ldkv = 0;           // [B*T, 2C]: K | V
+  const float* centre_xy = nullptr; int ld_c = 0;    // centre at centre_xy[row*ld_c + {0,1}]
+  const float* box = nullptr; int code = 0;          // [B*Q,code]
+  const float* radar_xy = nullptr; int ld_xy = 0;    // token xy at radar_xy[(b*T+t)*ld_xy + {0,1}]
+  int B = 0, Q = 0, T = 0, C = 0, H = 0, pad_mult = 0;
+  float rmin = 0, rmax = 0;
+  float* attn_out = nullptr;                         // [B*Q, C] (zero rows where no hit)
+  int* hit_counts = nullptr;                         // [B*Q]
   float qscale = 1.0f;                 // applied to qproj on load (1 when pre-scaled)
   DropK drop = DropK{0, 0, 1.0f, 0, 1500, 0, 0, 0};   // training: dropout on the attention probabilities (thr 0 = off)
 };

@@ -9,23 +9,9 @@
 #include <math.h>
 #include <string.h>
 
-#include "kernels.hpp"
+#include "chain_args.hpp"
 
 namespace tc {
-
-#define TS_TRY(expr)          \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-#define TS_HIP(expr)                                          \
-  do {                                                        \
-    hipError_t _e = (expr);                                   \
-    if (_e != hipSuccess) {                                   \
-      tc::set_error("%s: %s", #expr, hipGetErrorString(_e)); \
-      return (int)_e;                                         \
-    }                                                         \
-  } while (0)
 
 namespace {
 
@@ -103,15 +89,7 @@ int add_into(const float* src, float* dst, size_t n, hipStream_t s) {
 
 int lin(const float* x, const tc_linear& w, int M, int K, int N, int act, float* y, hipStream_t s,
         const float* res = nullptr, const int* gate = nullptr) {
-  GemmArgs g;
-  g.X = x; g.ldx = K; g.W = w.w; g.ldw = K; g.bias = w.b; g.R = res; g.ldr = N; g.rowgate = gate;
-  g.Y = y; g.ldy = N; g.M = M; g.K = K; g.N = N; g.act = act;
-  return launch_gemm(g, s);
-}
-int lnorm(const float* a, const float* b, const tc_lnorm& n, float* y, int M, int relu, hipStream_t s) {
-  LnArgs l;
-  l.a = a; l.b = b; l.gamma = n.g; l.beta = n.b; l.y = y; l.M = M; l.relu = relu;
-  return launch_ln256(l, s);
+  return linear(x, K, w, M, K, N, act, y, N, s, nullptr, res, N, gate);      // dense operands
 }
 // backward of y = act(x W^T + b): dW += dY~^T x, db += colsum dY~, dx (=|+=) dY~ W
 //   y_relu: this layer's saved ReLU output (mask on dY) or nullptr; x_relu: mask on dx
@@ -119,10 +97,10 @@ int lnorm(const float* a, const float* b, const tc_lnorm& n, float* y, int M, in
 int lin_bwd(const float* x, const float* dy, const float* y_relu, const int* gate, const tc_linear& w,
             const tc_linear& g, const float* x_relu, float* dx, int accumulate, int M, int K, int N,
             hipStream_t s, float dx_scale = 1.0f) {
-  TS_TRY(launch_linear_bwd_weight(x, dy, y_relu, gate, const_cast<float*>(g.w), const_cast<float*>(g.b),
+  TC_TRY(launch_linear_bwd_weight(x, dy, y_relu, gate, const_cast<float*>(g.w), const_cast<float*>(g.b),
                                   M, K, N, 1.0f, s));
   if (dx != nullptr)
-    TS_TRY(launch_linear_bwd_data(dy, y_relu, gate, w.w, x_relu, dx, M, K, N, dx_scale, accumulate, s));
+    TC_TRY(launch_linear_bwd_data(dy, y_relu, gate, w.w, x_relu, dx, M, K, N, dx_scale, accumulate, s));
   return 0;
 }
 int ln_bwd(const float* a, const float* b, const tc_lnorm& n, const tc_lnorm& g, const float* dy,
@@ -131,20 +109,24 @@ int ln_bwd(const float* a, const float* b, const tc_lnorm& n, const tc_lnorm& g,
                           M, s);
 }
 
-RadarAttnArgs core_args(const tc_head_weights* w, int r, const Tape& t, const float* box_prev,
-                        const float* tokens, int B, int T, int pad_mult, float drop_p = 0.0f,
-                        unsigned long long seed = 0) {
-  const int C = w->embed_dims, code = w->code_size;
-  RadarAttnArgs ra;
-  ra.qproj = t.L[r].qp; ra.ldq = C; ra.kv = t.L[r].kv; ra.ldkv = 2 * C;
-  ra.centre_xy = r == 0 ? t.cxy : box_prev; ra.ld_c = r == 0 ? 2 : code;
-  ra.box = box_prev; ra.code = code; ra.radar_xy = tokens; ra.ld_xy = w->radar_in_dims;
-  ra.B = B; ra.Q = w->num_query; ra.T = T; ra.C = C; ra.H = TC_RADAR_HEADS; ra.pad_mult = pad_mult;
-  ra.rmin = w->radar[r].radius_min; ra.rmax = w->radar[r].radius_max;
-  ra.attn_out = t.L[r].ao; ra.hit_counts = t.L[r].hits;
-  ra.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
+// the attention core of fusion layer r on its tape tensors, forward and backward: unscaled queries, dropout site 4 r
+RadarAttnArgs core_args(const tc_head_weights* w, int r, const Tape& t, const float* box_prev, const float* tokens, int B,
+                        int T, int pad_mult, float drop_p, unsigned long long seed) {
+  RadarAttnArgs ra = radar_attn_args(w, r, t.L[r].qp, t.L[r].kv, t.cxy, box_prev, tokens, B, T, pad_mult, t.L[r].ao, t.L[r].hits,
+                                     radar_qscale(w->embed_dims));
   ra.drop = make_drop(drop_p, seed, 4u * r + 0u, (unsigned)w->num_radar_tokens_ref);
   return ra;
+}
+
+// the tape pointer table of the row chains (TapeSlot order): fusion layer 0's tensors, then the token side's
+void tape_slots(const Tape& t, float* (&slots)[TS_COUNT]) {
+  memset(slots, 0, sizeof(slots));
+  const LayerTape& l0 = t.L[0];
+  slots[TS_QP] = l0.qp; slots[TS_AO] = l0.ao; slots[TS_X1] = l0.x1; slots[TS_X2] = l0.x2; slots[TS_H] = l0.h;
+  slots[TS_SUM] = l0.ff; slots[TS_X3] = l0.x3; slots[TS_C0] = l0.c0; slots[TS_C1] = l0.c1; slots[TS_C2] = l0.c2;
+  slots[TS_C3] = l0.c3; slots[TS_T0] = l0.t0; slots[TS_T1] = l0.t1; slots[TS_TREG] = l0.treg;
+  slots[TS_U0] = t.u0; slots[TS_U1] = t.u1; slots[TS_U2] = t.u2; slots[TS_POS] = t.pos;
+  slots[TS_F0] = t.f0; slots[TS_F1] = t.f1; slots[TS_F2] = t.f2; slots[TS_MEM] = t.mem;
 }
 
 // distance between the tape tensors / hit counts of consecutive fusion layers (a one-layer head: no second layer, 0)
@@ -162,268 +144,7 @@ int check(const tc_head_weights* w, int B, int T) {
   return 0;
 }
 
-}  // namespace
-}  // namespace tc
-
-using namespace tc;
-
-extern "C" {
-
-size_t tc_radar_train_tape_bytes(const tc_head_weights* w, int B, int T) {
-  if (check(w, B, T) != 0) return 0;
-  return tape_layout(w, B, T, nullptr, ~size_t(0), nullptr);
-}
-
-int tc_radar_train_fwd(const tc_head_weights* w, const float* hs_last, const float* ref_last,
-                       const float* last_box, const float* radar_tokens, int B, int T, int pad_mult,
-                       float* all_cls_scores, float* all_bbox_preds, void* tape, size_t tape_bytes,
-                       float dropout_p, unsigned long long dropout_seed, tc_stream_t stream) {
-  TS_TRY(check(w, B, T));
-  TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_fwd: dropout_p=%g", (double)dropout_p);
-  const bool drop = dropout_p > 0.0f;
-  const unsigned tref = (unsigned)w->num_radar_tokens_ref;
-  Tape t;
-  TC_REQUIRE(tape_layout(w, B, T, tape, tape_bytes, &t) <= tape_bytes, "radar_train_fwd: tape too small");
-  hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
-  const int ncls = w->num_classes, RI = w->radar_in_dims;
-  const int rows = B * Q, rt = B * T;
-  // radar encoders, HEAD:531-536 (Linear(3,C) as K = 4 with a zero column)
-  const tc_pos_encoder& pe = w->radar_position_encoder;
-  TS_HIP(hipMemsetAsync(t.xyz4, 0, (size_t)rt * 4 * 4, s));
-  TS_HIP(hipMemsetAsync(t.w0p, 0, (size_t)C * 4 * 4, s));
-  TS_TRY(copy_cols(radar_tokens, RI, t.xyz4, 4, rt, 3, 0, s));
-  TS_TRY(copy_cols(pe.l0.w, 3, t.w0p, 4, C, 3, 0, s));
-  TS_TRY(lin(t.xyz4, tc_linear{t.w0p, pe.l0.b}, rt, 4, C, 0, t.u0, s));
-  TS_TRY(lnorm(t.u0, nullptr, pe.n1, t.u1, rt, 1, s));
-  TS_TRY(lin(t.u1, pe.l3, rt, C, C, 0, t.u2, s));
-  TS_TRY(lnorm(t.u2, nullptr, pe.n4, t.pos, rt, 1, s));
-  TS_TRY(lin(radar_tokens, w->radar_feat0, rt, RI, 64, 1, t.f0, s));
-  TS_TRY(lin(t.f0, w->radar_feat2, rt, 64, 128, 1, t.f1, s));
-  TS_TRY(lin(t.f1, w->radar_feat4, rt, 128, C, 1, t.f2, s));
-  {
-    LnArgs l;      // mem = pos + f2 (plain sum)
-    l.a = t.pos; l.b = t.f2; l.y = t.mem; l.M = rt;
-    TS_TRY(launch_ln256(l, s));
-  }
-  TS_TRY(launch_radar_ref_l1(ref_last, w->pc_range, t.cxy, t.addref, rows, s));
-  const float* qin = hs_last;
-  for (int r = 0; r < w->num_radar_layers; ++r) {
-    const tc_radar_layer& rl = w->radar[r];
-    LayerTape& l = t.L[r];
-    float* cls_out = all_cls_scores + (size_t)r * rows * ncls;
-    float* box_out = all_bbox_preds + (size_t)r * rows * code;
-    const float* box_prev = r == 0 ? last_box : all_bbox_preds + (size_t)(r - 1) * rows * code;
-    const tc_linear wq{rl.attn.in_proj.w, rl.attn.in_proj.b};
-    const tc_linear wkv{rl.attn.in_proj.w + (size_t)C * C, rl.attn.in_proj.b + C};
-    TS_TRY(lin(qin, wq, rows, C, C, 0, l.qp, s));
-    TS_TRY(lin(t.mem, wkv, rt, C, 2 * C, 0, l.kv, s));
-    TS_TRY(launch_radar_attn(core_args(w, r, t, box_prev, radar_tokens, B, T, pad_mult, dropout_p, dropout_seed), s));
-    if (drop) {     // x1 = qin + gate * rf_dropout2(out_proj(ao)), HEAD:581 (l.ff is free until linear2)
-      TS_TRY(lin(l.ao, rl.attn.out_proj, rows, C, C, 0, l.ff, s));
-      TS_TRY(launch_dropout(l.ff, qin, l.hits, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 1u, tref), l.x1, s));
-    } else {
-      TS_TRY(lin(l.ao, rl.attn.out_proj, rows, C, C, 0, l.x1, s, qin, l.hits));
-    }
-    TS_TRY(lnorm(l.x1, nullptr, rl.norm2, l.x2, rows, 0, s));
-    TS_TRY(lin(l.x2, rl.linear1, rows, C, F, 1, l.h, s));
-    if (drop)       // rf_dropout(relu(linear1)), HEAD:584: the tape keeps the dropped activations
-      TS_TRY(launch_dropout(l.h, nullptr, nullptr, rows, F, make_drop(dropout_p, dropout_seed, 4u * r + 2u, tref), l.h, s));
-    TS_TRY(lin(l.h, rl.linear2, rows, F, C, 0, l.ff, s));
-    if (drop)       // rf_dropout3(ffn_out), HEAD:585
-      TS_TRY(launch_dropout(l.ff, nullptr, nullptr, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 3u, tref), l.ff, s));
-    TS_TRY(lnorm(l.x2, l.ff, rl.norm3, l.x3, rows, 0, s));
-    TS_TRY(lin(l.x3, rl.final_cls.l0, rows, C, C, 0, l.c0, s));
-    TS_TRY(lnorm(l.c0, nullptr, rl.final_cls.n1, l.c1, rows, 1, s));
-    TS_TRY(lin(l.c1, rl.final_cls.l3, rows, C, C, 0, l.c2, s));
-    TS_TRY(lnorm(l.c2, nullptr, rl.final_cls.n4, l.c3, rows, 1, s));
-    TS_TRY(lin(l.c3, rl.final_cls.l6, rows, C, ncls, 0, cls_out, s));
-    TS_TRY(lin(l.x3, rl.final_reg.l0, rows, C, C, 1, l.t0, s));
-    TS_TRY(lin(l.t0, rl.final_reg.l2, rows, C, C, 1, l.t1, s));
-    TS_TRY(lin(l.t1, rl.final_reg.l4, rows, C, code, 0, l.treg, s));
-    if (r == 0)
-      TS_TRY(launch_box_add_ref(l.treg, code, t.addref, 3, t.addref + 2, 3, box_out, nullptr, rows, s));
-    else
-      TS_TRY(launch_box_add_ref(l.treg, code, box_prev, code, box_prev + 4, code, box_out, nullptr, rows, s));
-    qin = l.x3;
-  }
-  return 0;
-}
-
-// The same forward as THREE launches of the fused row chains (chain.hip PROG_RADAR_ENC_TRAIN / PROG_RADAR_TRAIN)
-// plus the reference set-up: the encoder program writes the token-side tape (u0 u1 u2 pos f0 f1 f2 mem and the
-// three layers' K | V), the radar program walks the three fusion layers with the dropout sites in its epilogues
-// and stores every query-side tape tensor as it is produced.  The tape is the one tc_radar_train_fwd writes:
-// tc_radar_train_bwd takes either.  `packed_view`: the head's packed weights, re-packed for the CURRENT
-// parameters (tc_head_repack_trainable_ex(w, view, 1, ...) after an optimizer step).
-int tc_radar_train_fwd_fused(const tc_head_weights* packed_view, const float* hs_last, const float* ref_last,
-                             const float* last_box, const float* radar_tokens, int B, int T, int pad_mult,
-                             float* all_cls_scores, float* all_bbox_preds, void* tape, size_t tape_bytes,
-                             float dropout_p, unsigned long long dropout_seed, tc_stream_t stream) {
-  const tc_head_weights* w = packed_view;
-  TS_TRY(check(w, B, T));
-  TC_REQUIRE(w->l0_attn_out != nullptr, "radar_train_fwd_fused: packed_view was not produced by tc_head_pack_weights");
-  TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_fwd_fused: dropout_p=%g", (double)dropout_p);
-  // (round 3 refused T > 512 here although the chains take any T <= 1500 -- beyond 512 tokens the gate's hit masks
-  // are not kept in LDS and the attention step re-evaluates the gate, as the inference chain does; a frame with more
-  // than 511 radar points then failed mid-training: ADVICE r3.  Covered at T = 576 and T = 1500 by
-  // tests/test_gpu_training.py::test_fused_training_with_many_radar_tokens.)
-  TC_REQUIRE(w->code_size <= 10, "radar_train_fwd_fused: code_size=%d", w->code_size);
-  Tape t;
-  TC_REQUIRE(tape_layout(w, B, T, tape, tape_bytes, &t) <= tape_bytes, "radar_train_fwd_fused: tape too small");
-  hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, code = w->code_size, RI = w->radar_in_dims;
-  const int rows = B * Q, rt = B * T;
-  float* slots[TS_COUNT];
-  const LayerTape& l0 = t.L[0];
-  slots[TS_QP] = l0.qp; slots[TS_AO] = l0.ao; slots[TS_X1] = l0.x1; slots[TS_X2] = l0.x2; slots[TS_H] = l0.h;
-  slots[TS_SUM] = l0.ff; slots[TS_X3] = l0.x3; slots[TS_C0] = l0.c0; slots[TS_C1] = l0.c1; slots[TS_C2] = l0.c2;
-  slots[TS_C3] = l0.c3; slots[TS_T0] = l0.t0; slots[TS_T1] = l0.t1; slots[TS_TREG] = l0.treg;
-  slots[TS_U0] = t.u0; slots[TS_U1] = t.u1; slots[TS_U2] = t.u2; slots[TS_POS] = t.pos;
-  slots[TS_F0] = t.f0; slots[TS_F1] = t.f1; slots[TS_F2] = t.f2; slots[TS_MEM] = t.mem;
-  // encoders + K | V of the three layers (HEAD:531-536, 573-575): one launch
-  RadarEncodeArgs re;
-  re.tokens = radar_tokens; re.RI = RI; re.M = rt;
-  re.rpe = w->radar_position_encoder; re.f0 = w->radar_feat0; re.f2 = w->radar_feat2; re.f4 = w->radar_feat4;
-  re.nlayers = w->num_radar_layers;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) {          // (layers the head does not have: null weights, null tape)
-    const tc_mha& m = w->radar[r].attn;
-    re.kvproj[r] = tc_linear{m.in_proj.w ? m.in_proj.w + (size_t)C * C : nullptr, m.in_proj.b ? m.in_proj.b + C : nullptr};
-    re.kv[r] = t.L[r].kv;
-  }
-  re.radar_feat = nullptr; re.w16_delta = w->packed16_delta; re.tape = slots;
-  TS_TRY(launch_radar_encode(re, s));
-  TS_TRY(launch_radar_ref_l1(ref_last, w->pc_range, t.cxy, t.addref, rows, s));
-  // the three fusion layers: one launch
-  RadarChainArgs rc;
-  rc.qf = hs_last; rc.ref_last = ref_last; rc.box_m = last_box; rc.tokens = radar_tokens; rc.RI = RI;
-  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) { rc.kv[r] = t.L[r].kv; rc.w[r] = w->radar[r]; }
-  rc.nlayers = w->num_radar_layers; rc.Q = Q; rc.T = T; rc.pad_mult = pad_mult; rc.code = code;
-  rc.ncls = w->num_classes; rc.M = rows; rc.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
-  for (int i = 0; i < 6; ++i) rc.pc[i] = w->pc_range[i];
-  rc.all_cls = all_cls_scores; rc.all_box = all_bbox_preds; rc.hits = t.L[0].hits;
-  rc.tape = slots;
-  rc.tape_stride = layer_stride(w, t); rc.hits_stride = hits_stride(w, t);
-  rc.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
-  return launch_radar_chain(rc, s);
-}
-
-int tc_radar_train_bwd(const tc_head_weights* w, const tc_head_weights* grads, const float* hs_last,
-                       const float* last_box, const float* radar_tokens, int B, int T, int pad_mult,
-                       const float* all_bbox_preds, const float* d_all_cls, const float* d_all_box,
-                       void* tape, size_t tape_bytes, float dropout_p, unsigned long long dropout_seed,
-                       tc_stream_t stream) {
-  TS_TRY(check(w, B, T));
-  TC_REQUIRE(grads != nullptr, "radar_train_bwd: grads is NULL");
-  TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_bwd: dropout_p=%g", (double)dropout_p);
-  const bool drop = dropout_p > 0.0f;
-  const unsigned tref = (unsigned)w->num_radar_tokens_ref;
-  const float keep_scale = drop ? 1.0f / (1.0f - dropout_p) : 1.0f;
-  Tape t;
-  TC_REQUIRE(tape_layout(w, B, T, tape, tape_bytes, &t) <= tape_bytes, "radar_train_bwd: tape too small");
-  hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
-  const int ncls = w->num_classes, RI = w->radar_in_dims;
-  const int rows = B * Q, rt = B * T;
-  TS_HIP(hipMemsetAsync(t.dmem, 0, (size_t)rt * C * 4, s));
-  bool have_dqin = false;                       // gradient w.r.t. this layer's output from the layer above
-  bool have_dbox_next = false;
-  for (int r = w->num_radar_layers - 1; r >= 0; --r) {
-    const tc_radar_layer& rl = w->radar[r];
-    const tc_radar_layer& gl = grads->radar[r];
-    LayerTape& l = t.L[r];
-    const float* qin = r == 0 ? hs_last : t.L[r - 1].x3;
-    const float* box_prev = r == 0 ? last_box : all_bbox_preds + (size_t)(r - 1) * rows * code;
-    const float* dcls = d_all_cls + (size_t)r * rows * ncls;
-    // box_r = treg_r (+ prev box {0,1,4}); d box_r = given + what layer r+1 sent down (in t.dbox)
-    if (!have_dbox_next) TS_HIP(hipMemsetAsync(t.dbox, 0, (size_t)rows * code * 4, s));
-    TS_TRY(add_into(d_all_box + (size_t)r * rows * code, t.dbox, (size_t)rows * code, s));
-    // reg branch (Linear ReLU Linear ReLU Linear), dx3 -> dA (=)
-    TS_TRY(lin_bwd(l.t1, t.dbox, nullptr, nullptr, rl.final_reg.l4, gl.final_reg.l4, l.t1, t.dB, 0, rows, C, code, s));
-    TS_TRY(lin_bwd(l.t0, t.dB, nullptr, nullptr, rl.final_reg.l2, gl.final_reg.l2, l.t0, t.dC, 0, rows, C, C, s));
-    TS_TRY(lin_bwd(l.x3, t.dC, nullptr, nullptr, rl.final_reg.l0, gl.final_reg.l0, nullptr, t.dA, 0, rows, C, C, s));
-    // the reference of layer r is box_{r-1}: its {0,1,4} columns receive d box_r (HEAD:615-617, 661-662)
-    if (r > 0) {
-      // t.dbox becomes the incoming gradient of box_{r-1}: keep only columns 0,1,4
-      TS_HIP(hipMemsetAsync(t.dB, 0, (size_t)rows * code * 4, s));
-      TS_TRY(launch_box_ref_bwd(t.dbox, code, t.dB, rows, s));
-      TS_HIP(hipMemcpyAsync(t.dbox, t.dB, (size_t)rows * code * 4, hipMemcpyDeviceToDevice, s));
-      have_dbox_next = true;
-    }
-    // cls branch (Linear LN ReLU Linear LN ReLU Linear), dx3 +=
-    TS_TRY(lin_bwd(l.c3, dcls, nullptr, nullptr, rl.final_cls.l6, gl.final_cls.l6, nullptr, t.dB, 0, rows, C, ncls, s));
-    TS_TRY(ln_bwd(l.c2, nullptr, rl.final_cls.n4, gl.final_cls.n4, t.dB, l.c3, t.dC, rows, s));
-    TS_TRY(lin_bwd(l.c1, t.dC, nullptr, nullptr, rl.final_cls.l3, gl.final_cls.l3, nullptr, t.dB, 0, rows, C, C, s));
-    TS_TRY(ln_bwd(l.c0, nullptr, rl.final_cls.n1, gl.final_cls.n1, t.dB, l.c1, t.dC, rows, s));
-    TS_TRY(lin_bwd(l.x3, t.dC, nullptr, nullptr, rl.final_cls.l0, gl.final_cls.l0, nullptr, t.dA, 1, rows, C, C, s));
-    if (have_dqin) TS_TRY(add_into(t.dqin, t.dA, (size_t)rows * C, s));
-    // x3 = LN3(x2 + ff): dz -> dB (grad of x2 and of ff)
-    TS_TRY(ln_bwd(l.x2, l.ff, rl.norm3, gl.norm3, t.dA, nullptr, t.dB, rows, s));
-    const float* dff = t.dB;                                  // gradient of ffn_out
-    if (drop) {     // through rf_dropout3: same mask on the gradient; dz itself still feeds dx2 below
-      TS_TRY(launch_dropout(t.dB, nullptr, nullptr, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 3u, tref), t.dD, s));
-      dff = t.dD;
-    }
-    // l.h = rf_dropout(relu(.)): its zeros are the ReLU zeros and the dropped elements, the kept ones
-    // carry 1 / (1 - p)
-    TS_TRY(lin_bwd(l.h, dff, nullptr, nullptr, rl.linear2, gl.linear2, l.h, t.dh, 0, rows, F, C, s, keep_scale));
-    TS_TRY(lin_bwd(l.x2, t.dh, nullptr, nullptr, rl.linear1, gl.linear1, nullptr, t.dB, 1, rows, C, F, s));   // dx2 = dz + dh W1
-    // x2 = LN2(x1): dx1 -> dC
-    TS_TRY(ln_bwd(l.x1, nullptr, rl.norm2, gl.norm2, t.dB, nullptr, t.dC, rows, s));
-    // x1 = qin + gate * out_proj(ao): d ao -> dA, d qin = dx1
-    const float* dproj = t.dC;                                // gradient of out_proj(ao) before the row gate
-    if (drop) {     // through rf_dropout2
-      TS_TRY(launch_dropout(t.dC, nullptr, nullptr, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 1u, tref), t.dD, s));
-      dproj = t.dD;
-    }
-    TS_TRY(lin_bwd(l.ao, dproj, nullptr, l.hits, rl.attn.out_proj, gl.attn.out_proj, nullptr, t.dA, 0, rows, C, C, s));
-    TS_HIP(hipMemsetAsync(t.dkv, 0, (size_t)rt * 2 * C * 4, s));
-    {
-      RadarAttnArgs ra = core_args(w, r, t, box_prev, radar_tokens, B, T, pad_mult, dropout_p, dropout_seed);
-      const float qs = ra.qscale;
-      ra.qscale = 1.0f;
-      TS_TRY(launch_radar_attn_bwd(ra, qs, t.dA, t.dqp, t.dkv, s));
-    }
-    const tc_linear wq{rl.attn.in_proj.w, rl.attn.in_proj.b};
-    const tc_linear gq{gl.attn.in_proj.w, gl.attn.in_proj.b};
-    const tc_linear wkv{rl.attn.in_proj.w + (size_t)C * C, rl.attn.in_proj.b + C};
-    const tc_linear gkv{gl.attn.in_proj.w + (size_t)C * C, gl.attn.in_proj.b + C};
-    // d qin = dx1 + dqp Wq  (into dqin for the layer below; nothing below layer 0: the decoder is frozen)
-    if (r > 0) {
-      TS_HIP(hipMemcpyAsync(t.dqin, t.dC, (size_t)rows * C * 4, hipMemcpyDeviceToDevice, s));
-      TS_TRY(lin_bwd(qin, t.dqp, nullptr, nullptr, wq, gq, nullptr, t.dqin, 1, rows, C, C, s));
-      have_dqin = true;
-    } else {
-      TS_TRY(lin_bwd(qin, t.dqp, nullptr, nullptr, wq, gq, nullptr, nullptr, 0, rows, C, C, s));
-    }
-    TS_TRY(lin_bwd(t.mem, t.dkv, nullptr, nullptr, wkv, gkv, nullptr, t.dmem, 1, rt, C, 2 * C, s));
-  }
-  // encoders: mem = relu(LN4(u2)) + relu(feat4(f1)); both summands see dmem
-  const tc_pos_encoder& pe = w->radar_position_encoder;
-  const tc_pos_encoder& gpe = grads->radar_position_encoder;
-  TS_TRY(lin_bwd(t.f1, t.dmem, t.f2, nullptr, w->radar_feat4, grads->radar_feat4, t.f1, t.dt128, 0, rt, 128, C, s));
-  TS_TRY(lin_bwd(t.f0, t.dt128, nullptr, nullptr, w->radar_feat2, grads->radar_feat2, t.f0, t.dt64, 0, rt, 64, 128, s));
-  TS_TRY(lin_bwd(radar_tokens, t.dt64, nullptr, nullptr, w->radar_feat0, grads->radar_feat0, nullptr, nullptr, 0, rt, RI, 64, s));
-  // (rows of the token gradients reuse dqp/dkv-sized scratch: rt <= tape sizes by construction)
-  float* du = t.dkv;                 // [rt, C] scratch (dkv is [rt, 2C])
-  float* du2 = t.dkv + (size_t)rt * C;
-  TS_TRY(ln_bwd(t.u2, nullptr, pe.n4, gpe.n4, t.dmem, t.pos, du, rt, s));
-  TS_TRY(lin_bwd(t.u1, du, nullptr, nullptr, pe.l3, gpe.l3, nullptr, du2, 0, rt, C, C, s));
-  TS_TRY(ln_bwd(t.u0, nullptr, pe.n1, gpe.n1, du2, t.u1, du, rt, s));
-  TS_HIP(hipMemsetAsync(t.dw0p, 0, (size_t)C * 4 * 4, s));
-  // (the padded xyz operand is rebuilt here: the tape of tc_radar_train_fwd_fused does not carry it)
-  TS_HIP(hipMemsetAsync(t.xyz4, 0, (size_t)rt * 4 * 4, s));
-  TS_TRY(copy_cols(radar_tokens, RI, t.xyz4, 4, rt, 3, 0, s));
-  TS_TRY(launch_linear_bwd_weight(t.xyz4, du, nullptr, nullptr, t.dw0p, const_cast<float*>(gpe.l0.b), rt, 4, C,
-                                  1.0f, s));
-  TS_TRY(copy_cols(t.dw0p, 4, const_cast<float*>(gpe.l0.w), 3, C, 3, 1, s));
-  return 0;
-}
-
-// ---- the backward as ONE launch of the row chain for the query side + a handful for the token side + ONE
-// grouped weight-gradient launch (round 2: ~130 launches).  Workspace: the transposed packed weights of the
-// three layers, the dY tensors the chain stores, dK | dV of the three layers.
-namespace {
+// the workspace of the fused backward (tc_radar_train_bwd_fused_ex says what it holds)
 struct BwdWs {
   tc_radar_layer wT[TC_MAX_RADAR_LAYERS];
   float* dy[DY_COUNT]; size_t dy_stride;
@@ -472,7 +193,253 @@ size_t bwd_ws_layout(const tc_head_weights* w, int B, int T, void* base, size_t 
   if (out) *out = b;
   return a.off;
 }
+
+// Opens a training call `who`: lays the tape out and checks that it fits; with ws, the backward's workspace too
+int open_call(const char* who, const tc_head_weights* w, int B, int T, void* tape, size_t tape_bytes, Tape* t,
+              void* workspace = nullptr, size_t workspace_bytes = 0, BwdWs* ws = nullptr) {
+  TC_REQUIRE(tape_layout(w, B, T, tape, tape_bytes, t) <= tape_bytes, "%s: tape too small", who);
+  TC_REQUIRE(ws == nullptr || bwd_ws_layout(w, B, T, workspace, workspace_bytes, ws) <= workspace_bytes,
+             "%s: workspace too small", who);
+  return 0;
+}
+
 }  // namespace
+}  // namespace tc
+
+using namespace tc;
+
+extern "C" {
+
+size_t tc_radar_train_tape_bytes(const tc_head_weights* w, int B, int T) {
+  if (check(w, B, T) != 0) return 0;
+  return tape_layout(w, B, T, nullptr, ~size_t(0), nullptr);
+}
+
+int tc_radar_train_fwd(const tc_head_weights* w, const float* hs_last, const float* ref_last,
+                       const float* last_box, const float* radar_tokens, int B, int T, int pad_mult,
+                       float* all_cls_scores, float* all_bbox_preds, void* tape, size_t tape_bytes,
+                       float dropout_p, unsigned long long dropout_seed, tc_stream_t stream) {
+  TC_TRY(check(w, B, T));
+  TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_fwd: dropout_p=%g", (double)dropout_p);
+  const bool drop = dropout_p > 0.0f;
+  const unsigned tref = (unsigned)w->num_radar_tokens_ref;
+  Tape t;
+  TC_TRY(open_call("radar_train_fwd", w, B, T, tape, tape_bytes, &t));
+  hipStream_t s = as_stream(stream);
+  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
+  const int ncls = w->num_classes, RI = w->radar_in_dims;
+  const int rows = B * Q, rt = B * T;
+  // radar encoders, HEAD:531-536 (Linear(3,C) as K = 4 with a zero column)
+  const tc_pos_encoder& pe = w->radar_position_encoder;
+  TC_HIP(hipMemsetAsync(t.xyz4, 0, (size_t)rt * 4 * 4, s));
+  TC_HIP(hipMemsetAsync(t.w0p, 0, (size_t)C * 4 * 4, s));
+  TC_TRY(copy_cols(radar_tokens, RI, t.xyz4, 4, rt, 3, 0, s));
+  TC_TRY(copy_cols(pe.l0.w, 3, t.w0p, 4, C, 3, 0, s));
+  TC_TRY(lin(t.xyz4, tc_linear{t.w0p, pe.l0.b}, rt, 4, C, 0, t.u0, s));
+  TC_TRY(layernorm(t.u0, pe.n1, t.u1, rt, 1, s));
+  TC_TRY(lin(t.u1, pe.l3, rt, C, C, 0, t.u2, s));
+  TC_TRY(layernorm(t.u2, pe.n4, t.pos, rt, 1, s));
+  TC_TRY(lin(radar_tokens, w->radar_feat0, rt, RI, 64, 1, t.f0, s));
+  TC_TRY(lin(t.f0, w->radar_feat2, rt, 64, 128, 1, t.f1, s));
+  TC_TRY(lin(t.f1, w->radar_feat4, rt, 128, C, 1, t.f2, s));
+  {
+    LnArgs l;      // mem = pos + f2 (plain sum)
+    l.a = t.pos; l.b = t.f2; l.y = t.mem; l.M = rt;
+    TC_TRY(launch_ln256(l, s));
+  }
+  TC_TRY(launch_radar_ref_l1(ref_last, w->pc_range, t.cxy, t.addref, rows, s));
+  const float* qin = hs_last;
+  for (int r = 0; r < w->num_radar_layers; ++r) {
+    const tc_radar_layer& rl = w->radar[r];
+    LayerTape& l = t.L[r];
+    float* cls_out = all_cls_scores + (size_t)r * rows * ncls;
+    float* box_out = all_bbox_preds + (size_t)r * rows * code;
+    const float* box_prev = layer_box_prev(r, last_box, all_bbox_preds, rows, code);
+    TC_TRY(lin(qin, rl.attn.in_proj, rows, C, C, 0, l.qp, s));            // (Wq: rows 0 .. C - 1 of in_proj)
+    TC_TRY(lin(t.mem, kv_half(rl.attn, C), rt, C, 2 * C, 0, l.kv, s));
+    TC_TRY(launch_radar_attn(core_args(w, r, t, box_prev, radar_tokens, B, T, pad_mult, dropout_p, dropout_seed), s));
+    if (drop) {     // x1 = qin + gate * rf_dropout2(out_proj(ao)), HEAD:581 (l.ff is free until linear2)
+      TC_TRY(lin(l.ao, rl.attn.out_proj, rows, C, C, 0, l.ff, s));
+      TC_TRY(launch_dropout(l.ff, qin, l.hits, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 1u, tref), l.x1, s));
+    } else {
+      TC_TRY(lin(l.ao, rl.attn.out_proj, rows, C, C, 0, l.x1, s, qin, l.hits));
+    }
+    TC_TRY(layernorm(l.x1, rl.norm2, l.x2, rows, 0, s));
+    TC_TRY(lin(l.x2, rl.linear1, rows, C, F, 1, l.h, s));
+    if (drop)       // rf_dropout(relu(linear1)), HEAD:584: the tape keeps the dropped activations
+      TC_TRY(launch_dropout(l.h, nullptr, nullptr, rows, F, make_drop(dropout_p, dropout_seed, 4u * r + 2u, tref), l.h, s));
+    TC_TRY(lin(l.h, rl.linear2, rows, F, C, 0, l.ff, s));
+    if (drop)       // rf_dropout3(ffn_out), HEAD:585
+      TC_TRY(launch_dropout(l.ff, nullptr, nullptr, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 3u, tref), l.ff, s));
+    TC_TRY(layernorm(l.x2, rl.norm3, l.x3, rows, 0, s, l.ff));
+    TC_TRY(lin(l.x3, rl.final_cls.l0, rows, C, C, 0, l.c0, s));
+    TC_TRY(layernorm(l.c0, rl.final_cls.n1, l.c1, rows, 1, s));
+    TC_TRY(lin(l.c1, rl.final_cls.l3, rows, C, C, 0, l.c2, s));
+    TC_TRY(layernorm(l.c2, rl.final_cls.n4, l.c3, rows, 1, s));
+    TC_TRY(lin(l.c3, rl.final_cls.l6, rows, C, ncls, 0, cls_out, s));
+    TC_TRY(lin(l.x3, rl.final_reg.l0, rows, C, C, 1, l.t0, s));
+    TC_TRY(lin(l.t0, rl.final_reg.l2, rows, C, C, 1, l.t1, s));
+    TC_TRY(lin(l.t1, rl.final_reg.l4, rows, C, code, 0, l.treg, s));
+    if (r == 0)
+      TC_TRY(launch_box_add_ref(l.treg, code, t.addref, 3, t.addref + 2, 3, box_out, nullptr, rows, s));
+    else
+      TC_TRY(launch_box_add_ref(l.treg, code, box_prev, code, box_prev + 4, code, box_out, nullptr, rows, s));
+    qin = l.x3;
+  }
+  return 0;
+}
+
+// The same forward as THREE launches of the fused row chains (chain.hip PROG_RADAR_ENC_TRAIN / PROG_RADAR_TRAIN)
+// plus the reference set-up: the encoder program writes the token-side tape (u0 u1 u2 pos f0 f1 f2 mem and the
+// three layers' K | V), the radar program walks the three fusion layers with the dropout sites in its epilogues
+// and stores every query-side tape tensor as it is produced.  The tape is the one tc_radar_train_fwd writes:
+// tc_radar_train_bwd takes either.  `packed_view`: the head's packed weights, re-packed for the CURRENT
+// parameters (tc_head_repack_trainable_ex(w, view, 1, ...) after an optimizer step).
+int tc_radar_train_fwd_fused(const tc_head_weights* packed_view, const float* hs_last, const float* ref_last,
+                             const float* last_box, const float* radar_tokens, int B, int T, int pad_mult,
+                             float* all_cls_scores, float* all_bbox_preds, void* tape, size_t tape_bytes,
+                             float dropout_p, unsigned long long dropout_seed, tc_stream_t stream) {
+  const tc_head_weights* w = packed_view;
+  TC_TRY(check(w, B, T));
+  TC_REQUIRE(w->l0_attn_out != nullptr, "radar_train_fwd_fused: packed_view was not produced by tc_head_pack_weights");
+  TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_fwd_fused: dropout_p=%g", (double)dropout_p);
+  // (round 3 refused T > 512 here although the chains take any T <= 1500 -- beyond 512 tokens the gate's hit masks
+  // are not kept in LDS and the attention step re-evaluates the gate, as the inference chain does; a frame with more
+  // than 511 radar points then failed mid-training: ADVICE r3.  Covered at T = 576 and T = 1500 by
+  // tests/test_gpu_training.py::test_fused_training_with_many_radar_tokens.)
+  TC_REQUIRE(w->code_size <= 10, "radar_train_fwd_fused: code_size=%d", w->code_size);
+  Tape t;
+  TC_TRY(open_call("radar_train_fwd_fused", w, B, T, tape, tape_bytes, &t));
+  hipStream_t s = as_stream(stream);
+  float* slots[TS_COUNT];
+  tape_slots(t, slots);
+  float* kv[TC_MAX_RADAR_LAYERS];          // (layers the head does not have: null weights, null tape)
+  for (int r = 0; r < TC_MAX_RADAR_LAYERS; ++r) kv[r] = t.L[r].kv;
+  // encoders + K | V of the three layers (HEAD:531-536, 573-575): one launch.  As before the builders: the training
+  // forward names no matrix path, the encoder program runs on the default one
+  RadarEncodeArgs re = radar_encode_args(w, radar_tokens, B * T, kv);
+  re.tape = slots;
+  TC_TRY(launch_radar_encode(re, s));
+  TC_TRY(launch_radar_ref_l1(ref_last, w->pc_range, t.cxy, t.addref, B * w->num_query, s));
+  // the three fusion layers: one launch, the rows in their own order
+  RadarChainArgs rc = radar_chain_args(w, 0, w->num_radar_layers, kv, hs_last, ref_last, last_box, radar_tokens, B, T, pad_mult,
+                                       all_cls_scores, all_bbox_preds, t.L[0].hits);
+  rc.tape = slots; rc.tape_stride = layer_stride(w, t); rc.hits_stride = hits_stride(w, t);
+  rc.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
+  return launch_radar_chain(rc, s);
+}
+
+int tc_radar_train_bwd(const tc_head_weights* w, const tc_head_weights* grads, const float* hs_last,
+                       const float* last_box, const float* radar_tokens, int B, int T, int pad_mult,
+                       const float* all_bbox_preds, const float* d_all_cls, const float* d_all_box,
+                       void* tape, size_t tape_bytes, float dropout_p, unsigned long long dropout_seed,
+                       tc_stream_t stream) {
+  TC_TRY(check(w, B, T));
+  TC_REQUIRE(grads != nullptr, "radar_train_bwd: grads is NULL");
+  TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_bwd: dropout_p=%g", (double)dropout_p);
+  const bool drop = dropout_p > 0.0f;
+  const unsigned tref = (unsigned)w->num_radar_tokens_ref;
+  const float keep_scale = drop ? 1.0f / (1.0f - dropout_p) : 1.0f;
+  Tape t;
+  TC_TRY(open_call("radar_train_bwd", w, B, T, tape, tape_bytes, &t));
+  hipStream_t s = as_stream(stream);
+  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
+  const int ncls = w->num_classes, RI = w->radar_in_dims;
+  const int rows = B * Q, rt = B * T;
+  TC_HIP(hipMemsetAsync(t.dmem, 0, (size_t)rt * C * 4, s));
+  bool have_dqin = false;                       // gradient w.r.t. this layer's output from the layer above
+  bool have_dbox_next = false;
+  for (int r = w->num_radar_layers - 1; r >= 0; --r) {
+    const tc_radar_layer& rl = w->radar[r];
+    const tc_radar_layer& gl = grads->radar[r];
+    LayerTape& l = t.L[r];
+    const float* qin = r == 0 ? hs_last : t.L[r - 1].x3;
+    const float* box_prev = layer_box_prev(r, last_box, all_bbox_preds, rows, code);
+    const float* dcls = d_all_cls + (size_t)r * rows * ncls;
+    // box_r = treg_r (+ prev box {0,1,4}); d box_r = given + what layer r+1 sent down (in t.dbox)
+    if (!have_dbox_next) TC_HIP(hipMemsetAsync(t.dbox, 0, (size_t)rows * code * 4, s));
+    TC_TRY(add_into(d_all_box + (size_t)r * rows * code, t.dbox, (size_t)rows * code, s));
+    // reg branch (Linear ReLU Linear ReLU Linear), dx3 -> dA (=)
+    TC_TRY(lin_bwd(l.t1, t.dbox, nullptr, nullptr, rl.final_reg.l4, gl.final_reg.l4, l.t1, t.dB, 0, rows, C, code, s));
+    TC_TRY(lin_bwd(l.t0, t.dB, nullptr, nullptr, rl.final_reg.l2, gl.final_reg.l2, l.t0, t.dC, 0, rows, C, C, s));
+    TC_TRY(lin_bwd(l.x3, t.dC, nullptr, nullptr, rl.final_reg.l0, gl.final_reg.l0, nullptr, t.dA, 0, rows, C, C, s));
+    // the reference of layer r is box_{r-1}: its {0,1,4} columns receive d box_r (HEAD:615-617, 661-662)
+    if (r > 0) {
+      // t.dbox becomes the incoming gradient of box_{r-1}: keep only columns 0,1,4
+      TC_HIP(hipMemsetAsync(t.dB, 0, (size_t)rows * code * 4, s));
+      TC_TRY(launch_box_ref_bwd(t.dbox, code, t.dB, rows, s));
+      TC_HIP(hipMemcpyAsync(t.dbox, t.dB, (size_t)rows * code * 4, hipMemcpyDeviceToDevice, s));
+      have_dbox_next = true;
+    }
+    // cls branch (Linear LN ReLU Linear LN ReLU Linear), dx3 +=
+    TC_TRY(lin_bwd(l.c3, dcls, nullptr, nullptr, rl.final_cls.l6, gl.final_cls.l6, nullptr, t.dB, 0, rows, C, ncls, s));
+    TC_TRY(ln_bwd(l.c2, nullptr, rl.final_cls.n4, gl.final_cls.n4, t.dB, l.c3, t.dC, rows, s));
+    TC_TRY(lin_bwd(l.c1, t.dC, nullptr, nullptr, rl.final_cls.l3, gl.final_cls.l3, nullptr, t.dB, 0, rows, C, C, s));
+    TC_TRY(ln_bwd(l.c0, nullptr, rl.final_cls.n1, gl.final_cls.n1, t.dB, l.c1, t.dC, rows, s));
+    TC_TRY(lin_bwd(l.x3, t.dC, nullptr, nullptr, rl.final_cls.l0, gl.final_cls.l0, nullptr, t.dA, 1, rows, C, C, s));
+    if (have_dqin) TC_TRY(add_into(t.dqin, t.dA, (size_t)rows * C, s));
+    // x3 = LN3(x2 + ff): dz -> dB (grad of x2 and of ff)
+    TC_TRY(ln_bwd(l.x2, l.ff, rl.norm3, gl.norm3, t.dA, nullptr, t.dB, rows, s));
+    const float* dff = t.dB;                                  // gradient of ffn_out
+    if (drop) {     // through rf_dropout3: same mask on the gradient; dz itself still feeds dx2 below
+      TC_TRY(launch_dropout(t.dB, nullptr, nullptr, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 3u, tref), t.dD, s));
+      dff = t.dD;
+    }
+    // l.h = rf_dropout(relu(.)): its zeros are the ReLU zeros and the dropped elements, the kept ones
+    // carry 1 / (1 - p)
+    TC_TRY(lin_bwd(l.h, dff, nullptr, nullptr, rl.linear2, gl.linear2, l.h, t.dh, 0, rows, F, C, s, keep_scale));
+    TC_TRY(lin_bwd(l.x2, t.dh, nullptr, nullptr, rl.linear1, gl.linear1, nullptr, t.dB, 1, rows, C, F, s));   // dx2 = dz + dh W1
+    // x2 = LN2(x1): dx1 -> dC
+    TC_TRY(ln_bwd(l.x1, nullptr, rl.norm2, gl.norm2, t.dB, nullptr, t.dC, rows, s));
+    // x1 = qin + gate * out_proj(ao): d ao -> dA, d qin = dx1
+    const float* dproj = t.dC;                                // gradient of out_proj(ao) before the row gate
+    if (drop) {     // through rf_dropout2
+      TC_TRY(launch_dropout(t.dC, nullptr, nullptr, rows, C, make_drop(dropout_p, dropout_seed, 4u * r + 1u, tref), t.dD, s));
+      dproj = t.dD;
+    }
+    TC_TRY(lin_bwd(l.ao, dproj, nullptr, l.hits, rl.attn.out_proj, gl.attn.out_proj, nullptr, t.dA, 0, rows, C, C, s));
+    TC_HIP(hipMemsetAsync(t.dkv, 0, (size_t)rt * 2 * C * 4, s));
+    {
+      RadarAttnArgs ra = core_args(w, r, t, box_prev, radar_tokens, B, T, pad_mult, dropout_p, dropout_seed);
+      const float qs = ra.qscale;
+      ra.qscale = 1.0f;
+      TC_TRY(launch_radar_attn_bwd(ra, qs, t.dA, t.dqp, t.dkv, s));
+    }
+    // d qin = dx1 + dqp Wq  (into dqin for the layer below; nothing below layer 0: the decoder is frozen)
+    if (r > 0) {
+      TC_HIP(hipMemcpyAsync(t.dqin, t.dC, (size_t)rows * C * 4, hipMemcpyDeviceToDevice, s));
+      TC_TRY(lin_bwd(qin, t.dqp, nullptr, nullptr, rl.attn.in_proj, gl.attn.in_proj, nullptr, t.dqin, 1, rows, C, C, s));
+      have_dqin = true;
+    } else {
+      TC_TRY(lin_bwd(qin, t.dqp, nullptr, nullptr, rl.attn.in_proj, gl.attn.in_proj, nullptr, nullptr, 0, rows, C, C, s));
+    }
+    TC_TRY(lin_bwd(t.mem, t.dkv, nullptr, nullptr, kv_half(rl.attn, C), kv_half(gl.attn, C), nullptr, t.dmem, 1, rt, C, 2 * C, s));
+  }
+  // encoders: mem = relu(LN4(u2)) + relu(feat4(f1)); both summands see dmem
+  const tc_pos_encoder& pe = w->radar_position_encoder;
+  const tc_pos_encoder& gpe = grads->radar_position_encoder;
+  TC_TRY(lin_bwd(t.f1, t.dmem, t.f2, nullptr, w->radar_feat4, grads->radar_feat4, t.f1, t.dt128, 0, rt, 128, C, s));
+  TC_TRY(lin_bwd(t.f0, t.dt128, nullptr, nullptr, w->radar_feat2, grads->radar_feat2, t.f0, t.dt64, 0, rt, 64, 128, s));
+  TC_TRY(lin_bwd(radar_tokens, t.dt64, nullptr, nullptr, w->radar_feat0, grads->radar_feat0, nullptr, nullptr, 0, rt, RI, 64, s));
+  // (rows of the token gradients reuse dqp/dkv-sized scratch: rt <= tape sizes by construction)
+  float* du = t.dkv;                 // [rt, C] scratch (dkv is [rt, 2C])
+  float* du2 = t.dkv + (size_t)rt * C;
+  TC_TRY(ln_bwd(t.u2, nullptr, pe.n4, gpe.n4, t.dmem, t.pos, du, rt, s));
+  TC_TRY(lin_bwd(t.u1, du, nullptr, nullptr, pe.l3, gpe.l3, nullptr, du2, 0, rt, C, C, s));
+  TC_TRY(ln_bwd(t.u0, nullptr, pe.n1, gpe.n1, du2, t.u1, du, rt, s));
+  TC_HIP(hipMemsetAsync(t.dw0p, 0, (size_t)C * 4 * 4, s));
+  // (the padded xyz operand is rebuilt here: the tape of tc_radar_train_fwd_fused does not carry it)
+  TC_HIP(hipMemsetAsync(t.xyz4, 0, (size_t)rt * 4 * 4, s));
+  TC_TRY(copy_cols(radar_tokens, RI, t.xyz4, 4, rt, 3, 0, s));
+  TC_TRY(launch_linear_bwd_weight(t.xyz4, du, nullptr, nullptr, t.dw0p, const_cast<float*>(gpe.l0.b), rt, 4, C,
+                                  1.0f, s));
+  TC_TRY(copy_cols(t.dw0p, 4, const_cast<float*>(gpe.l0.w), 3, C, 3, 1, s));
+  return 0;
+}
+
+// ---- the backward as ONE launch of the row chain for the query side + a handful for the token side + ONE
+// grouped weight-gradient launch (round 2: ~130 launches).  Workspace: the transposed packed weights of the
+// three layers, the dY tensors the chain stores, dK | dV of the three layers.
 
 // the transposed packed weights of the three fusion layers (what the backward row chain multiplies by): pack jobs
 static int transposed_jobs(const tc_head_weights* w, const BwdWs& ws, PackJob* jobs) {
@@ -546,8 +513,8 @@ static int weight_gradients(const tc_head_weights* w, const tc_head_weights* gra
     const LayerTape& l = t.L[r];
     const size_t off = (size_t)r * ws.dy_stride;
     const float* qin = r == 0 ? hs_last : t.L[r - 1].x3;
-    job(qin, ws.dy[DY_DQP] + off, tc_linear{gl.attn.in_proj.w, gl.attn.in_proj.b}, rows, C, C);
-    job(t.mem, ws.dkv[r], tc_linear{gl.attn.in_proj.w + (size_t)C * C, gl.attn.in_proj.b + C}, rt, C, 2 * C);
+    job(qin, ws.dy[DY_DQP] + off, gl.attn.in_proj, rows, C, C);
+    job(t.mem, ws.dkv[r], kv_half(gl.attn, C), rt, C, 2 * C);
     job(l.ao, ws.dy[DY_DPROJ] + off, gl.attn.out_proj, rows, C, C);
     job(l.x2, ws.dy[DY_DH] + off, gl.linear1, rows, C, F);
     job(l.h, ws.dy[DY_DFF] + off, gl.linear2, rows, F, C);
@@ -575,17 +542,15 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
                                 void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
                                 float dropout_p, unsigned long long dropout_seed, const float* layer_losses,
                                 float* layer_losses_clean, int flags, tc_stream_t stream) {
-  TS_TRY(check(w, B, T));
+  TC_TRY(check(w, B, T));
   TC_REQUIRE(grads != nullptr && workspace != nullptr, "radar_train_bwd_fused: null argument");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_bwd_fused: dropout_p=%g", (double)dropout_p);
   TC_REQUIRE(w->code_size <= 10, "radar_train_bwd_fused: code_size=%d", w->code_size);
   Tape t;
-  TC_REQUIRE(tape_layout(w, B, T, tape, tape_bytes, &t) <= tape_bytes, "radar_train_bwd_fused: tape too small");
   BwdWs ws;
-  TC_REQUIRE(bwd_ws_layout(w, B, T, workspace, workspace_bytes, &ws) <= workspace_bytes,
-             "radar_train_bwd_fused: workspace too small");
+  TC_TRY(open_call("radar_train_bwd_fused", w, B, T, tape, tape_bytes, &t, workspace, workspace_bytes, &ws));
   hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
+  const int Q = w->num_query, C = w->embed_dims, code = w->code_size;
   const int ncls = w->num_classes, RI = w->radar_in_dims;
   const int rows = B * Q, rt = B * T;
   // 1. the transposed packed weights of the three layers: one launch -- unless the caller packed them together with the
@@ -593,23 +558,19 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   if (!(flags & 1)) {
     PackJob jobs[10 * TC_MAX_RADAR_LAYERS];
     const int n = transposed_jobs(w, ws, jobs);
-    TS_TRY(launch_pack_group(jobs, n, s));
+    TC_TRY(launch_pack_group(jobs, n, s));
   }
   // 2. accumulators
-  TS_HIP(hipMemsetAsync(ws.dkv[0], 0, (size_t)((char*)(ws.dmem + (size_t)rt * C) - (char*)ws.dkv[0]), s));   // dK|dV x N + dmem
+  TC_HIP(hipMemsetAsync(ws.dkv[0], 0, (size_t)((char*)(ws.dmem + (size_t)rt * C) - (char*)ws.dkv[0]), s));   // dK|dV x N + dmem
   // 3. the query side of all three layers: one launch
   float* slots[TS_COUNT];
-  memset(slots, 0, sizeof(slots));
-  const LayerTape& l0 = t.L[0];
-  slots[TS_QP] = l0.qp; slots[TS_AO] = l0.ao; slots[TS_X1] = l0.x1; slots[TS_X2] = l0.x2; slots[TS_H] = l0.h;
-  slots[TS_SUM] = l0.ff; slots[TS_X3] = l0.x3; slots[TS_C0] = l0.c0; slots[TS_C1] = l0.c1; slots[TS_C2] = l0.c2;
-  slots[TS_C3] = l0.c3; slots[TS_T0] = l0.t0; slots[TS_T1] = l0.t1; slots[TS_TREG] = l0.treg;
+  tape_slots(t, slots);
   RadarBwdChainArgs a;
   const int NR = w->num_radar_layers;
   for (int r = 0; r < NR; ++r) {
     a.wT[r] = ws.wT[r]; a.w[r] = w->radar[r]; a.grads[r] = grads->radar[r];
     a.kv[r] = t.L[r].kv; a.dkv[r] = ws.dkv[r];
-    const float* box_prev = r == 0 ? last_box : all_bbox_preds + (size_t)(r - 1) * rows * code;
+    const float* box_prev = layer_box_prev(r, last_box, all_bbox_preds, rows, code);
     a.cxy[r] = r == 0 ? t.cxy : box_prev; a.ld_c[r] = r == 0 ? 2 : code; a.box[r] = box_prev;
   }
   a.tape = slots; a.tape_stride = layer_stride(w, t);
@@ -618,7 +579,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   a.d_cls = d_all_cls; a.d_box = d_all_box; a.loss_vals = layer_losses; a.loss_out = layer_losses_clean;
   a.tokens = radar_tokens; a.RI = RI; a.T = T; a.pad_mult = pad_mult;
   a.nlayers = NR; a.Q = Q; a.M = rows; a.code = code; a.ncls = ncls;
-  a.qscale = 1.0f / sqrtf((float)(C / TC_RADAR_HEADS));
+  a.qscale = radar_qscale(C);
   a.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
   {
     // deterministic mode: the chain reads the ranges from a device copy in the last words of the caller's shadow buffer
@@ -626,28 +587,28 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
     const DetAcc& d = current_det();
     DetAcc* dev = current_det_device();
     if (d.shadow[0] != nullptr && d.shadow[1] != nullptr && dev != nullptr) {
-      TS_TRY(launch_det_store(d, dev, s));
+      TC_TRY(launch_det_store(d, dev, s));
       a.det_device = dev;
     }
   }
-  TS_TRY(launch_radar_chain_bwd(a, s));
+  TC_TRY(launch_radar_chain_bwd(a, s));
   // (deterministic mode: the chain's dK | dV sums sit in their shadow; the token side reads dK | dV next)
-  TS_TRY(launch_det_flush(current_det(), 1, s));
+  TC_TRY(launch_det_flush(current_det(), 1, s));
   // 4. the token side: dmem = sum_r dkv_r Wkv_r, then the encoders (data gradients only; weights below)
   for (int r = 0; r < NR; ++r)
-    TS_TRY(launch_linear_bwd_data(ws.dkv[r], nullptr, nullptr, w->radar[r].attn.in_proj.w + (size_t)C * C, nullptr, ws.dmem,
+    TC_TRY(launch_linear_bwd_data(ws.dkv[r], nullptr, nullptr, kv_half(w->radar[r].attn, C).w, nullptr, ws.dmem,
                                   rt, C, 2 * C, 1.0f, 1, s));
   const tc_pos_encoder& pe = w->radar_position_encoder;
   const tc_pos_encoder& gpe = grads->radar_position_encoder;
   // mem = relu(LN4(u2)) + relu(feat4(f1)): both summands see dmem
-  TS_TRY(launch_linear_bwd_data(ws.dmem, t.f2, nullptr, w->radar_feat4.w, t.f1, t.dt128, rt, 128, C, 1.0f, 0, s));
-  TS_TRY(launch_linear_bwd_data(t.dt128, nullptr, nullptr, w->radar_feat2.w, t.f0, t.dt64, rt, 64, 128, 1.0f, 0, s));
+  TC_TRY(launch_linear_bwd_data(ws.dmem, t.f2, nullptr, w->radar_feat4.w, t.f1, t.dt128, rt, 128, C, 1.0f, 0, s));
+  TC_TRY(launch_linear_bwd_data(t.dt128, nullptr, nullptr, w->radar_feat2.w, t.f0, t.dt64, rt, 64, 128, 1.0f, 0, s));
   float* du = t.dkv;                 // [rt, C] scratch of the tape
   float* du2 = t.dkv + (size_t)rt * C;
-  TS_TRY(ln_bwd(t.u2, nullptr, pe.n4, gpe.n4, ws.dmem, t.pos, du, rt, s));
-  TS_TRY(launch_linear_bwd_data(du, nullptr, nullptr, pe.l3.w, nullptr, du2, rt, C, C, 1.0f, 0, s));
+  TC_TRY(ln_bwd(t.u2, nullptr, pe.n4, gpe.n4, ws.dmem, t.pos, du, rt, s));
+  TC_TRY(launch_linear_bwd_data(du, nullptr, nullptr, pe.l3.w, nullptr, du2, rt, C, C, 1.0f, 0, s));
   float* du0 = ws.du0;               // [rt, C]
-  TS_TRY(ln_bwd(t.u0, nullptr, pe.n1, gpe.n1, du2, t.u1, du0, rt, s));
+  TC_TRY(ln_bwd(t.u0, nullptr, pe.n1, gpe.n1, du2, t.u1, du0, rt, s));
   // 5. every weight gradient: one grouped launch (two with the scalar variant for the 10-wide heads) -- or, flags bit 1,
   //    left to tc_radar_train_bwd_weights: one launch per fusion layer (top layer first) + one for the token side, so that
   //    the caller can start the gradient exchange of a chunk while the next one is computed (round 6)
@@ -655,7 +616,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
     TC_REQUIRE(current_det().shadow[0] == nullptr, "radar_train_bwd_fused: chunked weight gradients run with float atomics only");
     return 0;
   }
-  TS_TRY(weight_gradients(w, grads, hs_last, radar_tokens, B, T, t, ws, -1, s));
+  TC_TRY(weight_gradients(w, grads, hs_last, radar_tokens, B, T, t, ws, -1, s));
   return launch_det_flush(current_det(), 0, s);      // (deterministic mode: the bucket's sums back into the gradients)
 }
 
@@ -676,7 +637,7 @@ int tc_radar_train_bwd_fused_det(const tc_head_weights* w, const tc_head_weights
                                  float dropout_p, unsigned long long dropout_seed, const float* layer_losses,
                                  float* layer_losses_clean, int flags, float* grad_base, size_t grad_elems,
                                  long long* shadow, size_t shadow_elems, tc_stream_t stream) {
-  TS_TRY(check(w, B, T));
+  TC_TRY(check(w, B, T));
   TC_REQUIRE(grad_base != nullptr && shadow != nullptr && workspace != nullptr, "radar_train_bwd_fused_det: null argument");
   BwdWs ws;
   TC_REQUIRE(bwd_ws_layout(w, B, T, workspace, workspace_bytes, &ws) <= workspace_bytes,
@@ -714,14 +675,12 @@ int tc_radar_train_bwd_fused(const tc_head_weights* w, const tc_head_weights* gr
 int tc_radar_train_bwd_weights(const tc_head_weights* w, const tc_head_weights* grads, const float* hs_last,
                                const float* radar_tokens, int B, int T, void* tape, size_t tape_bytes, void* workspace,
                                size_t workspace_bytes, int group, tc_stream_t stream) {
-  TS_TRY(check(w, B, T));
+  TC_TRY(check(w, B, T));
   TC_REQUIRE(grads != nullptr && workspace != nullptr && tape != nullptr, "radar_train_bwd_weights: null argument");
   TC_REQUIRE(group >= 0 && group <= w->num_radar_layers, "radar_train_bwd_weights: group=%d (0..%d)", group, w->num_radar_layers);
   Tape t;
-  TC_REQUIRE(tape_layout(w, B, T, tape, tape_bytes, &t) <= tape_bytes, "radar_train_bwd_weights: tape too small");
   BwdWs ws;
-  TC_REQUIRE(bwd_ws_layout(w, B, T, workspace, workspace_bytes, &ws) <= workspace_bytes,
-             "radar_train_bwd_weights: workspace too small");
+  TC_TRY(open_call("radar_train_bwd_weights", w, B, T, tape, tape_bytes, &t, workspace, workspace_bytes, &ws));
   return weight_gradients(w, grads, hs_last, radar_tokens, B, T, t, ws, group, as_stream(stream));
 }
 
@@ -737,7 +696,7 @@ int tc_dropout_mask(float dropout_p, unsigned long long seed, int site, size_t n
   const float one = 1.0f;          // dropout of a tensor of ones
   unsigned bits;
   memcpy(&bits, &one, 4);
-  TS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), (int)bits, n, s));
+  TC_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), (int)bits, n, s));
   return launch_dropout(out, nullptr, nullptr, 1, (int)n, make_drop(dropout_p, seed, (unsigned)site, 1500u), out, s);
 }
 
