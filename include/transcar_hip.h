@@ -39,6 +39,17 @@ extern "C" {
 /* Heads of the radar fusion attention (rf_multihead_attn{,2,3}): the reference builds it as
  * nn.MultiheadAttention(embed_dims, 8) (HEAD:129-171) whatever the decoder's self-attention uses. */
 #define TC_RADAR_HEADS 8
+/* The distance gate of a fusion layer, a (radius_min, radius_max) pair wherever one is taken (tc_radar_layer,
+ * tc_radar_gated_xattn_fwd, tc_radar_attn_core_fwd / _bwd):
+ *   radius_min >= 0: three circles per query (centre, front and rear at +-0.25 * length) of the radius
+ *                    clamp(length / 2, radius_min, radius_max); a token is attended iff dist < radius for any of them.
+ *   radius_min == TC_RADAR_GATE_CIRCLE: one circle at the gate centre of the fixed radius radius_max; a token is attended
+ *                    iff not (dist > radius_max) -- the edge is inside.
+ * A radius is finite and at most TC_RADAR_RADIUS_MAX; any other negative radius_min, and radius_max < radius_min, are
+ * refused.  The Python layer also keeps radii at or above TC_RADAR_RADIUS_MIN (a zeroed pair stays accepted here). */
+#define TC_RADAR_GATE_CIRCLE (-1.0f)
+#define TC_RADAR_RADIUS_MIN 0.125f
+#define TC_RADAR_RADIUS_MAX 16.0f
 /* num_classes of a head (tc_head_weights, tc_decoder_heads): the class heads of the row chains take one or two
  * 16-column sub-tiles */
 #define TC_MAX_CLASSES 32
@@ -110,7 +121,8 @@ typedef struct {
   tc_lnorm norm3;                   /* rf_norm3{,_2,_3}                       */
   tc_cls_branch final_cls;          /* final_cls{,2,3}                        */
   tc_reg_branch final_reg;          /* final_reg{,2,3}                        */
-  float radius_min, radius_max;     /* clamp: (1,2),(1,2),(0.5,1)  HEAD:567,635,693 */
+  float radius_min, radius_max;     /* clamp: (1,2),(1,2),(0.5,1)  HEAD:567,635,693; or (TC_RADAR_GATE_CIRCLE, R):
+                                       one circle of radius R, edge inside (see TC_RADAR_GATE_CIRCLE) */
   size_t packed16_delta;            /* packed view only, as in tc_decoder_layer */
 } tc_radar_layer;
 
@@ -482,6 +494,13 @@ int tc_radar_fusion_fwd(const tc_head_weights* packed_view, const float* hs_last
  * ones) and adds the number of disagreements to *mismatches (device, 8 bytes, zeroed by the caller). */
 int tc_radar_gate_selfcheck(int n_radii, unsigned long long seed, unsigned long long* mismatches,
                             tc_stream_t stream);
+/* The same check for either comparison over a radius range: inclusive == 0 is the three-circle gate's dist < radius,
+ * inclusive == 1 the single circle's not (dist > radius) (TC_RADAR_GATE_CIRCLE) against its own threshold.  n_radii
+ * radii: rad_lo and rad_hi themselves first, then pseudo-random ones in [rad_lo, rad_hi], which must lie inside
+ * [TC_RADAR_RADIUS_MIN, TC_RADAR_RADIUS_MAX]; each x (every float within 256 ulps of radius^2 + 4096 random ones
+ * between -1 and 2.25 * rad_hi^2). */
+int tc_radar_gate_selfcheck_range(int n_radii, unsigned long long seed, float rad_lo, float rad_hi, int inclusive,
+                                  unsigned long long* mismatches, tc_stream_t stream);
 
 /* Self-check of the row-local arithmetic of the 16- / 32-row chains (round 6; no reference line: an implementation
  * invariant).  Three pieces were rewritten for fewer vector instructions and must give the same BITS as their plain forms:

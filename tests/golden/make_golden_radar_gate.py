@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Fixtures of the single-circle radar gate from the REFERENCE's own code: its models/dense_heads/detr3d_head_backup.py,
+the head with one circle of fixed radius 2 / 2 / 1 m per query (a token is masked iff its distance exceeds the radius), imported unmodified
+through oracle/ref_harness.py and run on G5's tiny rig and G8's training rig (make_golden.py's functions, weights and
+frame seeds).
+
+Run only in the authoring container:   python tests/golden/make_golden_radar_gate.py
+
+  g5_head_tiny_gate_circle.npz        outputs, per-layer hit counts (of the selected rows), fill_in, the radar seed and
+                                      its gate margin
+  g8_train_grads_gate_circle.npz      make_golden.write_g8's layout
+
+The radar seed is chosen as make_golden_variants.gate_margins chooses one: seeds 2 .. 39 are scanned on the CPU oracle
+under the circle gate (tests/radar_gate_rig.py) and the one whose closest gate decision is farthest from its radius is
+kept; that margin is stored."""
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
+
+import make_golden as MG                                 # noqa: E402
+import radar_gate_rig as G                               # noqa: E402
+from oracle import mmcv_bricks as B                      # noqa: E402
+from oracle import ref_harness as RH                     # noqa: E402
+from oracle import transcar_oracle as O                  # noqa: E402
+from transcar_amd import configs, synth                  # noqa: E402
+
+SEEDS = range(2, 40)
+
+
+def backup_module():
+    RH.load_reference()
+    B.HEADS.module_dict.pop('Detr3DHead', None)          # the backup file registers the same name: a second one raises
+    return RH._load('projects.mmdet3d_plugin.models.dense_heads.detr3d_head_backup',
+                    os.path.join(RH.PLUGIN, 'models/dense_heads/detr3d_head_backup.py'))
+
+
+def backup_head(mod, train=False):
+    cfg = configs.head_cfg()
+    cfg.pop('type', None)
+    if train:
+        cfg['train_cfg'] = configs.train_cfg_pts
+    head = mod.Detr3DHead(**cfg)
+    sd = synth.make_state_dict(seed=3)
+    assert {k: tuple(v.shape) for k, v in head.state_dict().items()} == {k: tuple(v.shape) for k, v in sd.items()}
+    head.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    return head.eval()
+
+
+def choose_seed(centres):
+    feats = synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)
+    sd = O.to_torch_sd(synth.make_state_dict(seed=3))
+    best = None
+    for seed in SEEDS:
+        frame = synth.make_radar_frame(seed=seed, n_per_radar=51, centres=centres)
+        m = G.gate_margin(G.CIRCLE, sd, feats, frame)
+        print('seed %d: margin %.3g m' % (seed, m))
+        if best is None or m > best[1]:
+            best = (seed, m)
+    return best
+
+
+def main():
+    mod = backup_module()
+    centres = np.load(os.path.join(HERE, 'g5_head_tiny.npz'))['radar_centres']
+    seed, margin = choose_seed(centres)
+    print('radar seed %d, margin %.3g m' % (seed, margin))
+    feats = synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)
+    l2i = synth.make_lidar2img()
+    frame = synth.make_radar_frame(seed=seed, n_per_radar=51, centres=centres)
+    outs, cap, tcap = MG.run_head(backup_head(mod), feats, l2i, frame)
+    tokens = cap['tokens'][0].numpy()
+    fill_in = int((tokens[:, 0] != 500.0).sum())
+    hits = [(~cap['mask%d' % i].numpy()).sum(1).astype(np.int32) for i in range(3)]
+    MG.save('g5_head_tiny_gate_circle.npz', all_cls_scores=outs['all_cls_scores'].numpy(),
+            all_bbox_preds=outs['all_bbox_preds'].numpy(), inter_refs=tcap['inter_refs'].numpy(),
+            Lq=np.array([cap['Lq%d' % i] for i in range(3)]), hit_counts0=hits[0], hit_counts1=hits[1], hit_counts2=hits[2],
+            fill_in=fill_in, radar_seed=seed, gate_margin=margin, radii=np.array(G.CIRCLE['radii']))
+    print('Lq', [cap['Lq%d' % i] for i in range(3)])
+    head = backup_head(mod, train=True)
+    MG.freeze_like_train_py(head)
+    boxes, labels = synth.make_gt(seed=7, n=24)
+    with torch.enable_grad():
+        outs, cap, _ = MG.run_head(head, feats, l2i, frame)
+        losses = head.loss([RH.GtBoxes(torch.from_numpy(boxes))], [torch.from_numpy(labels)], outs)
+        total = sum(v for k, v in losses.items() if 'loss' in k)
+        total.backward()
+    MG.write_g8('g8_train_grads_gate_circle.npz', head, outs, cap, losses, total, radar_seed=seed)
+
+
+if __name__ == '__main__':
+    main()

@@ -112,6 +112,73 @@ def check_num_fusion_layers(num_fusion_layers):
     return n
 
 
+# The distance gate of the radar fusion layers (include/transcar_hip.h, TC_RADAR_GATE_CIRCLE): a (radius_min, radius_max)
+# pair per layer; radius_min == TC_RADAR_GATE_CIRCLE encodes one circle of the fixed radius radius_max, edge inside.
+# A radius lies in [TC_RADAR_RADIUS_MIN, TC_RADAR_RADIUS_MAX] metres: below is under the sensor's resolution, beyond
+# a gate is no longer local (and the kernels' threshold search is checked on this range).
+TC_RADAR_GATE_CIRCLE = -1.0
+TC_RADAR_RADIUS_MIN, TC_RADAR_RADIUS_MAX = 0.125, 16.0
+RADAR_GATE_TYPES = ('three_circle', 'circle')
+#: the three-circle clamp pairs of the reference's three fusion layers (HEAD:567, 635, 693)
+RADAR_RADII = ((1.0, 2.0), (1.0, 2.0), (0.5, 1.0))
+
+
+def _gate_radius(v, gate):
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TransCARHipError('Detr3DHead(HIP): radar_gate=%r: radius %r is not a number' % (gate, v))
+    v = float(v)
+    if not TC_RADAR_RADIUS_MIN <= v <= TC_RADAR_RADIUS_MAX:        # (a NaN fails both comparisons)
+        raise TransCARHipError('Detr3DHead(HIP): radar_gate=%r: radius %r is outside %g .. %g m'
+                               % (gate, v, TC_RADAR_RADIUS_MIN, TC_RADAR_RADIUS_MAX))
+    return v
+
+
+def check_radar_gate(radar_gate, num_fusion_layers=TC_MAX_RADAR_LAYERS):
+    """The distance gate of the radar fusion layers, checked before anything is built, packed or launched; returns it
+    normalised: ``dict(type=..., radii=(one entry per fusion layer))``.
+
+    * ``None`` or ``dict(type='three_circle')``: three circles per query (centre, front and rear) of the radius
+      clamp(length / 2, rmin, rmax), a token attended iff ``dist < radius`` for any (HEAD:549-571), with the reference's
+      pairs RADAR_RADII; ``radii=[(rmin, rmax), ...]`` sets other pairs.
+    * ``dict(type='circle', radii=[R, ...])``: one circle of radius R at the gate centre, a token attended iff not
+      ``dist > R`` (the edge is inside).
+
+    ``radii`` has one entry per fusion layer; a list of TC_MAX_RADAR_LAYERS is also taken by a shallower head, which
+    uses its first entries."""
+    n = check_num_fusion_layers(num_fusion_layers)
+    gate = radar_gate
+    if gate is None:
+        gate = dict(type='three_circle')
+    if not isinstance(gate, dict) or set(gate) - {'type', 'radii'} or gate.get('type') not in RADAR_GATE_TYPES:
+        raise TransCARHipError("Detr3DHead(HIP): radar_gate=%r is not supported (None, dict(type='three_circle'[, radii="
+                               "[(rmin, rmax), ...]]) or dict(type='circle', radii=[R, ...]))" % (radar_gate,))
+    kind, radii = gate['type'], gate.get('radii')
+    if radii is None and kind == 'three_circle':
+        radii = RADAR_RADII
+    if not isinstance(radii, (list, tuple)) or len(radii) not in (n, TC_MAX_RADAR_LAYERS):
+        raise TransCARHipError('Detr3DHead(HIP): radar_gate=%r: radii needs one entry per fusion layer (%d, or %d of which '
+                               'the first %d are used)' % (radar_gate, n, TC_MAX_RADAR_LAYERS, n))
+    out = []
+    for entry in radii[:n]:
+        if kind == 'circle':
+            out.append(_gate_radius(entry, radar_gate))
+            continue
+        if not isinstance(entry, (list, tuple)) or len(entry) != 2:
+            raise TransCARHipError('Detr3DHead(HIP): radar_gate=%r: %r is not a (rmin, rmax) pair' % (radar_gate, entry))
+        rmin, rmax = (_gate_radius(v, radar_gate) for v in entry)
+        if rmin > rmax:
+            raise TransCARHipError('Detr3DHead(HIP): radar_gate=%r: rmin %r is above rmax %r' % (radar_gate, rmin, rmax))
+        out.append((rmin, rmax))
+    return dict(type=kind, radii=tuple(out))
+
+
+def radar_gate_pairs(gate):
+    """The (radius_min, radius_max) pairs of a normalised gate (check_radar_gate) as the C boundary takes them."""
+    if gate['type'] == 'circle':
+        return [(TC_RADAR_GATE_CIRCLE, r) for r in gate['radii']]
+    return [tuple(p) for p in gate['radii']]
+
+
 def cam_pregather_supported(embed_dims, num_levels, num_cams):
     """The shapes the camera pre-gather (tc_head_options.cam_pregather) runs:
     C = 256, 4 levels, at most 8 cameras.  Others take the chain's own gather,
@@ -273,6 +340,7 @@ SIGNATURES = {
     'tc_sdpa_fwd_f16x2_hd': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     'tc_radar_xattn_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'tc_radar_gate_selfcheck': (_i, [_i, C.c_ulonglong, _vp, _vp]),
+    'tc_radar_gate_selfcheck_range': (_i, [_i, C.c_ulonglong, C.c_float, C.c_float, _i, _vp, _vp]),
     'tc_rowops_selfcheck': (_i, [_i, C.c_ulonglong, _vp, _vp]),
     'tc_radar_gated_xattn_fwd': (_i, [_P(tc_mha), _vp, _vp, _vp, _i, _vp, _vp,
                                       _i, _i, _i, _i, _i, _i, _f, _f, _vp,

@@ -77,7 +77,7 @@ IMG_SHAPE = (928, 1600, 3)
 
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
              num_levels=None, num_heads=None, num_classes=None,
-             num_fusion_layers=None, pc_range=None, post_center_range=None):
+             num_fusion_layers=None, pc_range=None, post_center_range=None, radar_gate=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -95,7 +95,11 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     three, CFG:74, :85, :112; the result then carries ``train_cfg``, as
     ``train_cfg(pc_range)`` gives it); post_center_range sets the coder's
     (CFG:84).  The radar filter's range is no config value: the reference
-    writes it as a constant (HEAD:304)."""
+    writes it as a constant (HEAD:304).  radar_gate sets the distance gate of
+    the fusion layers (``_lib.check_radar_gate``: the reference head's three
+    circles with other clamp pairs, or ``dict(type='circle', radii=[R, ...])``,
+    the single circle of the paper's radius ablation; the reference writes its
+    radii as constants, HEAD:567, 635, 693)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -128,6 +132,10 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
         cfg['train_cfg'] = train_cfg(pc_range)
     if post_center_range is not None:
         cfg['bbox_coder']['post_center_range'] = _range6(post_center_range, 'post_center_range')
+    if radar_gate is not None:
+        from ._lib import check_radar_gate
+        gate = check_radar_gate(radar_gate, cfg.get('num_fusion_layers', 3))
+        cfg['radar_gate'] = dict(type=gate['type'], radii=list(gate['radii']))
     return cfg
 
 

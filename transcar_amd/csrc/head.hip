@@ -136,6 +136,8 @@ static int check_dims(const tc_head_weights* w) {
   TC_REQUIRE(w->num_classes >= 1 && w->num_classes <= TC_MAX_CLASSES, "num_classes=%d (1 .. %d supported)", w->num_classes,
              TC_MAX_CLASSES);
   TC_REQUIRE((w->ffn_dims & 31) == 0 && (w->radar_in_dims & 3) == 0, "ffn_dims/radar_in_dims alignment");
+  for (int r = 0; r < w->num_radar_layers; ++r)
+    TC_TRY(check_radar_radii(w->radar[r].radius_min, w->radar[r].radius_max, "radar", r));
   return 0;
 }
 
@@ -653,6 +655,7 @@ int tc_radar_gated_xattn_fwd(const tc_mha* w, const float* query, const float* c
                              tc_stream_t stream) {
   TC_REQUIRE(C == 256 && num_heads == TC_RADAR_HEADS, "radar_xattn: C=%d heads=%d (256/%d supported)", C, num_heads, TC_RADAR_HEADS);
   TC_REQUIRE(workspace_bytes >= tc_radar_xattn_workspace_bytes(B, Q, T, C), "radar_xattn: workspace too small");
+  TC_TRY(check_radar_radii(radius_min, radius_max, "radar_xattn"));
   hipStream_t s = as_stream(stream);
   const int rows = B * Q, rt = B * T;
   Arena a(workspace, workspace_bytes);
@@ -723,6 +726,11 @@ int tc_radar_fusion_fwd(const tc_head_weights* packed_view, const float* hs_last
 int tc_radar_gate_selfcheck(int n_radii, unsigned long long seed, unsigned long long* mismatches,
                             tc_stream_t stream) {
   return launch_gate_selfcheck(n_radii, seed, mismatches, as_stream(stream));
+}
+
+int tc_radar_gate_selfcheck_range(int n_radii, unsigned long long seed, float rad_lo, float rad_hi, int inclusive,
+                                  unsigned long long* mismatches, tc_stream_t stream) {
+  return launch_gate_selfcheck_range(n_radii, seed, rad_lo, rad_hi, inclusive, mismatches, as_stream(stream));
 }
 
 int tc_rowops_selfcheck(int n_blocks, unsigned long long seed, unsigned long long* mismatches, tc_stream_t stream) {
@@ -1200,6 +1208,7 @@ int tc_radar_attn_core_fwd(const float* qproj, float q_scale, const float* kv,
                            unsigned long long dropout_seed, int dropout_site, tc_stream_t stream) {
   TC_REQUIRE(attn_out != nullptr && hit_counts != nullptr, "radar_attn_core: NULL output");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core: dropout_p=%g", (double)dropout_p);
+  TC_TRY(check_radar_radii(radius_min, radius_max, "radar_attn_core"));
   RadarAttnArgs r = radar_attn_args(qproj, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads, pad_mult,
                                     radius_min, radius_max, attn_out, hit_counts, q_scale);
   r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, 1500u);
@@ -1214,6 +1223,7 @@ int tc_radar_attn_core_bwd(const float* qproj, float q_scale, const float* kv,
                            float dropout_p, unsigned long long dropout_seed, int dropout_site,
                            tc_stream_t stream) {
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core_bwd: dropout_p=%g", (double)dropout_p);
+  TC_TRY(check_radar_radii(radius_min, radius_max, "radar_attn_core_bwd"));
   RadarAttnArgs r = radar_attn_args(qproj, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads, pad_mult,
                                     radius_min, radius_max, const_cast<float*>(attn_out), nullptr);     // (q_scale: the launch's)
   r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, 1500u);

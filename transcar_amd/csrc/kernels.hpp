@@ -222,6 +222,11 @@ int launch_radar_compact(const float* ref_last, const float* box, int code, int 
                          float rmin, float rmax, int* flags, int* perm, hipStream_t s);
 
 int launch_gate_selfcheck(int n_radii, unsigned long long seed, unsigned long long* mismatches, hipStream_t s);
+int launch_gate_selfcheck_range(int n_radii, unsigned long long seed, float rad_lo, float rad_hi, int inclusive,
+                                unsigned long long* mismatches, hipStream_t s);
+// a gate's (radius_min, radius_max) as the C boundary accepts it (transcar_hip.h TC_RADAR_GATE_CIRCLE); what: the caller's
+// name, or with index >= 0 the array the pair is element `index` of
+int check_radar_radii(float rmin, float rmax, const char* what, int index = -1);
 int launch_rowops_selfcheck(int n_blocks, unsigned long long seed, unsigned long long* mismatches, hipStream_t s);   // chain.hip
 
 // ---- self_attn.hip ---------------------------------------------------------

@@ -145,10 +145,77 @@ int launch_gate_selfcheck(int n_radii, unsigned long long seed, unsigned long lo
   return check_launch("radar_gate_selfcheck");
 }
 
+// ---- the same over a radius range, for either comparison (tc_radar_gate_selfcheck_range) ------------
+// inclusive == 0: sqrtf(max(t, 1e-30)) < rad against sqrt_threshold; 1: not (... > rad) against sqrt_threshold_incl
+__global__ __launch_bounds__(256) void gate_selfcheck_range_kernel(int n_radii, unsigned long long seed, float rad_lo,
+                                                                   float rad_hi, int inclusive,
+                                                                   unsigned long long* mismatches) {
+  const int r = blockIdx.x;
+  if (r >= n_radii) return;
+  // radius r: the range's end points first, then pseudo-random ones between them
+  unsigned long long h = (seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(r + 1));
+  h ^= h >> 30; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 27; h *= 0x94D049BB133111EBull; h ^= h >> 31;
+  float rad = fminf(rad_lo + (rad_hi - rad_lo) * (float)(h >> 40) * (1.0f / 16777216.0f), rad_hi);
+  if (r == 0) rad = rad_lo;
+  if (r == 1) rad = rad_hi;
+  const float tstar = inclusive ? sqrt_threshold_incl(rad) : sqrt_threshold(rad);
+  const unsigned centre = __builtin_bit_cast(unsigned, rad * rad);
+  const float span = 1.0f + 2.25f * rad_hi * rad_hi;
+  unsigned long long bad = 0;
+  for (int i = threadIdx.x; i < 512 + 4096; i += 256) {
+    float t;
+    if (i < 512) t = __builtin_bit_cast(float, centre - 256u + (unsigned)i);
+    else {
+      unsigned long long g = h + 0xD1B54A32D192ED03ull * (unsigned long long)i;
+      g ^= g >> 29; g *= 0xBF58476D1CE4E5B9ull; g ^= g >> 32;
+      t = -1.0f + span * (float)(g >> 40) * (1.0f / 16777216.0f);      // both sides, and below the clamp
+    }
+    const float d = sqrtf(fmaxf(t, 1e-30f));
+    const bool ref = inclusive ? !(d > rad) : d < rad;
+    const bool fast = fmaxf(t, 1e-30f) < tstar;
+    bad += ref != fast;
+  }
+  if (bad) atomicAdd(mismatches, bad);
+}
+
+int launch_gate_selfcheck_range(int n_radii, unsigned long long seed, float rad_lo, float rad_hi, int inclusive,
+                                unsigned long long* mismatches, hipStream_t s) {
+  TC_REQUIRE(n_radii > 0 && mismatches != nullptr, "radar_gate_selfcheck_range: bad arguments");
+  TC_REQUIRE(rad_lo >= TC_RADAR_RADIUS_MIN && rad_lo <= rad_hi && rad_hi <= TC_RADAR_RADIUS_MAX,
+             "radar_gate_selfcheck_range: rad_lo=%g rad_hi=%g (%g <= rad_lo <= rad_hi <= %g)", (double)rad_lo, (double)rad_hi,
+             (double)TC_RADAR_RADIUS_MIN, (double)TC_RADAR_RADIUS_MAX);
+  TC_REQUIRE(inclusive == 0 || inclusive == 1, "radar_gate_selfcheck_range: inclusive=%d (0: dist < radius, 1: not dist > radius)",
+             inclusive);
+  hipLaunchKernelGGL(gate_selfcheck_range_kernel, dim3(n_radii), dim3(256), 0, s, n_radii, seed, rad_lo, rad_hi, inclusive,
+                     mismatches);
+  return check_launch("radar_gate_selfcheck_range");
+}
+
+// The (radius_min, radius_max) pair of a gate as the C boundary accepts it (transcar_hip.h, TC_RADAR_GATE_CIRCLE).  A zeroed
+// pair passes: hand-built structs that never run the radar part carry one.
+// index >= 0: the pair is what[index] (the name is formatted only for a refusal: every entry point checks every layer).
+int check_radar_radii(float rmin, float rmax, const char* what_, int index) {
+  const float floor_ = rmin >= 0.0f ? rmin : 0.0f;
+  if ((rmin >= 0.0f || rmin == TC_RADAR_GATE_CIRCLE) && rmax >= floor_ && rmax <= TC_RADAR_RADIUS_MAX) return 0;
+  char what[48];
+  if (index >= 0) snprintf(what, sizeof(what), "%s[%d]", what_, index);
+  else snprintf(what, sizeof(what), "%s", what_);
+  TC_REQUIRE(fabsf(rmin) <= 3.0e38f && fabsf(rmax) <= 3.0e38f,      // (a NaN fails the comparison too)
+             "%s: radius_min=%g radius_max=%g (a radius must be finite)", what, (double)rmin, (double)rmax);
+  TC_REQUIRE(rmin >= 0.0f || rmin == TC_RADAR_GATE_CIRCLE,
+             "%s: radius_min=%g (>= 0: the three-circle clamp; TC_RADAR_GATE_CIRCLE = %g: one circle of radius_max)", what,
+             (double)rmin, (double)TC_RADAR_GATE_CIRCLE);
+  TC_REQUIRE(rmax >= (rmin >= 0.0f ? rmin : 0.0f), "%s: radius_max=%g below radius_min=%g", what, (double)rmax,
+             (double)(rmin >= 0.0f ? rmin : 0.0f));
+  TC_REQUIRE(rmax <= TC_RADAR_RADIUS_MAX, "%s: radius_max=%g (at most %g m)", what, (double)rmax, (double)TC_RADAR_RADIUS_MAX);
+  return 0;
+}
+
 int launch_radar_compact(const float* ref_last, const float* box, int code, int cen_from_box,
                          const float* pc6_host, const float* tokens, int RI, int B, int Q, int T,
                          float rmin, float rmax, int* flags, int* perm, hipStream_t s) {
   TC_REQUIRE(B > 0 && Q > 0 && T > 0 && flags != nullptr && perm != nullptr, "radar_compact: bad arguments");
+  TC_TRY(check_radar_radii(rmin, rmax, "radar_compact"));
   CompactK p;
   p.ref_last = ref_last; p.box = box; p.tokens = tokens; p.code = code; p.cen_from_box = cen_from_box;
   p.RI = RI; p.B = B; p.Q = Q; p.T = T; p.rmin = rmin; p.rmax = rmax; p.flags = flags;

@@ -448,6 +448,24 @@ __device__ __forceinline__ float sqrt_threshold(float rad) {
   }
   return c;        // not reached for rad in the clamp range [0.5, 2]
 }
+// Its sibling for the single-circle gate (tc_radar_layer: radius_min == TC_RADAR_GATE_CIRCLE), whose comparison is
+// the inclusive  not (dist > rad):  the smallest float t with sqrtf(t) > rad, so that  max(t, 1e-30) < t*  <=>
+// sqrtf(max(t, 1e-30)) <= rad.  The same search from rad * rad: a correctly-rounded square root halves the relative
+// error of its argument, so the boundary lies within two floats of fl(rad * rad) in every binade -- the accepted
+// range [TC_RADAR_RADIUS_MIN, TC_RADAR_RADIUS_MAX] included (tc_radar_gate_selfcheck_range checks both searches there).
+__device__ __forceinline__ float sqrt_threshold_incl(float rad) {
+  float c = rad * rad;
+  for (int i = 0; i < 8 && sqrtf(c) > rad; ++i) c = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, c) - 1u);
+  for (int i = 0; i < 8; ++i) {
+    const float up = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, c) + 1u);
+    if (sqrtf(up) > rad) return up;
+    c = up;
+  }
+  return c;        // not reached for rad in the accepted range
+}
+// The gate kind of a (radius_min, radius_max) pair: a negative radius_min (TC_RADAR_GATE_CIRCLE) is the single circle
+// of fixed radius radius_max.  A launch argument, so the test is uniform over the grid.
+__device__ __forceinline__ bool gate_is_circle(float rmin) { return rmin < 0.0f; }
 // a * b + c with two roundings (torch: mul, then add).  HIP's __fmul_rn / __fadd_rn are the plain operators, and hipcc
 // contracts a product and a sum into one v_fma_f32 (its default is -ffp-contract=fast-honor-pragmas) unless the pragma
 // forbids it here.  The gate centre of fusion layer 1 is computed with it at every site -- tc_radar_reference_l1 (the
@@ -469,19 +487,24 @@ __device__ __forceinline__ float sqnorm2(float a, float b) {
 // DROP (training forward): dropout on the attention probabilities (nn.MultiheadAttention
 // dropout = 0.1, HEAD:129): the softmax denominator counts every hit token, the weighted sum only
 // the kept ones, scaled by 1 / (1 - p); mask index ((row * 8 + head) * tokens_ref + token).
-// gate geometry of one query, HEAD:553-567: three circles (centre, front, back) of one radius
+// gate geometry of one query, HEAD:553-567: three circles (centre, front, back) of one radius.
+// The single-circle gate (gate_is_circle) is the same geometry with a zero front / back offset -- three coincident
+// circles, so hit() stays one form for both kinds -- and the inclusive threshold; the kind is resolved here, once per row.
 struct GateGeom {
   float cx, cy, fx, fy, bx, by, cn, fn, bn, rad, tstar;
+  bool circle;
   __device__ __forceinline__ GateGeom(float cx_, float cy_, float b3, float b6, float b7, float rmin, float rmax) {
     const float len = expf(b3);
     const float rs = -b6, rc = -b7;
-    const float ox = __fmul_rn(__fmul_rn(len, 0.25f), rs), oy = __fmul_rn(__fmul_rn(len, 0.25f), rc);
+    circle = gate_is_circle(rmin);
+    const float ox = circle ? 0.0f : __fmul_rn(__fmul_rn(len, 0.25f), rs),
+                oy = circle ? 0.0f : __fmul_rn(__fmul_rn(len, 0.25f), rc);
     cx = cx_; cy = cy_;
     fx = __fadd_rn(cx, ox); fy = __fadd_rn(cy, oy);
     bx = __fsub_rn(cx, ox); by = __fsub_rn(cy, oy);
-    rad = fminf(fmaxf(len / 2.0f, rmin), rmax);
+    rad = circle ? rmax : fminf(fmaxf(len / 2.0f, rmin), rmax);
     cn = sqnorm2(cx, cy); fn = sqnorm2(fx, fy); bn = sqnorm2(bx, by);
-    tstar = sqrt_threshold(rad);
+    tstar = circle ? sqrt_threshold_incl(rad) : sqrt_threshold(rad);
   }
   // The expensive part of the constructor above (expf, the clamp, sqrt_threshold's square roots: ~300
   // instructions that every lane of every wave repeated per row) evaluated ONCE per row by one thread:
@@ -491,7 +514,12 @@ struct GateGeom {
     const float len = expf(b3);
     const float rs = -b6, rc = -b7;
     Pre p;
-    p.ox = __fmul_rn(__fmul_rn(len, 0.25f), rs); p.oy = __fmul_rn(__fmul_rn(len, 0.25f), rc);
+    if (gate_is_circle(rmin)) {      // one circle of fixed radius: no offset, the inclusive threshold
+      p.ox = 0.0f; p.oy = 0.0f;
+      p.tstar = sqrt_threshold_incl(rmax);
+      return p;
+    }
+    p.ox =__fmul_rn(__fmul_rn(len, 0.25f), rs); p.oy = __fmul_rn(__fmul_rn(len, 0.25f), rc);
     p.tstar = sqrt_threshold(fminf(fmaxf(len / 2.0f, rmin), rmax));
     return p;
   }
@@ -499,7 +527,7 @@ struct GateGeom {
     cx = cx_; cy = cy_;
     fx = __fadd_rn(cx, p.ox); fy = __fadd_rn(cy, p.oy);
     bx = __fsub_rn(cx, p.ox); by = __fsub_rn(cy, p.oy);
-    rad = 0.0f;                    // hit() does not use it
+    rad = 0.0f; circle = false;    // hit() uses neither
     cn = sqnorm2(cx, cy); fn = sqnorm2(fx, fy); bn = sqnorm2(bx, by);
     tstar = p.tstar;
   }
@@ -511,6 +539,7 @@ struct GateGeom {
   }
   // the literal form (a square root per circle): the device check of the equivalence, tests only
   __device__ __forceinline__ bool hit_sqrt(float y0, float y1, float yn) const {
+    if (circle) return !(cdist_mm(cx, cy, cn, y0, y1, yn) > rad);
     return (cdist_mm(cx, cy, cn, y0, y1, yn) < rad) || (cdist_mm(fx, fy, fn, y0, y1, yn) < rad) ||
            (cdist_mm(bx, by, bn, y0, y1, yn) < rad);
   }
@@ -519,6 +548,7 @@ struct GateGeom {
   __device__ __forceinline__ bool hit_approx(float y0, float y1, float yn) const {
     const float r2 = rad * rad;
     const float dc = fmaf(-2.0f * cx, y0, fmaf(-2.0f * cy, y1, cn + yn));
+    if (circle) return dc <= r2;   // (uniform over the launch) one circle, not three coincident ones
     const float df = fmaf(-2.0f * fx, y0, fmaf(-2.0f * fy, y1, fn + yn));
     const float db = fmaf(-2.0f * bx, y0, fmaf(-2.0f * by, y1, bn + yn));
     return fminf(dc, fminf(df, db)) < r2;
@@ -642,7 +672,8 @@ __device__ __forceinline__ float4 radar_attn_bwd_row(float cx, float cy, float b
   const float ox = __fmul_rn(__fmul_rn(len, 0.25f), rs), oy = __fmul_rn(__fmul_rn(len, 0.25f), rc);
   const float fx = __fadd_rn(cx, ox), fy = __fadd_rn(cy, oy);
   const float bxx = __fsub_rn(cx, ox), byy = __fsub_rn(cy, oy);
-  const float rad = fminf(fmaxf(len / 2.0f, rmin), rmax);
+  const bool circle = gate_is_circle(rmin);      // once per row: the single circle's literal form is not (d > rad)
+  const float rad = circle ? rmax : fminf(fmaxf(len / 2.0f, rmin), rmax);
   const float cn = sqnorm2(cx, cy), fn = sqnorm2(fx, fy), bn = sqnorm2(bxx, byy);
   const float D = head_sum8(dO.x * o4.x + dO.y * o4.y + dO.z * o4.z + dO.w * o4.w);
   float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -656,8 +687,11 @@ __device__ __forceinline__ float4 radar_attn_bwd_row(float cx, float cy, float b
         const float* y = rxy + (size_t)t * ld_xy;
         const float y0 = y[0], y1 = y[1];
         const float yn = sqnorm2(y0, y1);
-        hit = (cdist_mm(cx, cy, cn, y0, y1, yn) < rad) || (cdist_mm(fx, fy, fn, y0, y1, yn) < rad) ||
-              (cdist_mm(bxx, byy, bn, y0, y1, yn) < rad);
+        if (circle)
+          hit = !(cdist_mm(cx, cy, cn, y0, y1, yn) > rad);
+        else
+          hit = (cdist_mm(cx, cy, cn, y0, y1, yn) < rad) || (cdist_mm(fx, fy, fn, y0, y1, yn) < rad) ||
+                (cdist_mm(bxx, byy, bn, y0, y1, yn) < rad);
       }
       unsigned long long mask = __ballot(hit);
       while (mask) {

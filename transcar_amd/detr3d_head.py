@@ -38,7 +38,7 @@ from .bbox_util import normalize_bbox
 from .registry import (BBOX_ASSIGNERS, HEADS, build_bbox_coder,
                        build_transformer)
 
-RADAR_RADII = ((1.0, 2.0), (1.0, 2.0), (0.5, 1.0))     # HEAD:567, 635, 693
+RADAR_RADII = L.RADAR_RADII                            # HEAD:567, 635, 693: the default of Detr3DHead(radar_gate=)
 OUTPUTS = ('fusion', 'camera', 'all')                  # Detr3DHead.outputs
 
 
@@ -179,12 +179,18 @@ class Detr3DHead(BaseModule):
                  positional_encoding=None, loss_cls=None, loss_bbox=None,
                  loss_iou=None, train_cfg=None, test_cfg=None, init_cfg=None,
                  with_box_refine=False, as_two_stage=False, bbox_coder=None,
-                 num_cls_fcs=2, code_weights=None, outputs='fusion', num_fusion_layers=3, **kwargs):
+                 num_cls_fcs=2, code_weights=None, outputs='fusion', num_fusion_layers=3, radar_gate=None,
+                 **kwargs):
         super().__init__(init_cfg)
         #: depth N of the radar fusion stack, 1 .. 3 (the reference builds 3): only the first N sets of rf_* / final_*
         #: modules exist, every output has N fusion levels.  Level k reads layers <= k only, so an N-layer head with the
         #: first N layers' weights computes levels [0:N] of the three-layer head
         self.num_fusion_layers = L.check_num_fusion_layers(num_fusion_layers)
+        #: the distance gate of the fusion layers, normalised (_lib.check_radar_gate): dict(type='three_circle', radii=
+        #: ((rmin, rmax), ...)) -- the reference head's gate, RADAR_RADII by default -- or dict(type='circle', radii=(R, ...)),
+        #: the single circle of the paper's radius ablation (a token attended iff not dist > R).  Configuration, like
+        #: pc_range: it adds no parameter, so the weights of either kind of head load into the other unchanged
+        self.radar_gate = L.check_radar_gate(radar_gate, self.num_fusion_layers)
         if outputs not in OUTPUTS:
             raise ValueError("Detr3DHead: outputs=%r (one of 'fusion', 'camera', 'all')" % (outputs,))
         #: what ``forward`` returns as all_cls_scores / all_bbox_preds: 'fusion' the radar fusion levels (three by default; the
@@ -450,8 +456,9 @@ class Detr3DHead(BaseModule):
             else:
                 d.reg = L.tc_reg_branch()
         radar_table(self, w, ops._p)
-        for r in range(w.num_radar_layers):
-            w.radar[r].radius_min, w.radar[r].radius_max = RADAR_RADII[r]
+        # (radar_gate is a public attribute: checked again, as num_fusion_layers is)
+        for r, pair in enumerate(L.radar_gate_pairs(L.check_radar_gate(self.radar_gate, w.num_radar_layers))):
+            w.radar[r].radius_min, w.radar[r].radius_max = pair
         return w
 
     def decoder_heads_struct(self):
@@ -883,6 +890,7 @@ class Detr3DHead(BaseModule):
         mem = pos + f
 
         all_cls, all_box = [], []
+        gate_pairs = L.radar_gate_pairs(L.check_radar_gate(self.radar_gate, self.num_fusion_layers))
         for r in range(self.num_fusion_layers):
             m = fusion_modules(self, r)
             attn = m.attn
@@ -893,7 +901,7 @@ class Detr3DHead(BaseModule):
             qp = A.linear(qf, wq, bq)
             kv = A.linear(mem, wkv, bkv)
             centre, ld_c = (cxy, 2) if r == 0 else (prev_box, self.code_size)
-            rmin, rmax = RADAR_RADII[r]
+            rmin, rmax = gate_pairs[r]
             ao, hits = A.radar_attn_core(qp, kv, centre, ld_c, prev_box, tokens,
                                          pad_mult, rmin, rmax,
                                          heads=attn.num_heads,
