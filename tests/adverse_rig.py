@@ -31,8 +31,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from head_variant_rig import trainable
 from oracle import transcar_oracle as O
-from test_training import trainable
 from transcar_amd import configs, radar as R, synth
 
 PCR = configs.point_cloud_range
@@ -371,7 +371,7 @@ def tie_delta(x32, x64, real_tokens):
 
 
 def trainable_sd(sd):
-    """A copy of the state dict whose trainable entries (test_training.trainable) are autograd leaves."""
+    """A copy of the state dict whose trainable entries (head_variant_rig.trainable) are autograd leaves."""
     return {k: (v.detach().clone().requires_grad_(True) if trainable(k) and v.is_floating_point() else v)
             for k, v in sd.items()}
 

@@ -11,8 +11,8 @@ Run only in the authoring container:   python tests/golden/make_golden_radar_gat
   g8_train_grads_gate_circle.npz      make_golden.write_g8's layout
 
 The radar seed is chosen as make_golden_variants.gate_margins chooses one: seeds 2 .. 39 are scanned on the CPU oracle
-under the circle gate (tests/radar_gate_rig.py) and the one whose closest gate decision is farthest from its radius is
-kept; that margin is stored."""
+under the circle gate (head_variant_rig.gate_margin) and the one whose closest gate decision is farthest from its radius
+is kept; that margin is stored."""
 import os
 import sys
 
@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import make_golden as MG                                 # noqa: E402
-import radar_gate_rig as G                               # noqa: E402
+import head_variant_rig as R                             # noqa: E402
 from oracle import mmcv_bricks as B                      # noqa: E402
 from oracle import ref_harness as RH                     # noqa: E402
 from oracle import transcar_oracle as O                  # noqa: E402
@@ -59,7 +59,7 @@ def choose_seed(centres):
     best = None
     for seed in SEEDS:
         frame = synth.make_radar_frame(seed=seed, n_per_radar=51, centres=centres)
-        m = G.gate_margin(G.CIRCLE, sd, feats, frame)
+        m = R.gate_margin(sd, feats, frame, radar_gate=R.CIRCLE)
         print('seed %d: margin %.3g m' % (seed, m))
         if best is None or m > best[1]:
             best = (seed, m)
@@ -81,7 +81,7 @@ def main():
     MG.save('g5_head_tiny_gate_circle.npz', all_cls_scores=outs['all_cls_scores'].numpy(),
             all_bbox_preds=outs['all_bbox_preds'].numpy(), inter_refs=tcap['inter_refs'].numpy(),
             Lq=np.array([cap['Lq%d' % i] for i in range(3)]), hit_counts0=hits[0], hit_counts1=hits[1], hit_counts2=hits[2],
-            fill_in=fill_in, radar_seed=seed, gate_margin=margin, radii=np.array(G.CIRCLE['radii']))
+            fill_in=fill_in, radar_seed=seed, gate_margin=margin, radii=np.array(R.CIRCLE['radii']))
     print('Lq', [cap['Lq%d' % i] for i in range(3)])
     head = backup_head(mod, train=True)
     MG.freeze_like_train_py(head)

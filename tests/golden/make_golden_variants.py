@@ -89,6 +89,7 @@ from make_golden import g2_cross_atten, g345_head, g8_train_grads, ref_head     
 from oracle import transcar_oracle as O                  # noqa: E402
 from transcar_amd import configs, synth                  # noqa: E402
 
+import head_variant_rig as R                             # noqa: E402
 from head_variant_rig import GEOM                        # noqa: E402
 
 TINY, RES101 = configs.LEVEL_SHAPES['tiny'], configs.LEVEL_SHAPES['res101']
@@ -200,44 +201,25 @@ def geometry(ref):
     decode_geometry(ref)
 
 
-def gate_margins(seeds, g5_name=None, geometry=None, **sd_kw):
-    """Per radar seed: min over the three fusion layers, the queries, the three circles and the tokens of
-    |distance - radius| (metres), from the oracle at NC classes on G5-C23's centres -- or on fixture g5_name's, with
-    the state dict of sd_kw at the geometry."""
+def gate_margins(seeds, g5_name=None, **variant):
+    """Per radar seed: head_variant_rig.gate_margin (metres) of the oracle at NC classes on G5-C23's centres -- or on
+    fixture g5_name's, of the oracle of `variant`."""
     if g5_name is None:
-        g5_name, sd_kw = 'g5_head_tiny_c%d.npz' % NC, dict(num_classes=NC)
+        g5_name, variant = 'g5_head_tiny_c%d.npz' % NC, dict(num_classes=NC)
     g5 = np.load(os.path.join(HERE, g5_name))
-    sd = O.to_torch_sd(synth.make_state_dict(seed=3, **sd_kw))
-    feats = [torch.from_numpy(f) for f in synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)]
-    l2i, img_shape = MG.cameras(geometry)
-    l2i = torch.from_numpy(l2i).float()[None]
-    pc_range = configs.point_cloud_range if geometry is None else list(geometry.pc_range)
-    seen = []
-
-    def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
-        length = length_log.exp()
-        radii = torch.clamp((length / 2.0).reshape(-1, 1), min=rmin, max=rmax)
-        live = radar_xy[0, :, 0] != 500.0                  # the padding tokens sit far outside every circle
-        for sign in (0.0, 0.25, -0.25):
-            c = centre_xy.clone()
-            c[..., 0] = c[..., 0] + sign * length * -rot_sin
-            c[..., 1] = c[..., 1] + sign * length * -rot_cos
-            seen.append(float((torch.cdist(c, radar_xy, p=2.0)[0][:, live] - radii).abs().min()))
-
+    sd = O.to_torch_sd(synth.make_state_dict(seed=3, **R.state_dict_kw(**variant)))
+    feats = synth.make_feats('tiny', seed=1, smooth=MG.SMOOTH)
     out = {}
     for seed in seeds:
-        del seen[:]
         frame = synth.make_radar_frame(seed=seed, n_per_radar=51, centres=g5['radar_centres'])
-        O.head_forward(sd, feats, l2i, img_shape[:2], O.build_radar_features(frame), pc_range, gate_probe=probe)
-        assert len(seen) == 9
-        out[seed] = min(seen)
+        out[seed] = R.gate_margin(sd, feats, frame, **variant)
         print('radar seed %2d: closest gate decision %.2e m from its radius' % (seed, out[seed]))
     return out
 
 
 def main():
     if 'seeds' in sys.argv[1:]:
-        m = gate_margins(range(2, 40), 'g5_head_tiny_geom.npz', GEOM) if 'geometry' in sys.argv[1:] \
+        m = gate_margins(range(2, 40), 'g5_head_tiny_geom.npz', geometry=GEOM) if 'geometry' in sys.argv[1:] \
             else gate_margins(range(2, 40))
         best = max(m, key=m.get)
         print('largest: seed %d, %.2e m' % (best, m[best]))

@@ -1,13 +1,14 @@
 """The rig the tests of the head's variants share (num_points > 1, num_levels < 4, with_box_refine=False, num_heads 4 /
-16, num_classes up to 32, num_query, the decoder levels' own outputs and decoder layer 0's fold): heads and frames, the
-CPU oracle's forward, and the checks every variant repeats -- against the oracle, against the reference's fixtures, the
-train-mode decoder with read-back dropout masks, a training iteration against the reference's gradients, the plugin
-graphs, FramePipeline and a frame inside a nine-frame launch.
+16, num_classes up to 32, num_query, num_fusion_layers 1 / 2, radar_gate, the decoder levels' own outputs and decoder
+layer 0's fold): heads and frames, the CPU oracle's forward and training iteration, and the checks every variant repeats
+-- against the oracle, against the reference's fixtures, the train-mode decoder with read-back dropout masks, a training
+iteration against the reference's gradients, the plugin graphs, FramePipeline and a frame inside a nine-frame launch.
 
 A variant is keyword arguments named as CONFIGS' keys; what a key reaches differs (variant_kw, state_dict_kw,
-oracle_kw): the state dict does not depend on num_heads, and the oracle reads num_levels, num_points, num_classes and
-num_query off the state dict and the maps.  One more key, `geometry`, is a Geometry: the point-cloud range of the coder,
-the attentions and the assigner, the coder's post_center_range, the image size and the cameras' intrinsics.  It reaches
+oracle_kw, oracle_forward): the state dict does not depend on num_heads or on radar_gate (the gate adds no parameter),
+the oracle reads num_levels, num_points, num_classes and num_query off the state dict and the maps, and its decoder
+reads neither the fusion stack's depth nor its gate.  One more key, `geometry`, is a Geometry: the point-cloud range of
+the coder, the attentions and the assigner, the coder's post_center_range, the image size and the cameras' intrinsics.  It reaches
 the head's config, the oracle's pc_range / img_hw arguments, lidar2img and img_metas; the state dict does not depend on
 it.  Left out, it is DEFAULT, the TransCAR configs' -- whose x and y intervals are equal and centred on 0, so that an
 x / y swap, `2 * pc[3]` for `pc[3] - pc[0]`, `-pc[3]` for `pc[0]` or a folded 51.2 compute what correct code computes.
@@ -68,8 +69,14 @@ REFS_TOL = 5e-5         # inter_references against the oracle and the reference
 MAX_GATE_ROWS = 6       # rows whose radar gate decisions (hit counts) may differ: the gate is discontinuous
 BOX_TOL = 5e-5          # metres: fp32 spacing at 50 m is 3.8e-6, the reference and the oracle order add / sigmoid / scale differently
 # the TransCAR configs' variant
-CONFIGS = dict(num_levels=4, num_points=1, with_box_refine=True, num_heads=8, num_classes=10, num_query=900)
+CONFIGS = dict(num_levels=4, num_points=1, with_box_refine=True, num_heads=8, num_classes=10, num_query=900,
+               num_fusion_layers=3, radar_gate=None)
 HEADS = (4, 16)         # num_heads beside the configs' 8: head dimension 64 and 16
+DEPTHS = (1, 2)         # num_fusion_layers beside the configs' 3
+CIRCLE = dict(type='circle', radii=[2.0, 2.0, 1.0])                 # the single circle of the paper: 2 / 2 / 1 m
+WIDE3 = dict(type='three_circle', radii=[(0.75, 3.0), (0.5, 1.5), (0.25, 0.75)])
+# the reference's single-circle fixtures (tests/golden/make_golden_radar_gate.py), on g5_frame(<the seed they store>)
+G5_CIRCLE, G8_CIRCLE = 'g5_head_tiny_gate_circle.npz', 'g8_train_grads_gate_circle.npz'
 
 
 @pytest.fixture(autouse=True)
@@ -114,19 +121,26 @@ def variant_kw(**variant):
 
 
 def state_dict_kw(**variant):
-    """variant_kw for synth.make_state_dict: the state dict does not depend on the head count or on the geometry."""
-    return {k: v for k, v in variant_kw(**variant).items() if k not in ('num_heads', 'pc_range', 'post_center_range')}
+    """variant_kw for synth.make_state_dict: the state dict does not depend on the head count, the gate or the geometry."""
+    return {k: v for k, v in variant_kw(**variant).items()
+            if k not in ('num_heads', 'radar_gate', 'pc_range', 'post_center_range')}
 
 
 def oracle_kw(**variant):
-    """What the oracle cannot read off the state dict and the maps (their defaults spelled out)."""
+    """What the oracle's decoder cannot read off the state dict and the maps (their defaults spelled out)."""
     variant_kw(**variant)
     return {k: variant.get(k, CONFIGS[k]) for k in ('with_box_refine', 'num_heads')}
 
 
 def variant_key(**variant):
+    """Hashable, for the caches; a gate enters normalised (the two spellings of one gate are one entry; None is left out)."""
+    from transcar_amd._lib import check_radar_gate
     geom = geometry_of(variant)
-    return tuple(sorted(variant_kw(**variant).items())) + (() if geom == DEFAULT else (('geometry', geom),))
+    kw = variant_kw(**variant)
+    if 'radar_gate' in kw:
+        gate = check_radar_gate(kw['radar_gate'], kw.get('num_fusion_layers', CONFIGS['num_fusion_layers']))
+        kw['radar_gate'] = (gate['type'], gate['radii'])
+    return tuple(sorted(kw.items())) + (() if geom == DEFAULT else (('geometry', geom),))
 
 
 def make_head(T, *, seed=3, shared_branches=False, **variant):
@@ -138,6 +152,13 @@ def make_head(T, *, seed=3, shared_branches=False, **variant):
     sd_np = synth.make_state_dict(seed=seed, **sd_kw)
     h = T.build_head(configs.head_cfg(**variant_kw(**variant)))
     h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
+    check_head(h, **variant)
+    return h.to(dev()).eval(), O.to_torch_sd(sd_np)
+
+
+def check_head(h, **variant):
+    """The head carries the variant where the kernels read it."""
+    from transcar_amd._lib import check_radar_gate
     want = dict(CONFIGS, **variant)
     geom = geometry_of(variant)
     assert tuple(h.pc_range) == geom.pc_range, h.pc_range
@@ -145,7 +166,8 @@ def make_head(T, *, seed=3, shared_branches=False, **variant):
     assert tuple(h.bbox_coder.post_center_range) == geom.post_center_range
     assert h.weights_struct().num_heads == want['num_heads']
     assert h.weights_struct().num_classes == h.bbox_coder.num_classes == want['num_classes']
-    return h.to(dev()).eval(), O.to_torch_sd(sd_np)
+    assert h.num_fusion_layers == h.weights_struct().num_radar_layers == want['num_fusion_layers']
+    assert h.radar_gate == check_radar_gate(want['radar_gate'], want['num_fusion_layers'])
 
 
 _HEADS = {}
@@ -164,8 +186,21 @@ def train_head(**variant):
     cfg = configs.head_cfg(**variant_kw(**variant))
     cfg.setdefault('train_cfg', configs.train_cfg_pts)        # (head_cfg(pc_range=...) brings its own)
     h = T_.build_head(cfg)
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(3, **state_dict_kw(**variant)).items()})
+    h.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(3, **state_dict_kw(**variant)).items()},
+                      strict=True)
+    check_head(h, **variant)
     return h.to(dev()).freeze_decoder().set_dropout(0.0)
+
+
+def g5_frame(radar_seed=2):
+    """G5's tiny rig: (feats_np, radar frame of `radar_seed` near the centres tests/golden/g5_head_tiny.npz stores)."""
+    feats = synth.make_feats('tiny', seed=1, smooth=SMOOTH)
+    return feats, synth.make_radar_frame(seed=radar_seed, n_per_radar=51, centres=gold('g5_head_tiny.npz')['radar_centres'])
+
+
+def empty_frame():
+    """A radar frame without a single return: every token is padding, no query has a hit in any layer."""
+    return synth.make_radar_frame(seed=5, n_per_radar=[0, 0, 0, 0, 0])
 
 
 def g8_frame(g5_name, shapes='tiny', radar_seed=2, num_classes=10, centres=None, geometry=DEFAULT):
@@ -178,7 +213,9 @@ def g8_frame(g5_name, shapes='tiny', radar_seed=2, num_classes=10, centres=None,
                                    centres=gold(g5_name)['radar_centres'] if centres is None else centres)
     boxes, labels = synth.make_gt(seed=7, n=24, num_classes=num_classes)
     assert labels.max() > 15 or num_classes <= 16
-    f = dict(feats_np=feats_np, l2i_np=l2i, frame=frame, boxes=boxes, labels=labels)
+    key = (g5_name, shapes if isinstance(shapes, str) else tuple(shapes), radar_seed, num_classes,
+           None if centres is None else np.asarray(centres).tobytes(), geometry)
+    f = dict(feats_np=feats_np, l2i_np=l2i, frame=frame, boxes=boxes, labels=labels, key=key)
     if torch.cuda.is_available():
         metas = geometry.metas(1, l2i=l2i)
         metas[0]['radar'] = frame
@@ -191,19 +228,50 @@ def g8_frame(g5_name, shapes='tiny', radar_seed=2, num_classes=10, centres=None,
 _ORACLE = {}
 
 
+def oracle_forward(sd, feats_np, frame, variant, **kw):
+    """O.head_forward of the variant (its geometry, depth, gate and oracle_kw) on one frame; kw: head_forward's other
+    arguments."""
+    geom = geometry_of(variant)
+    want = dict(CONFIGS, **variant)
+    l2i = torch.from_numpy(geom.lidar2img()).float()[None]
+    return O.head_forward(sd, [torch.as_tensor(f) for f in feats_np], l2i, geom.hw, O.build_radar_features(frame),
+                          list(geom.pc_range), num_fusion_layers=want['num_fusion_layers'], radar_gate=want['radar_gate'],
+                          **oracle_kw(**variant), **kw)
+
+
 def oracle_head(sd, feats_np, frame, key=None, **variant):
     """The oracle's head_forward of the variant with its debug dict.  key: keep the result under it and the variant (one
     forward for the parametrised cases that share weights, maps and radar frame)."""
     key = None if key is None else (key, variant_key(**variant))
     if key is None or key not in _ORACLE:
-        geom = geometry_of(variant)
-        l2i = torch.from_numpy(geom.lidar2img()).float()[None]
-        res = O.head_forward(sd, [torch.from_numpy(f) for f in feats_np], l2i, geom.hw, O.build_radar_features(frame),
-                             list(geom.pc_range), return_debug=True, **oracle_kw(**variant))
+        res = oracle_forward(sd, feats_np, frame, variant, return_debug=True)
         if key is None:
             return res
         _ORACLE[key] = res
     return _ORACLE[key]
+
+
+def gate_margin(sd, feats_np, frame, **variant):
+    """The distance (m) between the frame's closest gate decision and its radius: the minimum over the variant's fusion
+    layers, the queries, the gate's circles and the radar tokens of |distance - radius|, measured on the oracle through
+    head_forward's gate_probe.  The padding tokens are left out (they sit far outside every circle)."""
+    from transcar_amd._lib import TC_RADAR_GATE_CIRCLE
+    margins = []
+
+    def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
+        centres, radii = [centre_xy], rmax
+        if rmin != TC_RADAR_GATE_CIRCLE:             # O.circle_mask's front and rear circles and its clamped radius
+            length = length_log.exp()
+            off = torch.stack((length * 0.25 * -rot_sin, length * 0.25 * -rot_cos), -1)
+            centres += [centre_xy + off, centre_xy - off]
+            radii = torch.clamp((length / 2.0).reshape(-1, 1), min=rmin, max=rmax)
+        live = radar_xy[0, :, 0] != O.PAD_VALUE
+        margins.append(min(float((torch.cdist(c, radar_xy, p=2.0)[0][:, live] - radii).abs().min()) for c in centres))
+
+    with torch.no_grad():
+        oracle_forward(sd, feats_np, frame, variant, gate_probe=probe)
+    assert len(margins) == dict(CONFIGS, **variant)['num_fusion_layers']
+    return min(margins)
 
 
 _TRACE, _OUT = {}, {}
@@ -284,8 +352,7 @@ def oracle_fp64_deviation(sd, feats_np, frame, want, dbg, **variant):
                             l2i.double(), geom.hw, **oracle_kw(**variant))
     hs_dev = (dbg['hs'].double() - trace64[0].permute(0, 2, 1, 3)).abs().amax(dim=(0, 1, 3))
     trace = tuple(t.float() if torch.is_tensor(t) else t for t in trace64)
-    outs64 = O.head_forward(sd, feats, l2i, geom.hw, O.build_radar_features(frame), list(geom.pc_range), decoder_trace=trace,
-                            **oracle_kw(**variant))
+    outs64 = oracle_forward(sd, feats, frame, variant, decoder_trace=trace)
     out_dev = torch.stack([(want[k] - outs64[k]).abs().amax(dim=(0, 1, 3)) for k in ('all_cls_scores', 'all_bbox_preds')]).amax(0)
     return hs_dev.numpy(), out_dev.numpy()
 
@@ -322,7 +389,9 @@ def check_against_oracle(outs, want, dbg, hs_tol=E2E_TOL, refs_initial=False, ou
 
 def check_against_fixture(outs, want, dbg, fixture, tie_rule=False, refs_initial=False):
     """A free-running head's outputs against the reference's (a G5 fixture) on the rows whose radar gate decisions
-    agree with the oracle's AND the reference's, and against the oracle on the same rows.
+    agree with the oracle's AND the reference's, and against the oracle on the same rows.  The head may have fewer fusion
+    layers than the oracle's run and the fixture: its N levels are held to their levels [:N] (the layers are causally
+    ordered).
 
     tie_rule: a radar gate decision of the rig can sit within 1e-4 m of its radius (G5-L2: query 880, 2.1e-4 m in fusion
     layer 3): where the oracle on this machine and the reference took it differently, the stored hit counts cannot say
@@ -333,28 +402,32 @@ def check_against_fixture(outs, want, dbg, fixture, tie_rule=False, refs_initial
     if refs_initial:
         refs_are_initial(aux)
     np.testing.assert_allclose(_np(aux['inter_references']), fixture['inter_refs'], atol=REFS_TOL, rtol=0)
-    # the fixture stores the hit counts of the selected rows; rebuilt to [3, Q] as test_head_end_to_end does
-    want_hits = np.stack([_np(h) for h in dbg['hit_counts']])
+    levels = outs['all_cls_scores'].shape[0]
+    # the fixture stores the hit counts of the selected rows; rebuilt to [levels, Q] as test_head_end_to_end does
+    want_hits = np.stack([_np(h) for h in dbg['hit_counts']])[:levels]
     gold_hits = np.zeros_like(want_hits)
-    for i in range(3):
+    for i in range(levels):
         rows = np.where(want_hits[i] > 0)[0]
         gold_hits[i] = want_hits[i]
         if len(rows) == int(fixture['Lq'][i]):
             gold_hits[i] = 0
             gold_hits[i, rows] = fixture['hit_counts%d' % i]
     hits = _np(aux['radar_hit_counts'][:, 0])
+    assert hits.shape == want_hits.shape, (hits.shape, want_hits.shape)
     agree = np.all(hits == want_hits, axis=0) & np.all(hits == gold_hits, axis=0)
     assert int((~agree).sum()) <= MAX_GATE_ROWS
+    cut = {k: (_np(want[k][:levels, 0]), fixture[k][:levels, 0]) for k in ('all_cls_scores', 'all_bbox_preds')}
     tie = np.zeros(agree.shape, bool)
     if tie_rule:
-        for k in ('all_cls_scores', 'all_bbox_preds'):
-            tie |= np.abs(_np(want[k][:, 0]) - fixture[k][:, 0]).max(axis=(0, 2)) > 1e-2
+        for oracle, reference in cut.values():
+            tie |= np.abs(oracle - reference).max(axis=(0, 2)) > 1e-2
         assert int(tie.sum()) <= 2, np.where(tie)[0].tolist()
-    for k in ('all_cls_scores', 'all_bbox_preds'):
+    for k, (oracle, reference) in cut.items():
         got = _np(outs[k][:, 0])
-        assert_all_but_two_queries(got[:, agree & ~tie], fixture[k][:, 0][:, agree & ~tie], E2E_TOL, k + ' vs reference')
+        assert got.shape == oracle.shape == reference.shape, (k, got.shape, oracle.shape, reference.shape)
+        assert_all_but_two_queries(got[:, agree & ~tie], reference[:, agree & ~tie], E2E_TOL, k + ' vs reference')
         # and the oracle, which tests/test_*_golden.py hold to the same fixture
-        assert_all_but_two_queries(got[:, agree], _np(want[k][:, 0])[:, agree], E2E_TOL, k + ' vs oracle')
+        assert_all_but_two_queries(got[:, agree], oracle[:, agree], E2E_TOL, k + ' vs oracle')
 
 
 # ---- dropout masks as the kernels draw them ------------------------------------------------------------------------------
@@ -417,9 +490,32 @@ def check_train_mode_decoder(frame, rows, matrix, refs_atol=2e-4, **variant):
     np.testing.assert_allclose(hs.cpu().numpy()[:, 0], want_hs[:, :, 0].numpy(), atol=2e-3, rtol=0)
 
 
+# ---- a training iteration: the reference's gradient fixtures (G8), the oracle's autograd, the trainer -------------------------
+FROZEN = ('transformer.', 'cls_branches.', 'reg_branches.', 'query_embedding.', 'code_weights')
+
+
+def trainable(name):
+    """tools/train.py:245-252 freezes the DETR3D part of the head."""
+    return not name.startswith(FROZEN)
+
+
+def g8_name(tag='tiny'):
+    return 'g8_train_grads.npz' if tag == 'tiny' else 'g8_train_grads_%s.npz' % tag
+
+
+def g8_inputs(golden_dir, tag='tiny'):
+    """tag: 'tiny' FPN shapes, or 'res101' = the ResNet-101 shapes of BASELINE.json configs[2]"""
+    g5 = np.load(os.path.join(golden_dir, 'g5_head_%s.npz' % tag))
+    feats = synth.make_feats(tag, seed=1, smooth=(4, 6))
+    l2i = synth.make_lidar2img()
+    frame = synth.make_radar_frame(seed=2, n_per_radar=51, centres=g5['radar_centres'])
+    boxes, labels = synth.make_gt(seed=7, n=24)
+    return feats, l2i, frame, boxes, labels
+
+
 class GradStats(dict):
     """Gradients {name: tensor or None} in the layout of a G8 fixture (make_golden.write_g8): the reference side of
-    test_training.check_grads_against_g8 where no fixture exists."""
+    check_grads_against_g8 where no fixture exists."""
     def __init__(self, grads):
         super().__init__()
         for k, g in grads.items():
@@ -436,23 +532,89 @@ class GradStats(dict):
         return list(self)
 
 
-def trainer_iteration(frame, **kw):
-    """One FusionTrainer.step_fused_nhwc(update=False) (frozen decoder -> radar stack -> loss -> backward) of a fresh
-    head.  frame: g8_frame(...); kw: the variant, and what is no variant key goes to FusionTrainer.
-    -> (losses {name: float}, {name: gradient or None} of the trainable parameters)"""
-    from test_training import trainable
+def check_grads_against_g8(grads, g8, rtol, what, expected=98):
+    """grads {state_dict key: tensor or None} against a G8 fixture (or GradStats): every parameter of `grads` has an entry
+    in the fixture -- its gradient's [sum, sum|.|, l2] and first 16 values, or `__none` (the reference's forward never
+    uses it: no gradient, or a zero one) -- the fixture has no entry beyond them, and `expected` of them carry a
+    gradient (the three-layer head: 98; N fusion layers: the encoders' 14 + 28 N)."""
+    stats = {k[:-len('__stats')] for k in g8.files if k.endswith('__stats')}
+    nones = {k[:-len('__none')] for k in g8.files if k.endswith('__none')}
+    assert len(stats) == expected, (what, len(stats), expected)
+    keys = {k.replace('.', '__') for k in grads}
+    assert keys == stats | nones, (what, sorted(keys ^ (stats | nones)))
+    checked = 0
+    for k, g in grads.items():
+        key = k.replace('.', '__')
+        if key in nones:
+            assert g is None or float(g.abs().max()) == 0.0, k
+            continue
+        assert g is not None, (what, k)
+        ref = g8[key + '__stats']
+        gd = g.detach().double().flatten().cpu()
+        got = np.array([gd.sum(), gd.abs().sum(), gd.norm()])
+        scale = ref[1]                      # sum |g|: the natural magnitude for all three
+        assert abs(got[1] - ref[1]) <= rtol * scale, (what, k, got, ref)
+        assert abs(got[2] - ref[2]) <= rtol * max(ref[2], 1e-12), (what, k, got, ref)
+        assert abs(got[0] - ref[0]) <= rtol * scale, (what, k, got, ref)
+        head = g8[key + '__head']
+        tol = rtol * max(np.abs(head).max(), ref[2] / np.sqrt(gd.numel()))
+        assert np.abs(gd[:16].float().numpy() - head).max() <= 4 * tol, (what, k)
+        checked += 1
+    assert checked == expected, (what, checked, expected)
+    return checked
+
+
+_FORWARD, _TRAINING = {}, {}
+
+
+def oracle_training(host, levels=None, **variant):
+    """One training iteration of the oracle on the host side of a g8_frame: the variant's seed-3 weights with the
+    trainable ones as autograd leaves, head_forward, O.loss at the variant's class count, backward.  levels=N: the loss
+    and the backward on levels [:N] of that forward (the fusion layers are causally ordered: one forward serves every N).
+    -> (outs, losses {name: float}, matched gt per level, {name: gradient or None} of the trainable parameters), kept per
+    variant, frame and levels."""
+    key = (host['key'], variant_key(**variant))
+    if key not in _FORWARD:
+        sd = O.to_torch_sd(synth.make_state_dict(3, **state_dict_kw(**variant)))
+        for k, v in sd.items():
+            if trainable(k):
+                v.requires_grad_(True)
+        with torch.enable_grad():
+            _FORWARD[key] = sd, oracle_forward(sd, host['feats_np'], host['frame'], variant)
+    if (key, levels) not in _TRAINING:
+        sd, outs = _FORWARD[key]
+        for v in sd.values():
+            v.grad = None
+        with torch.enable_grad():
+            cut = {k: outs[k][:levels] for k in ('all_cls_scores', 'all_bbox_preds')}
+            res, matches = O.loss(cut, torch.from_numpy(host['boxes']), torch.from_numpy(host['labels']), sd['code_weights'],
+                                  num_classes=dict(CONFIGS, **variant)['num_classes'])
+            sum(res.values()).backward(retain_graph=True)
+        _TRAINING[key, levels] = ({k: v.detach() for k, v in cut.items()}, {k: float(v.detach()) for k, v in res.items()},
+                                  matches, {k: v.grad for k, v in sd.items() if trainable(k)})
+    return _TRAINING[key, levels]
+
+
+def iteration_inputs(h, frame):
+    """FusionTrainer.step_fused_nhwc's arguments for head `h` on a g8_frame"""
     from transcar_amd import ops
+    metas = frame['metas']
+    tokens, pad_mult = h.radar_tokens(metas, dev())
+    return ([ops.to_nhwc(f) for f in frame['feats']], ops.lidar2img_tensor(metas, dev()), metas[0]['img_shape'][0][:2], tokens,
+            pad_mult, [frame['gt']], [frame['gt_labels']])
+
+
+def trainer_iteration(frame, head=None, **kw):
+    """One FusionTrainer.step_fused_nhwc(update=False) (frozen decoder -> radar stack -> loss -> backward) of a fresh
+    head (or of `head`, a train_head of the variant).  frame: g8_frame(...); kw: the variant, and what is no variant key
+    goes to FusionTrainer.
+    -> (losses {name: float}, {name: gradient or None} of the trainable parameters)"""
     from transcar_amd.trainer import FusionTrainer
     variant = {k: kw.pop(k) for k in list(kw) if k in CONFIGS or k == 'geometry'}
-    h = train_head(**variant)
-    metas = frame['metas']
-    nhwc = [ops.to_nhwc(f) for f in frame['feats']]
-    l2i = ops.lidar2img_tensor(metas, dev())
-    tokens, pad_mult = h.radar_tokens(metas, dev())
+    h = head or train_head(**variant)
     tr = FusionTrainer(h, dropout=0.0, **kw)
     with torch.enable_grad():
-        losses = tr.step_fused_nhwc(nhwc, l2i, metas[0]['img_shape'][0][:2], tokens, pad_mult, [frame['gt']],
-                                    [frame['gt_labels']], update=False)
+        losses = tr.step_fused_nhwc(*iteration_inputs(h, frame), update=False)
     torch.cuda.synchronize()
     used = {n for n, _ in h.trainable_parameters()}
     grads = {k: (p.grad.clone() if (p.grad is not None and k in used) else None)
@@ -460,16 +622,20 @@ def trainer_iteration(frame, **kw):
     return {k: float(v) for k, v in losses.items()}, grads
 
 
-def check_training_iteration(frame, g8_name, what, **variant):
+def check_training_iteration(frame, g8_name, what, expected=98, **variant):
     """trainer_iteration against the reference's losses and gradients (a G8 fixture), 2e-3 as test_training's
-    oracle-vs-reference check."""
-    from test_training import check_grads_against_g8
+    oracle-vs-reference check.  expected: the parameters an iteration gives a gradient, as the caller states it; it is
+    the head's count and the fixture's."""
     g8 = gold(g8_name)
-    losses, grads = trainer_iteration(frame, **variant)
+    h = train_head(**variant)
+    assert len(h.trainable_parameters()) == expected
+    losses, grads = trainer_iteration(frame, head=h)
+    assert sorted('loss__' + k.replace('.', '_') for k in losses) == sorted(k for k in g8.files if k.startswith('loss__'))
     for k, v in losses.items():
         ref = float(g8['loss__' + k.replace('.', '_')])
-        assert abs(v - ref) < 2e-3 * max(1.0, abs(ref)), (k, v, ref)
-    assert check_grads_against_g8(grads, g8, 2e-3, what) == 98
+        print('%s %s: %.6f (reference %.6f)' % (what, k, v, ref))
+        assert abs(v - ref) < 2e-3 * max(1.0, abs(ref)), (what, k, v, ref)
+    assert check_grads_against_g8(grads, g8, 2e-3, what, expected) == expected
 
 
 def check_plugin_graph_replay(hg, he, shapes='tiny', geometry=DEFAULT):

@@ -1,7 +1,7 @@
 """What the tests of the head's class count (num_classes 17 .. 32: a second 16-column sub-tile in the class heads of
 the row chains; the configs: 10) add to head_variant_rig.py, whose heads, frames and trainer iteration they use with
-num_classes=NC: the fixtures' names and seeds, the small two-sample case the fused radar chain is fed, and the oracle's
-training iteration.  The oracle's class heads take their width from the state dict; its loss takes num_classes.
+num_classes=NC: the fixtures' names and seeds and the small two-sample case the fused radar chain is fed.  The oracle's
+class heads take their width from the state dict; its loss takes num_classes (head_variant_rig.oracle_training).
 
 A plain helper module.  Everything computed on the CPU is computed once per class count and kept."""
 import numpy as np
@@ -30,10 +30,6 @@ KERNEL_CLASSES = (10, 16, 17, 23, 32)    # 10, 16: one sub-tile (the controls); 
 # the third layer fewer; measured: between 22 and 27 rows in the first two layers and between 11 and 15 in the third)
 KERNEL_SEEDS = (2, 4)
 MIN_HIT_ROWS = 10
-
-
-def state_dict(NC, num_query=900):
-    return synth.make_state_dict(seed=3, **R.state_dict_kw(num_classes=NC, num_query=num_query))
 
 
 def centres_of(dbg):
@@ -89,28 +85,3 @@ def one_layer_head(T, NC, num_points=1):
 def hit_rows(case):
     """[sample][fusion layer] -> rows with a radar hit, of a kernel_case"""
     return [[int((h.numpy() > 0).sum()) for h in dbg['hit_counts']] for _, dbg, _ in case['samples']]
-
-
-# ---- training ------------------------------------------------------------------------------------------------------------
-_TRAIN = {}
-
-
-def oracle_training(NC, host):
-    """One training iteration of the oracle (autograd) on the host side of a head_variant_rig.g8_frame: -> (outs, losses
-    {name: float}, matched gt per level, {name: gradient or None} of the trainable parameters).  Kept per class count."""
-    from test_training import trainable
-    if NC not in _TRAIN:
-        sd = O.to_torch_sd(state_dict(NC))
-        for k, v in sd.items():
-            if trainable(k):
-                v.requires_grad_(True)
-        with torch.enable_grad():
-            outs = O.head_forward(sd, [torch.from_numpy(f) for f in host['feats_np']],
-                                  torch.from_numpy(synth.make_lidar2img()).float()[None], R.HW,
-                                  O.build_radar_features(host['frame']), R.PCR)
-            res, matches = O.loss(outs, torch.from_numpy(host['boxes']), torch.from_numpy(host['labels']),
-                                  sd['code_weights'], num_classes=NC)
-            sum(res.values()).backward()
-        _TRAIN[NC] = ({k: v.detach() for k, v in outs.items() if v is not None}, {k: float(v.detach()) for k, v in res.items()},
-                      matches, {k: v.grad for k, v in sd.items() if trainable(k)})
-    return _TRAIN[NC]

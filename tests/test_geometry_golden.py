@@ -116,22 +116,12 @@ def test_decoder_levels_geom_on_the_oracles_trace():
 
 def test_oracle_backward_matches_reference_geom():
     """test_training.test_oracle_backward_matches_reference at the geometry (G8-GEOM), 2e-3."""
-    from test_training import check_grads_against_g8, trainable
     g8 = R.gold('g8_train_grads_geom.npz')
     f = R.g8_frame('g5_head_tiny_geom.npz', radar_seed=int(g8['radar_seed']), geometry=GEOM)
-    sd = O.to_torch_sd(synth.make_state_dict(3))
-    for k, v in sd.items():
-        if trainable(k):
-            v.requires_grad_(True)
-    with torch.enable_grad():
-        outs = O.head_forward(sd, [torch.from_numpy(x) for x in f['feats_np']], torch.from_numpy(f['l2i_np']).float()[None], HW,
-                              O.build_radar_features(f['frame']), PCR)
-        assert np.abs(outs['all_cls_scores'].detach().numpy() - g8['all_cls_scores']).max() < 5e-4
-        res, _ = O.loss(outs, torch.from_numpy(f['boxes']), torch.from_numpy(f['labels']), sd['code_weights'])
-        total = sum(res.values())
-        assert abs(float(total) - float(g8['total_loss'])) < 1e-4 * float(g8['total_loss'])
-        total.backward()
-    check_grads_against_g8({k: v.grad for k, v in sd.items() if trainable(k)}, g8, 2e-3, 'oracle, geometry')
+    outs, losses, _, grads = R.oracle_training(f, geometry=GEOM)
+    assert np.abs(outs['all_cls_scores'].numpy() - g8['all_cls_scores']).max() < 5e-4
+    assert abs(sum(losses.values()) - float(g8['total_loss'])) < 1e-4 * float(g8['total_loss'])
+    R.check_grads_against_g8(grads, g8, 2e-3, 'oracle, geometry')
 
 
 def test_decode_geom():

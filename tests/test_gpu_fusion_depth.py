@@ -10,7 +10,6 @@ import ctypes as C
 import pytest
 import torch
 
-import fusion_depth_rig as F
 import head_variant_rig as R
 from head_variant_rig import T, gpu, no_grad  # noqa: F401  (T, no_grad: fixtures)
 from transcar_amd import synth
@@ -27,19 +26,20 @@ def full_outputs(T, frame_name, rows, matrix, compact, **extra):
     """The three-layer head's outputs on a frame and path, once for both depths."""
     key = (frame_name, rows, matrix, compact, tuple(sorted(extra.items())))
     if key not in _FULL:
-        feats, frame = F.g5_frame()
+        feats, frame = R.g5_frame()
         if frame_name == 'empty':
-            frame = F.empty_frame()
+            frame = R.empty_frame()
         h3, _ = R.shared_head(T)
         _FULL[key] = R.run_head(h3, feats, frame, tile_rows=rows, matrix_path=matrix, radar_compact=compact, **extra)
     return _FULL[key]
 
 
 def depth_outputs(T, depth, frame_name, rows, matrix, compact, **extra):
-    feats, frame = F.g5_frame()
+    feats, frame = R.g5_frame()
     if frame_name == 'empty':
-        frame = F.empty_frame()
-    return R.run_head(F.shared_head(T, depth), feats, frame, tile_rows=rows, matrix_path=matrix, radar_compact=compact, **extra)
+        frame = R.empty_frame()
+    return R.run_head(R.shared_head(T, num_fusion_layers=depth)[0], feats, frame, tile_rows=rows, matrix_path=matrix,
+                      radar_compact=compact, **extra)
 
 
 def assert_first_levels(got, full, depth):
@@ -56,14 +56,14 @@ def assert_first_levels(got, full, depth):
 # ---- 1. identity with the three-layer head --------------------------------------------------------------------------------
 @pytest.mark.parametrize('compact', [False, True], ids=['order1', 'order2'])
 @pytest.mark.parametrize('rows,matrix', PATHS)
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_first_levels_of_the_three_layer_head_bit_for_bit(T, depth, rows, matrix, compact):
     full = full_outputs(T, 'g5', rows, matrix, compact)
     assert int((full['aux']['radar_hit_counts'][0] > 0).sum()) > 32            # hit and no-hit tiles
     assert_first_levels(depth_outputs(T, depth, 'g5', rows, matrix, compact), full, depth)
 
 
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_first_levels_inside_a_nine_frame_launch(T, depth):
     """check_frame_of_nine's launch (32-row tiles, nine frames): every frame's levels [:N] equal the three-layer head's,
     and frame 4 launched alone equals its place in the nine."""
@@ -73,7 +73,7 @@ def test_first_levels_inside_a_nine_frame_launch(T, depth):
     frames = [synth.make_radar_frame(seed=60 + i, n_per_radar=45) for i in range(9)]
     stacked = [gpu(torch.cat([torch.from_numpy(f[l]) for f in feats], 0)) for l in range(len(feats[0]))]
     res = {}
-    for name, head in (('full', R.shared_head(T)[0]), ('depth', F.shared_head(T, depth))):
+    for name, head in (('full', R.shared_head(T)[0]), ('depth', R.shared_head(T, num_fusion_layers=depth)[0])):
         head.forward_options = head_options(tile_rows=32, matrix_path='f16x2')
         try:
             res[name] = head(stacked, synth.make_img_metas(9, l2i, radar=frames))
@@ -88,7 +88,7 @@ def test_first_levels_inside_a_nine_frame_launch(T, depth):
 
 
 @pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_last_level_cls_only_means_level_n_minus_1(T, depth, rows, matrix):
     """options.last_level_cls_only: the class MLPs of level N - 1 run, those before are skipped (their slices are left
     as they were); the boxes of every level and the scores of level N - 1 are the three-layer head's."""
@@ -100,7 +100,7 @@ def test_last_level_cls_only_means_level_n_minus_1(T, depth, rows, matrix):
 
 
 @pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_first_levels_on_a_frame_without_a_radar_return(T, depth, rows, matrix):
     """Every tile skips the gated part; N = 1 has no K/V half B (its second decoder layer is launched alone)."""
     full = full_outputs(T, 'empty', rows, matrix, None)
@@ -110,17 +110,19 @@ def test_first_levels_on_a_frame_without_a_radar_return(T, depth, rows, matrix):
 
 # ---- 2. against the reference ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('rows,matrix', PATHS)
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_first_levels_against_the_reference_fixture(T, depth, rows, matrix):
-    F.check_against_fixture(depth_outputs(T, depth, 'g5', rows, matrix, None), depth)
+    """head_variant_rig.check_against_fixture's rule on levels [:N] of the three-layer oracle and of g5_head_tiny.npz"""
+    want, dbg = R.oracle_head(R.shared_head(T)[1], *R.g5_frame(), key='g5')
+    R.check_against_fixture(depth_outputs(T, depth, 'g5', rows, matrix, None), want, dbg, R.gold('g5_head_tiny.npz'))
 
 
 # ---- 3. levels and decode -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_outputs_all_and_get_bboxes(T, depth):
-    feats, frame = F.g5_frame()
+    feats, frame = R.g5_frame()
     metas = synth.make_img_metas(1, synth.make_lidar2img(), radar=frame)
-    h3, hn = R.make_head(T)[0], F.make_head(T, depth)
+    h3, hn = R.make_head(T)[0], R.make_head(T, num_fusion_layers=depth)[0]
     h3.plugin_graphs = hn.plugin_graphs = False
     res = {}
     for name, head in (('full', h3), ('depth', hn)):
@@ -146,60 +148,38 @@ def test_outputs_all_and_get_bboxes(T, depth):
 
 
 # ---- 4. the entry points that replay captured graphs ------------------------------------------------------------------------
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_plugin_graph_replay(T, depth):
-    R.check_plugin_graph_replay(F.make_head(T, depth), F.make_head(T, depth))
+    R.check_plugin_graph_replay(R.make_head(T, num_fusion_layers=depth)[0], R.make_head(T, num_fusion_layers=depth)[0])
 
 
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_frame_pipeline_two_lanes(T, depth):
-    R.check_frame_pipeline(F.make_head(T, depth), nlanes=2)
+    R.check_frame_pipeline(R.make_head(T, num_fusion_layers=depth)[0], nlanes=2)
 
 
 # ---- 5. training ------------------------------------------------------------------------------------------------------------
 def _iteration_inputs(h):
-    from transcar_amd import ops
-    frame = R.g8_frame('g5_head_tiny.npz')
-    metas = frame['metas']
-    nhwc = [ops.to_nhwc(f) for f in frame['feats']]
-    l2i = ops.lidar2img_tensor(metas, R.dev())
-    tokens, pad_mult = h.radar_tokens(metas, R.dev())
-    return (nhwc, l2i, metas[0]['img_shape'][0][:2], tokens, pad_mult, [frame['gt']], [frame['gt_labels']])
+    return R.iteration_inputs(h, R.g8_frame('g5_head_tiny.npz'))
 
 
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_training_iteration_against_the_reference(T, depth):
     """One step_fused_nhwc(update=False): losses and every trainable parameter's gradient against the reference's own
     loss() and backward on levels [:N], 2e-3; the parameter count is the head's and must be the fixture's."""
-    from test_training import trainable
     from transcar_amd.trainer import FusionTrainer
-    g8 = R.gold('g8_train_grads_f%d.npz' % depth)
-    h = F.train_head(depth)
-    tr = FusionTrainer(h, dropout=0.0)
-    assert len(tr.bucket.chunk_ranges) == depth + 1
-    with torch.enable_grad():
-        losses = tr.step_fused_nhwc(*_iteration_inputs(h), update=False)
-    torch.cuda.synchronize()
-    assert sorted('loss__' + k.replace('.', '_') for k in losses) == sorted(k for k in g8.files if k.startswith('loss__'))
-    for k, v in losses.items():
-        ref = float(g8['loss__' + k.replace('.', '_')])
-        print('%s: %.6f (reference %.6f)' % (k, float(v), ref))
-        assert abs(float(v) - ref) < 2e-3 * max(1.0, abs(ref)), (k, float(v), ref)
-    used = {n for n, _ in h.trainable_parameters()}
-    grads = {k: (p.grad.clone() if (p.grad is not None and k in used) else None)
-             for k, p in h.named_parameters() if trainable(k)}
-    expected = F.num_trained(h)
-    assert expected == 14 + 28 * depth
-    assert F.check_grads_against_g8(grads, g8, 2e-3, 'fused iteration, %d layers' % depth, expected) == expected
+    assert len(FusionTrainer(R.train_head(num_fusion_layers=depth), dropout=0.0).bucket.chunk_ranges) == depth + 1
+    R.check_training_iteration(R.g8_frame('g5_head_tiny.npz'), 'g8_train_grads_f%d.npz' % depth,
+                               'fused iteration, %d layers' % depth, expected=14 + 28 * depth, num_fusion_layers=depth)
 
 
 @pytest.mark.parametrize('p', [0.0, 0.1])
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_chain_paths_equal_operator_paths(T, depth, p):
     """test_gpu_training's test_chain_forward_equals_operator_forward_with_dropout and
     test_chain_backward_equals_operator_backward for N layers: the same dropout masks, the same losses and gradients."""
     from transcar_amd.trainer import FusionTrainer
-    h = F.train_head(depth)
+    h = R.train_head(num_fusion_layers=depth)
     inputs = _iteration_inputs(h)
     tr = FusionTrainer(h, dropout=p, seed=7, decoder_dropout=0.0)
     res = {}
@@ -226,12 +206,12 @@ def test_chain_paths_equal_operator_paths(T, depth, p):
         assert float((got - want).abs().max()) <= 2e-4 * max(scale, 1e-6) + 1e-7, (n, scale)
 
 
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_deterministic_backward_twice(T, depth):
     from transcar_amd.trainer import FusionTrainer
     grads = {}
     for mode in ('det', 'det2', 'atomic'):
-        h = F.train_head(depth)
+        h = R.train_head(num_fusion_layers=depth)
         tr = FusionTrainer(h, dropout=0.1, seed=2, lr=1e-5, deterministic=mode != 'atomic')
         with torch.enable_grad():
             tr.step_fused_nhwc(*_iteration_inputs(h), update=False)
@@ -246,13 +226,13 @@ def test_deterministic_backward_twice(T, depth):
     assert float((grads['det'] - grads['atomic']).abs().max()) <= 2e-6 * float(grads['det'].abs().max())
 
 
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_weight_gradient_groups_sum_to_the_grouped_launch(T, depth):
     """tc_radar_train_bwd_weights(group 0 .. N): fusion layer N .. 1, then the encoders -- each writes only its chunk of the
     bucket, together they add the grouped launch's gradients; group N + 1 and -1 are refused, naming the group."""
     from transcar_amd import _lib as L
     from transcar_amd.trainer import FusionTrainer, exchange_chunk_of
-    h = F.train_head(depth)
+    h = R.train_head(num_fusion_layers=depth)
     tr = FusionTrainer(h, dropout=0.1, seed=4)
     tr.keep_last = True
     with torch.enable_grad():
@@ -294,13 +274,13 @@ def test_weight_gradient_groups_sum_to_the_grouped_launch(T, depth):
             weights(bad)
 
 
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_optimizer_step_then_inference(T, depth):
     """One real step, then an eval forward: the lazy re-pack of the trainable weights works for N layers -- the forward
     equals that of a fresh head loaded with the updated parameters."""
     from transcar_amd.trainer import FusionTrainer
-    feats, frame = F.g5_frame()
-    h = F.train_head(depth)
+    feats, frame = R.g5_frame()
+    h = R.train_head(num_fusion_layers=depth)
     before = R.run_head(h.eval(), feats, frame, tile_rows=16, matrix_path='f16x2')
     tr = FusionTrainer(h, lr=1e-3, dropout=0.0)
     h.train()
@@ -309,7 +289,7 @@ def test_optimizer_step_then_inference(T, depth):
     assert h._packed_dirty
     after = R.run_head(h.eval(), feats, frame, tile_rows=16, matrix_path='f16x2')
     assert not h._packed_dirty
-    fresh = F.make_head(T, depth)
+    fresh = R.make_head(T, num_fusion_layers=depth)[0]
     fresh.load_state_dict(h.state_dict(), strict=True)
     want = R.run_head(fresh, feats, frame, tile_rows=16, matrix_path='f16x2')
     for k in KEYS:

@@ -14,7 +14,6 @@ from head_variant_rig import SMOOTH, T, gpu, no_grad  # noqa: F401  (T, no_grad:
 from parity_util import assert_rows_match
 from teacher_forced_checks import LAYER_TOL, hit_aware
 from oracle import transcar_oracle as O
-from test_training import check_grads_against_g8
 from transcar_amd import radar as RD, synth
 
 pytestmark = pytest.mark.gpu
@@ -210,30 +209,30 @@ def c23():
 def test_training_iteration_23_classes_gradients_match_reference(T, c23):
     g8, _, losses, grads = c23
     _losses_close(losses, {k: float(g8['loss__' + k.replace('.', '_')]) for k in losses}, 'fused c23')
-    assert check_grads_against_g8(grads, g8, 2e-3, 'fused c23') == 98
+    assert R.check_grads_against_g8(grads, g8, 2e-3, 'fused c23') == 98
 
 
 def test_training_iteration_32_classes_gradients_match_oracle_autograd(T):
     """32 classes (the full second sub-tile, no fixture): the oracle's autograd on the CPU is the reference side.  The
     radar frame: G5's rig around the centres the oracle's decoder predicts, the seed chosen as G8-C23's."""
     with torch.no_grad():
-        sd = O.to_torch_sd(NC.state_dict(32))
+        sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_classes=32))
         _, dbg0 = R.oracle_head(sd, synth.make_feats('tiny', seed=1, smooth=SMOOTH),
                                 synth.make_radar_frame(seed=2, n_per_radar=51))
     frame = R.g8_frame(None, radar_seed=NC.C32_RADAR_SEED, num_classes=32, centres=NC.centres_of(dbg0))
-    _, want_losses, matches, want_grads = NC.oracle_training(32, frame)
+    _, want_losses, matches, want_grads = R.oracle_training(frame, num_classes=32)
     for m in matches:
         assert (frame['labels'][m[m > 0].numpy() - 1] > 15).sum() >= 1
     losses, grads = R.trainer_iteration(frame, num_classes=32)
     _losses_close(losses, want_losses, 'fused c32')
-    assert check_grads_against_g8(grads, R.GradStats(want_grads), 2e-3, 'fused c32 vs oracle') == 98
+    assert R.check_grads_against_g8(grads, R.GradStats(want_grads), 2e-3, 'fused c32 vs oracle') == 98
 
 
 def test_deterministic_backward_23_classes_twice(T, c23):
     g8, frame, _, _ = c23
     a = R.trainer_iteration(frame, num_classes=23, deterministic=True)
     b = R.trainer_iteration(frame, num_classes=23, deterministic=True)
-    assert check_grads_against_g8(a[1], g8, 2e-3, 'deterministic c23') == 98
+    assert R.check_grads_against_g8(a[1], g8, 2e-3, 'deterministic c23') == 98
     for k, g in a[1].items():
         assert (g is None) == (b[1][k] is None) and (g is None or torch.equal(g, b[1][k])), k
 
@@ -244,8 +243,8 @@ def test_operator_training_path_agrees_with_the_fused_one_23_classes(T, c23):
     g8, frame, fused_losses, fused = c23
     losses, grads = R.trainer_iteration(frame, num_classes=23, chain_forward=False, chain_backward=False)
     _losses_close(losses, fused_losses, 'operators vs fused c23')
-    assert check_grads_against_g8(grads, g8, 2e-3, 'operators c23') == 98
-    assert check_grads_against_g8(grads, R.GradStats(fused), 2e-3, 'operators vs fused c23') == 98
+    assert R.check_grads_against_g8(grads, g8, 2e-3, 'operators c23') == 98
+    assert R.check_grads_against_g8(grads, R.GradStats(fused), 2e-3, 'operators vs fused c23') == 98
 
 
 # ---- 5. the replay paths ---------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Detr3DHead(radar_gate=...) on the MI355X: the single circle's inclusive edge at the smallest shape that has it, the
 threshold self-check over the accepted radius range, the circle gate and a three-circle gate with other radii end to end
-against the CPU oracle under the same gate (radar_gate_rig.gated) on every chain path -- the circle also against the
+against the CPU oracle under the same gate (head_forward(radar_gate=)) on every chain path -- the circle also against the
 reference's single-circle head (tests/golden/make_golden_radar_gate.py) --, the identities (default spellings, row
 orders, nine-frame launch, plugin graph, shallower heads), and a training iteration against the reference's gradients and
 the oracle's autograd under the same gate.  Tiny level shapes, 900 queries, G5's radar centres.  pytest -m gpu"""
@@ -10,39 +10,29 @@ import numpy as np
 import pytest
 import torch
 
-import fusion_depth_rig as F
 import head_variant_rig as R
-import radar_gate_rig as G
 from head_variant_rig import T, gpu, no_grad  # noqa: F401  (T, no_grad: fixtures)
-from oracle import transcar_oracle as O
 from transcar_amd import _lib as L
-from transcar_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 #: (tile rows, matrix path) of the chains, and the operator-by-operator path
 PATHS = [(4, 'f32'), (4, 'f16x2'), (8, 'f32'), (8, 'f16x2'), (16, 'f32'), (16, 'f16x2'), (32, 'f16x2'), (0, 'unfused')]
 KEYS = ('all_cls_scores', 'all_bbox_preds')
-GATES = {'circle': G.CIRCLE, 'wide3': G.WIDE3}
-_HEADS, _ORACLE = {}, {}
+GATES = {'circle': R.CIRCLE, 'wide3': R.WIDE3}
 
 
 def shared_head(T, name, depth=3):
-    if (name, depth) not in _HEADS:
-        _HEADS[name, depth] = G.make_head(T, GATES.get(name), depth)
-    return _HEADS[name, depth]
+    return R.shared_head(T, radar_gate=GATES[name], num_fusion_layers=depth)[0]
 
 
 def frame_of(name):
     """the circle on the frame of the reference's single-circle fixture, the others on G5's"""
-    return G.circle_frame() if name == 'circle' else F.g5_frame()
+    return R.g5_frame(int(R.gold(R.G5_CIRCLE)['radar_seed'])) if name == 'circle' else R.g5_frame()
 
 
-def oracle(name):
-    if name not in _ORACLE:
-        feats, frame = frame_of(name)
-        _ORACLE[name] = G.oracle_head(GATES[name], O.to_torch_sd(synth.make_state_dict(seed=3)), feats, frame)
-    return _ORACLE[name]
+def oracle(T, name):
+    return R.oracle_head(R.shared_head(T)[1], *frame_of(name), key='gate frame ' + name, radar_gate=GATES[name])
 
 
 def run(head, rows, matrix, name=None, **extra):
@@ -118,12 +108,12 @@ def test_threshold_selfcheck_over_the_accepted_range(T, inclusive):
 @pytest.mark.parametrize('rows,matrix', PATHS)
 @pytest.mark.parametrize('name', sorted(GATES))
 def test_end_to_end_against_the_oracle(T, name, rows, matrix):
-    want, dbg = oracle(name)
+    want, dbg = oracle(T, name)
     rows_hit = [int((h > 0).sum()) for h in dbg['hit_counts']]
     assert min(rows_hit) > 32, rows_hit
     outs = run(shared_head(T, name), rows, matrix, name)
     if name == 'circle':                             # ... and the reference's backup head on the same frame
-        R.check_against_fixture(outs, want, dbg, R.gold(G.G5_CIRCLE))
+        R.check_against_fixture(outs, want, dbg, R.gold(R.G5_CIRCLE))
     want_hits = np.stack([h.numpy() for h in dbg['hit_counts']])
     differ = int((~np.all(outs['aux']['radar_hit_counts'][:, 0].cpu().numpy() == want_hits, axis=0)).sum())
     print('%s %s/%s: hit rows %s, %d rows differ in a hit count' % (name, rows, matrix, rows_hit, differ))
@@ -135,7 +125,7 @@ def test_end_to_end_against_the_oracle(T, name, rows, matrix):
 def test_default_spellings_are_one_head(T, rows, matrix):
     base = run(R.shared_head(T)[0], rows, matrix)
     for gate in (None, dict(type='three_circle'), dict(type='three_circle', radii=[(1.0, 2.0), (1.0, 2.0), (0.5, 1.0)])):
-        got = run(G.make_head(T, gate), rows, matrix)
+        got = run(R.make_head(T, radar_gate=gate)[0], rows, matrix)
         for k in KEYS:
             assert torch.equal(got[k], base[k]), (gate, k)
         assert torch.equal(got['aux']['radar_hit_counts'], base['aux']['radar_hit_counts'])
@@ -152,11 +142,11 @@ def test_row_orders_agree_with_the_circle(T, rows, matrix):
 
 def test_circle_frame_of_nine_and_plugin_graph(T):
     R.check_frame_of_nine(shared_head(T, 'circle'))
-    R.check_plugin_graph_replay(G.make_head(T, G.CIRCLE), G.make_head(T, G.CIRCLE))
+    R.check_plugin_graph_replay(R.make_head(T, radar_gate=R.CIRCLE)[0], R.make_head(T, radar_gate=R.CIRCLE)[0])
 
 
 @pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (16, 'f16x2'), (32, 'f16x2'), (0, 'unfused')])
-@pytest.mark.parametrize('depth', F.DEPTHS)
+@pytest.mark.parametrize('depth', R.DEPTHS)
 def test_shallower_circle_heads_are_the_first_levels(T, depth, rows, matrix):
     full, got = run(shared_head(T, 'circle'), rows, matrix), run(shared_head(T, 'circle', depth), rows, matrix)
     for k in KEYS:
@@ -165,67 +155,29 @@ def test_shallower_circle_heads_are_the_first_levels(T, depth, rows, matrix):
 
 
 # ---- 4. training -----------------------------------------------------------------------------------------------------------
-def _oracle_gradients(frame):
-    """The oracle's loss and autograd gradients under the circle gate, in a G8 fixture's layout."""
-    from test_training import trainable
-    from transcar_amd import configs
-    sd = O.to_torch_sd(synth.make_state_dict(3))
-    for k, v in sd.items():
-        if trainable(k):
-            v.requires_grad_(True)
-    with torch.enable_grad(), G.gated(G.CIRCLE):
-        outs = O.head_forward(sd, [torch.from_numpy(f) for f in frame['feats_np']], torch.from_numpy(frame['l2i_np']).float()[None],
-                              configs.IMG_SHAPE[:2], O.build_radar_features(frame['frame']), configs.point_cloud_range)
-        res, _ = O.loss(outs, torch.from_numpy(frame['boxes']), torch.from_numpy(frame['labels']), sd['code_weights'])
-        total = sum(res.values())
-        total.backward()
-    return float(total), R.GradStats({k: v.grad for k, v in sd.items() if trainable(k)})
-
-
-def _iteration(frame, **kw):
-    """head_variant_rig.trainer_iteration with a circle-gate head"""
-    from test_training import trainable
-    from transcar_amd import ops
-    from transcar_amd.trainer import FusionTrainer
-    import transcar_amd as T_
-    h = G.make_head(T_, G.CIRCLE, train_cfg=True).freeze_decoder().set_dropout(0.0)
-    metas = frame['metas']
-    nhwc = [ops.to_nhwc(f) for f in frame['feats']]
-    l2i = ops.lidar2img_tensor(metas, R.dev())
-    tokens, pad_mult = h.radar_tokens(metas, R.dev())
-    tr = FusionTrainer(h, dropout=0.0, **kw)
-    with torch.enable_grad():
-        losses = tr.step_fused_nhwc(nhwc, l2i, metas[0]['img_shape'][0][:2], tokens, pad_mult, [frame['gt']],
-                                    [frame['gt_labels']], update=False)
-    torch.cuda.synchronize()
-    used = {n for n, _ in h.trainable_parameters()}
-    grads = {k: (p.grad.clone() if (p.grad is not None and k in used) else None) for k, p in h.named_parameters() if trainable(k)}
-    return {k: float(v) for k, v in losses.items()}, grads
-
-
 def test_training_iteration_against_the_reference_and_the_oracle(T):
     """One iteration's losses and gradients on the chain backward, the deterministic one (twice: bit-identical) and the
     per-operator backward, against the reference's backup head (g8_train_grads_gate_circle.npz) and against the oracle's
     autograd under the same gate, 2e-3 as test_gpu_training holds G8."""
-    from test_training import check_grads_against_g8
-    g8_ref = R.gold(G.G8_CIRCLE)
+    g8_ref = R.gold(R.G8_CIRCLE)
     frame = R.g8_frame('g5_head_tiny.npz', radar_seed=int(g8_ref['radar_seed']))
-    total, g8 = _oracle_gradients(frame)
+    _, oracle_losses, _, oracle_grads = R.oracle_training(frame, radar_gate=R.CIRCLE)
+    total, g8 = sum(oracle_losses.values()), R.GradStats(oracle_grads)
     assert abs(total - float(g8_ref['total_loss'])) < 1e-4 * float(g8_ref['total_loss'])
     runs = {}
     for what, kw in (('chain', dict(chain_forward=True, chain_backward=True)),
                      ('deterministic', dict(chain_forward=True, chain_backward=True, deterministic=True)),
                      ('deterministic again', dict(chain_forward=True, chain_backward=True, deterministic=True)),
                      ('operators', dict(chain_forward=False, chain_backward=False))):
-        losses, grads = _iteration(frame, **kw)
+        losses, grads = R.trainer_iteration(frame, radar_gate=R.CIRCLE, **kw)
         loss = sum(losses.values())
         print('%s: total loss %.6f (oracle %.6f, reference %.6f)' % (what, loss, total, float(g8_ref['total_loss'])))
         assert abs(loss - total) < 2e-3 * max(1.0, abs(total)), (what, loss, total)
         for k, v in losses.items():
             ref = float(g8_ref['loss__' + k.replace('.', '_')])
             assert abs(v - ref) < 2e-3 * max(1.0, abs(ref)), (what, k, v, ref)
-        assert check_grads_against_g8(grads, g8_ref, 2e-3, what + ' vs reference') == 98
-        assert check_grads_against_g8(grads, g8, 2e-3, what + ' vs oracle') == 98
+        assert R.check_grads_against_g8(grads, g8_ref, 2e-3, what + ' vs reference') == 98
+        assert R.check_grads_against_g8(grads, g8, 2e-3, what + ' vs oracle') == 98
         runs[what] = grads
     for k, g in runs['deterministic'].items():
         if g is not None:

@@ -16,9 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from head_variant_rig import decoder_dropout_masks, dropout_mask
+from head_variant_rig import check_grads_against_g8, decoder_dropout_masks, dropout_mask, g8_inputs, g8_name, trainable
 from oracle import transcar_oracle as O
-from test_training import check_grads_against_g8, g8_inputs, g8_name, trainable
 from transcar_amd import configs, synth
 
 pytestmark = pytest.mark.gpu

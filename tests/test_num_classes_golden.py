@@ -9,7 +9,6 @@ import torch
 import head_variant_rig as R
 import num_classes_rig as NC
 from oracle import transcar_oracle as O
-from test_training import check_grads_against_g8
 from transcar_amd import synth
 
 E2E_TOL = 5e-4          # test_oracle_golden.test_g5_full_head, test_num_heads_golden
@@ -28,7 +27,7 @@ def g8():
 @pytest.fixture(scope='module')
 def forward(g5):
     with torch.no_grad():
-        sd = O.to_torch_sd(NC.state_dict(NC.NC_FIXTURE))
+        sd = O.to_torch_sd(synth.make_state_dict(seed=3, num_classes=NC.NC_FIXTURE))
         frame = synth.make_radar_frame(seed=2, n_per_radar=51, centres=g5['radar_centres'])
         f36 = O.build_radar_features(frame)
         np.testing.assert_allclose(f36.astype(np.float32), g5['radar_tokens'], atol=1e-6, rtol=0)
@@ -74,14 +73,14 @@ def test_g8_forward_is_the_oracle_head(g5, g8):
     """The gradient fixture's forward (the radar frame of the seed it stores) is the oracle's head at 23 classes."""
     assert np.isfinite(g8['total_loss']) and int(g8['radar_seed']) == NC.G8_C23_RADAR_SEED
     host = R.g8_frame(NC.G5_C23, radar_seed=NC.G8_C23_RADAR_SEED, num_classes=23)
-    outs, _, _, _ = NC.oracle_training(23, host)
+    outs, _, _, _ = R.oracle_training(host, num_classes=23)
     for k in ('all_cls_scores', 'all_bbox_preds'):
         _all_but_two(outs[k].numpy(), g8[k], k)
 
 
 def test_oracle_backward_matches_reference_23_classes(g5, g8):
     host = R.g8_frame(NC.G5_C23, radar_seed=NC.G8_C23_RADAR_SEED, num_classes=23)
-    _, losses, matches, grads = NC.oracle_training(23, host)
+    _, losses, matches, grads = R.oracle_training(host, num_classes=23)
     # matched labels lie above 15 in every level: the second sub-tile's columns see positive targets
     for m in matches:
         assert (host['labels'][m[m > 0].numpy() - 1] > 15).sum() >= 1
@@ -89,4 +88,4 @@ def test_oracle_backward_matches_reference_23_classes(g5, g8):
         ref = float(g8['loss__' + k.replace('.', '_')])
         assert abs(v - ref) < 1e-4 * max(1.0, abs(ref)), (k, v, ref)
     assert abs(sum(losses.values()) - float(g8['total_loss'])) < 1e-4 * float(g8['total_loss'])
-    assert check_grads_against_g8(grads, g8, 2e-3, 'oracle c23') == 98
+    assert R.check_grads_against_g8(grads, g8, 2e-3, 'oracle c23') == 98

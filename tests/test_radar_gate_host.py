@@ -5,12 +5,11 @@ import ctypes
 import pytest
 
 import transcar_amd as T
+from head_variant_rig import CIRCLE, WIDE3
 from transcar_amd import _lib as L
 from transcar_amd import configs
 from transcar_amd import detr3d_head as D
 
-CIRCLE = dict(type='circle', radii=[2.0, 2.0, 1.0])
-WIDE3 = dict(type='three_circle', radii=[(0.75, 3.0), (0.5, 1.5), (0.25, 0.75)])
 DEFAULT3 = dict(type='three_circle', radii=((1.0, 2.0), (1.0, 2.0), (0.5, 1.0)))
 
 
