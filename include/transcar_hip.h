@@ -36,9 +36,18 @@ extern "C" {
 #define TC_MAX_RADAR_LAYERS 3
 /* num_cams * num_levels * num_points of Detr3DCrossAtten: the logits of a row fit one 256-wide activation unit */
 #define TC_MAX_CAM_LOGITS 256
-/* Heads of the radar fusion attention (rf_multihead_attn{,2,3}): the reference builds it as
- * nn.MultiheadAttention(embed_dims, 8) (HEAD:129-171) whatever the decoder's self-attention uses. */
+/* Default head count of the radar fusion attention (rf_multihead_attn{,2,3}): the reference builds it as
+ * nn.MultiheadAttention(embed_dims, 8) (HEAD:129-171) whatever the decoder's self-attention uses.  4 and 16 heads
+ * (head dimension 64 and 16 at embed_dims 256) are accepted too; the count adds no parameter. */
 #define TC_RADAR_HEADS 8
+/* tc_head_weights.num_heads carries both head counts: the decoder self-attention's in its lower 16 bits, the radar
+ * fusion attention's in its upper 16.  An upper half of 0 reads as TC_RADAR_HEADS, so a caller that stores the decoder's
+ * count alone (every caller before the radar count could be chosen) keeps the 8-head fusion attention. */
+#define TC_NUM_HEADS_PACK(decoder_heads, radar_heads) \
+  ((int)((((unsigned)(radar_heads) & 0xffffu) << 16) | ((unsigned)(decoder_heads) & 0xffffu)))
+#define TC_NUM_HEADS_DECODER(num_heads) ((int)((unsigned)(num_heads) & 0xffffu))
+#define TC_NUM_HEADS_RADAR(num_heads) \
+  (((unsigned)(num_heads) >> 16) != 0u ? (int)((unsigned)(num_heads) >> 16) : TC_RADAR_HEADS)
 /* The distance gate of a fusion layer, a (radius_min, radius_max) pair wherever one is taken (tc_radar_layer,
  * tc_radar_gated_xattn_fwd, tc_radar_attn_core_fwd / _bwd):
  *   radius_min >= 0: three circles per query (centre, front and rear at +-0.25 * length) of the radius
@@ -129,9 +138,11 @@ typedef struct {
 /* All parameters Detr3DHead.forward reads (HEAD:43-238), in eval mode. */
 typedef struct {
   int abi_version;                  /* TC_ABI_VERSION                         */
-  /* num_heads: heads of the DECODER's self-attention (attn_cfgs[0].num_heads): 4, 8 or 16 at embed_dims 256 (head
-   * dimension 64, 32, 16); another count is refused naming it (tc_head_packed_bytes / tc_head_workspace_bytes return 0).
-   * The radar fusion attention does not read it: it has TC_RADAR_HEADS heads. */
+  /* num_heads, lower 16 bits (TC_NUM_HEADS_DECODER): heads of the DECODER's self-attention (attn_cfgs[0].num_heads): 4, 8
+   * or 16 at embed_dims 256 (head dimension 64, 32, 16); another count is refused as num_heads=<count>.
+   * Upper 16 bits (TC_NUM_HEADS_RADAR): heads of the radar fusion attention: 0 (= TC_RADAR_HEADS), 4, 8 or 16; another
+   * count is refused as radar_num_heads=<count>.  Either refusal comes from every entry that takes the struct
+   * (tc_head_packed_bytes / tc_head_workspace_bytes and the other size queries return 0).  TC_NUM_HEADS_PACK builds it. */
   int num_query, embed_dims, num_heads, ffn_dims, num_layers;
   int num_cams, num_levels, num_classes, code_size;   /* num_levels: 1 .. TC_MAX_LEVELS */
   int radar_in_dims, num_radar_layers, num_radar_tokens_ref; /* 36, 1..3, 1500 (0: camera only) */
@@ -447,8 +458,8 @@ int tc_sdpa_fwd_f16x2_hd(const float* qk, const float* vt, int ldt, float* out, 
  * (HEAD:549-581 / :619-653 / :675-711): three-circle gate around
  * (centre, front, rear), masked nn.MultiheadAttention of the gated queries
  * over the radar tokens, residual add on the rows that have at least one hit.
- * num_heads = TC_RADAR_HEADS only.
- *   query      [B,Q,C]   query_feat before the layer
+ * num_heads: 4, 8 (TC_RADAR_HEADS) or 16 at C = 256; another count is refused naming it before any pointer is read.
+ *   query     [B,Q,C]   query_feat before the layer
  *   centre_xy  [B,Q,2]   metres;  box [B,Q,code]: log-length at [3], sin/cos at [6],[7]
  *   radar_feat [B,T,C]   encoded tokens; radar_xy [B,T,2]
  *   pad_mult   multiplicity of the LAST token (the reference always attends
@@ -680,7 +691,9 @@ int tc_box_add_ref_bwd(const float* d_box, int code_size, float* d_prev_box, int
  *   kv [B*T,2C] = K | V, centre at centre_xy[m*ld_c + {0,1}], box [B*Q,code],
  *   token xy at radar_xy[(b*T+t)*ld_xy + {0,1}]
  *   -> attn_out [B*Q,C] (zero rows without a hit), hit_counts [B*Q].
- * Backward: dq [B*Q,C] (=), dkv [B*T,2C] (+=). */
+ * Backward: dq [B*Q,C] (=), dkv [B*T,2C] (+=).
+ * num_heads (H): 4, 8 or 16 at C = 256, as tc_radar_gated_xattn_fwd; the dropout mask of the probabilities is indexed
+ * (row * H + head) * num_radar_tokens_ref + token, the reference's [heads, Q, 1500] mask. */
 int tc_radar_attn_core_fwd(const float* qproj, float q_scale, const float* kv,
                            const float* centre_xy, int ld_c, const float* box, int code_size,
                            const float* radar_xy, int ld_xy, int B, int Q, int T, int C,

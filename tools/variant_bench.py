@@ -6,6 +6,7 @@ values.  The first value is the base of `relative_to_first`.
     python tools/variant_bench.py --vary num_points 1 5 [--rounds 3] [--steps 20]        (one JSON line)
     python tools/variant_bench.py --vary num_levels 4 3 2 1
     python tools/variant_bench.py --vary num_heads 8 4 16
+    python tools/variant_bench.py --vary radar_num_heads 8 4 16
     python tools/variant_bench.py --vary with_box_refine 1 0
 
 num_points       Detr3DCrossAtten.num_points (DESIGN.md "num_points").
@@ -13,6 +14,8 @@ num_levels       the head is fed the FIRST L res101 levels; L = 4 is the headlin
                  chain kernels (DESIGN.md "num_levels < 4").
 num_heads        the decoder self-attention's head count: 8 is the headline (head dimension 32); 4 and 16 run the
                  attention cores' D = 64 and D = 16 instantiations.  The state dict does not depend on it.
+radar_num_heads  the radar fusion attention's head count (8 is the headline): the same kernels with 16 / 8 / 4 lanes per
+                 head.  The state dict does not depend on it either.
 with_box_refine  both heads carry synth.make_state_dict(with_box_refine=False)'s shared branches; the results are keyed
                  'refine' / 'norefine' and `norefine_over_refine` is reported, as profiles/box_refine_bench.json has it."""
 import argparse
@@ -31,11 +34,11 @@ import bench  # noqa: E402
 import transcar_amd as T  # noqa: E402
 from transcar_amd import configs, synth  # noqa: E402
 
-KEYWORDS = ('num_points', 'num_levels', 'num_heads', 'with_box_refine')
+KEYWORDS = ('num_points', 'num_levels', 'num_heads', 'radar_num_heads', 'with_box_refine')
 
 
 def build_head(dev, keyword, value):
-    sd_kw = {'num_heads': {}, 'with_box_refine': dict(with_box_refine=False)}.get(keyword, {keyword: value})
+    sd_kw = {'num_heads': {}, 'radar_num_heads': {}, 'with_box_refine': dict(with_box_refine=False)}.get(keyword, {keyword: value})
     head = T.build_head(configs.head_cfg(**{keyword: bool(value) if keyword == 'with_box_refine' else value}))
     head.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(seed=3, **sd_kw).items()}, strict=True)
     return head.to(dev).eval()

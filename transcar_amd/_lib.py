@@ -55,8 +55,15 @@ def check_num_levels(num_levels):
 
 # heads of the decoder's MultiheadAttention at embed_dims 256: head dimension 64, 32, 16 (include/transcar_hip.h)
 TC_NUM_HEADS = (4, 8, 16)
-# heads of the radar fusion attention: nn.MultiheadAttention(embed_dims, 8) in the reference, whatever the decoder uses
+# default heads of the radar fusion attention: nn.MultiheadAttention(embed_dims, 8) in the reference, whatever the decoder
+# uses; Detr3DHead(radar_num_heads=) takes TC_NUM_HEADS too
 TC_RADAR_HEADS = 8
+
+
+def pack_num_heads(decoder_heads, radar_heads=TC_RADAR_HEADS):
+    """tc_head_weights.num_heads (TC_NUM_HEADS_PACK): the decoder's count in the lower 16 bits, the radar fusion
+    attention's in the upper 16 -- left 0 (= TC_RADAR_HEADS) at the default, which keeps the default head's struct as it was."""
+    return decoder_heads | ((radar_heads << 16) if radar_heads != TC_RADAR_HEADS else 0)
 
 # num_classes of a head (tc_head_weights, tc_decoder_heads)
 TC_MAX_CLASSES = 32
@@ -89,6 +96,17 @@ def check_num_heads(num_heads):
         raise TransCARHipError(
             'MultiheadAttention(HIP): num_heads=%r is not supported (4, 8 or 16 heads at embed_dims 256: '
             'head dimension 64, 32 or 16)' % (num_heads,))
+
+
+def check_radar_num_heads(radar_num_heads):
+    """The library's limit on the head count of the radar fusion attention (rf_multihead_attn{,2,3}: 4, 8 or 16 at
+    embed_dims 256), checked before anything is built, packed or launched.  Returns the count."""
+    h = radar_num_heads
+    if isinstance(h, bool) or not isinstance(h, int) or h not in TC_NUM_HEADS:
+        raise TransCARHipError(
+            'Detr3DHead(HIP): radar_num_heads=%r is not supported (4, 8 or 16 heads at embed_dims 256: '
+            'head dimension 64, 32 or 16)' % (h,))
+    return h
 
 
 def check_num_classes(num_classes):

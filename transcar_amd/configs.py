@@ -77,7 +77,8 @@ IMG_SHAPE = (928, 1600, 3)
 
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
              num_levels=None, num_heads=None, num_classes=None,
-             num_fusion_layers=None, pc_range=None, post_center_range=None, radar_gate=None):
+             num_fusion_layers=None, pc_range=None, post_center_range=None, radar_gate=None,
+             radar_num_heads=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -85,7 +86,7 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     Detr3DCrossAtten.num_levels and the transformer's num_feature_levels (the
     configs: the class defaults, 4 FPN levels); num_heads overrides the
     decoder MultiheadAttention's (attn_cfgs[0]; the configs: 8, CFG:69; 4, 8
-    or 16 -- the radar fusion attention keeps its 8, HEAD:129-171);
+    or 16 -- the radar fusion attention has its own count, radar_num_heads);
     num_classes sets the head's and the bbox_coder's (the configs: 10, CFG:54
     and :89; 1 .. 32 -- the coder's is the modulus that turns a score index
     into a label, CODER:54-55); num_fusion_layers sets the depth of the radar
@@ -99,7 +100,10 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     the fusion layers (``_lib.check_radar_gate``: the reference head's three
     circles with other clamp pairs, or ``dict(type='circle', radii=[R, ...])``,
     the single circle of the paper's radius ablation; the reference writes its
-    radii as constants, HEAD:567, 635, 693)."""
+    radii as constants, HEAD:567, 635, 693).  radar_num_heads sets the head
+    count of the fusion attention rf_multihead_attn{,2,3} (the reference writes
+    8, HEAD:129-171; 4, 8 or 16): the key is added only for a count other than
+    8, it adds no parameter."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -136,6 +140,10 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
         from ._lib import check_radar_gate
         gate = check_radar_gate(radar_gate, cfg.get('num_fusion_layers', 3))
         cfg['radar_gate'] = dict(type=gate['type'], radii=list(gate['radii']))
+    if radar_num_heads is not None:
+        from ._lib import check_radar_num_heads, TC_RADAR_HEADS
+        if check_radar_num_heads(radar_num_heads) != TC_RADAR_HEADS:
+            cfg['radar_num_heads'] = radar_num_heads
     return cfg
 
 

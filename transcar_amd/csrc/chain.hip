@@ -427,6 +427,7 @@ struct ChainDev {
   const float* pre; const int* premask;     // round 6: the sampling step's pre-gathered level values / visibility masks, or null
   // radar
   const float* tokens; int RI, T, pad_mult;
+  int rlph;                    // lanes per head of the fusion attention: 64 / heads (rowdev.hpp head_sum)
   const float* ref_last; const float* box_in;
   int cen_from_box;            // the first layer run is not fusion layer 1: gate centre = previous box
   float rmin[TC_MAX_RADAR_LAYERS], rmax[TC_MAX_RADAR_LAYERS];
@@ -2472,11 +2473,11 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
             DropK dk = k.rdrop;
             dk.site = 4u * (unsigned)rep;
             o = radar_attn_row_g<true>(gg, q4, k.tokens + (size_t)b * k.T * k.RI, k.RI, kv + (size_t)b * k.T * 512, 512,
-                                       k.T, k.pad_mult, lane, count, dk, grow, hm);
+                                       k.T, k.pad_mult, lane, k.rlph, count, dk, grow, hm);
             if (m0 + row < M) st4(r.gd + (size_t)grow * 256 + 4 * lane, o);          // tape: attention output
           } else {
             o = radar_attn_row_g(gg, q4, k.tokens + (size_t)b * k.T * k.RI, k.RI, kv + (size_t)b * k.T * 512, 512,
-                                 k.T, k.pad_mult, lane, count, DropK(), 0, hm);
+                                 k.T, k.pad_mult, lane, k.rlph, count, DropK(), 0, hm);
           }
           act_st4<PL>(buf_ptr(S, r.dst) + row * LD2, 4 * lane, o);
           if (lane == 0) S.gate[row] = count;        // the same count as K_RADAR_GATE's (same predicate)
@@ -2622,7 +2623,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
             dq = radar_attn_bwd_row(cxy[0], cxy[1], bx[3], bx[6], bx[7], k.rmin[layer], k.rmax[layer], q4,
                                     k.tokens + (size_t)b * k.T * k.RI, k.RI, uptr(r.p2) + (size_t)b * k.T * 512,
                                     const_cast<float*>(uptr(r.p3)) + (size_t)b * k.T * 512, 512, k.T, k.pad_mult, dO, o4,
-                                    dk, grow, lane,
+                                    dk, grow, lane, k.rlph,
                                     k.detp != nullptr ? det_shadow_of(*k.detp, uptr(r.p3) + (size_t)b * k.T * 512) : nullptr);
             dq.x *= k.qscale; dq.y *= k.qscale; dq.z *= k.qscale; dq.w *= k.qscale;
           }
@@ -3318,7 +3319,8 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {
   }
   k.g[G_QF] = const_cast<float*>(a.qf);
   k.g[G_CLS] = a.all_cls; k.g_ld[G_CLS] = a.ncls;
-  k.qscale = a.qscale;
+  TC_REQUIRE(heads_ok(a.heads), "radar_chain: heads=%d", a.heads);
+  k.qscale = a.qscale; k.rlph = 64 / a.heads;
   k.tokens = a.tokens; k.RI = a.RI; k.T = a.T; k.pad_mult = a.pad_mult;
   k.ref_last = a.ref_last; k.box_in = a.box_m; k.cen_from_box = a.cen_from_box;
   TC_REQUIRE(a.cen_from_box || a.ref_last != nullptr, "radar_chain: ref_last is null");
@@ -3379,7 +3381,8 @@ int launch_radar_chain_bwd(const RadarBwdChainArgs& a, hipStream_t s) {
   k.dy_stride = a.dy_stride;
   k.d_cls = a.d_cls; k.d_box = a.d_box; k.loss_vals = a.loss_vals; k.loss_out = a.loss_out;
   k.hits = const_cast<int*>(a.hits);
-  k.qscale = a.qscale; k.tokens = a.tokens; k.RI = a.RI; k.T = a.T; k.pad_mult = a.pad_mult;
+  TC_REQUIRE(heads_ok(a.heads), "radar_chain_bwd: heads=%d", a.heads);
+  k.qscale = a.qscale; k.rlph = 64 / a.heads; k.tokens = a.tokens; k.RI = a.RI; k.T = a.T; k.pad_mult = a.pad_mult;
   k.rdrop = a.drop;
   k.detp = a.det_device;
   // 8 rows when asked, or when the rule's automatic height for M rows is beyond 4; anything else runs 4.  Not the rule's

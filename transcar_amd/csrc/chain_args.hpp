@@ -11,7 +11,16 @@ namespace tc {
 inline tc_linear kv_half(const tc_mha& m, int C) {
   return tc_linear{m.in_proj.w ? m.in_proj.w + (size_t)C * C : nullptr, m.in_proj.b ? m.in_proj.b + C : nullptr};
 }
-inline float radar_qscale(int C) { return 1.0f / sqrtf((float)(C / TC_RADAR_HEADS)); }
+// 1 / sqrt(head dimension) of the fusion attention at H heads
+inline float radar_qscale(int C, int H) { return 1.0f / sqrtf((float)(C / H)); }
+// both halves of tc_head_weights.num_heads, as every entry that takes the struct checks them (`what`: the message's prefix)
+inline int check_head_counts(const tc_head_weights* w, const char* what) {
+  TC_REQUIRE(w->embed_dims == 256 && heads_ok(decoder_heads(w)), "%sembed_dims=%d num_heads=%d (256 with 4, 8 or 16 heads supported)",
+             what, w->embed_dims, decoder_heads(w));
+  TC_REQUIRE(heads_ok(radar_heads(w)), "%sradar_num_heads=%d (the upper 16 bits of num_heads: 0, 4, 8 or 16 supported)", what,
+             radar_heads(w));
+  return 0;
+}
 inline void copy_pc(float (&dst)[6], const float* pc) { for (int i = 0; i < 6; ++i) dst[i] = pc[i]; }
 // the box fusion layer r refines: the decoder's last box, then the layer below's output (HEAD:615-617)
 inline const float* layer_box_prev(int r, const float* last_box, const float* all_bbox_preds, int rows, int code) {
@@ -42,7 +51,7 @@ inline RadarChainArgs radar_chain_args(const tc_head_weights* w, int first_layer
   rc.qf = qf; rc.ref_last = ref_last; rc.box_m = box_m; rc.tokens = tokens; rc.RI = w->radar_in_dims;
   for (int r = 0; first_layer + r < TC_MAX_RADAR_LAYERS; ++r) { rc.kv[r] = kv[first_layer + r]; rc.w[r] = w->radar[first_layer + r]; }
   rc.nlayers = num_layers; rc.Q = w->num_query; rc.T = T; rc.pad_mult = pad_mult; rc.code = w->code_size;
-  rc.ncls = w->num_classes; rc.M = rows; rc.qscale = radar_qscale(w->embed_dims);
+  rc.ncls = w->num_classes; rc.M = rows; rc.heads = radar_heads(w); rc.qscale = radar_qscale(w->embed_dims, rc.heads);
   copy_pc(rc.pc, w->pc_range);
   rc.all_cls = all_cls + (size_t)first_layer * rows * w->num_classes;
   rc.all_box = all_box + (size_t)first_layer * rows * w->code_size;
@@ -71,7 +80,7 @@ inline RadarAttnArgs radar_attn_args(const tc_head_weights* w, int r, const floa
                                      const float* box_prev, const float* tokens, int B, int T, int pad_mult, float* attn_out,
                                      int* hit_counts, float qscale = 1.0f) {
   return radar_attn_args(qproj, kv, r == 0 ? cxy : box_prev, r == 0 ? 2 : w->code_size, box_prev, w->code_size, tokens,
-                         w->radar_in_dims, B, w->num_query, T, w->embed_dims, TC_RADAR_HEADS, pad_mult, w->radar[r].radius_min,
+                         w->radar_in_dims, B, w->num_query, T, w->embed_dims, radar_heads(w), pad_mult, w->radar[r].radius_min,
                          w->radar[r].radius_max, attn_out, hit_counts, qscale);
 }
 

@@ -124,8 +124,7 @@ static int check_dims(const tc_head_weights* w) {
   TC_REQUIRE(w != nullptr, "weights pointer is null");
   TC_REQUIRE(w->abi_version == TC_ABI_VERSION, "tc_head_weights.abi_version=%d, library=%d",
              w->abi_version, TC_ABI_VERSION);
-  TC_REQUIRE(w->embed_dims == 256 && heads_ok(w->num_heads), "embed_dims=%d num_heads=%d (256 with 4, 8 or 16 heads supported)",
-             w->embed_dims, w->num_heads);
+  TC_TRY(check_head_counts(w, ""));
   TC_REQUIRE(w->num_layers >= 1 && w->num_layers <= TC_MAX_LAYERS, "num_layers=%d", w->num_layers);
   TC_REQUIRE(w->num_radar_layers >= 0 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
              "num_radar_layers=%d (0 .. %d supported)", w->num_radar_layers, TC_MAX_RADAR_LAYERS);
@@ -222,7 +221,7 @@ static const float* l0_consts_of(const tc_head_weights* packed_view, int variant
 // chain `d` (pre-gather workgroups: the layer's reference points are final since the previous chain).
 static int launch_layer_attn_core(const tc_head_weights* w, int B, const tc_head_options& opt, const HeadWs& h, int variant,
                                   DecoderChainArgs& d, hipStream_t s) {
-  const int Q = w->num_query, C = w->embed_dims, H = w->num_heads, rows = B * Q;
+  const int Q = w->num_query, C = w->embed_dims, H = decoder_heads(w), rows = B * Q;
   const DropK* drop = opt.decoder_dropout_p > 0.0f ? &d.drop : nullptr;
   if (variant_mm(variant) != 1)
     return launch_self_attn_core(h.qk, h.qk + C, 2 * C, h.vt, h.qpad, h.attn_o, C, B, Q, H, C / H, s, drop);
@@ -243,7 +242,7 @@ static int launch_layer_attn_core(const tc_head_weights* w, int B, const tc_head
 static int fused_decoder_layers(const tc_head_weights* w, const tc_feats_nhwc* feats, int B, const float* lidar2img,
                                 float img_h, float img_w, const RadarEncodeArgs* re, unsigned long long* pairs,
                                 const tc_head_options& opt, const HeadWs& h, bool refine, bool folded, hipStream_t s) {
-  const int Q = w->num_query, C = w->embed_dims, L = w->num_layers, H = w->num_heads, rows = B * Q;
+  const int Q = w->num_query, C = w->embed_dims, L = w->num_layers, H = decoder_heads(w), rows = B * Q;
   const float* qe = w->query_embedding;
   // the radar encoders and K/V projections do not depend on the decoder: they ride in the launches of two
   // decoder layers as extra workgroups (chain_dual_kernel): layers 0 and 1 in the one-call forward; the LAST
@@ -653,7 +652,7 @@ int tc_radar_gated_xattn_fwd(const tc_mha* w, const float* query, const float* c
                              int pad_mult, float radius_min, float radius_max, float* out,
                              int* hit_counts, void* workspace, size_t workspace_bytes,
                              tc_stream_t stream) {
-  TC_REQUIRE(C == 256 && num_heads == TC_RADAR_HEADS, "radar_xattn: C=%d heads=%d (256/%d supported)", C, num_heads, TC_RADAR_HEADS);
+  TC_REQUIRE(C == 256 && heads_ok(num_heads), "radar_xattn: C=%d num_heads=%d (256 with 4, 8 or 16 heads supported)", C, num_heads);
   TC_REQUIRE(workspace_bytes >= tc_radar_xattn_workspace_bytes(B, Q, T, C), "radar_xattn: workspace too small");
   TC_TRY(check_radar_radii(radius_min, radius_max, "radar_xattn"));
   hipStream_t s = as_stream(stream);
@@ -667,7 +666,7 @@ int tc_radar_gated_xattn_fwd(const tc_mha* w, const float* query, const float* c
   GemmArgs g;
   g.X = query; g.ldx = C; g.W = w->in_proj.w; g.ldw = C; g.bias = w->in_proj.b;
   g.Y = qproj; g.ldy = C; g.M = rows; g.K = C; g.N = C;
-  g.scale = 1.0f / sqrtf((float)(C / num_heads)); g.scale_cols = C;
+  g.scale = radar_qscale(C, num_heads); g.scale_cols = C;
   TC_TRY(launch_gemm(g, s));
   TC_TRY(launch_radar_attn(radar_attn_args(qproj, kv, centre_xy, 2, box, code_size, radar_xy, 2, B, Q, T, C, num_heads, pad_mult,
                                            radius_min, radius_max, rattn, hits), s));
@@ -830,7 +829,7 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
   // QKV projection and softmax(QK^T)V are constants of the checkpoint.  Evaluate them
   // here with the forward's own kernels (prologue chain + attention core, one batch).
   {
-    const int Q = w->num_query, C = w->embed_dims, H = w->num_heads;
+    const int Q = w->num_query, C = w->embed_dims, H = decoder_heads(w);
     const int qpad = ((Q + 15) / 16) * 16;
     float* init_ref = a.take<float>((size_t)Q * 3);
     float* attn_o = a.take<float>((size_t)Q * C);
@@ -934,7 +933,7 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   bool refine = true;
   TC_TRY(decoder_refines(w, &refine));
   hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, L = w->num_layers, H = w->num_heads;
+  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, L = w->num_layers, H = decoder_heads(w);
   const int code = w->code_size, ncls = w->num_classes;
   const int rows = B * Q, rt = B * T;
   const float* pc = w->pc_range;
@@ -1025,7 +1024,7 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
     TC_TRY(linear(h.radar_feat, C, kv_half(rl.attn, C), rt, C, 2 * C, 0, h.kv, 2 * C, s));
     GemmArgs g;
     g.X = qf; g.ldx = C; g.W = rl.attn.in_proj.w; g.ldw = C; g.bias = rl.attn.in_proj.b;
-    g.Y = h.qproj; g.ldy = C; g.M = rows; g.K = C; g.N = C; g.scale = radar_qscale(C); g.scale_cols = C;
+    g.Y = h.qproj; g.ldy = C; g.M = rows; g.K = C; g.N = C; g.scale = radar_qscale(C, radar_heads(w)); g.scale_cols = C;
     TC_TRY(launch_gemm(g, s));
     TC_TRY(launch_radar_attn(radar_attn_args(w, r, h.qproj, h.kv, h.cxy, box_prev, radar_tokens, B, T, pad_mult, h.rattn, hits), s));
     // HEAD:581-586
@@ -1206,6 +1205,7 @@ int tc_radar_attn_core_fwd(const float* qproj, float q_scale, const float* kv,
                            int num_heads, int pad_mult, float radius_min, float radius_max,
                            float* attn_out, int* hit_counts, float dropout_p,
                            unsigned long long dropout_seed, int dropout_site, tc_stream_t stream) {
+  TC_REQUIRE(C == 256 && heads_ok(num_heads), "radar_attn_core: C=%d num_heads=%d (256 with 4, 8 or 16 heads supported)", C, num_heads);
   TC_REQUIRE(attn_out != nullptr && hit_counts != nullptr, "radar_attn_core: NULL output");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core: dropout_p=%g", (double)dropout_p);
   TC_TRY(check_radar_radii(radius_min, radius_max, "radar_attn_core"));
@@ -1222,6 +1222,8 @@ int tc_radar_attn_core_bwd(const float* qproj, float q_scale, const float* kv,
                            const float* attn_out, const float* d_attn, float* dq, float* dkv,
                            float dropout_p, unsigned long long dropout_seed, int dropout_site,
                            tc_stream_t stream) {
+  TC_REQUIRE(C == 256 && heads_ok(num_heads), "radar_attn_core_bwd: C=%d num_heads=%d (256 with 4, 8 or 16 heads supported)", C,
+             num_heads);
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core_bwd: dropout_p=%g", (double)dropout_p);
   TC_TRY(check_radar_radii(radius_min, radius_max, "radar_attn_core_bwd"));
   RadarAttnArgs r = radar_attn_args(qproj, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads, pad_mult,

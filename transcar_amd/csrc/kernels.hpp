@@ -159,6 +159,7 @@ struct RadarChainArgs {
   tc_radar_layer w[TC_MAX_RADAR_LAYERS] = {};
   int nlayers = 0, Q = 0, T = 0, pad_mult = 0, code = 0, ncls = 0, M = 0;
   float qscale = 1.0f; float pc[6] = {0, 0, 0, 0, 0, 0};
+  int heads = TC_RADAR_HEADS;                // of the fusion attention: 4, 8 or 16 (qscale goes with it)
   float* all_cls = nullptr; float* all_box = nullptr; int* hits = nullptr;
   int tile_rows = 0;
   int matrix_path = 0;                       // as DecoderChainArgs
@@ -189,6 +190,7 @@ struct RadarBwdChainArgs {
   const float* tokens = nullptr; int RI = 0, T = 0, pad_mult = 0;
   int nlayers = 0, Q = 0, M = 0, code = 0, ncls = 0;
   float qscale = 1.0f;
+  int heads = TC_RADAR_HEADS;                  // as RadarChainArgs
   DropK drop = DropK{0, 0, 1.0f, 0, 1500, 0, 0, 0};
   int tile_rows = 0;
   const DetAcc* det_device = nullptr;          // deterministic mode: a device copy of the thread's DetAcc (launch_det_store)
@@ -232,6 +234,10 @@ int launch_rowops_selfcheck(int n_blocks, unsigned long long seed, unsigned long
 // ---- self_attn.hip ---------------------------------------------------------
 // head counts of the decoder's self-attention at embed_dims 256: head dimension 64, 32, 16
 inline bool heads_ok(int num_heads) { return num_heads == 4 || num_heads == 8 || num_heads == 16; }
+// the two halves of tc_head_weights.num_heads (transcar_hip.h TC_NUM_HEADS_PACK): the radar fusion attention takes the
+// same three counts, and an upper half of 0 is its default
+inline int decoder_heads(const tc_head_weights* w) { return TC_NUM_HEADS_DECODER(w->num_heads); }
+inline int radar_heads(const tc_head_weights* w) { return TC_NUM_HEADS_RADAR(w->num_heads); }
 // q,k: [B*Q, ld] token-major with head h at column h*D; vt: [B, C, ldt] (V transposed), C = H*D; head dimension D: 16, 32, 64
 // drop (may be null / thr 0 = eval): dropout on the attention probabilities, index ((b*H+h)*Q+i)*Q+j
 int launch_self_attn_core(const float* q, const float* k, int ld, const float* vt, int ldt,

@@ -578,10 +578,26 @@ __device__ __forceinline__ int radar_gate_count(float cx, float cy, float b3, fl
   return count;
 }
 
+// A head of the fusion attention is `lph` consecutive lanes of the row's wave (a lane holds 4 channels): 64 / heads =
+// 16, 8 or 4, wave-uniform.  4, 8 and 16 lanes all lie inside one 16-lane row, and the butterfly adds in the same order
+// at 8 lanes as the three fixed steps it replaces.
+__device__ __forceinline__ float head_sum(float s, int lph) {
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  if (lph >= 8) s += __shfl_xor(s, 4, 64);
+  if (lph >= 16) s += __shfl_xor(s, 8, 64);
+  return s;
+}
+// the dropout index of an attention probability: the reference's [heads, Q, tokens_ref] mask
+__device__ __forceinline__ unsigned radar_prob_index(int row, int lane, int lph, unsigned tokens_ref, int tok) {
+  const unsigned hshift = (unsigned)__ffs(lph) - 1u;        // lph is 4, 8 or 16
+  return (((unsigned)row << (6u - hshift)) + ((unsigned)lane >> hshift)) * tokens_ref + (unsigned)tok;
+}
+
 template <bool DROP = false>
 __device__ __forceinline__ float4 radar_attn_row_g(const GateGeom& gg, float4 q4,
                                                    const float* rxy, int ld_xy, const float* kv,
-                                                   int ldkv, int T, int pad_mult, int lane, int& count,
+                                                   int ldkv, int T, int pad_mult, int lane, int lph, int& count,
                                                    DropK drop = DropK(), int row = 0,
                                                    const unsigned long long* hit_masks = nullptr) {
   // hit_masks (chain.hip, K_RADAR_GATE): the gate of this row already evaluated, one 64-token word per
@@ -613,18 +629,15 @@ __device__ __forceinline__ float4 radar_attn_row_g(const GateGeom& gg, float4 q4
       const float* kvr = kv + (size_t)tok * ldkv + 4 * lane;
       const float4 k4 = ld4(kvr);
       const float4 v4 = ld4(kvr + 256);
-      float s = q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w;
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
+      const float s = head_sum(q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w, lph);
       const float mnew = fmaxf(m, s);
       const float alpha = expf(m - mnew);
       const float pw = (float)mult * expf(s - mnew);
       l = l * alpha + pw;
       float pv = pw;
       if (DROP)
-        pv = drop_keep(drop.seed, drop.site, ((unsigned)row * 8u + (unsigned)(lane >> 3)) * drop.tokens_ref + (unsigned)tok,
-                       drop.thr) ? pw * drop.scale : 0.0f;
+        pv = drop_keep(drop.seed, drop.site, radar_prob_index(row, lane, lph, drop.tokens_ref, tok), drop.thr)
+                 ? pw * drop.scale : 0.0f;
       acc.x = acc.x * alpha + pv * v4.x; acc.y = acc.y * alpha + pv * v4.y;
       acc.z = acc.z * alpha + pv * v4.z; acc.w = acc.w * alpha + pv * v4.w;
       m = mnew;
@@ -641,11 +654,11 @@ template <bool DROP = false>
 __device__ __forceinline__ float4 radar_attn_row(float cx, float cy, float b3, float b6, float b7,
                                                  float rmin, float rmax, float4 q4,
                                                  const float* rxy, int ld_xy, const float* kv,
-                                                 int ldkv, int T, int pad_mult, int lane, int& count,
+                                                 int ldkv, int T, int pad_mult, int lane, int lph, int& count,
                                                  DropK drop = DropK(), int row = 0,
                                                  const unsigned long long* hit_masks = nullptr) {
   const GateGeom gg(cx, cy, b3, b6, b7, rmin, rmax);
-  return radar_attn_row_g<DROP>(gg, q4, rxy, ld_xy, kv, ldkv, T, pad_mult, lane, count, drop, row, hit_masks);
+  return radar_attn_row_g<DROP>(gg, q4, rxy, ld_xy, kv, ldkv, T, pad_mult, lane, lph, count, drop, row, hit_masks);
 }
 
 // ---- backward of the gated attention core for ONE query row (one wavefront) ----------------------
@@ -655,16 +668,10 @@ __device__ __forceinline__ float4 radar_attn_row(float cx, float cy, float b3, f
 // are recomputed over the few hit tokens; dK | dV go to the token rows with atomics.  Returns dq w.r.t. the
 // scaled query (the caller multiplies by the scale).  Used by train.hip (radar_attn_bwd_kernel) and by the
 // backward row chain (chain.hip K_ATTN_BWD).
-__device__ __forceinline__ float head_sum8(float s) {      // 8 lanes = one 32-channel head
-  s += __shfl_xor(s, 1, 64);
-  s += __shfl_xor(s, 2, 64);
-  s += __shfl_xor(s, 4, 64);
-  return s;
-}
 __device__ __forceinline__ float4 radar_attn_bwd_row(float cx, float cy, float b3, float b6, float b7, float rmin,
                                                      float rmax, float4 q4, const float* rxy, int ld_xy,
                                                      const float* kv, float* dkv, int ldkv, int T, int pad_mult,
-                                                     float4 dO, float4 o4, const DropK& drop, int row, int lane,
+                                                     float4 dO, float4 o4, const DropK& drop, int row, int lane, int lph,
                                                      long long* sdkv = nullptr) {      // the shadow of dkv (DetAcc) or null
   // gate geometry: identical to radar_attn_row (HEAD:553-567)
   const float len = expf(b3);
@@ -675,7 +682,7 @@ __device__ __forceinline__ float4 radar_attn_bwd_row(float cx, float cy, float b
   const bool circle = gate_is_circle(rmin);      // once per row: the single circle's literal form is not (d > rad)
   const float rad = circle ? rmax : fminf(fmaxf(len / 2.0f, rmin), rmax);
   const float cn = sqnorm2(cx, cy), fn = sqnorm2(fx, fy), bn = sqnorm2(bxx, byy);
-  const float D = head_sum8(dO.x * o4.x + dO.y * o4.y + dO.z * o4.z + dO.w * o4.w);
+  const float D = head_sum(dO.x * o4.x + dO.y * o4.y + dO.z * o4.z + dO.w * o4.w, lph);
   float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
   float m = -INFINITY, l = 0.f;
   // pass 0: softmax statistics over the hit tokens;  pass 1: gradients
@@ -701,7 +708,7 @@ __device__ __forceinline__ float4 radar_attn_bwd_row(float cx, float cy, float b
         const float mult = (tok == T - 1) ? (float)pad_mult : 1.0f;
         const float* kvr = kv + (size_t)tok * ldkv + 4 * lane;
         const float4 k4 = ld4(kvr);
-        const float sc = head_sum8(q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w);
+        const float sc = head_sum(q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w, lph);
         if (pass == 0) {
           const float mnew = fmaxf(m, sc);
           l = l * expf(m - mnew) + mult * expf(sc - mnew);
@@ -712,10 +719,9 @@ __device__ __forceinline__ float4 radar_attn_bwd_row(float cx, float cy, float b
           // O = sum_j keep_j p_j v_j: dP_j = keep_j (dO . v_j), dV_j = keep_j p_j dO; D = dO . O as without
           float keep = 1.0f;
           if (drop.thr != 0)
-            keep = drop_keep(drop.seed, drop.site,
-                             ((unsigned)row * 8u + (unsigned)(lane >> 3)) * drop.tokens_ref + (unsigned)tok,
-                             drop.thr) ? drop.scale : 0.0f;
-          const float dp = keep * head_sum8(dO.x * v4.x + dO.y * v4.y + dO.z * v4.z + dO.w * v4.w);
+            keep = drop_keep(drop.seed, drop.site, radar_prob_index(row, lane, lph, drop.tokens_ref, tok), drop.thr)
+                       ? drop.scale : 0.0f;
+          const float dp = keep * head_sum(dO.x * v4.x + dO.y * v4.y + dO.z * v4.z + dO.w * v4.w, lph);
           const float ds = pj * (dp - D);
           const float pk = pj * keep;
           dq.x += ds * k4.x; dq.y += ds * k4.y; dq.z += ds * k4.z; dq.w += ds * k4.w;

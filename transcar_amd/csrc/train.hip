@@ -445,6 +445,7 @@ struct RadBwdK {
   const float* qproj; const float* kv; const float* cxy; const float* box; const float* rxy;
   const float* attn_out; const float* d_attn;
   int ldq, ldkv, code, ld_xy, ld_c, B, Q, T, pad_mult;
+  int lph;                     // lanes per head: 64 / heads
   float rmin, rmax, qscale;
   float* dq; float* dkv;
   DropK drop;                  // dropout on the attention probabilities (thr 0 = off)
@@ -465,20 +466,21 @@ __global__ __launch_bounds__(256) void radar_attn_bwd_kernel(RadBwdK p) {
   const float4 dq = radar_attn_bwd_row(cx, cy, bx[3], bx[6], bx[7], p.rmin, p.rmax, q4,
                                        p.rxy + (size_t)b * p.T * p.ld_xy, p.ld_xy, p.kv + (size_t)b * p.T * p.ldkv,
                                        p.dkv + (size_t)b * p.T * p.ldkv, p.ldkv, p.T, p.pad_mult, dO, o4, p.drop, row, lane,
-                                       det_shadow_of(p.det, p.dkv + (size_t)b * p.T * p.ldkv));
+                                       p.lph, det_shadow_of(p.det, p.dkv + (size_t)b * p.T * p.ldkv));
   st4(p.dq + (size_t)row * 256 + 4 * lane,
       make_float4(dq.x * p.qscale, dq.y * p.qscale, dq.z * p.qscale, dq.w * p.qscale));
 }
 
 int launch_radar_attn_bwd(const RadarAttnArgs& a, float qscale, const float* d_attn, float* dq,
                           float* dkv, hipStream_t s) {
-  TC_REQUIRE(a.C == 256 && a.H == 8, "radar_attn_bwd: C=%d H=%d (256/8 supported)", a.C, a.H);
+  TC_REQUIRE(a.C == 256 && heads_ok(a.H), "radar_attn_bwd: C=%d num_heads=%d (256 with 4, 8 or 16 heads supported)", a.C, a.H);
   TC_REQUIRE(a.T > 0 && a.pad_mult >= 1, "radar_attn_bwd: T=%d pad_mult=%d", a.T, a.pad_mult);
   RadBwdK p;
   p.qproj = a.qproj; p.kv = a.kv; p.cxy = a.centre_xy; p.box = a.box; p.rxy = a.radar_xy;
   p.attn_out = a.attn_out; p.d_attn = d_attn;
   p.ldq = a.ldq; p.ldkv = a.ldkv; p.code = a.code; p.ld_xy = a.ld_xy; p.ld_c = a.ld_c;
   p.B = a.B; p.Q = a.Q; p.T = a.T; p.pad_mult = a.pad_mult; p.rmin = a.rmin; p.rmax = a.rmax;
+  p.lph = 64 / a.H;
   p.qscale = qscale; p.dq = dq; p.dkv = dkv; p.drop = a.drop; p.det = current_det();
   const int rows = a.B * a.Q;
   hipLaunchKernelGGL(radar_attn_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, p);

@@ -113,7 +113,7 @@ int ln_bwd(const float* a, const float* b, const tc_lnorm& n, const tc_lnorm& g,
 RadarAttnArgs core_args(const tc_head_weights* w, int r, const Tape& t, const float* box_prev, const float* tokens, int B,
                         int T, int pad_mult, float drop_p, unsigned long long seed) {
   RadarAttnArgs ra = radar_attn_args(w, r, t.L[r].qp, t.L[r].kv, t.cxy, box_prev, tokens, B, T, pad_mult, t.L[r].ao, t.L[r].hits,
-                                     radar_qscale(w->embed_dims));
+                                     radar_qscale(w->embed_dims, radar_heads(w)));
   ra.drop = make_drop(drop_p, seed, 4u * r + 0u, (unsigned)w->num_radar_tokens_ref);
   return ra;
 }
@@ -135,9 +135,8 @@ size_t hits_stride(const tc_head_weights* w, const Tape& t) { return w->num_rada
 
 int check(const tc_head_weights* w, int B, int T) {
   TC_REQUIRE(w != nullptr && w->abi_version == TC_ABI_VERSION, "radar_train: bad weights struct");
-  // (num_heads is the decoder self-attention's; the fusion attention trained here has TC_RADAR_HEADS heads)
-  TC_REQUIRE(w->embed_dims == 256 && heads_ok(w->num_heads), "radar_train: embed_dims=%d num_heads=%d", w->embed_dims,
-             w->num_heads);
+  // (num_heads: the decoder self-attention's count below, the count of the fusion attention trained here above)
+  TC_TRY(check_head_counts(w, "radar_train: "));
   TC_REQUIRE(w->num_radar_layers >= 1 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
              "radar_train: num_radar_layers=%d (1 .. %d supported)", w->num_radar_layers, TC_MAX_RADAR_LAYERS);
   TC_REQUIRE(B >= 1 && T >= 1 && (w->radar_in_dims & 3) == 0, "radar_train: B=%d T=%d", B, T);
@@ -579,7 +578,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   a.d_cls = d_all_cls; a.d_box = d_all_box; a.loss_vals = layer_losses; a.loss_out = layer_losses_clean;
   a.tokens = radar_tokens; a.RI = RI; a.T = T; a.pad_mult = pad_mult;
   a.nlayers = NR; a.Q = Q; a.M = rows; a.code = code; a.ncls = ncls;
-  a.qscale = radar_qscale(C);
+  a.heads = radar_heads(w); a.qscale = radar_qscale(C, a.heads);
   a.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
   {
     // deterministic mode: the chain reads the ranges from a device copy in the last words of the caller's shadow buffer

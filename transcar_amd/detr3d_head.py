@@ -180,7 +180,7 @@ class Detr3DHead(BaseModule):
                  loss_iou=None, train_cfg=None, test_cfg=None, init_cfg=None,
                  with_box_refine=False, as_two_stage=False, bbox_coder=None,
                  num_cls_fcs=2, code_weights=None, outputs='fusion', num_fusion_layers=3, radar_gate=None,
-                 **kwargs):
+                 radar_num_heads=L.TC_RADAR_HEADS, **kwargs):
         super().__init__(init_cfg)
         #: depth N of the radar fusion stack, 1 .. 3 (the reference builds 3): only the first N sets of rf_* / final_*
         #: modules exist, every output has N fusion levels.  Level k reads layers <= k only, so an N-layer head with the
@@ -191,6 +191,9 @@ class Detr3DHead(BaseModule):
         #: the single circle of the paper's radius ablation (a token attended iff not dist > R).  Configuration, like
         #: pc_range: it adds no parameter, so the weights of either kind of head load into the other unchanged
         self.radar_gate = L.check_radar_gate(radar_gate, self.num_fusion_layers)
+        #: heads of the fusion attention rf_multihead_attn{,2,3}: 4, 8 (the reference's, HEAD:129-171) or 16, head dimension
+        #: 64 / 32 / 16.  Configuration too: in_proj / out_proj keep their shapes, a checkpoint records nothing about it
+        self.radar_num_heads = L.check_radar_num_heads(radar_num_heads)
         if outputs not in OUTPUTS:
             raise ValueError("Detr3DHead: outputs=%r (one of 'fusion', 'camera', 'all')" % (outputs,))
         #: what ``forward`` returns as all_cls_scores / all_bbox_preds: 'fusion' the radar fusion levels (three by default; the
@@ -248,7 +251,7 @@ class Detr3DHead(BaseModule):
             setattr(self, nm['final_cls'], _cls_branch(E, self.cls_out_channels))
             setattr(self, nm['final_reg'], _reg_branch(E, self.code_size))
         for nm in names:
-            setattr(self, nm['attn'], nn.MultiheadAttention(E, 8, dropout=0.1))
+            setattr(self, nm['attn'], nn.MultiheadAttention(E, self.radar_num_heads, dropout=0.1))
             setattr(self, nm['linear1'], nn.Linear(E, F))
             setattr(self, nm['linear2'], nn.Linear(F, E))
             for n in ('norm1', 'norm2', 'norm3'):
@@ -410,6 +413,14 @@ class Detr3DHead(BaseModule):
         if any(ly.attentions[0].num_heads != w.num_heads for ly in dec.layers):
             raise NotImplementedError('MultiheadAttention: num_heads differs between decoder layers')
         L.check_num_heads(w.num_heads)
+        # the fusion attention's count rides in the upper half of num_heads (TC_NUM_HEADS_PACK), left 0 at the default 8
+        # (radar_num_heads is a public attribute: checked again, and against the modules the unfused training path reads)
+        rh = L.check_radar_num_heads(self.radar_num_heads)
+        for r in range(L.check_num_fusion_layers(self.num_fusion_layers)):
+            if fusion_modules(self, r).attn.num_heads != rh:
+                raise L.TransCARHipError('Detr3DHead(HIP): radar_num_heads=%r, but fusion layer %d has an attention of %r heads'
+                                         % (rh, r, fusion_modules(self, r).attn.num_heads))
+        w.num_heads = L.pack_num_heads(w.num_heads, rh)
         w.ffn_dims = dec.layers[0].ffns[0].feedforward_channels
         w.num_layers = dec.num_layers
         w.num_cams = dec.layers[0].attentions[1].num_cams
