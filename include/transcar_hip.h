@@ -79,6 +79,16 @@ extern "C" {
 #define TC_LSA_AUTO 0
 #define TC_LSA_SMALL 1
 #define TC_LSA_LARGE 2
+/* The radar input of a head (tc_head_weights.num_radar_tokens_ref, .radar_in_dims; tc_radar_build_tokens*_n,
+ * tc_radar_pack_rows_batch).  num_radar_tokens_ref is the token count N the head attends over -- a frame's first N kept
+ * points, the rest 500.0 pad tokens (HEAD:526-530) -- and the stride of the attention-probability dropout's index:
+ * TC_MIN_RADAR_TOKENS .. TC_MAX_RADAR_TOKENS, TC_RADAR_TOKENS_REF in the reference; 0 reads as TC_RADAR_TOKENS_REF.
+ * radar_in_dims is the feature count of a token, a multiple of 4 from 4 to TC_MAX_RADAR_IN_DIMS (36 in the reference);
+ * columns 0..2 are x, y, z. */
+#define TC_RADAR_TOKENS_REF 1500
+#define TC_MIN_RADAR_TOKENS 64
+#define TC_MAX_RADAR_TOKENS 4096
+#define TC_MAX_RADAR_IN_DIMS 64
 #define TC_ABI_VERSION 13
 
 typedef void* tc_stream_t;
@@ -145,7 +155,12 @@ typedef struct {
    * (tc_head_packed_bytes / tc_head_workspace_bytes and the other size queries return 0).  TC_NUM_HEADS_PACK builds it. */
   int num_query, embed_dims, num_heads, ffn_dims, num_layers;
   int num_cams, num_levels, num_classes, code_size;   /* num_levels: 1 .. TC_MAX_LEVELS */
-  int radar_in_dims, num_radar_layers, num_radar_tokens_ref; /* 36, 1..3, 1500 (0: camera only) */
+  /* radar_in_dims: 4, 8, .. TC_MAX_RADAR_IN_DIMS features per token (36 in the reference; radar_feat0 is [64, radar_in_dims]);
+   * num_radar_layers: 1..3 (0: camera only); num_radar_tokens_ref: TC_MIN_RADAR_TOKENS .. TC_MAX_RADAR_TOKENS, the token count
+   * the head attends over (1500 in the reference, which 0 reads as): the forward, training and backward entries refuse
+   * T above it, pad_mult is num_radar_tokens_ref - T + 1.  A value outside is refused by name by every entry that takes
+   * the struct. */
+  int radar_in_dims, num_radar_layers, num_radar_tokens_ref;
   float pc_range[6];
   const float* query_embedding;     /* [Q, 2C]: (query_pos | query) XFMR:119  */
   tc_linear reference_points;       /* transformer.reference_points [3,C]     */
@@ -326,6 +341,31 @@ typedef struct {
 } tc_radar_frame_desc;
 int tc_radar_build_tokens_batch(const double* raw, const double* times, const tc_radar_frame_desc* desc,
                                 int P, int cap, float* tokens, int T, int* count, tc_stream_t stream);
+
+/* tc_radar_build_tokens / _batch for a head of another token count (tc_head_weights.num_radar_tokens_ref = num_tokens,
+ * TC_MIN_RADAR_TOKENS .. TC_MAX_RADAR_TOKENS; the entries above are these at TC_RADAR_TOKENS_REF): T <= num_tokens, row
+ * T-1 stays a pad row iff T < num_tokens, the head is called with pad_mult = num_tokens - T + 1. */
+int tc_radar_build_tokens_n(const double* raw, const double* times, const int* chan_start, int num_chan,
+                            const double* radar_rot, const double* lidar_rot, const double* point_range,
+                            float* tokens, int T, int num_tokens, int* count, tc_stream_t stream);
+int tc_radar_build_tokens_batch_n(const double* raw, const double* times, const tc_radar_frame_desc* desc,
+                                  int P, int cap, float* tokens, int T, int num_tokens, int* count, tc_stream_t stream);
+
+/* Feature rows that already lie on the device -> the token matrices of P samples in ONE launch (one workgroup per
+ * sample); every input is device-resident, so a captured hipGraph replays on new frames.  The reference's filter and
+ * padding (HEAD:512-530) without its feature arithmetic: for sensors whose rows are not the 18 devkit columns.
+ *   rows         device [total_rows, radar_in_dims] float32; columns 0..2 are x, y, z
+ *   offsets      device [P+1] int32: sample b owns rows offsets[b] .. offsets[b+1]-1 (clamped ascending into
+ *                [0, total_rows]: a bad array reads nothing out of bounds)
+ *   radar_in_dims 4, 8, .. TC_MAX_RADAR_IN_DIMS
+ *   point_range  device [6] float64 or NULL (no filter): x0 y0 z0 x1 y1 z1, strict inequalities on the coordinate
+ *                widened to float64 (HEAD:514-519); a NaN coordinate fails the filter
+ *   tokens       device [P, T, radar_in_dims]: the kept rows in order -- at most T-1 when T < num_tokens (row T-1 stays
+ *                the pad row that carries pad_mult), T otherwise -- then rows of 500.0
+ *   count        device [P] (may be NULL): rows kept BEFORE the truncation (count > the rows written: overflow) */
+int tc_radar_pack_rows_batch(const float* rows, int total_rows, const int* offsets, int P, int radar_in_dims,
+                             const double* point_range, float* tokens, int T, int num_tokens, int* count,
+                             tc_stream_t stream);
 
 /* ---- operators, one per reference call site ---- */
 
@@ -707,6 +747,25 @@ int tc_radar_attn_core_bwd(const float* qproj, float q_scale, const float* kv,
                            const float* attn_out, const float* d_attn, float* dq, float* dkv,
                            float dropout_p, unsigned long long dropout_seed, int dropout_site,
                            tc_stream_t stream);
+
+/* tc_radar_attn_core_fwd / _bwd for a head of another token count: num_tokens (TC_MIN_RADAR_TOKENS ..
+ * TC_MAX_RADAR_TOKENS, T <= num_tokens) is the stride of the probabilities' dropout index, (row * heads + head) *
+ * num_tokens + token; the entries above are these at TC_RADAR_TOKENS_REF (num_tokens = 0 here).  With dropout_p > 0 an
+ * index space rows * heads * num_tokens of 2^32 or more is refused. */
+int tc_radar_attn_core_fwd_n(const float* qproj, float q_scale, const float* kv,
+                           const float* centre_xy, int ld_c, const float* box, int code_size,
+                           const float* radar_xy, int ld_xy, int B, int Q, int T, int C,
+                           int num_heads, int pad_mult, float radius_min, float radius_max,
+                           float* attn_out, int* hit_counts, float dropout_p,
+                           unsigned long long dropout_seed, int dropout_site, int num_tokens, tc_stream_t stream);
+int tc_radar_attn_core_bwd_n(const float* qproj, float q_scale, const float* kv,
+                           const float* centre_xy, int ld_c, const float* box, int code_size,
+                           const float* radar_xy, int ld_xy, int B, int Q, int T, int C,
+                           int num_heads, int pad_mult, float radius_min, float radius_max,
+                           const float* attn_out, const float* d_attn, float* dq, float* dkv,
+                           float dropout_p, unsigned long long dropout_seed, int dropout_site,
+                           int num_tokens, tc_stream_t stream);
+
 /* out[i] = keep(seed, site, i) ? x[i] / (1 - p) : 0 (nn.Dropout in train mode with the counter-based
  * masks described at tc_radar_train_fwd; in place allowed; applied to a gradient with the same
  * (seed, site) it is the backward).  dropout_p / seed / site of the attention core: the mask on the

@@ -197,6 +197,44 @@ def radar_gate_pairs(gate):
     return [tuple(p) for p in gate['radii']]
 
 
+# The radar input of a head (include/transcar_hip.h): the token count it attends over, the features per token and the
+# range of the radar filter.  The defaults are the reference's constants (HEAD:526, 183, 304).
+TC_RADAR_TOKENS_REF = 1500
+TC_MIN_RADAR_TOKENS, TC_MAX_RADAR_TOKENS = 64, 4096
+TC_MAX_RADAR_IN_DIMS = 64
+RADAR_IN_DIMS_REF = 36
+RADAR_POINT_RANGE_REF = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0)
+
+
+def check_radar_input(radar_num_tokens=TC_RADAR_TOKENS_REF, radar_in_dims=RADAR_IN_DIMS_REF, radar_point_range=None):
+    """The library's limits on a head's radar input, checked before anything is built, packed or launched; returns
+    (radar_num_tokens, radar_in_dims, radar_point_range as six floats).
+
+    * ``radar_num_tokens``: TC_MIN_RADAR_TOKENS .. TC_MAX_RADAR_TOKENS tokens attended per frame (a frame's first N kept
+      points; the reference's 1500, HEAD:526-530);
+    * ``radar_in_dims``: 4, 8, .. TC_MAX_RADAR_IN_DIMS features per token, columns 0..2 being x, y, z (36 in the reference);
+    * ``radar_point_range``: (x0, y0, z0, x1, y1, z1) of the radar filter, finite with x0 < x1, y0 < y1, z0 < z1; None is the
+      reference's constant (HEAD:304) -- it does not follow pc_range."""
+    n, f, rng = radar_num_tokens, radar_in_dims, radar_point_range
+    if isinstance(n, bool) or not isinstance(n, int) or not TC_MIN_RADAR_TOKENS <= n <= TC_MAX_RADAR_TOKENS:
+        raise TransCARHipError('Detr3DHead(HIP): radar_num_tokens=%r is not supported (%d .. %d tokens)'
+                               % (n, TC_MIN_RADAR_TOKENS, TC_MAX_RADAR_TOKENS))
+    if isinstance(f, bool) or not isinstance(f, int) or not 4 <= f <= TC_MAX_RADAR_IN_DIMS or f % 4:
+        raise TransCARHipError('Detr3DHead(HIP): radar_in_dims=%r is not supported (4, 8, .. %d features per token)'
+                               % (f, TC_MAX_RADAR_IN_DIMS))
+    if rng is None:
+        rng = RADAR_POINT_RANGE_REF
+    ok = isinstance(rng, (list, tuple)) and len(rng) == 6 and \
+        all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in rng)
+    if ok:
+        rng = tuple(float(v) for v in rng)
+        ok = all(abs(v) < float('inf') for v in rng) and all(rng[i] < rng[3 + i] for i in range(3))   # (a NaN fails both)
+    if not ok:
+        raise TransCARHipError('Detr3DHead(HIP): radar_point_range=%r is not supported ((x0, y0, z0, x1, y1, z1), finite, '
+                               'x0 < x1, y0 < y1, z0 < z1)' % (radar_point_range,))
+    return n, f, rng
+
+
 def cam_pregather_supported(embed_dims, num_levels, num_cams):
     """The shapes the camera pre-gather (tc_head_options.cam_pregather) runs:
     C = 256, 4 levels, at most 8 cameras.  Others take the chain's own gather,
@@ -325,6 +363,10 @@ SIGNATURES = {
     'tc_radar_build_tokens': (_i, [_vp, _vp, _P(_i), _i, _P(C.c_double), _P(C.c_double),
                                    _P(C.c_double), _vp, _i, _vp, _vp]),
     'tc_radar_build_tokens_batch': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    'tc_radar_build_tokens_n': (_i, [_vp, _vp, _P(_i), _i, _P(C.c_double), _P(C.c_double),
+                                     _P(C.c_double), _vp, _i, _i, _vp, _vp]),
+    'tc_radar_build_tokens_batch_n': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    'tc_radar_pack_rows_batch': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     'tc_linear_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'tc_add_layernorm_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'tc_refine_reference_fwd': (_i, [_vp, _i, _vp, _vp, _i, _vp]),
@@ -400,6 +442,12 @@ SIGNATURES = {
     'tc_radar_attn_core_fwd': (_i, [_vp, _f, _vp, _vp, _i, _vp, _i, _vp, _i,
                                     _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp,
                                     _f, C.c_ulonglong, _i, _vp]),
+    'tc_radar_attn_core_fwd_n': (_i, [_vp, _f, _vp, _vp, _i, _vp, _i, _vp, _i,
+                                      _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp,
+                                      _f, C.c_ulonglong, _i, _i, _vp]),
+    'tc_radar_attn_core_bwd_n': (_i, [_vp, _f, _vp, _vp, _i, _vp, _i, _vp, _i,
+                                      _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp,
+                                      _vp, _vp, _f, C.c_ulonglong, _i, _i, _vp]),
     'tc_dropout': (_i, [_vp, _i, _i, _f, C.c_ulonglong, _i, _vp, _vp]),
     'tc_radar_attn_core_bwd': (_i, [_vp, _f, _vp, _vp, _i, _vp, _i, _vp, _i,
                                     _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp,

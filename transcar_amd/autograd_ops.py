@@ -145,13 +145,15 @@ class _RadarAttnCore(Function):
         scale = 1.0 / float(Cd // heads) ** 0.5
         meta = (scale, int(ld_c), box.shape[-1], tokens.shape[-1], B, Q, T, Cd, int(heads),
                 int(pad_mult), float(rmin), float(rmax))
-        L.check(L.lib().tc_radar_attn_core_fwd(
+        # drop = (p, seed, site[, num_tokens]): num_tokens is the stride of the probabilities' dropout index, the head's
+        # radar_num_tokens (left out: the reference's 1500)
+        ctx.drop = (float(drop[0]), int(drop[1]), int(drop[2]), int(drop[3]) if len(drop) > 3 else L.TC_RADAR_TOKENS_REF)
+        L.check(L.lib().tc_radar_attn_core_fwd_n(
             _p(qproj), scale, _p(kv), _p(centre), meta[1], _p(box), meta[2], _p(tokens), meta[3],
             B, Q, T, Cd, meta[8], meta[9], meta[10], meta[11], _p(out), _p(hits),
-            float(drop[0]), int(drop[1]), int(drop[2]), L.stream_ptr()),
-            'tc_radar_attn_core_fwd')
+            ctx.drop[0], ctx.drop[1], ctx.drop[2], ctx.drop[3], L.stream_ptr()),
+            'tc_radar_attn_core_fwd_n')
         ctx.meta = meta
-        ctx.drop = (float(drop[0]), int(drop[1]), int(drop[2]))
         ctx.save_for_backward(qproj, kv, centre, box, tokens, out)
         ctx.mark_non_differentiable(hits)
         return out, hits
@@ -164,10 +166,10 @@ class _RadarAttnCore(Function):
         d_out = _c(d_out)
         dq = torch.empty_like(qproj)
         dkv = _zeros_like(kv)
-        L.check(L.lib().tc_radar_attn_core_bwd(
+        L.check(L.lib().tc_radar_attn_core_bwd_n(
             _p(qproj), scale, _p(kv), _p(centre), ld_c, _p(box), code, _p(tokens), ld_xy,
             B, Q, T, Cd, heads, pad_mult, rmin, rmax, _p(out), _p(d_out), _p(dq), _p(dkv),
-            ctx.drop[0], ctx.drop[1], ctx.drop[2], L.stream_ptr()), 'tc_radar_attn_core_bwd')
+            ctx.drop[0], ctx.drop[1], ctx.drop[2], ctx.drop[3], L.stream_ptr()), 'tc_radar_attn_core_bwd_n')
         return dq, dkv, None, None, None, None, None, None, None, None, None
 
 

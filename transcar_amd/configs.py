@@ -78,7 +78,7 @@ IMG_SHAPE = (928, 1600, 3)
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
              num_levels=None, num_heads=None, num_classes=None,
              num_fusion_layers=None, pc_range=None, post_center_range=None, radar_gate=None,
-             radar_num_heads=None):
+             radar_num_heads=None, radar_num_tokens=None, radar_in_dims=None, radar_point_range=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -95,15 +95,22 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     the assigner together (the configs write one ``point_cloud_range`` into all
     three, CFG:74, :85, :112; the result then carries ``train_cfg``, as
     ``train_cfg(pc_range)`` gives it); post_center_range sets the coder's
-    (CFG:84).  The radar filter's range is no config value: the reference
-    writes it as a constant (HEAD:304).  radar_gate sets the distance gate of
+    (CFG:84).  The radar filter's range does not follow pc_range: the
+    reference writes it as a constant (HEAD:304), which is the default of
+    radar_point_range.  radar_gate sets the distance gate of
     the fusion layers (``_lib.check_radar_gate``: the reference head's three
     circles with other clamp pairs, or ``dict(type='circle', radii=[R, ...])``,
     the single circle of the paper's radius ablation; the reference writes its
     radii as constants, HEAD:567, 635, 693).  radar_num_heads sets the head
     count of the fusion attention rf_multihead_attn{,2,3} (the reference writes
     8, HEAD:129-171; 4, 8 or 16): the key is added only for a count other than
-    8, it adds no parameter."""
+    8, it adds no parameter.  radar_num_tokens (64 .. 4096), radar_in_dims (4,
+    8, .. 64) and radar_point_range set the head's radar input
+    (``_lib.check_radar_input``): the tokens attended per frame, the features
+    per token (``radar_feat_encoder.0`` becomes Linear(radar_in_dims, 64)) and
+    the radar filter's range; the reference writes 1500, 36 and
+    +-51.2 / +-51.2 / -5 .. 3 m as constants (HEAD:526, 183, 304), and a key is
+    added only for another value."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -144,6 +151,16 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
         from ._lib import check_radar_num_heads, TC_RADAR_HEADS
         if check_radar_num_heads(radar_num_heads) != TC_RADAR_HEADS:
             cfg['radar_num_heads'] = radar_num_heads
+    if radar_num_tokens is not None or radar_in_dims is not None or radar_point_range is not None:
+        from . import _lib as L
+        n, f, rng = L.check_radar_input(L.TC_RADAR_TOKENS_REF if radar_num_tokens is None else radar_num_tokens,
+                                        L.RADAR_IN_DIMS_REF if radar_in_dims is None else radar_in_dims, radar_point_range)
+        if n != L.TC_RADAR_TOKENS_REF:
+            cfg['radar_num_tokens'] = n
+        if f != L.RADAR_IN_DIMS_REF:
+            cfg['radar_in_dims'] = f
+        if rng != L.RADAR_POINT_RANGE_REF:
+            cfg['radar_point_range'] = list(rng)
     return cfg
 
 

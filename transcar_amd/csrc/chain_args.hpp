@@ -21,6 +21,32 @@ inline int check_head_counts(const tc_head_weights* w, const char* what) {
              radar_heads(w));
   return 0;
 }
+// The radar input of a head: tokens the reference would attend over (its padded count, the stride of the attention-probability
+// dropout's index; 0 reads as TC_RADAR_TOKENS_REF, as a zeroed radar head count reads as TC_RADAR_HEADS) and features per token.
+inline int radar_tokens_ref(const tc_head_weights* w) { return w->num_radar_tokens_ref != 0 ? w->num_radar_tokens_ref : TC_RADAR_TOKENS_REF; }
+inline int check_radar_input(const tc_head_weights* w, const char* what) {
+  TC_REQUIRE(w->num_radar_layers <= 0 || (radar_tokens_ref(w) >= TC_MIN_RADAR_TOKENS && radar_tokens_ref(w) <= TC_MAX_RADAR_TOKENS),
+             "%snum_radar_tokens_ref=%d (%d .. %d supported; 0: %d)", what, w->num_radar_tokens_ref, TC_MIN_RADAR_TOKENS,
+             TC_MAX_RADAR_TOKENS, TC_RADAR_TOKENS_REF);
+  // (a camera-only head reads no token: its feature count only keeps the alignment every caller so far was held to)
+  TC_REQUIRE((w->radar_in_dims & 3) == 0 && (w->num_radar_layers <= 0 || (w->radar_in_dims >= 4 && w->radar_in_dims <= TC_MAX_RADAR_IN_DIMS)),
+             "%sradar_in_dims=%d (4, 8, .. %d supported)", what, w->radar_in_dims, TC_MAX_RADAR_IN_DIMS);
+  return 0;
+}
+// the forward, training and backward entries: the launch's T against the head's token count ...
+inline int check_radar_tokens(const tc_head_weights* w, int T, const char* what) {
+  TC_REQUIRE(w->num_radar_layers <= 0 || T <= radar_tokens_ref(w), "%sT=%d is above num_radar_tokens_ref=%d", what, T,
+             radar_tokens_ref(w));
+  return 0;
+}
+// ... and, where the attention probabilities are dropped out (dropout_p > 0), their index (row * heads + head) * N + token against 32 bits
+inline int check_radar_dropout_index(const tc_head_weights* w, int B, float dropout_p, const char* what) {
+  if (!(dropout_p > 0.0f)) return 0;            // no mask is drawn: no index
+  const unsigned long long n = (unsigned long long)B * w->num_query * radar_heads(w) * radar_tokens_ref(w);
+  TC_REQUIRE(n < (1ull << 32), "%srows * heads * num_radar_tokens_ref = %d * %d * %d = %llu does not fit the dropout index (2^32)",
+             what, B * w->num_query, radar_heads(w), radar_tokens_ref(w), n);
+  return 0;
+}
 inline void copy_pc(float (&dst)[6], const float* pc) { for (int i = 0; i < 6; ++i) dst[i] = pc[i]; }
 // the box fusion layer r refines: the decoder's last box, then the layer below's output (HEAD:615-617)
 inline const float* layer_box_prev(int r, const float* last_box, const float* all_bbox_preds, int rows, int code) {

@@ -134,7 +134,8 @@ static int check_dims(const tc_head_weights* w) {
              "num_points=%d (num_cams * num_levels * num_points <= %d supported)", w->num_points, TC_MAX_CAM_LOGITS);
   TC_REQUIRE(w->num_classes >= 1 && w->num_classes <= TC_MAX_CLASSES, "num_classes=%d (1 .. %d supported)", w->num_classes,
              TC_MAX_CLASSES);
-  TC_REQUIRE((w->ffn_dims & 31) == 0 && (w->radar_in_dims & 3) == 0, "ffn_dims/radar_in_dims alignment");
+  TC_REQUIRE((w->ffn_dims & 31) == 0, "ffn_dims=%d (a multiple of 32)", w->ffn_dims);
+  TC_TRY(check_radar_input(w, ""));
   for (int r = 0; r < w->num_radar_layers; ++r)
     TC_TRY(check_radar_radii(w->radar[r].radius_min, w->radar[r].radius_max, "radar", r));
   return 0;
@@ -474,12 +475,33 @@ int tc_radar_build_tokens(const double* raw, const double* times, const int* cha
                           const double* radar_rot, const double* lidar_rot, const double* point_range,
                           float* tokens, int T, int* count, tc_stream_t stream) {
   return launch_radar_ingest(raw, times, chan_start, num_chan, radar_rot, lidar_rot, point_range, tokens, T,
-                             count, as_stream(stream));
+                             TC_RADAR_TOKENS_REF, count, as_stream(stream));
+}
+
+int tc_radar_build_tokens_n(const double* raw, const double* times, const int* chan_start, int num_chan,
+                            const double* radar_rot, const double* lidar_rot, const double* point_range,
+                            float* tokens, int T, int num_tokens, int* count, tc_stream_t stream) {
+  TC_TRY(check_radar_budget("radar_build_tokens_n", T, num_tokens));
+  return launch_radar_ingest(raw, times, chan_start, num_chan, radar_rot, lidar_rot, point_range, tokens, T,
+                             num_tokens, count, as_stream(stream));
 }
 
 int tc_radar_build_tokens_batch(const double* raw, const double* times, const tc_radar_frame_desc* desc,
                                 int P, int cap, float* tokens, int T, int* count, tc_stream_t stream) {
-  return launch_radar_ingest_batch(raw, times, desc, P, cap, tokens, T, count, as_stream(stream));
+  return launch_radar_ingest_batch(raw, times, desc, P, cap, tokens, T, TC_RADAR_TOKENS_REF, count, as_stream(stream));
+}
+
+int tc_radar_build_tokens_batch_n(const double* raw, const double* times, const tc_radar_frame_desc* desc,
+                                  int P, int cap, float* tokens, int T, int num_tokens, int* count, tc_stream_t stream) {
+  TC_TRY(check_radar_budget("radar_build_tokens_batch_n", T, num_tokens));
+  return launch_radar_ingest_batch(raw, times, desc, P, cap, tokens, T, num_tokens, count, as_stream(stream));
+}
+
+int tc_radar_pack_rows_batch(const float* rows, int total_rows, const int* offsets, int P, int radar_in_dims,
+                             const double* point_range, float* tokens, int T, int num_tokens, int* count,
+                             tc_stream_t stream) {
+  return launch_radar_pack_rows(rows, total_rows, offsets, P, radar_in_dims, point_range, tokens, T, num_tokens, count,
+                                as_stream(stream));
 }
 
 int tc_linear_fwd(const float* x, const float* x2, const float* w, const float* b, const float* res,
@@ -707,6 +729,7 @@ int tc_radar_fusion_fwd(const tc_head_weights* packed_view, const float* hs_last
   TC_REQUIRE(hs_last && prev_box && radar_tokens && all_cls_scores && all_bbox_preds && (first_layer > 0 || ref_last),
              "radar_fusion: null argument");
   TC_REQUIRE(B >= 1 && T >= 1 && pad_mult >= 1, "radar_fusion: B=%d T=%d pad_mult=%d", B, T, pad_mult);
+  TC_TRY(check_radar_tokens(w, T, "radar_fusion: "));
   tc_head_options opt;
   TC_TRY(read_options(options, opt));
   HeadWs h;
@@ -925,6 +948,7 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   TC_REQUIRE(B >= 1, "B=%d", B);
   TC_REQUIRE(w->num_radar_layers == 0 || (radar_tokens != nullptr && T >= 1 && pad_mult >= 1),
              "radar tokens missing (T=%d pad_mult=%d)", T, pad_mult);
+  TC_TRY(check_radar_tokens(w, T, ""));
   HeadWs h;
   const size_t need = head_ws_layout(w, B, T, workspace, workspace_bytes, &h);
   TC_REQUIRE(need <= workspace_bytes, "workspace too small: need %zu, have %zu", need, workspace_bytes);
@@ -1199,19 +1223,41 @@ int tc_box_add_ref_bwd(const float* d_box, int code_size, float* d_prev_box, int
   return launch_box_ref_bwd(d_box, code_size, d_prev_box, M, as_stream(stream));
 }
 
+// the attention probabilities' dropout index (row * heads + head) * num_tokens + token of the two core entries
+static int check_core_stride(const char* who, int B, int Q, int T, int num_heads, int num_tokens, float dropout_p) {
+  TC_TRY(check_radar_budget(who, T, num_tokens));
+  const unsigned long long n = (unsigned long long)B * Q * num_heads * num_tokens;
+  TC_REQUIRE(dropout_p == 0.0f || n < (1ull << 32), "%s: rows * heads * num_tokens = %d * %d * %d = %llu does not fit the dropout index (2^32)",
+             who, B * Q, num_heads, num_tokens, n);
+  return 0;
+}
+
 int tc_radar_attn_core_fwd(const float* qproj, float q_scale, const float* kv,
                            const float* centre_xy, int ld_c, const float* box, int code_size,
                            const float* radar_xy, int ld_xy, int B, int Q, int T, int C,
                            int num_heads, int pad_mult, float radius_min, float radius_max,
                            float* attn_out, int* hit_counts, float dropout_p,
                            unsigned long long dropout_seed, int dropout_site, tc_stream_t stream) {
+  return tc_radar_attn_core_fwd_n(qproj, q_scale, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads,
+                                  pad_mult, radius_min, radius_max, attn_out, hit_counts, dropout_p, dropout_seed, dropout_site,
+                                  0, stream);
+}
+
+int tc_radar_attn_core_fwd_n(const float* qproj, float q_scale, const float* kv,
+                             const float* centre_xy, int ld_c, const float* box, int code_size,
+                             const float* radar_xy, int ld_xy, int B, int Q, int T, int C,
+                             int num_heads, int pad_mult, float radius_min, float radius_max,
+                             float* attn_out, int* hit_counts, float dropout_p,
+                             unsigned long long dropout_seed, int dropout_site, int num_tokens, tc_stream_t stream) {
+  if (num_tokens != 0) TC_TRY(check_core_stride("radar_attn_core_n", B, Q, T, num_heads, num_tokens, dropout_p));
+  const unsigned stride = num_tokens != 0 ? (unsigned)num_tokens : (unsigned)TC_RADAR_TOKENS_REF;
   TC_REQUIRE(C == 256 && heads_ok(num_heads), "radar_attn_core: C=%d num_heads=%d (256 with 4, 8 or 16 heads supported)", C, num_heads);
   TC_REQUIRE(attn_out != nullptr && hit_counts != nullptr, "radar_attn_core: NULL output");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core: dropout_p=%g", (double)dropout_p);
   TC_TRY(check_radar_radii(radius_min, radius_max, "radar_attn_core"));
   RadarAttnArgs r = radar_attn_args(qproj, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads, pad_mult,
                                     radius_min, radius_max, attn_out, hit_counts, q_scale);
-  r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, 1500u);
+  r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, stride);
   return launch_radar_attn(r, as_stream(stream));
 }
 
@@ -1222,13 +1268,27 @@ int tc_radar_attn_core_bwd(const float* qproj, float q_scale, const float* kv,
                            const float* attn_out, const float* d_attn, float* dq, float* dkv,
                            float dropout_p, unsigned long long dropout_seed, int dropout_site,
                            tc_stream_t stream) {
+  return tc_radar_attn_core_bwd_n(qproj, q_scale, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads,
+                                  pad_mult, radius_min, radius_max, attn_out, d_attn, dq, dkv, dropout_p, dropout_seed,
+                                  dropout_site, 0, stream);
+}
+
+int tc_radar_attn_core_bwd_n(const float* qproj, float q_scale, const float* kv,
+                             const float* centre_xy, int ld_c, const float* box, int code_size,
+                             const float* radar_xy, int ld_xy, int B, int Q, int T, int C,
+                             int num_heads, int pad_mult, float radius_min, float radius_max,
+                             const float* attn_out, const float* d_attn, float* dq, float* dkv,
+                             float dropout_p, unsigned long long dropout_seed, int dropout_site,
+                             int num_tokens, tc_stream_t stream) {
+  if (num_tokens != 0) TC_TRY(check_core_stride("radar_attn_core_bwd_n", B, Q, T, num_heads, num_tokens, dropout_p));
+  const unsigned stride = num_tokens != 0 ? (unsigned)num_tokens : (unsigned)TC_RADAR_TOKENS_REF;
   TC_REQUIRE(C == 256 && heads_ok(num_heads), "radar_attn_core_bwd: C=%d num_heads=%d (256 with 4, 8 or 16 heads supported)", C,
              num_heads);
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_attn_core_bwd: dropout_p=%g", (double)dropout_p);
   TC_TRY(check_radar_radii(radius_min, radius_max, "radar_attn_core_bwd"));
   RadarAttnArgs r = radar_attn_args(qproj, kv, centre_xy, ld_c, box, code_size, radar_xy, ld_xy, B, Q, T, C, num_heads, pad_mult,
                                     radius_min, radius_max, const_cast<float*>(attn_out), nullptr);     // (q_scale: the launch's)
-  r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, 1500u);
+  r.drop = make_drop(dropout_p, dropout_seed, (unsigned)dropout_site, stride);
   return launch_radar_attn_bwd(r, q_scale, d_attn, dq, dkv, as_stream(stream));
 }
 

@@ -332,9 +332,13 @@ int launch_nchw_to_nhwc_levels(const float* const* src, float* const* dst, int n
 // ---- radar_ingest.hip ------------------------------------------------------
 int launch_radar_ingest(const double* raw, const double* times, const int* chan_start_host, int num_chan,
                         const double* radar_rot_host, const double* lidar_rot_host,
-                        const double* point_range_host, float* tokens, int T, int* count, hipStream_t s);
+                        const double* point_range_host, float* tokens, int T, int budget, int* count, hipStream_t s);
 int launch_radar_ingest_batch(const double* raw, const double* times, const tc_radar_frame_desc* desc, int P, int cap,
-                              float* tokens, int T, int* count, hipStream_t s);
+                              float* tokens, int T, int budget, int* count, hipStream_t s);
+// budget: the head's token count (tc_head_weights.num_radar_tokens_ref; 1500 in the reference): T < budget keeps row T - 1 a pad row
+int check_radar_budget(const char* who, int T, int budget);
+int launch_radar_pack_rows(const float* rows, int total_rows, const int* offsets, int P, int F, const double* point_range,
+                           float* tokens, int T, int budget, int* count, hipStream_t s);
 
 // ---- decode.hip ------------------------------------------------------------
 // the rows NMSFreeCoder keeps, compacted in score order (CODER:62-84): [B,max_num,9] / [B,max_num] / [B,max_num]

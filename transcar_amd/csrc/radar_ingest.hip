@@ -7,7 +7,9 @@
 // the point-range filter (HEAD:304, 512-521) as an order-preserving compaction, float32
 // conversion and the 500.0 padding (HEAD:523-530).  All arithmetic in float64 like the reference,
 // rounded to float32 once.  With a fixed T this makes the radar input of a frame pipeline lane a
-// pure device-side refill (pad_mult = 1500 - T + 1 does not depend on the frame).
+// pure device-side refill (pad_mult = N - T + 1 does not depend on the frame; N = the head's token budget, 1500 in the
+// reference).  Feature rows that already exist on the device (a sensor with another column set, a producer that builds
+// them itself) take radar_pack_rows_kernel below: the same filter, compaction and padding, no feature arithmetic.
 #include "kernels.hpp"
 
 namespace tc {
@@ -15,13 +17,13 @@ namespace tc {
 namespace {
 
 constexpr int RI_RAW = 18, RI_OUT = 36, MAX_CHAN = 8, NT = 256;
-constexpr int REF_TOKENS = 1500;     // HEAD:526: the reference always attends over 1500 tokens
 
 struct IngestK {
   const double* raw;        // [N, 18] point-major
   const double* times;      // [N]
   int chan_start[MAX_CHAN + 1];
   int num_chan, N, T;
+  int budget;               // the head's token count (Detr3DHead.radar_num_tokens; REF_TOKENS in the reference)
   double rot_radar[MAX_CHAN][9];   // radar -> ego, row-major
   double rot_ref[9];               // lidar -> ego (applied transposed)
   double lo[3], hi[3];
@@ -53,10 +55,10 @@ __device__ __forceinline__ void radar_ingest_body(const IngestK& k) {
     if (m) atomicMax(&tmax[c], m);
   }
   __syncthreads();
-  // T < 1500: row T - 1 stands for the 1500 - T + 1 pad rows the head folds into it (pad_mult), so it must
+  // T < budget: row T - 1 stands for the budget - T + 1 pad rows the head folds into it (pad_mult), so it must
   // STAY a 500.0 pad row -- a real return there would be weighted pad_mult times by the gate and the
   // attention.  At most T - 1 points are kept then; `count` (> T - 1) tells the caller the frame did not fit.
-  const int limit = k.T < REF_TOKENS ? k.T - 1 : k.T;
+  const int limit = k.T < k.budget ? k.T - 1 : k.T;
   for (int i0 = 0; i0 < k.N; i0 += NT) {
     const int i = i0 + tid;
     bool keep = false;
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(NT) void radar_ingest_kernel(IngestK k) { radar_ing
 // P samples in one launch, workgroup b = sample b, its parameters from a DEVICE-resident descriptor: the form a
 // captured hipGraph can replay on new frames (a lane's producer refills raw rows + descriptors, nothing is baked
 // into the graph's kernel arguments).  raw [P, cap, 18], times [P, cap], tokens [P, T, 36], count [P].
-struct IngestBatchK { const double* raw; const double* times; const tc_radar_frame_desc* desc; int cap, T; float* tokens; int* count; };
+struct IngestBatchK { const double* raw; const double* times; const tc_radar_frame_desc* desc; int cap, T, budget; float* tokens; int* count; };
 __global__ __launch_bounds__(NT) void radar_ingest_batch_kernel(IngestBatchK a) {
   __shared__ IngestK sk;
   const int b = blockIdx.x;
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(NT) void radar_ingest_batch_kernel(IngestBatchK a) 
       v = c == 0 ? 0 : (v < prev ? prev : v > a.cap ? a.cap : v);
       sk.chan_start[c] = v; prev = v;
     }
-    sk.N = sk.chan_start[nc]; sk.T = a.T;
+    sk.N = sk.chan_start[nc]; sk.T = a.T; sk.budget = a.budget;
     for (int c = 0; c < MAX_CHAN; ++c)
       for (int j = 0; j < 9; ++j) sk.rot_radar[c][j] = c < nc ? d.radar_rot[c * 9 + j] : 0.0;
     for (int j = 0; j < 9; ++j) sk.rot_ref[j] = d.lidar_rot[j];
@@ -145,26 +147,104 @@ __global__ __launch_bounds__(NT) void radar_ingest_batch_kernel(IngestBatchK a) 
   radar_ingest_body(sk);
 }
 
+// Feature rows that are already on the device -> the token matrix: P samples in one launch, workgroup b = sample b, rows
+// [offsets[b], offsets[b + 1]) of the slab `rows` [total, F].  The range filter of HEAD:514-519 on columns 0..2 (strict,
+// the coordinate widened to double: a NaN fails it; range == nullptr: no filter), order-preserving compaction by ballot
+// and prefix, at most T - 1 rows when T < budget (row T - 1 stays the pad row), 500.0 behind them; count[b] = rows kept
+// BEFORE the truncation.  Offsets, range and rows are device-resident: a captured graph replays on new frames.
+struct PackRowsK { const float* rows; const int* offsets; const double* range; int total, F, T, budget; float* tokens; int* count; };
+__global__ __launch_bounds__(NT) void radar_pack_rows_kernel(PackRowsK a) {
+  __shared__ int wave_cnt[NT / 64];
+  __shared__ int dst[NT];            // destination token of the chunk's row, -1: dropped
+  __shared__ int base, span[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+  if (tid == 0) {
+    int prev = 0;                    // ascending, inside [0, total]: a bad offsets array cannot read out of bounds
+    for (int c = 0; c <= b + 1; ++c) {
+      int v = a.offsets[c];
+      v = v < prev ? prev : v > a.total ? a.total : v;
+      prev = v;
+      if (c >= b) span[c - b] = v;
+    }
+    base = 0;
+  }
+  __syncthreads();
+  const int r0 = span[0], r1 = span[1], F = a.F;
+  const int limit = a.T < a.budget ? a.T - 1 : a.T;
+  float* tok = a.tokens + (size_t)b * a.T * F;
+  double lo[3], hi[3];
+  const bool filter = a.range != nullptr;
+  for (int j = 0; j < 3; ++j) { lo[j] = filter ? a.range[j] : 0.0; hi[j] = filter ? a.range[3 + j] : 0.0; }
+  for (int i0 = r0; i0 < r1; i0 += NT) {
+    const int i = i0 + tid;
+    bool keep = false;
+    if (i < r1) {
+      const float* r = a.rows + (size_t)i * F;
+      const double x = (double)r[0], y = (double)r[1], z = (double)r[2];
+      keep = !filter || (x > lo[0] && y > lo[1] && z > lo[2] && x < hi[0] && y < hi[1] && z < hi[2]);
+    }
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+    off += __popcll(bal & ((1ull << lane) - 1ull));
+    dst[tid] = keep && off < limit ? off : -1;
+    __syncthreads();
+    // the chunk's rows, element by element: consecutive threads read consecutive floats
+    const int n = min(NT, r1 - i0);
+    const float* src = a.rows + (size_t)i0 * F;
+    for (int e = tid; e < n * F; e += NT) {
+      const int r = e / F, d = dst[r];
+      if (d >= 0) tok[(size_t)d * F + (e - r * F)] = src[e];
+    }
+    if (tid == 0) { int s = base; for (int w = 0; w < NT / 64; ++w) s += wave_cnt[w]; base = s; }
+    __syncthreads();
+  }
+  const int filled = min(base, limit);
+  for (int j = filled * F + tid; j < a.T * F; j += NT) tok[j] = 500.0f;
+  if (tid == 0 && a.count != nullptr) a.count[b] = base;
+}
+
 }  // namespace
 
+int check_radar_budget(const char* who, int T, int budget) {
+  TC_REQUIRE(budget >= TC_MIN_RADAR_TOKENS && budget <= TC_MAX_RADAR_TOKENS, "%s: num_tokens=%d (%d .. %d supported)", who, budget,
+             TC_MIN_RADAR_TOKENS, TC_MAX_RADAR_TOKENS);
+  TC_REQUIRE(T >= 1 && T <= budget, "%s: T=%d (1 .. num_tokens=%d)", who, T, budget);
+  return 0;
+}
+
+int launch_radar_pack_rows(const float* rows, int total_rows, const int* offsets, int P, int F, const double* point_range,
+                           float* tokens, int T, int budget, int* count, hipStream_t s) {
+  TC_REQUIRE(P >= 1 && total_rows >= 0, "radar_pack_rows: P=%d total_rows=%d", P, total_rows);
+  TC_REQUIRE(F >= 4 && F <= TC_MAX_RADAR_IN_DIMS && (F & 3) == 0, "radar_pack_rows: radar_in_dims=%d (4, 8, .. %d supported)", F,
+             TC_MAX_RADAR_IN_DIMS);
+  TC_TRY(check_radar_budget("radar_pack_rows", T, budget));
+  TC_REQUIRE(offsets != nullptr && tokens != nullptr && (rows != nullptr || total_rows == 0), "radar_pack_rows: null argument");
+  PackRowsK a{rows, offsets, point_range, total_rows, F, T, budget, tokens, count};
+  hipLaunchKernelGGL(radar_pack_rows_kernel, dim3(P), dim3(NT), 0, s, a);
+  return check_launch("radar_pack_rows");
+}
+
 int launch_radar_ingest_batch(const double* raw, const double* times, const tc_radar_frame_desc* desc, int P, int cap,
-                              float* tokens, int T, int* count, hipStream_t s) {
+                              float* tokens, int T, int budget, int* count, hipStream_t s) {
   static_assert(TC_MAX_RADAR_CHANNELS == MAX_CHAN, "descriptor layout");
   TC_REQUIRE(P >= 1 && cap >= 1 && T >= 1, "radar_ingest_batch: P=%d cap=%d T=%d", P, cap, T);
   TC_REQUIRE(raw != nullptr && times != nullptr && desc != nullptr && tokens != nullptr, "radar_ingest_batch: null argument");
-  IngestBatchK a{raw, times, desc, cap, T, tokens, count};
+  IngestBatchK a{raw, times, desc, cap, T, budget, tokens, count};
   hipLaunchKernelGGL(radar_ingest_batch_kernel, dim3(P), dim3(NT), 0, s, a);
   return check_launch("radar_ingest_batch");
 }
 
 int launch_radar_ingest(const double* raw, const double* times, const int* chan_start_host, int num_chan,
                         const double* radar_rot_host, const double* lidar_rot_host,
-                        const double* point_range_host, float* tokens, int T, int* count, hipStream_t s) {
+                        const double* point_range_host, float* tokens, int T, int budget, int* count, hipStream_t s) {
   TC_REQUIRE(num_chan >= 1 && num_chan <= MAX_CHAN, "radar_ingest: num_chan=%d (1..%d)", num_chan, MAX_CHAN);
   TC_REQUIRE(tokens != nullptr && T >= 1 && chan_start_host != nullptr && radar_rot_host != nullptr &&
                  lidar_rot_host != nullptr && point_range_host != nullptr, "radar_ingest: null argument");
   IngestK k;
-  k.raw = raw; k.times = times; k.num_chan = num_chan; k.T = T; k.tokens = tokens; k.count = count;
+  k.raw = raw; k.times = times; k.num_chan = num_chan; k.T = T; k.budget = budget; k.tokens = tokens; k.count = count;
   for (int c = 0; c <= MAX_CHAN; ++c) k.chan_start[c] = chan_start_host[c <= num_chan ? c : num_chan];
   TC_REQUIRE(k.chan_start[0] == 0, "radar_ingest: chan_start[0] must be 0");
   for (int c = 0; c < num_chan; ++c)

@@ -114,7 +114,7 @@ RadarAttnArgs core_args(const tc_head_weights* w, int r, const Tape& t, const fl
                         int T, int pad_mult, float drop_p, unsigned long long seed) {
   RadarAttnArgs ra = radar_attn_args(w, r, t.L[r].qp, t.L[r].kv, t.cxy, box_prev, tokens, B, T, pad_mult, t.L[r].ao, t.L[r].hits,
                                      radar_qscale(w->embed_dims, radar_heads(w)));
-  ra.drop = make_drop(drop_p, seed, 4u * r + 0u, (unsigned)w->num_radar_tokens_ref);
+  ra.drop = make_drop(drop_p, seed, 4u * r + 0u, (unsigned)radar_tokens_ref(w));
   return ra;
 }
 
@@ -139,7 +139,9 @@ int check(const tc_head_weights* w, int B, int T) {
   TC_TRY(check_head_counts(w, "radar_train: "));
   TC_REQUIRE(w->num_radar_layers >= 1 && w->num_radar_layers <= TC_MAX_RADAR_LAYERS,
              "radar_train: num_radar_layers=%d (1 .. %d supported)", w->num_radar_layers, TC_MAX_RADAR_LAYERS);
-  TC_REQUIRE(B >= 1 && T >= 1 && (w->radar_in_dims & 3) == 0, "radar_train: B=%d T=%d", B, T);
+  TC_REQUIRE(B >= 1 && T >= 1, "radar_train: B=%d T=%d", B, T);
+  TC_TRY(check_radar_input(w, "radar_train: "));
+  TC_TRY(check_radar_tokens(w, T, "radar_train: "));
   return 0;
 }
 
@@ -220,8 +222,9 @@ int tc_radar_train_fwd(const tc_head_weights* w, const float* hs_last, const flo
                        float dropout_p, unsigned long long dropout_seed, tc_stream_t stream) {
   TC_TRY(check(w, B, T));
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_fwd: dropout_p=%g", (double)dropout_p);
+  TC_TRY(check_radar_dropout_index(w, B, dropout_p, "radar_train_fwd: "));
   const bool drop = dropout_p > 0.0f;
-  const unsigned tref = (unsigned)w->num_radar_tokens_ref;
+  const unsigned tref = (unsigned)radar_tokens_ref(w);
   Tape t;
   TC_TRY(open_call("radar_train_fwd", w, B, T, tape, tape_bytes, &t));
   hipStream_t s = as_stream(stream);
@@ -302,6 +305,7 @@ int tc_radar_train_fwd_fused(const tc_head_weights* packed_view, const float* hs
   TC_TRY(check(w, B, T));
   TC_REQUIRE(w->l0_attn_out != nullptr, "radar_train_fwd_fused: packed_view was not produced by tc_head_pack_weights");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_fwd_fused: dropout_p=%g", (double)dropout_p);
+  TC_TRY(check_radar_dropout_index(w, B, dropout_p, "radar_train_fwd_fused: "));
   // (round 3 refused T > 512 here although the chains take any T <= 1500 -- beyond 512 tokens the gate's hit masks
   // are not kept in LDS and the attention step re-evaluates the gate, as the inference chain does; a frame with more
   // than 511 radar points then failed mid-training: ADVICE r3.  Covered at T = 576 and T = 1500 by
@@ -324,7 +328,7 @@ int tc_radar_train_fwd_fused(const tc_head_weights* packed_view, const float* hs
   RadarChainArgs rc = radar_chain_args(w, 0, w->num_radar_layers, kv, hs_last, ref_last, last_box, radar_tokens, B, T, pad_mult,
                                        all_cls_scores, all_bbox_preds, t.L[0].hits);
   rc.tape = slots; rc.tape_stride = layer_stride(w, t); rc.hits_stride = hits_stride(w, t);
-  rc.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
+  rc.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)radar_tokens_ref(w));
   return launch_radar_chain(rc, s);
 }
 
@@ -336,8 +340,9 @@ int tc_radar_train_bwd(const tc_head_weights* w, const tc_head_weights* grads, c
   TC_TRY(check(w, B, T));
   TC_REQUIRE(grads != nullptr, "radar_train_bwd: grads is NULL");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_bwd: dropout_p=%g", (double)dropout_p);
+  TC_TRY(check_radar_dropout_index(w, B, dropout_p, "radar_train_bwd: "));
   const bool drop = dropout_p > 0.0f;
-  const unsigned tref = (unsigned)w->num_radar_tokens_ref;
+  const unsigned tref = (unsigned)radar_tokens_ref(w);
   const float keep_scale = drop ? 1.0f / (1.0f - dropout_p) : 1.0f;
   Tape t;
   TC_TRY(open_call("radar_train_bwd", w, B, T, tape, tape_bytes, &t));
@@ -544,6 +549,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   TC_TRY(check(w, B, T));
   TC_REQUIRE(grads != nullptr && workspace != nullptr, "radar_train_bwd_fused: null argument");
   TC_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "radar_train_bwd_fused: dropout_p=%g", (double)dropout_p);
+  TC_TRY(check_radar_dropout_index(w, B, dropout_p, "radar_train_bwd_fused: "));
   TC_REQUIRE(w->code_size <= 10, "radar_train_bwd_fused: code_size=%d", w->code_size);
   Tape t;
   BwdWs ws;
@@ -579,7 +585,7 @@ int tc_radar_train_bwd_fused_ex(const tc_head_weights* w, const tc_head_weights*
   a.tokens = radar_tokens; a.RI = RI; a.T = T; a.pad_mult = pad_mult;
   a.nlayers = NR; a.Q = Q; a.M = rows; a.code = code; a.ncls = ncls;
   a.heads = radar_heads(w); a.qscale = radar_qscale(C, a.heads);
-  a.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)w->num_radar_tokens_ref);
+  a.drop = make_drop(dropout_p, dropout_seed, 0u, (unsigned)radar_tokens_ref(w));
   {
     // deterministic mode: the chain reads the ranges from a device copy in the last words of the caller's shadow buffer
     // (tc_radar_train_bwd_fused_det)

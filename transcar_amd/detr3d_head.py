@@ -120,7 +120,7 @@ def _rank():
 def radar_frames(img_metas):
     """[img_metas[i]['radar']]; a frame without one is refused."""
     if any('radar' not in m for m in img_metas):
-        raise KeyError("img_metas[i]['radar'] is required: raw sweeps (transcar_amd/radar.py) or an [n,36] feature array")
+        raise KeyError("img_metas[i]['radar'] is required: raw sweeps (transcar_amd/radar.py) or an [n,radar_in_dims] feature array")
     return [m['radar'] for m in img_metas]
 
 
@@ -180,8 +180,19 @@ class Detr3DHead(BaseModule):
                  loss_iou=None, train_cfg=None, test_cfg=None, init_cfg=None,
                  with_box_refine=False, as_two_stage=False, bbox_coder=None,
                  num_cls_fcs=2, code_weights=None, outputs='fusion', num_fusion_layers=3, radar_gate=None,
-                 radar_num_heads=L.TC_RADAR_HEADS, **kwargs):
+                 radar_num_heads=L.TC_RADAR_HEADS, radar_num_tokens=L.TC_RADAR_TOKENS_REF,
+                 radar_in_dims=L.RADAR_IN_DIMS_REF, radar_point_range=None, **kwargs):
         super().__init__(init_cfg)
+        #: the radar input (_lib.check_radar_input).  radar_num_tokens N: a frame's first N kept points are attended, the
+        #: rest dropped (HEAD:526-530 at 1500); pad_mult = N - T + 1.  radar_in_dims F: features per token, columns 0..2 being
+        #: x, y, z -- radar_feat_encoder.0 is Linear(F, 64), so a checkpoint of another F fails to load by shape; with
+        #: F != 36 raw sweeps are refused (their 36 features are the reference's) and frames arrive as [n,F] rows.
+        #: radar_point_range: the radar filter's range, by default the reference's constant (HEAD:304) -- it does not
+        #: follow pc_range.  Raw sweeps and [n,F] rows given as CUDA tensors are always filtered by it; [n,F] rows on the
+        #: host (numpy, CPU tensors) are filtered by a range other than the default and taken as they are at the default
+        #: (the reference's rows come out of its own filter).  Configuration: a trainer checkpoint records none of the three
+        self.radar_num_tokens, self.radar_in_dims, self.radar_point_range = L.check_radar_input(
+            radar_num_tokens, radar_in_dims, radar_point_range)
         #: depth N of the radar fusion stack, 1 .. 3 (the reference builds 3): only the first N sets of rf_* / final_*
         #: modules exist, every output has N fusion levels.  Level k reads layers <= k only, so an N-layer head with the
         #: first N layers' weights computes levels [0:N] of the three-layer head
@@ -263,7 +274,7 @@ class Detr3DHead(BaseModule):
             nn.Linear(3, E), nn.LayerNorm(E), nn.ReLU(inplace=True),
             nn.Linear(E, E), nn.LayerNorm(E), nn.ReLU(inplace=True))
         self.radar_feat_encoder = nn.Sequential(
-            nn.Linear(36, 64), nn.ReLU(inplace=True),
+            nn.Linear(self.radar_in_dims, 64), nn.ReLU(inplace=True),
             nn.Linear(64, 128), nn.ReLU(inplace=True),
             nn.Linear(128, E), nn.ReLU(inplace=True))
         # constructed but never used by the reference forward (HEAD:191-195); kept at every fusion depth, so that the
@@ -302,6 +313,7 @@ class Detr3DHead(BaseModule):
         self._plugin_graphs = None
         self.plugin_graphs = True
         self._radar_stage = {}
+        self._radar_range = None        # ((device, radar_point_range), the range as six float64 on the device)
         self._ingest_streams = {}       # device -> side stream of the two-phase forward (forward_nhwc(fill_tokens=))
         #: bumped whenever a device buffer a captured hipGraph may point at (packed weights,
         #: lane workspaces) is re-allocated: FramePipeline refuses to replay a stale capture
@@ -437,8 +449,12 @@ class Detr3DHead(BaseModule):
         L.check_num_points(w.num_points, w.num_cams, w.num_levels)
         L.check_num_classes(self.cls_out_channels)
         w.num_classes, w.code_size = self.cls_out_channels, self.code_size
-        w.radar_in_dims = radar.NUM_FEATURES
-        w.num_radar_tokens_ref = radar.NUM_RADAR_TOKENS
+        # (public attributes: checked again, and the feature count against the encoder the checkpoint was loaded into)
+        w.num_radar_tokens_ref, w.radar_in_dims, _ = L.check_radar_input(self.radar_num_tokens, self.radar_in_dims,
+                                                                         self.radar_point_range)
+        if self.radar_feat_encoder[0].in_features != w.radar_in_dims:
+            raise L.TransCARHipError('Detr3DHead(HIP): radar_in_dims=%r, but radar_feat_encoder.0 takes %d features'
+                                     % (w.radar_in_dims, self.radar_feat_encoder[0].in_features))
         for i in range(6):
             w.pc_range[i] = float(self.pc_range[i])
         w.query_embedding = self.query_embedding.weight.data_ptr()
@@ -582,7 +598,7 @@ class Detr3DHead(BaseModule):
         img_hw = img_metas[0]['img_shape'][0][:2]
         B = l2i.shape[0]
         # (a decoder-only forward reads no token: the tensor only gives the workspace layout its T)
-        tokens = torch.empty((B, 64, radar.NUM_FEATURES), dtype=torch.float32, device=dev)
+        tokens = torch.empty((B, 64, self.radar_in_dims), dtype=torch.float32, device=dev)
         base = self.forward_nhwc(feats_nhwc, l2i, img_hw, tokens, 1, aux=True, decoder_only=True,
                                  options=self.forward_options)
         cls, box = self.decoder_outputs(base['aux'])
@@ -653,52 +669,82 @@ class Detr3DHead(BaseModule):
     # forward
     # ------------------------------------------------------------------
     def radar_tokens(self, img_metas, device, T=None, ingest=None):
-        """img_metas[i]['radar'] -> (tokens [B,T,36] on device, pad_mult).
+        """img_metas[i]['radar'] -> (tokens [B,T,radar_in_dims] on device, pad_mult).
 
         Raw sweeps (the dict layout of transcar_amd/radar.py, what the devkit returns for HEAD:301-309) are
         turned into the 36-feature rows ON THE DEVICE (``self.radar_ingest == 'device'``, the default:
         tc_radar_build_tokens_batch -- the raw rows go up as they are, one launch builds all samples' tokens;
         float64 arithmetic as HEAD:311-521, bit-equal to the host builder except the six rotated-velocity
         columns, which agree to 1 ulp); [n,36] feature arrays, or ``ingest='host'``, take the numpy route of
-        the reference.  T: fixed token count (default: the smallest multiple of 64 that holds the frame)."""
+        the reference; [n,F] rows given as CUDA tensors are filtered (radar_point_range), compacted and padded on
+        the device (tc_radar_pack_rows_batch).  T: fixed token count (default: the smallest multiple of 64 that holds the
+        frame, at most radar_num_tokens)."""
         tokens, pad_mult, fill = self._radar_tokens_plan(radar_frames(img_metas), device, T, ingest)
         if fill is not None:
             fill()
         return tokens, pad_mult
 
     def _radar_tokens_plan(self, raws, device, T=None, ingest=None):
-        """-> (tokens [B,T,36], pad_mult, fill).  Device ingest of raw sweeps: `tokens` is allocated but EMPTY and
+        """-> (tokens [B,T,F], pad_mult, fill).  Device ingest of raw sweeps: `tokens` is allocated but EMPTY and
         ``fill()`` does the work (host packing of the raw rows, three H2D copies per sample, one launch) -- so that
         ``forward`` can enqueue the part of the decoder that does not read the tokens first
-        (tc_head_options.phase).  Otherwise the tokens are ready and fill is None."""
+        (tc_head_options.phase).  Otherwise the tokens are ready and fill is None: [n,F] rows that are CUDA tensors
+        take tc_radar_pack_rows_batch (filter, compaction and padding on the device), numpy rows the host route."""
         mode = ingest or self.radar_ingest
+        N, F, rng = L.check_radar_input(self.radar_num_tokens, self.radar_in_dims, self.radar_point_range)
+        if F != radar.NUM_FEATURES and any(isinstance(r, dict) for r in raws):
+            raise L.TransCARHipError(
+                "Detr3DHead(HIP): radar_in_dims=%d: raw radar sweeps give the %d features of the reference; hand "
+                "img_metas[i]['radar'] over as [n,%d] feature rows" % (F, radar.NUM_FEATURES, F))
         if mode == 'device' and all(isinstance(r, dict) for r in raws):
             n_raw = [sum(int(np.asarray(r['points'][c]).shape[1]) for c in radar.RADAR_CHANNELS) for r in raws]
             if T is None:
-                T = ops.radar_tokens_T(max(n_raw))       # n_raw >= the points the range filter keeps
+                T = ops.radar_tokens_T(max(n_raw), num_tokens=N)       # n_raw >= the points the range filter keeps
             B = len(raws)
             cap = max(64, ((max(n_raw) + 63) // 64) * 64)
             key = (B, str(device))
             stage = self._radar_stage.get(key)
-            if stage is None or stage.cap < cap:
-                stage = self._radar_stage[key] = ops.RadarRawStage(B, cap, device)
-            tokens = torch.empty((B, T, radar.NUM_FEATURES), dtype=torch.float32, device=device)
+            if stage is None or stage.cap < cap or stage.num_tokens != N or tuple(stage.point_range) != rng:
+                stage = self._radar_stage[key] = ops.RadarRawStage(B, cap, device, point_range=rng, num_tokens=N)
+            tokens = torch.empty((B, T, F), dtype=torch.float32, device=device)
 
             def fill():
                 stage.put_all(raws)              # host pack of every sample, then three H2D copies for the batch
                 stage.build(tokens)
-                if T < radar.NUM_RADAR_TOKENS and max(n_raw) > T - 1:
-                    ops.radar_check_fits(stage.count, T)     # an explicit T: the kept points must fit (one D2H sync)
-            return tokens, radar.NUM_RADAR_TOKENS - T + 1, fill
-        feats = [radar.build_radar_features(r) for r in raws]
-        tokens, pad_mult = radar.pack_tokens(feats, T=T)
+                if T < N and max(n_raw) > T - 1:
+                    ops.radar_check_fits(stage.count, T, N)     # an explicit T: the kept points must fit (one D2H sync)
+            return tokens, N - T + 1, fill
+        if all(torch.is_tensor(r) and r.is_cuda for r in raws):
+            for r in raws:
+                if r.dim() != 2 or r.shape[1] != F or r.dtype != torch.float32:
+                    raise L.TransCARHipError('radar feature rows must be fp32 [n,%d] tensors (radar_in_dims=%d), got %s %s'
+                                             % (F, F, tuple(r.shape), r.dtype))
+            n_rows = [int(r.shape[0]) for r in raws]
+            if T is None:
+                T = ops.radar_tokens_T(max(n_rows), num_tokens=N)
+            rows = torch.cat([r.to(device) for r in raws]) if len(raws) > 1 else raws[0].to(device).contiguous()
+            offsets = torch.tensor(np.concatenate(([0], np.cumsum(n_rows))), dtype=torch.int32).to(device, non_blocking=True)
+            rk = (str(device), rng)
+            if self._radar_range is None or self._radar_range[0] != rk:
+                self._radar_range = (rk, ops.radar_range_tensor(rng, device))
+            tokens, count, pad_mult = ops.radar_pack_rows(rows, offsets, T, N, self._radar_range[1])
+            if T < N and max(n_rows) > T - 1:
+                ops.radar_check_fits(count, T, N)
+            return tokens, pad_mult, None
+        raws = [r.detach().cpu().numpy() if torch.is_tensor(r) else r for r in raws]      # (rows as host tensors)
+        feats = [radar.build_radar_features(r, point_range=rng, num_features=F) for r in raws]
+        if rng != L.RADAR_POINT_RANGE_REF:
+            # a range of the head's own applies to prebuilt rows too, as the device route applies it (at the reference's
+            # constant the host route takes prebuilt rows as their producer filtered them, as it always has)
+            feats = [f[radar.in_range(f, rng)] if not isinstance(r, dict) else f for f, r in zip(feats, raws)]
+        tokens, pad_mult = radar.pack_tokens(feats, T=T, num_tokens=N)
         return torch.from_numpy(tokens).to(device), pad_mult, None
 
     def forward_nhwc(self, feats_nhwc, lidar2img, img_hw, tokens, pad_mult,
                      aux=False, _allow_train=False, lane=0, decoder_only=False,
                      options=None, fill_tokens=None, _out=None):
         """The device-side forward: everything already on the GPU.
-        feats_nhwc: list of [B*N,H,W,C]; lidar2img [B,N,4,4]; tokens [B,T,36].
+        feats_nhwc: list of [B*N,H,W,C]; lidar2img [B,N,4,4]; tokens [B,T,radar_in_dims].
         Only enqueues work on the current stream (graph-capturable).
         lane: forwards that may be in flight at the same time (on different
         streams, transcar_amd/pipeline.py) need different lanes -- each lane
@@ -724,6 +770,9 @@ class Detr3DHead(BaseModule):
                 return dst
             w, packed = _no_radar(w), _no_radar(packed)
         B = lidar2img.shape[0]
+        if tokens.dim() != 3 or tokens.shape[2] != self.radar_in_dims:
+            raise L.TransCARHipError('forward_nhwc: tokens of shape %s, the head takes [B,T,%d] (radar_in_dims=%d)'
+                                     % (tuple(tokens.shape), self.radar_in_dims, self.radar_in_dims))
         T = tokens.shape[1]
         dev = lidar2img.device
         lib = L.lib()
@@ -916,7 +965,7 @@ class Detr3DHead(BaseModule):
             ao, hits = A.radar_attn_core(qp, kv, centre, ld_c, prev_box, tokens,
                                          pad_mult, rmin, rmax,
                                          heads=attn.num_heads,
-                                         drop=(p_attn, seed, 4 * r + 0))
+                                         drop=(p_attn, seed, 4 * r + 0, self.radar_num_tokens))
             if p2 > 0.0:            # qf + gate * rf_dropout2(out_proj(ao)), HEAD:581
                 y = A.dropout(A.linear(ao, attn.out_proj.weight, attn.out_proj.bias),
                               p2, seed, 4 * r + 1)

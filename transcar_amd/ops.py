@@ -359,16 +359,17 @@ def radar_raw_arrays(frame):
     return raw, np.concatenate(times) if start[-1] else np.zeros(0), np.asarray(start, np.int32), rr, lr
 
 
-def radar_build_tokens(frame, T, device, out=None, point_range=None, check=False):
+def radar_build_tokens(frame, T, device, out=None, point_range=None, check=False, num_tokens=None):
     """Radar ingest of one sample on the device (tc_radar_build_tokens, HEAD:301-536): the raw
     rows go up as they are (H2D of N x 19 float64), one launch writes the [T,36] token matrix.
     Returns (tokens [1,T,36] -- ``out`` when given, e.g. a pipeline lane's static tensor --,
     count: int32 device tensor with the number of points kept by the range filter,
-    pad_mult = 1500 - T + 1).  With T < 1500 at most T - 1 points are written (row T - 1 carries
-    pad_mult and stays a pad row); ``check=True`` reads `count` back (one D2H sync) and raises when
-    the frame did not fit -- a pipeline checks its lanes' counts after the replay instead
-    (FramePipeline.radar_overflow)."""
+    pad_mult = N - T + 1), N = ``num_tokens`` (the head's radar_num_tokens; default the reference's 1500).  With T < N at
+    most T - 1 points are written (row T - 1 carries pad_mult and stays a pad row); ``check=True`` reads `count` back
+    (one D2H sync) and raises when the frame did not fit -- a pipeline checks its lanes' counts after the replay
+    instead (FramePipeline.radar_overflow)."""
     from . import radar as R
+    N = R.NUM_RADAR_TOKENS if num_tokens is None else int(num_tokens)
     raw, times, start, rr, lr = radar_raw_arrays(frame)
     n = int(start[-1])
     raw_d = torch.from_numpy(raw).to(device, non_blocking=True) if n else None
@@ -379,13 +380,13 @@ def radar_build_tokens(frame, T, device, out=None, point_range=None, check=False
         raise L.TransCARHipError('out must be a contiguous [1,%d,%d] tensor' % (T, R.NUM_FEATURES))
     count = torch.zeros(1, dtype=torch.int32, device=device)
     pr = (C.c_double * 6)(*[float(v) for v in (point_range or R.POINT_RANGE)])
-    L.check(L.lib().tc_radar_build_tokens(
+    L.check(L.lib().tc_radar_build_tokens_n(
         _p(raw_d), _p(times_d), start.ctypes.data_as(C.POINTER(C.c_int)), len(R.RADAR_CHANNELS),
         rr.ctypes.data_as(C.POINTER(C.c_double)), lr.ctypes.data_as(C.POINTER(C.c_double)), pr,
-        _p(out), int(T), _p(count), L.stream_ptr()), 'tc_radar_build_tokens')
+        _p(out), int(T), N, _p(count), L.stream_ptr()), 'tc_radar_build_tokens_n')
     if check:
-        radar_check_fits(count, T)
-    return out, count, R.NUM_RADAR_TOKENS - T + 1
+        radar_check_fits(count, T, N)
+    return out, count, N - T + 1
 
 
 class RadarRawStage:
@@ -395,10 +396,12 @@ class RadarRawStage:
     matrix) and enqueues its three H2D copies on the current stream; ``build(tokens)`` is ONE launch that
     writes the [P,T,36] token tensor (graph-capturable: nothing of a frame is baked into its arguments)."""
 
-    def __init__(self, P, cap, device, point_range=None):
+    def __init__(self, P, cap, device, point_range=None, num_tokens=None):
         from . import radar as R
         self.P, self.cap, self.device = int(P), int(cap), device
         self.point_range = [float(v) for v in (point_range or R.POINT_RANGE)]
+        #: the token count of the head the stage feeds (Detr3DHead.radar_num_tokens)
+        self.num_tokens = R.NUM_RADAR_TOKENS if num_tokens is None else int(num_tokens)
         dsz = C.sizeof(L.tc_radar_frame_desc)
         self.raw = torch.zeros((P, cap, 18), dtype=torch.float64, device=device)
         self.times = torch.zeros((P, cap), dtype=torch.float64, device=device)
@@ -502,27 +505,97 @@ class RadarRawStage:
         if tokens.dim() != 3 or tokens.shape[0] < n or tokens.shape[2] != R.NUM_FEATURES or not tokens.is_contiguous() \
                 or tokens.dtype != torch.float32:
             raise L.TransCARHipError('tokens must be a contiguous fp32 [>=%d,T,%d] tensor' % (n, R.NUM_FEATURES))
-        L.check(L.lib().tc_radar_build_tokens_batch(_p(self.raw), _p(self.times), _p(self.desc), n, self.cap,
-                                                    _p(tokens), T, _p(self.count), L.stream_ptr()),
-                'tc_radar_build_tokens_batch')
-        return tokens, R.NUM_RADAR_TOKENS - T + 1
+        L.check(L.lib().tc_radar_build_tokens_batch_n(_p(self.raw), _p(self.times), _p(self.desc), n, self.cap,
+                                                      _p(tokens), T, self.num_tokens, _p(self.count), L.stream_ptr()),
+                'tc_radar_build_tokens_batch_n')
+        return tokens, self.num_tokens - T + 1
 
 
-def radar_tokens_T(n_points, granule=64):
+def radar_range_tensor(point_range, device):
+    """The radar filter's range as tc_radar_pack_rows_batch takes it: six float64 on the device."""
+    return torch.tensor([float(v) for v in point_range], dtype=torch.float64).to(device)
+
+
+def radar_pack_rows(rows, offsets, T, num_tokens, point_range=None, out=None, count=None, P=None):
+    """Feature rows on the device -> tokens (tc_radar_pack_rows_batch; one launch, enqueue-only, graph-capturable).
+    rows [total,F] fp32, offsets [P+1] int32 and point_range ([6] float64, or None: no filter), all on the device.
+    -> (tokens [P,T,F] -- ``out`` when given --, count [P] int32: rows kept before the truncation, pad_mult)."""
+    _chk(rows, 'rows')
+    P = int(offsets.numel()) - 1 if P is None else int(P)
+    F = int(rows.shape[-1])
+    if rows.dim() != 2 or offsets.dtype != torch.int32 or not offsets.is_cuda or not offsets.is_contiguous() \
+            or not 1 <= P <= offsets.numel() - 1:
+        raise L.TransCARHipError('radar_pack_rows: rows [total,F] fp32 and offsets [P+1] int32 on the GPU')
+    if point_range is not None and (point_range.dtype != torch.float64 or not point_range.is_cuda or point_range.numel() != 6):
+        raise L.TransCARHipError('radar_pack_rows: point_range must be six float64 on the GPU (radar_range_tensor)')
+    if out is None:
+        out = torch.empty((P, int(T), F), dtype=torch.float32, device=rows.device)
+    if out.dim() != 3 or out.shape[0] < P or tuple(out.shape[1:]) != (int(T), F) or not out.is_contiguous() \
+            or out.dtype != torch.float32:
+        raise L.TransCARHipError('tokens must be a contiguous fp32 [>=%d,%d,%d] tensor' % (P, T, F))
+    if count is None:
+        count = torch.empty(P, dtype=torch.int32, device=rows.device)
+    L.check(L.lib().tc_radar_pack_rows_batch(_p(rows), int(rows.shape[0]), _p(offsets), P, F, _p(point_range), _p(out),
+                                             int(T), int(num_tokens), _p(count), L.stream_ptr()),
+            'tc_radar_pack_rows_batch')
+    return out, count, int(num_tokens) - int(T) + 1
+
+
+class RadarRowsStage:
+    """Feature rows of P samples staged for tc_radar_pack_rows_batch: a device slab rows [P * cap, F] in which frame slot
+    j owns rows j * cap .. (j + 1) * cap - 1 (the fixed offsets a captured graph replays on), and count [P].
+    ``put(slot, rows)`` copies one sample's [n,F] rows (device tensor, or pinned host tensor: asynchronous) to the front of
+    its slot; the rows of the slot behind them carry NaN coordinates, which the range filter drops like any NaN point --
+    so the stage always filters (the head's radar_point_range).  ``build(tokens)`` is ONE launch."""
+
+    def __init__(self, P, cap, in_dims, device, point_range, num_tokens):
+        self.P, self.cap, self.in_dims, self.device = int(P), int(cap), int(in_dims), device
+        self.num_tokens = int(num_tokens)
+        self.rows = torch.full((self.P * self.cap, self.in_dims), float('nan'), dtype=torch.float32, device=device)
+        self.offsets = (torch.arange(self.P + 1, dtype=torch.int32) * self.cap).to(device)
+        self.range = radar_range_tensor(point_range, device)
+        self.count = torch.zeros(self.P, dtype=torch.int32, device=device)
+        self.n_rows = [0] * self.P
+
+    def put(self, slot, rows):
+        n = int(rows.shape[0])
+        if rows.dim() != 2 or rows.shape[1] != self.in_dims or rows.dtype != torch.float32:
+            raise L.TransCARHipError('radar_rows must be an fp32 [n,%d] tensor (radar_in_dims=%d), got %s %s'
+                                     % (self.in_dims, self.in_dims, tuple(rows.shape), rows.dtype))
+        if n > self.cap:
+            raise L.TransCARHipError('radar frame with %d rows, the stage holds %d per sample' % (n, self.cap))
+        dst = self.rows[slot * self.cap:(slot + 1) * self.cap]
+        if n:
+            dst[:n].copy_(rows, non_blocking=True)
+        if self.n_rows[slot] > n:                    # what the slot's previous frame left behind the new one
+            dst[n:self.n_rows[slot], :3] = float('nan')
+        self.n_rows[slot] = n
+        return n
+
+    def build(self, tokens, n=None):
+        """One launch: the first n (default all) slots' rows -> tokens[:n] ([n,T,F], contiguous)."""
+        n = self.P if n is None else int(n)
+        return radar_pack_rows(self.rows, self.offsets, int(tokens.shape[1]), self.num_tokens, self.range, out=tokens,
+                               count=self.count, P=n)[::2]
+
+
+def radar_tokens_T(n_points, granule=64, num_tokens=None):
     """Token count for frames of at most n_points kept (or raw) points: the smallest multiple of `granule`
-    that holds them plus the pad row, at most 1500 (radar.pack_tokens's rule)."""
+    that holds them plus the pad row, at most the head's token count (default 1500; radar.pack_tokens's rule)."""
     from . import radar as R
-    return min(R.NUM_RADAR_TOKENS, ((min(int(n_points), R.NUM_RADAR_TOKENS) + 1 + granule - 1) // granule) * granule)
+    N = R.NUM_RADAR_TOKENS if num_tokens is None else int(num_tokens)
+    return min(N, ((min(int(n_points), N) + 1 + granule - 1) // granule) * granule)
 
 
-def radar_check_fits(count, T):
-    """Raise when the device ingest kept more points than a [T,36] token matrix can hold
-    (T < 1500: T - 1 points + the pad row; T = 1500: the reference's own truncation)."""
+def radar_check_fits(count, T, num_tokens=None):
+    """Raise when the device ingest kept more points than a [T,F] token matrix can hold
+    (T < N: T - 1 points + the pad row; T = N, the head's token count: the reference's own truncation)."""
     from . import radar as R
+    N = R.NUM_RADAR_TOKENS if num_tokens is None else int(num_tokens)
     n = int(count.max().item())
-    if T < R.NUM_RADAR_TOKENS and n > T - 1:
+    if T < N and n > T - 1:
         raise L.TransCARHipError('radar ingest: %d points kept, T=%d holds %d (+ the pad row): use a '
-                                 'larger T (up to %d)' % (n, T, T - 1, R.NUM_RADAR_TOKENS))
+                                 'larger T (up to %d)' % (n, T, T - 1, N))
 
 
 def box_decode_topk(cls_scores, bbox_preds, post_center_range, max_num=300, path=0):

@@ -68,7 +68,7 @@ class FramePipeline:
     """
 
     def __init__(self, head, static_inputs, decode=True, tile_rows=None, options=None, streams=None,
-                 partial_graphs=True, radar_raw_capacity=None):
+                 partial_graphs=True, radar_raw_capacity=None, radar_rows_capacity=None):
         if not static_inputs:
             raise ValueError('at least one lane')
         from .detr3d_head import head_options
@@ -99,10 +99,25 @@ class FramePipeline:
         # N raw points per frame slot + descriptors) and its graph STARTS with the device-side radar ingest
         # (tc_radar_build_tokens_batch, HEAD:301-536) writing the lane's static `tokens`; the producer hands
         # over raw sweeps (`write_inputs(lane, radar_frame=..., slot=j)`: host pack + three small H2D copies)
+        # radar_rows_capacity = n: the same for feature rows that already lie on the device (ops.RadarRowsStage: n rows
+        # of radar_in_dims features per frame slot); the graph starts with tc_radar_pack_rows_batch and the producer hands
+        # over [n,F] rows (`write_inputs(lane, radar_rows=..., slot=j)`: one device copy)
         self.radar_stage = None
-        if radar_raw_capacity:
+        if radar_raw_capacity and radar_rows_capacity:
+            raise TransCARHipError('FramePipeline: radar_raw_capacity and radar_rows_capacity exclude each other')
+        if radar_raw_capacity or radar_rows_capacity:
             dev = self.inputs[0]['l2i'].device
-            self.radar_stage = [ops.RadarRawStage(self.frames_per_launch, int(radar_raw_capacity), dev)
+            for inp in self.inputs:
+                if int(inp['pad_mult']) != head.radar_num_tokens - int(inp['tokens'].shape[1]) + 1:
+                    raise TransCARHipError('FramePipeline: pad_mult=%d with tokens of T=%d, the head has radar_num_tokens=%d'
+                                           % (inp['pad_mult'], inp['tokens'].shape[1], head.radar_num_tokens))
+        if radar_raw_capacity:
+            self.radar_stage = [ops.RadarRawStage(self.frames_per_launch, int(radar_raw_capacity), dev,
+                                                  point_range=head.radar_point_range, num_tokens=head.radar_num_tokens)
+                                for _ in self.inputs]
+        if radar_rows_capacity:
+            self.radar_stage = [ops.RadarRowsStage(self.frames_per_launch, int(radar_rows_capacity), head.radar_in_dims, dev,
+                                                   head.radar_point_range, head.radar_num_tokens)
                                 for _ in self.inputs]
         self.graphs, self.outputs = [], []
         #: (lane, n) -> (graph, outputs): a partly filled lane (``flush`` with n < frames_per_launch valid
@@ -308,7 +323,7 @@ class FramePipeline:
         torch.cuda.current_stream().wait_event(self.done[lane])
 
     def write_inputs(self, lane, nhwc=None, nchw=None, l2i=None, tokens=None, pad_mult=None, slot=None,
-                     radar_frame=None):
+                     radar_frame=None, radar_rows=None):
         """Refill a lane's static inputs in place from the current stream (device tensors or
         pinned host tensors: ``copy_`` is asynchronous), ordered after the lane's previous
         replay.  tokens must have the captured shape and pad_mult (radar.pack_tokens(T=...)).
@@ -319,10 +334,20 @@ class FramePipeline:
         if slot is not None and not 0 <= slot < P:
             raise TransCARHipError('slot %r of %d' % (slot, P))
         self.producer_wait(lane)
+        if radar_rows is not None:
+            # [n,F] feature rows of ONE frame (slot j; slot None: a list with one tensor per slot) for the lane's
+            # device-side packing node
+            if self.radar_stage is None or not isinstance(self.radar_stage[lane], ops.RadarRowsStage):
+                raise TransCARHipError('FramePipeline was built without radar_rows_capacity')
+            frames = [radar_rows] if slot is not None or torch.is_tensor(radar_rows) else list(radar_rows)
+            if slot is None and len(frames) != P:
+                raise TransCARHipError('radar_rows: %d frames for %d slots' % (len(frames), P))
+            for j, fr in enumerate(frames):
+                self.radar_stage[lane].put(slot if slot is not None else j, fr)
         if radar_frame is not None:
             # raw sweeps of ONE frame (slot j; slot None: a list with one frame per slot) for the lane's
             # device-side ingest node
-            if self.radar_stage is None:
+            if self.radar_stage is None or not isinstance(self.radar_stage[lane], ops.RadarRawStage):
                 raise TransCARHipError('FramePipeline was built without radar_raw_capacity')
             frames = [radar_frame] if slot is not None or isinstance(radar_frame, dict) else list(radar_frame)
             if slot is None and len(frames) != P:
@@ -366,10 +391,9 @@ class FramePipeline:
         if self.radar_stage is None:
             return False
         T = int(self.inputs[lane]['tokens'].shape[1])
-        from . import radar as R
         # only the slots the last launch filled: after a partial launch the others hold counts of older frames
         n = self._last[lane][0] if self._last[lane] is not None else self.frames_per_launch
-        return bool(T < R.NUM_RADAR_TOKENS and int(self.radar_stage[lane].count[:n].max().item()) > T - 1)
+        return bool(T < self.head.radar_num_tokens and int(self.radar_stage[lane].count[:n].max().item()) > T - 1)
 
     def wait(self, lane):
         """Block until the lane's last launch has finished.  Also reads the f16-range status the launch left in the

@@ -60,13 +60,13 @@ class PluginGraphs:
             return False
         if getattr(h, 'radar_ingest', 'device') != 'device':
             return False
-        if not all(isinstance(m.get('radar'), dict) for m in img_metas):
-            return False
+        if not all(isinstance(m.get('radar'), dict) for m in img_metas) or h.radar_in_dims != radar.NUM_FEATURES:
+            return False                                      # (raw sweeps at another feature count: the eager path refuses)
         return all(f.is_cuda and f.dtype == torch.float32 for f in mlvl_feats)
 
     def key_of(self, mlvl_feats, img_metas, n_raw):
         h = self.head
-        T = ops.radar_tokens_T(max(n_raw))
+        T = ops.radar_tokens_T(max(n_raw), num_tokens=h.radar_num_tokens)
         cap = max(256, ((max(n_raw) + 255) // 256) * 256)
         o = h.forward_options
         ob = bytes(o) if o is not None else b''
@@ -74,7 +74,7 @@ class PluginGraphs:
         hw = tuple(img_metas[0]['img_shape'][0][:2])
         ncam = len(img_metas[0]['lidar2img'])
         return (len(img_metas), str(mlvl_feats[0].device), fk, T, cap, hw, ob, h.buffers_generation, bool(h.matrix_fallback),
-                torch.cuda.current_stream().cuda_stream, ncam)
+                torch.cuda.current_stream().cuda_stream, ncam, h.radar_num_tokens, tuple(h.radar_point_range))
 
     # ------------------------------------------------------------------
     def forward(self, mlvl_feats, img_metas):
@@ -125,7 +125,7 @@ class PluginGraphs:
         # allocator's hands and change the very addresses the key relies on)
         l2i_np = np.asarray([m['lidar2img'] for m in img_metas], dtype=np.float32)           # [B, N, 4, 4] (XFMR:382-386)
         e.l2i_host = torch.zeros(l2i_np.shape, dtype=torch.float32).pin_memory()
-        e.stage = ops.RadarRawStage(B, cap, dev)
+        e.stage = ops.RadarRawStage(B, cap, dev, point_range=h.radar_point_range, num_tokens=h.radar_num_tokens)
         e.status_host = torch.zeros(1 + B, dtype=torch.int32).pin_memory()
         Q, ncls, code, mx = h.num_query, h.cls_out_channels, h.code_size, h.bbox_coder.max_num
         NF = e.NF = h.num_fusion_layers
@@ -157,8 +157,8 @@ class PluginGraphs:
                 e.status_host.copy_(status[:1 + B], non_blocking=True)
         with torch.no_grad(), torch.cuda.stream(side):
             e.l2i_dev = torch.empty(l2i_np.shape, dtype=torch.float32, device=dev)
-            e.tokens = torch.empty((B, T, radar.NUM_FEATURES), dtype=torch.float32, device=dev)
-            e.pad_mult = radar.NUM_RADAR_TOKENS - T + 1
+            e.tokens = torch.empty((B, T, h.radar_in_dims), dtype=torch.float32, device=dev)
+            e.pad_mult = h.radar_num_tokens - T + 1
             e.l2i_host.numpy()[...] = l2i_np
             e.stage.pack_host([m['radar'] for m in img_metas])
             warm = torch.empty(n_lab + n_out + n_box + n_sc, dtype=torch.float32, device=dev)

@@ -9,7 +9,10 @@ pipeline:
                  radar_rot={chan: wxyz}, lidar_rot=wxyz)
 
 or an already-built ``[n,36]`` feature array.  The 36-column layout is the
-contract of ``radar_feat_encoder`` (HEAD:183, 499-510).
+contract of ``radar_feat_encoder`` (HEAD:183, 499-510).  The three module
+constants POINT_RANGE, NUM_RADAR_TOKENS and NUM_FEATURES are the reference's and
+the defaults of ``Detr3DHead(radar_point_range=, radar_num_tokens=,
+radar_in_dims=)``; a head with another feature count takes ``[n,F]`` rows only.
 """
 import numpy as np
 
@@ -61,11 +64,18 @@ def _channel_features(points, times, rot_radar, rot_ref):
          _one_hot(rows[:, 15].astype(int), 8)), axis=1)   # pdh0
 
 
-def build_radar_features(radar, point_range=POINT_RANGE):
-    """Raw multi-sweep radar of one sample -> [n_kept, 36] float64."""
+def build_radar_features(radar, point_range=POINT_RANGE, num_features=NUM_FEATURES):
+    """Raw multi-sweep radar of one sample -> [n_kept, 36] float64.  An ``[n, num_features]`` array is a frame whose rows
+    the producer built (and filtered) itself: returned as it is.  The raw route exists for the 36 features of the
+    reference alone."""
     if isinstance(radar, np.ndarray):
-        assert radar.ndim == 2 and radar.shape[1] == NUM_FEATURES
+        if radar.ndim != 2 or radar.shape[1] != num_features:
+            raise ValueError('radar feature rows of shape %s: [n, %d] expected (radar_in_dims=%d)'
+                             % (radar.shape, num_features, num_features))
         return radar
+    if num_features != NUM_FEATURES:
+        raise ValueError('raw radar sweeps give the %d features of the reference; a head with radar_in_dims=%d takes '
+                         '[n, %d] feature rows' % (NUM_FEATURES, num_features, num_features))
     rot_ref = quaternion_rotation_matrix(radar['lidar_rot'])
     per_chan = []
     for chan in RADAR_CHANNELS:
@@ -80,27 +90,40 @@ def build_radar_features(radar, point_range=POINT_RANGE):
     return allp[keep]
 
 
-def pack_tokens(feature_list, granule=64, T=None):
-    """Batch of [n_i,36] arrays -> (tokens [B,T,36] float32, pad_mult).
+def in_range(rows, point_range):
+    """HEAD:514-519 on rows [n, >= 3]: x, y, z strictly inside the range (float64; a NaN fails) -> bool [n]."""
+    xyz = np.asarray(rows)[:, :3].astype(np.float64)
+    return np.all(xyz > np.asarray(point_range[:3]), axis=1) & np.all(xyz < np.asarray(point_range[3:]), axis=1)
+
+
+def pack_tokens(feature_list, granule=64, T=None, num_tokens=NUM_RADAR_TOKENS):
+    """Batch of [n_i,F] arrays -> (tokens [B,T,F] float32, pad_mult).
 
     T: fixed token count (a frame pipeline's static ``tokens`` tensor has one
     shape for every frame: T and pad_mult are baked into its captured graph);
     None picks the smallest multiple of ``granule`` that holds the frame.
+    num_tokens: the head's token count N (Detr3DHead.radar_num_tokens).
 
-    The reference always attends over 1500 tokens, the unused ones filled
-    with 500.0 (HEAD:526-530).  Identical pad tokens have identical keys and
-    values, so only T = round_up(max n_i + 1, granule) tokens are
-    materialised and the last one carries the multiplicity of the missing
-    1500 - T pad tokens (see tc_radar_gated_xattn_fwd)."""
-    n_max = max(min(f.shape[0], NUM_RADAR_TOKENS) for f in feature_list)
+    The reference always attends over N = 1500 tokens, the unused ones filled
+    with 500.0 (HEAD:526-530); a frame's points beyond the first N are dropped
+    (HEAD:528).  Identical pad tokens have identical keys and values, so only
+    T = round_up(max n_i + 1, granule) tokens are materialised and the last one
+    carries the multiplicity of the missing N - T pad tokens (see
+    tc_radar_gated_xattn_fwd); a frame that fills all N tokens has no pad row
+    (T = N, pad_mult = 1)."""
+    N = int(num_tokens)
+    n_max = max(min(f.shape[0], N) for f in feature_list)
+    widths = {f.shape[1] for f in feature_list}
+    if len(widths) != 1:
+        raise ValueError('radar feature rows of different widths in one batch: %s' % sorted(widths))
     if T is None:
-        T = min(NUM_RADAR_TOKENS, ((n_max + 1 + granule - 1) // granule) * granule)
-    elif not (1 <= T <= NUM_RADAR_TOKENS) or (n_max + 1 > T and T < NUM_RADAR_TOKENS):
+        T = min(N, ((n_max + 1 + granule - 1) // granule) * granule)
+    elif not (1 <= T <= N) or (n_max + 1 > T and T < N):
         raise ValueError('T=%d cannot hold %d radar points + one pad token (max %d)'
-                         % (T, n_max, NUM_RADAR_TOKENS))
-    tokens = np.full((len(feature_list), T, NUM_FEATURES), PAD_VALUE,
+                         % (T, n_max, N))
+    tokens = np.full((len(feature_list), T, widths.pop()), PAD_VALUE,
                      dtype=np.float32)
     for b, f in enumerate(feature_list):
         n = min(f.shape[0], T)
         tokens[b, :n] = f[:n].astype(np.float32)
-    return tokens, NUM_RADAR_TOKENS - T + 1
+    return tokens, N - T + 1
