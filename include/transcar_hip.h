@@ -36,6 +36,9 @@ extern "C" {
 #define TC_MAX_RADAR_LAYERS 3
 /* num_cams * num_levels * num_points of Detr3DCrossAtten: the logits of a row fit one 256-wide activation unit */
 #define TC_MAX_CAM_LOGITS 256
+/* num_cams of a head and of the camera-sampling entries: the sampling kernels give a row 16 lanes, one per camera (16
+ * cameras x 4 levels are the 64 lanes of a wave) */
+#define TC_MAX_CAMS 16
 /* Default head count of the radar fusion attention (rf_multihead_attn{,2,3}): the reference builds it as
  * nn.MultiheadAttention(embed_dims, 8) (HEAD:129-171) whatever the decoder's self-attention uses.  4 and 16 heads
  * (head dimension 64 and 16 at embed_dims 256) are accepted too; the count adds no parameter. */
@@ -154,7 +157,12 @@ typedef struct {
    * count is refused as radar_num_heads=<count>.  Either refusal comes from every entry that takes the struct
    * (tc_head_packed_bytes / tc_head_workspace_bytes and the other size queries return 0).  TC_NUM_HEADS_PACK builds it. */
   int num_query, embed_dims, num_heads, ffn_dims, num_layers;
-  int num_cams, num_levels, num_classes, code_size;   /* num_levels: 1 .. TC_MAX_LEVELS */
+  /* num_cams: 1 .. TC_MAX_CAMS cameras per frame (Detr3DCrossAtten.num_cams; lidar2img is [B, num_cams, 4, 4] and level l
+   * of the maps [B * num_cams, H, W, C]); a count outside is refused as num_cams=<count> by every entry that takes the
+   * struct (the size queries return 0).  Up to 8 cameras at 4 levels and one point run the fixed-level kernels; more
+   * cameras run the generic cross-attention kernels (as num_points > 1 and num_levels < 4 do), without the layer-0
+   * constants and without the camera pre-gather.  num_levels: 1 .. TC_MAX_LEVELS */
+  int num_cams, num_levels, num_classes, code_size;
   /* radar_in_dims: 4, 8, .. TC_MAX_RADAR_IN_DIMS features per token (36 in the reference; radar_feat0 is [64, radar_in_dims]);
    * num_radar_layers: 1..3 (0: camera only); num_radar_tokens_ref: TC_MIN_RADAR_TOKENS .. TC_MAX_RADAR_TOKENS, the token count
    * the head attends over (1500 in the reference, which 0 reads as): the forward, training and backward entries refuse

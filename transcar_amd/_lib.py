@@ -44,6 +44,34 @@ def check_num_points(num_points, num_cams, num_levels):
             % (num_points, num_cams, num_levels, TC_MAX_CAM_LOGITS))
 
 
+# cameras per frame of a head and of the camera-sampling entries (include/transcar_hip.h)
+TC_MAX_CAMS = 16
+
+
+def check_num_cams(num_cams):
+    """The library's limit on Detr3DCrossAtten.num_cams (1 .. TC_MAX_CAMS: the sampling kernels give a row one lane
+    per camera, 16 lanes), checked before anything is packed or launched.  Returns the count."""
+    if isinstance(num_cams, bool) or not isinstance(num_cams, int) or not 1 <= num_cams <= TC_MAX_CAMS:
+        raise TransCARHipError(
+            'Detr3DCrossAtten(HIP): num_cams=%r is not supported (an int, 1 .. %d cameras)' % (num_cams, TC_MAX_CAMS))
+    return num_cams
+
+
+def check_frame_cams(num_cams, lidar2img_cams, B=None, feat_rows=None):
+    """A frame against the head that takes it: lidar2img carries `lidar2img_cams` matrices per sample and every feature
+    map `feat_rows` leading rows (an iterable, one per level); the kernels index both by the head's num_cams, so a
+    frame of another rig is refused before any launch."""
+    if lidar2img_cams is not None and int(lidar2img_cams) != num_cams:
+        raise TransCARHipError(
+            'Detr3DHead(HIP): the frame has %d lidar2img matrices per sample, the head was built for num_cams=%d'
+            % (lidar2img_cams, num_cams))
+    for lvl, rows in enumerate(feat_rows or ()):
+        if int(rows) != B * num_cams:
+            raise TransCARHipError(
+                'Detr3DHead(HIP): feature map %d has %d images, B * num_cams = %d * %d = %d expected'
+                % (lvl, rows, B, num_cams, B * num_cams))
+
+
 def check_num_levels(num_levels):
     """The library's limit on Detr3DCrossAtten.num_levels (1 .. TC_MAX_LEVELS),
     checked before anything is packed or launched."""

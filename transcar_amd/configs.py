@@ -78,7 +78,8 @@ IMG_SHAPE = (928, 1600, 3)
 def head_cfg(num_query=900, num_points=None, with_box_refine=None,
              num_levels=None, num_heads=None, num_classes=None,
              num_fusion_layers=None, pc_range=None, post_center_range=None, radar_gate=None,
-             radar_num_heads=None, radar_num_tokens=None, radar_in_dims=None, radar_point_range=None):
+             radar_num_heads=None, radar_num_tokens=None, radar_in_dims=None, radar_point_range=None,
+             num_cams=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -110,7 +111,11 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     per token (``radar_feat_encoder.0`` becomes Linear(radar_in_dims, 64)) and
     the radar filter's range; the reference writes 1500, 36 and
     +-51.2 / +-51.2 / -5 .. 3 m as constants (HEAD:526, 183, 304), and a key is
-    added only for another value."""
+    added only for another value.  num_cams sets the cameras per frame of every
+    Detr3DCrossAtten and of the transformer (the configs: the class defaults,
+    6; 1 .. 16 -- the reference reads the count off ``lidar2img`` and sizes
+    ``attention_weights`` as Linear(C, num_cams * num_points * num_levels),
+    XFMR:280-292): the keys are added only for a count other than 6."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -122,6 +127,12 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
         layers = cfg['transformer']['decoder']['transformerlayers']
         layers['attn_cfgs'][1]['num_levels'] = int(num_levels)
         cfg['transformer']['num_feature_levels'] = int(num_levels)
+    if num_cams is not None:
+        from ._lib import check_num_cams
+        if check_num_cams(num_cams) != 6:
+            layers = cfg['transformer']['decoder']['transformerlayers']
+            layers['attn_cfgs'][1]['num_cams'] = num_cams
+            cfg['transformer']['num_cams'] = num_cams
     if num_heads is not None:
         from ._lib import check_num_heads
         check_num_heads(num_heads)

@@ -72,6 +72,7 @@ int launch_cam_sample(const CamSampleArgs& a, hipStream_t s) {
   TC_REQUIRE(a.C == 256, "cam_sample: C=%d (256 supported)", a.C);
   TC_REQUIRE(a.feats.num_levels >= 1 && a.feats.num_levels <= TC_MAX_LEVELS, "cam_sample: num_levels=%d (1 .. %d supported)",
              a.feats.num_levels, TC_MAX_LEVELS);
+  TC_REQUIRE(a.num_cams >= 1 && a.num_cams <= TC_MAX_CAMS, "cam_sample: num_cams=%d (1 .. %d supported)", a.num_cams, TC_MAX_CAMS);
   for (int l = 0; l < a.feats.num_levels; ++l)      // pixel indices are 32-bit in the kernels
     TC_REQUIRE((long long)a.B * a.num_cams * a.feats.H[l] * a.feats.W[l] < (1ll << 31),
                "cam_sample: level %d has too many pixels for one call", l);

@@ -85,6 +85,7 @@ constexpr int nw_of(int R) { return R == 32 ? 8 : 4; }
 constexpr int LD5 = 516;   // 512 + 4 floats
 constexpr int LD2 = 260;   // 256 + 4
 constexpr int LDL = 36;
+constexpr int FIXED_LOGITS = 32;      // logits of a ChainLds::l row (LDL less its padding): the fixed-level kernels' limit
 
 // a step of the table with every pointer / size resolved (built once per launch, on the host)
 struct StepRes {
@@ -460,9 +461,12 @@ struct ChainK : ChainDev {
   int l0_seq = 0;              // decoder: the record sequence -- 0 PROG_DECODER_T, 1 PROG_DECODER_L0_T, 2 PROG_DECODER_L0GEN_T
 };
 
-// the decoder's cross-attention takes the generic (MP) kernels with num_points > 1 or fewer than 4 levels; P = 1 at
-// 4 levels (the TransCAR configs) keeps kernels of its own
-inline bool generic_xattn(const ChainK& k) { return k.npoints > 1 || k.cam.num_levels < 4; }
+// the decoder's cross-attention takes the generic (MP) kernels with num_points > 1, fewer than 4 levels, or more
+// (camera, level) logits than a row of ChainLds::l holds (LDL floats: more than 8 cameras at 4 levels); P = 1 at 4 levels
+// and up to 8 cameras (the TransCAR configs) keeps kernels of its own
+inline bool generic_xattn(const ChainK& k) {
+  return k.npoints > 1 || k.cam.num_levels < 4 || k.cam.num_cams * k.cam.num_levels > FIXED_LOGITS;
+}
 
 constexpr int table_steps(int prog) {
   return (prog == PROG_DECODER ? (int)(sizeof(PROG_DECODER_T) / sizeof(StepDesc))
@@ -3144,10 +3148,11 @@ int launch_prologue(const PrologueArgs& a, hipStream_t s) {
 static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   TC_REQUIRE(a.cam.feats.num_levels >= 1 && a.cam.feats.num_levels <= TC_MAX_LEVELS,
              "decoder_chain: num_levels=%d (1 .. %d supported)", a.cam.feats.num_levels, TC_MAX_LEVELS);
-  TC_REQUIRE(a.code <= 12 && a.cam.num_cams * a.cam.feats.num_levels <= 32, "decoder_chain: code/logit width");
+  TC_REQUIRE(a.code <= 12, "decoder_chain: code=%d (<= 12)", a.code);
   TC_REQUIRE(a.cam.num_points >= 1 && a.cam.num_cams * a.cam.feats.num_levels * a.cam.num_points <= TC_MAX_CAM_LOGITS,
              "decoder_chain: num_points=%d (num_cams * num_levels * num_points <= %d)", a.cam.num_points, TC_MAX_CAM_LOGITS);
-  TC_REQUIRE(a.cam.num_cams <= 8, "decoder_chain: num_cams=%d (<= 8)", a.cam.num_cams);
+  TC_REQUIRE(a.cam.num_cams >= 1 && a.cam.num_cams <= TC_MAX_CAMS, "decoder_chain: num_cams=%d (1 .. %d supported)", a.cam.num_cams,
+             TC_MAX_CAMS);
   for (int l = 0; l < a.cam.feats.num_levels; ++l)      // pixel indices are 32-bit in the kernel
     TC_REQUIRE((long long)a.cam.B * a.cam.num_cams * a.cam.feats.H[l] * a.cam.feats.W[l] < (1ll << 31),
                "decoder_chain: level %d has too many pixels for one call", l);
@@ -3187,6 +3192,10 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   k.matrix_path = a.matrix_path;
   k.drop = a.drop;
   k.range_status = a.range_status;
+  // the fixed-level kernels keep a row's logits in ChainLds::l; everything wider runs the generic ones (logits in unit 3)
+  TC_REQUIRE(generic_xattn(k) || k.nlogits <= FIXED_LOGITS, "decoder_chain: %d logits in a %d-float row", k.nlogits, FIXED_LOGITS);
+  TC_REQUIRE(a.pre == nullptr || a.cam.num_cams <= 8,
+             "decoder_chain: num_cams=%d (the camera pre-gather exists for up to 8 cameras)", a.cam.num_cams);
   if (a.l0_consts != nullptr) {
     // layer 0 from its pack-time constants (PROG_DECODER_L0_T): [Q, 256] each, rows % Q
     TC_REQUIRE(!generic_xattn(k) && k.drop.thr == 0 && a.pre == nullptr,

@@ -19,6 +19,7 @@ inline int check_head_counts(const tc_head_weights* w, const char* what) {
              what, w->embed_dims, decoder_heads(w));
   TC_REQUIRE(heads_ok(radar_heads(w)), "%sradar_num_heads=%d (the upper 16 bits of num_heads: 0, 4, 8 or 16 supported)", what,
              radar_heads(w));
+  TC_REQUIRE(w->num_cams >= 1 && w->num_cams <= TC_MAX_CAMS, "%snum_cams=%d (1 .. %d supported)", what, w->num_cams, TC_MAX_CAMS);
   return 0;
 }
 // The radar input of a head: tokens the reference would attend over (its padded count, the stride of the attention-probability

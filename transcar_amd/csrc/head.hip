@@ -201,7 +201,9 @@ static size_t head_ws_layout(const tc_head_weights* w, int B, int T, void* base,
 // Layer 0's pack-time constants (chain.hip PROG_DECODER_L0_T) exist for the heads that take the one-point, four-level
 // kernels; they lie behind l0_attn_out in the packed buffer, over the scratch the layer-0 attention was evaluated from:
 // TC_L0_VARIANTS blocks of decoder_l0_const_floats(Q) floats.
-static bool l0_foldable(const tc_head_weights* w) { return head_points(w) == 1 && w->num_levels == TC_MAX_LEVELS; }
+static bool l0_foldable(const tc_head_weights* w) {
+  return head_points(w) == 1 && w->num_levels == TC_MAX_LEVELS && w->num_cams <= 8;
+}
 static size_t l0_scratch_bytes(const tc_head_weights* w) {
   const size_t Q = w->num_query, C = w->embed_dims, qpad = ((Q + 15) / 16) * 16;
   const size_t scratch = arena_slice(Q * 2 * C, 4) + arena_slice(C * qpad, 4);       // qk, vt of the layer-0 evaluation
@@ -952,6 +954,8 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   HeadWs h;
   const size_t need = head_ws_layout(w, B, T, workspace, workspace_bytes, &h);
   TC_REQUIRE(need <= workspace_bytes, "workspace too small: need %zu, have %zu", need, workspace_bytes);
+  TC_REQUIRE(opt.cam_pregather == 0 || w->num_cams <= 8, "options.cam_pregather: num_cams=%d (the camera pre-gather exists for "
+             "up to 8 cameras)", w->num_cams);
   TC_REQUIRE(opt.cam_pregather == 0 || opt.cam_pregather_bytes >= tc_cam_pregather_workspace_bytes(w, B),
              "options.cam_pregather_ws holds %zu bytes, %zu needed", opt.cam_pregather_bytes, tc_cam_pregather_workspace_bytes(w, B));
   bool refine = true;

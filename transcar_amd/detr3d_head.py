@@ -435,7 +435,7 @@ class Detr3DHead(BaseModule):
         w.num_heads = L.pack_num_heads(w.num_heads, rh)
         w.ffn_dims = dec.layers[0].ffns[0].feedforward_channels
         w.num_layers = dec.num_layers
-        w.num_cams = dec.layers[0].attentions[1].num_cams
+        w.num_cams = L.check_num_cams(dec.layers[0].attentions[1].num_cams)
         w.num_levels = dec.layers[0].attentions[1].num_levels
         w.num_points = dec.layers[0].attentions[1].num_points
         for ly in dec.layers:
@@ -620,6 +620,17 @@ class Detr3DHead(BaseModule):
             raise L.TransCARHipError('Detr3DHead: %d feature levels given, the head has num_levels=%d'
                                      % (n, nl))
 
+    def check_frame_cams(self, lidar2img_cams, B=None, feat_rows=None):
+        """The head indexes lidar2img and the feature maps by its num_cams: a frame of another camera count raises
+        (_lib.check_frame_cams), naming both, before anything is launched."""
+        L.check_frame_cams(self.transformer.decoder.layers[0].attentions[1].num_cams, lidar2img_cams, B, feat_rows)
+
+    def check_frame_nhwc(self, feats_nhwc, lidar2img):
+        """check_frame_cams of the device-side entries: lidar2img [B,num_cams,4,4], maps [B*num_cams,H,W,C]"""
+        if lidar2img.dim() != 4:
+            raise L.TransCARHipError('lidar2img of shape %s, [B,num_cams,4,4] expected' % (tuple(lidar2img.shape),))
+        self.check_frame_cams(lidar2img.shape[1], lidar2img.shape[0], [f.shape[0] for f in feats_nhwc])
+
     def refresh_weights(self):
         """Re-read the parameter pointers and re-pack the weights; call after
         the parameters were changed in place (e.g. an optimizer step) or moved
@@ -758,6 +769,7 @@ class Detr3DHead(BaseModule):
         if not _allow_train:
             require_eval(self)
         self.check_feature_levels(len(feats_nhwc))
+        self.check_frame_nhwc(feats_nhwc, lidar2img)
         w = self.head_weights()
         if not decoder_only:
             self.sync_packed_weights()
@@ -847,6 +859,10 @@ class Detr3DHead(BaseModule):
         -> dict(all_cls_scores [N,B,Q,10], all_bbox_preds [N,B,Q,10], enc_*), N = num_fusion_layers (3)."""
         self.check_feature_levels(len(mlvl_feats))
         self._check_outputs()
+        # (before the plugin graphs look at the call: a frame of another rig never reaches a capture)
+        for m in img_metas:
+            self.check_frame_cams(len(m['lidar2img']))
+        self.check_frame_cams(None, len(img_metas), [f.shape[0] * f.shape[1] if f.dim() == 5 else f.shape[0] for f in mlvl_feats])
         dev = mlvl_feats[0].device
         if dev.type != 'cuda':
             raise L.TransCARHipError(

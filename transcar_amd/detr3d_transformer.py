@@ -86,6 +86,7 @@ class Detr3DCrossAtten(BaseModule):
             raise ValueError('embed_dims must be divisible by num_heads, '
                              'but got %d and %d' % (embed_dims, num_heads))
         L.check_num_levels(num_levels)
+        L.check_num_cams(num_cams)
         L.check_num_points(num_points, num_cams, num_levels)
         self.norm_cfg = norm_cfg
         self.dropout = nn.Dropout(dropout)

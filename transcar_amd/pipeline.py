@@ -80,6 +80,8 @@ class FramePipeline:
         self.frames_per_launch = int(self.inputs[0]['l2i'].shape[0])
         if any(int(i['l2i'].shape[0]) != self.frames_per_launch for i in self.inputs):
             raise ValueError('all lanes must have the same number of frame slots')
+        for inp in self.inputs:                # (a lane of another camera count than the head's: before anything is captured)
+            head.check_frame_nhwc(inp['nhwc'], inp['l2i'])
         self._filled = [0] * len(self.inputs)
         self._fill_lane = 0
         # streams: reuse the HIP streams of another (idle) pipeline.  A process has a handful of hardware

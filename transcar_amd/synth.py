@@ -97,8 +97,8 @@ def state_dict_spec(num_query=900, embed=256, ffn=512, num_layers=6,
     _linear(s, 'radar_feat_encoder.0', 64, radar_in)
     _linear(s, 'radar_feat_encoder.2', 128, 64)
     _linear(s, 'radar_feat_encoder.4', c, 128)
-    for n in (2, 3):      # (HEAD:191: 6 * 4 rows whatever the decoder's levels)
-        _linear(s, 'attention_weights%d' % n, num_cams * 4, c)
+    for n in (2, 3):      # (HEAD:191-192: the constant 6 * 4 rows whatever the decoder's cameras and levels)
+        _linear(s, 'attention_weights%d' % n, 6 * 4, c)
         _linear(s, 'output_proj%d' % n, c, c)
     return s
 
@@ -182,9 +182,14 @@ def make_state_dict(seed=3, **dims):
 CAM_YAWS_DEG = (0.0, -55.0, 55.0, 180.0, 110.0, -110.0)
 
 
+def ring_yaws(num_cams):
+    """Yaws in degrees of a test rig of ``num_cams`` cameras evenly spaced round the vehicle, from -180 degrees."""
+    return tuple(-180.0 + 360.0 * i / num_cams for i in range(num_cams))
+
+
 def make_lidar2img(focal=1266.0, pp=(800.0, 464.0), yaws_deg=CAM_YAWS_DEG,
                    jitter_seed=None):
-    """[6,4,4] float64 pinhole cameras in a ring (nuScenes-like rig).
+    """[len(yaws_deg),4,4] float64 pinhole cameras in a ring (nuScenes-like rig at the default yaws).
 
     Lidar frame: z up; camera ``i`` looks along yaw_i in the xy plane from a
     mount point 0.5..1.5 m off the origin."""

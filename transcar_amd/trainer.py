@@ -302,6 +302,7 @@ class FusionTrainer:
         skip: frames of an earlier look-ahead still to be consumed before these (their iterations draw the seeds in
         between).  step_fused_nhwc(prefetch=...) calls this at the right moment."""
         head = self.head
+        head.check_frame_nhwc(feats_nhwc, lidar2img)
         if not head.training:
             head.train()
         cur = torch.cuda.current_stream()
@@ -375,6 +376,7 @@ class FusionTrainer:
         is started: the frames that follow the `skip` frames of the look-ahead still in use (P > 1: the next batch is
         started one iteration before the current one runs out)."""
         head, lib = self.head, L.lib()
+        head.check_frame_nhwc(feats_nhwc, lidar2img)       # (a frame of another camera count: before the seed counter moves)
         if not head.training:                      # (Module.train() walks ~380 submodules: 0.7 ms of host time per call)
             head.train()
         if self.device_loss:
