@@ -251,12 +251,11 @@ def oracle_head(sd, feats_np, frame, key=None, **variant):
     return _ORACLE[key]
 
 
-def gate_margin(sd, feats_np, frame, **variant):
-    """The distance (m) between the frame's closest gate decision and its radius: the minimum over the variant's fusion
-    layers, the queries, the gate's circles and the radar tokens of |distance - radius|, measured on the oracle through
-    head_forward's gate_probe.  The padding tokens are left out (they sit far outside every circle)."""
+def margin_probe(margins):
+    """A gate_probe for O.head_forward that appends, per fusion layer, the distance (m) between the layer's closest gate
+    decision and its radius: the minimum over the queries, the gate's circles and the radar tokens of |distance - radius|.
+    The padding tokens are left out (they sit far outside every circle)."""
     from transcar_amd._lib import TC_RADAR_GATE_CIRCLE
-    margins = []
 
     def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
         centres, radii = [centre_xy], rmax
@@ -267,9 +266,15 @@ def gate_margin(sd, feats_np, frame, **variant):
             radii = torch.clamp((length / 2.0).reshape(-1, 1), min=rmin, max=rmax)
         live = radar_xy[0, :, 0] != O.PAD_VALUE
         margins.append(min(float((torch.cdist(c, radar_xy, p=2.0)[0][:, live] - radii).abs().min()) for c in centres))
+    return probe
 
+
+def gate_margin(sd, feats_np, frame, **variant):
+    """The distance (m) between the frame's closest gate decision and its radius: the minimum over the variant's fusion
+    layers of what margin_probe measures on the oracle through head_forward's gate_probe."""
+    margins = []
     with torch.no_grad():
-        oracle_forward(sd, feats_np, frame, variant, gate_probe=probe)
+        oracle_forward(sd, feats_np, frame, variant, gate_probe=margin_probe(margins))
     assert len(margins) == dict(CONFIGS, **variant)['num_fusion_layers']
     return min(margins)
 
@@ -638,11 +643,12 @@ def check_training_iteration(frame, g8_name, what, expected=98, **variant):
     assert check_grads_against_g8(grads, g8, 2e-3, what, expected) == expected
 
 
-def check_plugin_graph_replay(hg, he, shapes='tiny', geometry=DEFAULT):
+def check_plugin_graph_replay(hg, he, shapes='tiny', geometry=DEFAULT, num_cams=6):
     """The plugin entry's captured graphs (plugin_graph.py) of head `hg` replay, bit for bit, what the eager entry of
     its twin `he` computes.  Two fresh heads: `he` loses its graphs.  geometry: the frames' cameras and image size, or
     one Geometry per call (the warm-up call and the three compared ones): a graph keyed without the image size would
-    replay a stale one."""
+    replay a stale one.  num_cams: the cameras of the maps (a ring geometry's count).  The radar inputs are raw sweeps:
+    the graphs serve no other (a head of another radar_in_dims takes [n, F] rows on the eager path)."""
     geoms = list(geometry) if isinstance(geometry, list) else [geometry] * 4
     assert len(geoms) == 4
     if isinstance(shapes, str):
@@ -650,13 +656,14 @@ def check_plugin_graph_replay(hg, he, shapes='tiny', geometry=DEFAULT):
     he.plugin_graphs = False
     g = torch.Generator(device=dev())
     g.manual_seed(5)
-    feats = [torch.randn((1, 6, 256, h_, w_), device=dev(), generator=g) for (h_, w_) in shapes]
-    hg(feats, geoms[0].metas(1, radar=synth.make_radar_frame(seed=39, n_per_radar=30)))
+    radar = [synth.make_radar_frame(seed=39 + it, n_per_radar=30) for it in range(4)]
+    feats = [torch.randn((1, num_cams, 256, h_, w_), device=dev(), generator=g) for (h_, w_) in shapes]
+    hg(feats, geoms[0].metas(1, radar=radar[0]))
     base = dict(hg._plugin_graphs.stats)
     for it in range(3):
         for f in feats:
             f.mul_(0.9).add_(0.01 * (it + 1))
-        metas = geoms[it + 1].metas(1, radar=synth.make_radar_frame(seed=40 + it, n_per_radar=30))
+        metas = geoms[it + 1].metas(1, radar=radar[it + 1])
         og, oe = hg(feats, metas), he(feats, metas)
         torch.cuda.synchronize()
         for k in ('all_cls_scores', 'all_bbox_preds'):
@@ -696,12 +703,15 @@ def check_frame_pipeline(head, nlanes=2, shapes='tiny', pregather_off=False, geo
             assert torch.equal(a_, b_)
 
 
-def check_frame_of_nine(head, shapes='tiny', refs_initial=False, geometry=DEFAULT):
+def check_frame_of_nine(head, shapes='tiny', refs_initial=False, geometry=DEFAULT, num_cams=6, radar=None):
     """One frame of a nine-frame launch (32-row tiles) is bit-identical to that frame launched alone with the same
-    tile height and matrix path.  refs_initial (no box refinement): so are its reference points, the initial ones."""
+    tile height and matrix path.  refs_initial (no box refinement): so are its reference points, the initial ones.
+    num_cams: the cameras of the maps (a ring geometry's count).  radar: the nine frames' radar inputs as img_metas carry
+    them (raw frames, or [n, F] rows for a head of another radar_in_dims); None: raw frames of seeds 60 .. 68."""
     from transcar_amd.detr3d_head import head_options
-    feats = [synth.make_feats(shapes, seed=40 + i, smooth=SMOOTH) for i in range(9)]
-    frames = [synth.make_radar_frame(seed=60 + i, n_per_radar=45) for i in range(9)]
+    feats = [synth.make_feats(shapes, seed=40 + i, num_cams=num_cams, smooth=SMOOTH) for i in range(9)]
+    frames = [synth.make_radar_frame(seed=60 + i, n_per_radar=45) for i in range(9)] if radar is None else list(radar)
+    assert len(frames) == 9
     kw = dict(aux=True) if refs_initial else {}
     head.forward_options = head_options(tile_rows=32, matrix_path='f16x2')
     try:

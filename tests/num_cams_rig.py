@@ -29,11 +29,11 @@ G5_CAMS12, G8_CAMS12 = 'g5_head_tiny_cams12.npz', 'g8_train_grads_cams12.npz'
 
 
 class Ring(R.Geometry):
-    """The configs' geometry with a ring of `num_cams` cameras (jitter_seed: the mounts moved, a second lidar2img set).
-    Equal to no Geometry but a Ring of the same count and seed."""
+    """A geometry (`base`; None: the configs') with a ring of `num_cams` cameras (jitter_seed: the mounts moved, a second
+    lidar2img set).  Equal to no Geometry but a Ring of the same base, count and seed."""
 
-    def __new__(cls, num_cams, jitter_seed=None):
-        self = super().__new__(cls, *R.DEFAULT)
+    def __new__(cls, num_cams, jitter_seed=None, base=None):
+        self = super().__new__(cls, *(R.DEFAULT if base is None else tuple(base)))
         self.num_cams, self.jitter_seed = int(num_cams), jitter_seed
         return self
 
@@ -158,17 +158,19 @@ def oracle(N, jitter_seed=None, **kw):
 
 
 # ---- coverage: what a count's rig must exercise -------------------------------------------------------------------------------
-def visibility(N, dbg, jitter_seed=None):
-    """[layers, Q, N] bool: camera n sees the reference point layer l samples at (the oracle's projection)"""
+def visibility(N, dbg, jitter_seed=None, base=None):
+    """[layers, Q, N] bool: camera n sees the reference point layer l samples at (the oracle's projection); base: the
+    ring's base geometry (None: the configs')"""
     refs = [dbg['init_ref']] + list(dbg['inter_refs'][:-1])
-    l2i = torch.from_numpy(Ring(N, jitter_seed).lidar2img()).float()[None]
-    return np.stack([O.project_points(r, list(R.PCR), l2i, R.HW)[1][0].numpy().T for r in refs])
+    ring = Ring(N, jitter_seed, base)
+    l2i = torch.from_numpy(ring.lidar2img()).float()[None]
+    return np.stack([O.project_points(r, list(ring.pc_range), l2i, ring.hw)[1][0].numpy().T for r in refs])
 
 
-def coverage(N, dbg=None, jitter_seed=None):
+def coverage(N, dbg=None, jitter_seed=None, base=None):
     """Per decoder layer: queries per visible-camera count, queries seeing only cameras >= 8, queries seeing a camera below
     8 and one from 8 up, queries seeing the last camera.  -> list of dicts"""
-    vis = visibility(N, oracle(N)[4] if dbg is None else dbg, jitter_seed)
+    vis = visibility(N, oracle(N)[4] if dbg is None else dbg, jitter_seed, base)
     out = []
     for v in vis:
         lo, hi = v[:, :8].any(1), v[:, 8:].any(1)
@@ -177,13 +179,19 @@ def coverage(N, dbg=None, jitter_seed=None):
     return out
 
 
-def assert_coverage(N, dbg=None, jitter_seed=None):
-    """The conditions of a rig with more than 8 cameras, in every decoder layer"""
-    for l, c in enumerate(coverage(N, dbg, jitter_seed)):
-        assert c['high_only'] >= 2, (N, l, c)
-        assert c['low_and_high'] >= 9, (N, l, c)
-        assert N == 9 or sum(c['per_count'][3:]) >= 3, (N, l, c)
-        assert c['last'] >= 10, (N, l, c)
+LEAST = dict(high_only=2, low_and_high=9, three=3, last=10)       # what a 72-query rig of the configs' geometry must show
+
+
+def assert_coverage(N, dbg=None, jitter_seed=None, base=None, least=LEAST):
+    """The conditions of a rig with more than 8 cameras, in every decoder layer.  least: the queries that must see only
+    cameras >= 8, a camera below 8 and one from 8 up, three cameras or more (N > 9), the last camera; `either` (optional):
+    those of the first two kinds together"""
+    for l, c in enumerate(coverage(N, dbg, jitter_seed, base)):
+        assert c['high_only'] >= least['high_only'], (N, l, c)
+        assert c['low_and_high'] >= least['low_and_high'], (N, l, c)
+        assert c['high_only'] + c['low_and_high'] >= least.get('either', 0), (N, l, c)
+        assert N == 9 or sum(c['per_count'][3:]) >= least['three'], (N, l, c)
+        assert c['last'] >= least['last'], (N, l, c)
 
 
 # ---- the device side ----------------------------------------------------------------------------------------------------------

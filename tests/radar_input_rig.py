@@ -2,11 +2,12 @@
 at 128 queries on the tiny maps, frames of [n,F] feature rows scattered around the oracle's gate centres, and the CPU oracle
 at N tokens.
 
-head_variant_rig's CONFIGS rejects keys it does not know, so the heads and the oracle calls are made here (as
-radar_heads_rig does); the checks that take a head or tensors are head_variant_rig's, as they are.  The reference writes 1500
-and 36 into its program text, so there is no reference fixture off those values: the yardstick is the oracle, which the G5 /
-G8 fixtures pin to the reference at 1500 / 36.  It reads F off the rows and the state dict and N off its module attribute
-NUM_RADAR_TOKENS, which `oracle_case` sets through the test's monkeypatch fixture for the duration of the oracle's call."""
+head_variant_rig's CONFIGS rejects keys it does not know, so the heads and the oracle calls of this axis alone are made
+here (as radar_heads_rig does); heads that combine these keys with the other axes' are variant_pairs_rig's.  The checks that
+take a head or tensors are head_variant_rig's, as they are.  The reference writes 1500 and 36 into its program text, so there
+is no reference fixture off those values: the yardstick is the oracle, which the G5 / G8 fixtures pin to the reference at
+1500 / 36.  It reads F off the rows and the state dict and N off its module attribute NUM_RADAR_TOKENS, which `oracle_case`
+sets through the test's monkeypatch fixture for the duration of the oracle's call."""
 import numpy as np
 import torch
 
@@ -29,6 +30,10 @@ CASES = {
     'range': (1500, 36, 300, 37, (-51.2, -51.2, -5.0, 20.0, 51.2, 3.0)),
     'train-F8': (1500, 8, 300, 38, None),            # the second training frame
 }
+FACE_RANGE = (-40.0, -30.0, -2.0, 25.0, 35.0, 1.5)      # a filter range with every face moved (the pack kernel's and the pair rows')
+# FusionTrainer's arguments per backward of the training tests
+BACKWARDS = {'chain': dict(chain_forward=True, chain_backward=True), 'operators': dict(chain_forward=False, chain_backward=False),
+             'deterministic': dict(chain_forward=True, chain_backward=True, deterministic=True)}
 NEAR = 120              # rows of a frame that lie near a gate centre; the others are kept out of every gate's reach
 
 
@@ -79,15 +84,16 @@ def gate_centres():
     return O.denormalised_refs(decoder_trace()[2][-1], list(R.PCR))[0, :, :2].numpy().astype(np.float64)
 
 
-def make_rows(seed, n, F, near=NEAR):
-    """[n,F] float32 rows: `near` of them 0.6 m around gate centres (at random row indices, so that hits lie beyond any
-    token count below n), the others at least 8 m from every centre; columns 3.. are noise."""
+def make_rows(seed, n, F, near=NEAR, centres=None, near_sigma=0.6):
+    """[n,F] float32 rows: `near` of them `near_sigma` m around gate centres (at random row indices, so that hits lie
+    beyond any token count below n), the others at least 8 m from every centre; columns 3.. are noise.  centres: [m,2]
+    metres (None: this rig's gate_centres())."""
     rng = np.random.RandomState(1000 + seed)
-    cen = gate_centres()
+    cen = gate_centres() if centres is None else np.asarray(centres, np.float64)
     near = min(near, n)
     xyz = np.empty((n, 3))
     pick = cen[rng.randint(0, len(cen), near)]
-    xyz[:near, :2] = pick + 0.6 * rng.standard_normal((near, 2))
+    xyz[:near, :2] = pick + near_sigma * rng.standard_normal((near, 2))
     k = near
     while k < n:
         cand = rng.uniform(-50.0, 50.0, (4 * (n - k) + 16, 2))

@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 gpu = R.gpu
 PATHS = {'f32-4': dict(tile_rows=4, matrix_path='f32'), 'f16x2-16': dict(tile_rows=16, matrix_path='f16x2'),
          'f16x2-32': dict(tile_rows=32, matrix_path='f16x2')}
-FACE_RANGE = (-40.0, -30.0, -2.0, 25.0, 35.0, 1.5)
+FACE_RANGE = RI.FACE_RANGE
 
 
 # ---- 1. the pack kernel ------------------------------------------------------------------------------------------------------
@@ -171,8 +171,7 @@ def test_forward_against_oracle(T, monkeypatch, case, path):
 
 # ---- 3. training ---------------------------------------------------------------------------------------------------------------
 TRAIN = {'N2048': 'N2048-n1700', 'F8': 'train-F8'}
-BACKWARDS = {'chain': dict(chain_forward=True, chain_backward=True), 'operators': dict(chain_forward=False, chain_backward=False),
-             'deterministic': dict(chain_forward=True, chain_backward=True, deterministic=True)}
+BACKWARDS = RI.BACKWARDS
 P_DROP = 0.1
 _ORACLE_TRAIN = {}
 
