@@ -682,6 +682,22 @@ int tc_decoder_outputs_fwd(const tc_decoder_heads* packed_view,
                            float* all_cls_scores /* [L,B,Q,num_classes] */,
                            float* all_bbox_preds /* [L,B,Q,code_size]   */,
                            const tc_head_options* options /*may be NULL*/, tc_stream_t stream);
+/* The same launch over decoder levels [first_level, first_level + num_levels) only: num_levels x row tiles, the tile
+ * height chosen from num_levels * B * Q rows.  The three inputs keep their full [L,...] layout (level l reads
+ * inter_states[l] and inter_references[l - 1], level 0 init_reference; without box refinement inter_references holds
+ * the initial reference at every level); the outputs hold the selected levels alone, the first at index 0.  What a
+ * captured frame graph launches when only the last level is decoded (FramePipeline(outputs='camera',
+ * decoder_levels='last')).  tc_decoder_outputs_fwd is this call with (0, packed_view->num_levels).  Every refusal of
+ * tc_decoder_outputs_fwd, and first_level < 0, num_levels < 1, first_level + num_levels > packed_view->num_levels,
+ * each before any launch.  Enqueue-only: no allocation, no synchronisation. */
+int tc_decoder_outputs_levels_fwd(const tc_decoder_heads* packed_view,
+                                  const float* inter_states     /* [L,B,Q,C] */,
+                                  const float* init_reference   /* [B,Q,3]   */,
+                                  const float* inter_references /* [L,B,Q,3] */,
+                                  int B, int Q, int first_level, int num_levels,
+                                  float* cls_out /* [num_levels,B,Q,num_classes] */,
+                                  float* box_out /* [num_levels,B,Q,code_size]   */,
+                                  const tc_head_options* options /*may be NULL*/, tc_stream_t stream);
 
 
 /* ======================================================================

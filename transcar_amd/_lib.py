@@ -456,6 +456,8 @@ SIGNATURES = {
     'tc_decoder_heads_pack': (_i, [_P(tc_decoder_heads), _vp, _sz, _P(tc_decoder_heads), _vp]),
     'tc_decoder_outputs_fwd': (_i, [_P(tc_decoder_heads), _vp, _vp, _vp, _i, _i, _vp, _vp,
                                     _P(tc_head_options), _vp]),
+    'tc_decoder_outputs_levels_fwd': (_i, [_P(tc_decoder_heads), _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp,
+                                           _P(tc_head_options), _vp]),
     # training (backward of the trainable radar stack + optimizer)
     'tc_linear_gated_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'tc_linear_bwd_data': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f,

@@ -2995,9 +2995,10 @@ ChainK heads_level_k(const DecoderHeadsArgs& a, int l) {
   const tc_cls_branch& c = a.cls[l]; const tc_reg_branch& g = a.reg[l];
   k.pairs[0] = c.l0; k.pairs[1] = ln_pair(c.n1); k.pairs[2] = c.l3; k.pairs[3] = ln_pair(c.n4);
   k.pairs[4] = c.l6; k.pairs[5] = g.l0; k.pairs[6] = g.l2; k.pairs[7] = g.l4;
-  k.g[G_HS] = const_cast<float*>(a.hs) + (size_t)l * a.M * 256; k.g_ld[G_HS] = 256;
+  const int dl = a.first + l;                 // the decoder level whose states and references entry l reads
+  k.g[G_HS] = const_cast<float*>(a.hs) + (size_t)dl * a.M * 256; k.g_ld[G_HS] = 256;
   k.g[G_CLS] = a.all_cls + (size_t)l * a.M * a.ncls; k.g_ld[G_CLS] = a.ncls;
-  k.ref_in = l == 0 ? a.init_ref : a.inter_refs + (size_t)(l - 1) * a.M * 3;
+  k.ref_in = dl == 0 ? a.init_ref : a.inter_refs + (size_t)(dl - 1) * a.M * 3;
   k.box_m = a.all_box + (size_t)l * a.M * a.code;
   for (int i = 0; i < 6; ++i) k.cam.pc[i] = a.pc[i];
   return k;
@@ -3353,7 +3354,8 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s) {
 // cls_branches / reg_branches of every decoder level (HEAD:277-298): one launch after the decoder chains.  The tile
 // height and the matrix path follow the rule of the other chains, from the rows of the launch (levels * M).
 int launch_decoder_heads(const DecoderHeadsArgs& a, hipStream_t s) {
-  TC_REQUIRE(a.levels >= 1 && a.levels <= TC_MAX_LAYERS && a.M >= 1, "decoder_heads: levels=%d M=%d", a.levels, a.M);
+  TC_REQUIRE(a.levels >= 1 && a.first >= 0 && a.first + a.levels <= TC_MAX_LAYERS && a.M >= 1,
+             "decoder_heads: first=%d levels=%d M=%d", a.first, a.levels, a.M);
   TC_REQUIRE(a.code >= 1 && a.code <= 12 && a.ncls >= 1 && a.ncls <= 32, "decoder_heads: code=%d ncls=%d", a.code, a.ncls);
   TC_REQUIRE((long long)a.levels * a.M < (1ll << 24), "decoder_heads: %lld rows in one launch", (long long)a.levels * a.M);
   return with_variant(tile_variant(a.levels * a.M, a.tile_rows, a.matrix_path, "decoder_heads"),

@@ -1158,30 +1158,43 @@ int tc_decoder_heads_pack(const tc_decoder_heads* w, void* packed, size_t packed
   return 0;
 }
 
-int tc_decoder_outputs_fwd(const tc_decoder_heads* packed_view, const float* inter_states, const float* init_reference,
-                           const float* inter_references, int B, int Q, float* all_cls_scores, float* all_bbox_preds,
-                           const tc_head_options* options, tc_stream_t stream) {
+int tc_decoder_outputs_levels_fwd(const tc_decoder_heads* packed_view, const float* inter_states, const float* init_reference,
+                                  const float* inter_references, int B, int Q, int first_level, int num_levels,
+                                  float* cls_out, float* box_out, const tc_head_options* options, tc_stream_t stream) {
   const tc_decoder_heads* w = packed_view;
   TC_TRY(check_decoder_heads(w, "decoder_outputs"));
   TC_REQUIRE(w->packed16_delta != 0, "decoder_outputs: packed_view was not produced by tc_decoder_heads_pack");
-  TC_REQUIRE(inter_states && init_reference && all_cls_scores && all_bbox_preds && (w->num_levels == 1 || inter_references),
+  TC_REQUIRE(inter_states && init_reference && cls_out && box_out && (w->num_levels == 1 || inter_references),
              "decoder_outputs: null argument");
   TC_REQUIRE(B >= 1 && Q >= 1, "decoder_outputs: B=%d Q=%d", B, Q);
+  TC_REQUIRE(first_level >= 0, "decoder_outputs: first_level=%d (0 .. %d)", first_level, w->num_levels - 1);
+  TC_REQUIRE(num_levels >= 1, "decoder_outputs: num_levels=%d (at least one level)", num_levels);
+  TC_REQUIRE(first_level <= w->num_levels - num_levels, "decoder_outputs: first_level=%d + num_levels=%d exceeds the %d levels of the view",
+             first_level, num_levels, w->num_levels);
   tc_head_options opt;
   TC_TRY(read_options(options, opt));
   TC_REQUIRE(opt.decoder_dropout_p == 0.0f, "decoder_outputs: options.decoder_dropout_p=%g (eval-mode levels only)",
              (double)opt.decoder_dropout_p);
   TC_REQUIRE(!opt.unfused, "decoder_outputs: options.unfused=%d (the decoder heads exist as a row chain only)", opt.unfused);
   DecoderHeadsArgs a;
-  a.levels = w->num_levels; a.M = B * Q;
-  for (int l = 0; l < w->num_levels; ++l) { a.cls[l] = w->cls[l]; a.reg[l] = w->reg[l]; }
+  a.first = first_level; a.levels = num_levels; a.M = B * Q;
+  for (int l = 0; l < num_levels; ++l) { a.cls[l] = w->cls[first_level + l]; a.reg[l] = w->reg[first_level + l]; }
   a.w16_delta = w->packed16_delta;
   a.hs = inter_states; a.init_ref = init_reference; a.inter_refs = inter_references;
-  a.all_cls = all_cls_scores; a.all_box = all_bbox_preds;
+  a.all_cls = cls_out; a.all_box = box_out;
   a.ncls = w->num_classes; a.code = w->code_size;
   copy_pc(a.pc, w->pc_range);
   a.tile_rows = opt.chain_tile_rows; a.matrix_path = opt.matrix_path; a.range_status = opt.range_status;
   return launch_decoder_heads(a, as_stream(stream));
+}
+
+int tc_decoder_outputs_fwd(const tc_decoder_heads* packed_view, const float* inter_states, const float* init_reference,
+                           const float* inter_references, int B, int Q, float* all_cls_scores, float* all_bbox_preds,
+                           const tc_head_options* options, tc_stream_t stream) {
+  // (a null view is refused by the range entry's own check, before num_levels is read there)
+  return tc_decoder_outputs_levels_fwd(packed_view, inter_states, init_reference, inter_references, B, Q, 0,
+                                       packed_view != nullptr ? packed_view->num_levels : 1, all_cls_scores, all_bbox_preds,
+                                       options, stream);
 }
 
 // ---- training entry points (train.hip) ---------------------------------------

@@ -203,13 +203,16 @@ int launch_radar_chain(const RadarChainArgs& a, hipStream_t s);
 
 // cls_branches[l] / reg_branches[l] of every decoder level on the stored decoder states (chain.hip PROG_DECODER_HEADS):
 // one launch, levels x row tiles.  cls / reg: a tc_decoder_heads_pack view (the last Linear of a branch unpacked).
+// The launch covers decoder levels [first, first + levels): entry i of cls / reg / all_cls / all_box is level first + i,
+// while hs / inter_refs keep the decoder's full layout.
 struct DecoderHeadsArgs {
   int levels = 0, M = 0;                     // M = B * Q rows per level
+  int first = 0;                             // the decoder level of entry 0
   tc_cls_branch cls[TC_MAX_LAYERS] = {}; tc_reg_branch reg[TC_MAX_LAYERS] = {};
   size_t w16_delta = 0;
-  const float* hs = nullptr;                 // [levels, M, 256]
+  const float* hs = nullptr;                 // [first + levels, M, 256]
   const float* init_ref = nullptr;           // [M, 3]: the reference points of level 0
-  const float* inter_refs = nullptr;         // [levels, M, 3]: level l > 0 reads slice l - 1
+  const float* inter_refs = nullptr;         // [first + levels, M, 3]: level l > 0 reads slice l - 1
   float* all_cls = nullptr; float* all_box = nullptr;   // [levels, M, ncls / code]
   int ncls = 0, code = 0; float pc[6] = {0, 0, 0, 0, 0, 0};
   int tile_rows = 0, matrix_path = 0;

@@ -294,6 +294,9 @@ class Detr3DHead(BaseModule):
         #: cls_branches / reg_branches packed for tc_decoder_outputs_fwd: (buffer, view, key), built by the first
         #: forward with outputs != 'fusion', dropped whenever the packed weights are (refresh_weights, load_state_dict)
         self._dec_heads = None
+        #: (buffer, bytes of the struct it was packed from) of the last `decoder_heads()` pack; outlives `_dec_heads`, so
+        #: that the next pack writes the same buffer (dropped with the device: `_apply`)
+        self._dec_heads_last = None
         #: the trainable (radar) weights changed in place since they were last re-packed
         #: (an optimizer step): the next forward / pipeline replay that reads them re-packs first
         self._packed_dirty = False
@@ -351,6 +354,7 @@ class Detr3DHead(BaseModule):
         self._workspace = {}
         self._packed = None
         self._dec_heads = None
+        self._dec_heads_last = None
         self.buffers_generation += 1
         return super()._apply(fn, *a, **k)
 
@@ -372,8 +376,8 @@ class Detr3DHead(BaseModule):
         generation = self.buffers_generation
         w = self.refresh_weights()
         if dec is not None and self.buffers_generation == generation:
-            # the packed cls / reg branches of the decoder levels: same buffer, new values (a buffer of their own, which
-            # decoder_heads() would allocate anew for the new pointer table while a captured graph reads the old one)
+            # the packed cls / reg branches of the decoder levels: same buffer, new values, written at once (a captured
+            # graph with outputs 'camera' / 'all' reads them; decoder_heads() would re-pack only at the next eager call)
             buf, view, _ = dec
             h, lib = self.decoder_heads_struct(), L.lib()
             if lib.tc_decoder_heads_packed_bytes(C.byref(h)) == buf.numel():
@@ -513,7 +517,20 @@ class Detr3DHead(BaseModule):
         h = self.decoder_heads_struct()
         lib = L.lib()
         dev = self.query_embedding.weight.device
-        buf = L.device_bytes(dev, lib.tc_decoder_heads_packed_bytes, C.byref(h))
+        # As `_pack`: written again IN PLACE where the last buffer fits (captured graphs -- FramePipeline lanes and plugin
+        # entries with outputs 'camera' / 'all' -- hold raw pointers into it).  A buffer that replaces an older one, or
+        # branch parameters at other addresses than the last view named, bump buffers_generation: a stale capture refuses
+        # to replay.  (The first buffer bumps nothing: no graph can point at what did not exist.)
+        nbytes = L.size_query(lib.tc_decoder_heads_packed_bytes, C.byref(h))
+        last = self._dec_heads_last
+        buf = last[0] if last is not None else None
+        if buf is None or buf.numel() != nbytes or buf.device != dev:
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            if last is not None:
+                self.buffers_generation += 1
+        elif last[1] != bytes(h):
+            self.buffers_generation += 1
+        self._dec_heads_last = (buf, bytes(h))
         view = L.tc_decoder_heads()
         L.check(lib.tc_decoder_heads_pack(C.byref(h), buf.data_ptr(), buf.numel(), C.byref(view), L.stream_ptr(dev)),
                 'tc_decoder_heads_pack')
@@ -559,27 +576,74 @@ class Detr3DHead(BaseModule):
             own.cam_pregather_ws, own.cam_pregather_bytes = self._workspace[pk].data_ptr(), self._workspace[pk].numel()
         return own
 
-    def decoder_outputs(self, aux_t, options=None):
-        """cls_branches[l] / reg_branches[l] of every decoder level (HEAD:277-298) from the decoder's kept states and
-        references (``aux`` of a forward): -> (all_cls_scores [L,B,Q,num_classes], all_bbox_preds [L,B,Q,code_size]).
-        One launch (tc_decoder_outputs_fwd), enqueue-only."""
+    def _output_views(self, out, levels, B, dev, who):
+        """(cls [levels,B,Q,num_classes], box [levels,B,Q,code_size]) over `out`: None = one new allocation; a contiguous
+        fp32 buffer of levels * B * Q * (num_classes + code_size) elements (class scores first); or a pair of
+        contiguous fp32 tensors of the two shapes' sizes, e.g. slices of a [levels + more,B,Q,.] pair."""
+        Q, ncls, code = self.num_query, self.cls_out_channels, self.code_size
+        n_cls, n_box = levels * B * Q * ncls, levels * B * Q * code
+
+        def ok(t, n):
+            return torch.is_tensor(t) and t.numel() == n and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+        if isinstance(out, (tuple, list)):
+            if len(out) != 2 or not ok(out[0], n_cls) or not ok(out[1], n_box):
+                raise L.TransCARHipError('%s: out must be a pair of contiguous fp32 tensors of %d and %d elements on %s'
+                                         % (who, n_cls, n_box, dev))
+            return out[0].view(levels, B, Q, ncls), out[1].view(levels, B, Q, code)
+        if out is None:
+            out = torch.empty(n_cls + n_box, dtype=torch.float32, device=dev)
+        elif not ok(out, n_cls + n_box):
+            raise L.TransCARHipError('%s: out must be a contiguous fp32 buffer of %d elements on %s' % (who, n_cls + n_box, dev))
+        out = out.view(-1)
+        return out[:n_cls].view(levels, B, Q, ncls), out[n_cls:].view(levels, B, Q, code)
+
+    def all_outputs_buffer(self, B, dev, flat=None):
+        """(cls [L + NF,B,Q,num_classes], box [L + NF,B,Q,code_size]) of outputs='all' in one allocation (or over `flat`,
+        a contiguous fp32 buffer of that size): decoder levels first; rows [:L] go to decoder_outputs(out=), rows [L:]
+        to forward_nhwc(_out=)."""
+        return self._output_views(flat, self.transformer.decoder.num_layers + self.num_fusion_layers, B, dev, 'all_outputs_buffer')
+
+    def decoder_level_range(self, levels):
+        """(first, count) of decoder_outputs(levels=): None every level, 'last' the last one, or the pair itself."""
+        Lyr = self.transformer.decoder.num_layers
+        if levels is None or levels == 'all':
+            return 0, Lyr
+        if levels == 'last':
+            return Lyr - 1, 1
+        try:
+            first, count = (int(v) for v in levels)
+        except (TypeError, ValueError):
+            raise L.TransCARHipError("decoder_outputs: levels=%r (None, 'last' or (first, count))" % (levels,)) from None
+        if first < 0 or count < 1 or first + count > Lyr:
+            raise L.TransCARHipError('decoder_outputs: levels=(%d, %d) of a decoder with %d levels' % (first, count, Lyr))
+        return first, count
+
+    def decoder_outputs(self, aux_t, options=None, levels=None, out=None):
+        """cls_branches[l] / reg_branches[l] of the decoder levels (HEAD:277-298) from the decoder's kept states and
+        references (``aux`` of a forward): -> (all_cls_scores [n,B,Q,num_classes], all_bbox_preds [n,B,Q,code_size]).
+        levels: None every level (n = L); 'last' or (first, count) that range alone (n = 1 / count) -- the launch is
+        n x row tiles, its automatic tile height that of n * B * Q rows.  out: where to write (`_output_views`: a
+        caller-owned buffer, e.g. a captured graph's static outputs, or the decoder levels' rows of an 'all' result).
+        One launch (tc_decoder_outputs_levels_fwd), enqueue-only."""
         hs = aux_t['inter_states']
         Lyr, B, Q = hs.shape[:3]
         dev = hs.device
+        first, count = self.decoder_level_range(levels)
+        if Lyr != self.transformer.decoder.num_layers or Q != self.num_query:
+            raise L.TransCARHipError('decoder_outputs: inter_states of shape %s, the head has %d levels of %d queries'
+                                     % (tuple(hs.shape), self.transformer.decoder.num_layers, self.num_query))
         view = self.decoder_heads()
-        ncls, code = self.cls_out_channels, self.code_size
-        out = torch.empty(Lyr * B * Q * (ncls + code), dtype=torch.float32, device=dev)
-        cls = out[:Lyr * B * Q * ncls].view(Lyr, B, Q, ncls)
-        box = out[Lyr * B * Q * ncls:].view(Lyr, B, Q, code)
+        cls, box = self._output_views(out, count, B, dev, 'decoder_outputs')
         src = options if options is not None else (self.forward_options if self.forward_options is not None
                                                    else head_options())
         own = L.tc_head_options()          # (of a forward's options this launch takes these three alone)
         own.chain_tile_rows = self.effective_tile_rows(src.chain_tile_rows, src.matrix_path)
         own.matrix_path = self.effective_matrix_path(src.matrix_path)
         own.range_status = src.range_status or self.status_buffer(dev).data_ptr()
-        L.check(L.lib().tc_decoder_outputs_fwd(
+        L.check(L.lib().tc_decoder_outputs_levels_fwd(
             C.byref(view), hs.data_ptr(), aux_t['init_reference'].data_ptr(), aux_t['inter_references'].data_ptr(),
-            B, Q, cls.data_ptr(), box.data_ptr(), C.byref(own), L.stream_ptr(dev)), 'tc_decoder_outputs_fwd')
+            B, Q, first, count, cls.data_ptr(), box.data_ptr(), C.byref(own), L.stream_ptr(dev)),
+            'tc_decoder_outputs_levels_fwd')
         return cls, box
 
     def _check_outputs(self):
@@ -796,26 +860,45 @@ class Detr3DHead(BaseModule):
         Q, ncls, code = self.num_query, self.cls_out_channels, self.code_size
         NF = self.num_fusion_layers
         # one allocation, two views (_out: a static buffer of a captured graph, transcar_amd/plugin_graph.py)
-        out = _out if _out is not None else torch.empty(NF * B * Q * (ncls + code), dtype=torch.float32, device=dev)
-        if out.numel() != NF * B * Q * (ncls + code) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise L.TransCARHipError('forward_nhwc: _out must be a contiguous fp32 buffer of %d elements' % (NF * B * Q * (ncls + code)))
-        cls = out[:NF * B * Q * ncls].view(NF, B, Q, ncls)
-        box = out[NF * B * Q * ncls:].view(NF, B, Q, code)
+        if isinstance(_out, (tuple, list)):
+            # a pair (class scores, boxes): the fusion levels' rows of an [L + NF,B,Q,.] result (outputs='all')
+            cls, box = self._output_views(_out, NF, B, dev, 'forward_nhwc')
+        else:
+            out = _out if _out is not None else torch.empty(NF * B * Q * (ncls + code), dtype=torch.float32, device=dev)
+            if out.numel() != NF * B * Q * (ncls + code) or out.dtype != torch.float32 or not out.is_contiguous():
+                raise L.TransCARHipError('forward_nhwc: _out must be a contiguous fp32 buffer of %d elements' % (NF * B * Q * (ncls + code)))
+            cls = out[:NF * B * Q * ncls].view(NF, B, Q, ncls)
+            box = out[NF * B * Q * ncls:].view(NF, B, Q, code)
         fv = ops.feats_view(feats_nhwc)
         aux_s, aux_t = None, None
         if aux:
             # aux='train': what a training iteration needs of the frozen decoder (FusionTrainer), its states / references
             # / last box, written in place by the chains -- no init_reference copy, no pair counter (a zero fill + atomics)
-            Lyr, full, f32 = w.num_layers, aux != 'train', dict(dtype=torch.float32, device=dev)
-            aux_t = dict(inter_states=torch.empty((Lyr, B, Q, self.embed_dims), **f32))
-            if full:
-                aux_t['init_reference'] = torch.empty((B, Q, 3), **f32)
-            aux_t['inter_references'] = torch.empty((Lyr, B, Q, 3), **f32)
-            if full:
-                aux_t['radar_hit_counts'] = torch.empty((NF, B, Q), dtype=torch.int32, device=dev)
-            aux_t['last_box'] = torch.empty((B, Q, code), **f32)
-            if full:
-                aux_t['sample_pairs'] = torch.zeros(1, dtype=torch.int64, device=dev)
+            # aux='levels': what decoder_outputs reads (a frame graph with outputs 'camera' / 'all'): the states and the
+            # references of every level -- no hit counts, no pair counter
+            # a dict: tensors of an earlier call with aux='levels', written again (the two phases of a plugin graph entry
+            # are two calls that must share the states)
+            Lyr, f32 = w.num_layers, dict(dtype=torch.float32, device=dev)
+            if isinstance(aux, dict):
+                want = dict(inter_states=(Lyr, B, Q, self.embed_dims), init_reference=(B, Q, 3), inter_references=(Lyr, B, Q, 3))
+                for k, shape in want.items():
+                    t = aux.get(k)
+                    if t is None or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                        raise L.TransCARHipError('forward_nhwc: aux[%r] must be a contiguous fp32 tensor of shape %s on %s'
+                                                 % (k, shape, dev))
+                aux_t = {k: aux[k] for k in want}
+            else:
+                full, levels = aux not in ('train', 'levels'), aux == 'levels'
+                aux_t = dict(inter_states=torch.empty((Lyr, B, Q, self.embed_dims), **f32))
+                if full or levels:
+                    aux_t['init_reference'] = torch.empty((B, Q, 3), **f32)
+                aux_t['inter_references'] = torch.empty((Lyr, B, Q, 3), **f32)
+                if full:
+                    aux_t['radar_hit_counts'] = torch.empty((NF, B, Q), dtype=torch.int32, device=dev)
+                if not levels:
+                    aux_t['last_box'] = torch.empty((B, Q, code), **f32)
+                if full:
+                    aux_t['sample_pairs'] = torch.zeros(1, dtype=torch.int64, device=dev)
             aux_s = L.tc_head_aux(**{k: t.data_ptr() for k, t in aux_t.items()})
 
         def call(opts):
@@ -868,9 +951,8 @@ class Detr3DHead(BaseModule):
             raise L.TransCARHipError(
                 'Detr3DHead.forward needs the feature maps on the MI355X '
                 '(got %s); transcar_amd has no CPU path' % dev)
-        if self.outputs == 'camera':
-            return self._forward_camera(mlvl_feats, img_metas, aux)
-        raws = radar_frames(img_metas)
+        camera = self.outputs == 'camera'
+        raws = None if camera else radar_frames(img_metas)   # ('camera' neither reads nor requires radar)
         # round 6: a call signature seen before (same feature-map addresses, shapes, options) replays two captured
         # graphs instead of ~20 eager launches (transcar_amd/plugin_graph.py); anything else takes the eager path below
         if self._plugin_graphs is None:
@@ -880,6 +962,8 @@ class Detr3DHead(BaseModule):
             outs = self._plugin_graphs.forward(mlvl_feats, img_metas)
             if outs is not None:
                 return outs
+        if camera:
+            return self._forward_camera(mlvl_feats, img_metas, aux)
         feats_nhwc = ops.to_nhwc_levels(mlvl_feats)       # one launch; channels_last levels zero-copy
         l2i = ops.lidar2img_tensor(img_metas, dev, staged=True)    # pinned ring, one async H2D (none if unchanged)
         img_hw = img_metas[0]['img_shape'][0][:2]           # XFMR:403-404
@@ -893,11 +977,13 @@ class Detr3DHead(BaseModule):
         if self.outputs == 'all':
             # the default forward with the decoder's states kept, then the decoder levels' own branches; the
             # reference's order with HEAD:607-608 commented out: decoder levels first
-            outs = self.forward_nhwc(feats_nhwc, l2i, img_hw, tokens, pad_mult,
-                                     aux=True, fill_tokens=fill, options=self.forward_options)
-            cls, box = self.decoder_outputs(outs['aux'])
-            outs['all_cls_scores'] = torch.cat((cls, outs['all_cls_scores']))
-            outs['all_bbox_preds'] = torch.cat((box, outs['all_bbox_preds']))
+            # -- both launches write their rows of ONE [L + NF,B,Q,.] allocation (`all_outputs_buffer`), no torch.cat
+            Lyr = self.transformer.decoder.num_layers
+            cls, box = self.all_outputs_buffer(len(img_metas), dev)
+            outs = self.forward_nhwc(feats_nhwc, l2i, img_hw, tokens, pad_mult, aux=True, fill_tokens=fill,
+                                     options=self.forward_options, _out=(cls[Lyr:], box[Lyr:]))
+            self.decoder_outputs(outs['aux'], out=(cls[:Lyr], box[:Lyr]))
+            outs['all_cls_scores'], outs['all_bbox_preds'] = cls, box
             if not aux:
                 del outs['aux']
             return outs

@@ -65,15 +65,44 @@ class FramePipeline:
     height of the full launch (``tile_rows_of``): it shares the chip with the other lanes' launches, where the
     matrix-pipe time per row counts (16x16x4 MFMA tiles), not the latency of a launch that is alone (the automatic
     rule's 8- or 4-row tiles for few rows): the driver's 20-step window (9 + 9 + 2 frames) 5 372 -> 5 490 frames/s.
+    outputs (None = 'fusion' | 'camera' | 'all'): what the lanes compute, as ``Detr3DHead.outputs`` names it; fixed for
+    the pipeline's life, and ``head.outputs`` must equal it at construction, capture and launch.
+    'camera': the DETR3D camera detector alone -- a lane's dict needs nhwc, l2i and hw (optionally nchw), no tokens and no
+    pad_mult; the graph is the optional hand-off, the decoder (no radar encoders, no fusion stage), ONE launch of the
+    decoder levels' heads and the box decode of the last decoder level.  ``decoder_levels='last'`` launches the last
+    level's heads alone (tc_decoder_outputs_levels_fwd): all_cls_scores / all_bbox_preds are [1,P,Q,.] instead of
+    [L,P,Q,.].  The radar stages and write_inputs(tokens= / pad_mult= / radar_frame= / radar_rows=) are refused.
+    'all': lanes as for 'fusion', radar stages included; outputs [L + N,P,Q,.] in one static buffer, decoder levels first;
+    the decode reads the last fusion level.  Partial launches, results, recapture, the range-guard status copy, the
+    re-pack after an optimizer step and the generation check are the same in every mode.
     """
 
     def __init__(self, head, static_inputs, decode=True, tile_rows=None, options=None, streams=None,
-                 partial_graphs=True, radar_raw_capacity=None, radar_rows_capacity=None):
+                 partial_graphs=True, radar_raw_capacity=None, radar_rows_capacity=None, outputs=None,
+                 decoder_levels='all'):
         if not static_inputs:
             raise ValueError('at least one lane')
-        from .detr3d_head import head_options
+        from .detr3d_head import OUTPUTS, head_options
         self.head, self.decode = head, decode
+        #: what the lanes' graphs compute, fixed for the pipeline's life (None = 'fusion'); ``head.outputs`` must equal it
+        self.mode = 'fusion' if outputs is None else outputs
+        if self.mode not in OUTPUTS:
+            raise TransCARHipError("FramePipeline: outputs=%r (one of 'fusion', 'camera', 'all')" % (outputs,))
+        if decoder_levels not in ('all', 'last'):
+            raise TransCARHipError("FramePipeline: decoder_levels=%r ('all' or 'last')" % (decoder_levels,))
+        if decoder_levels == 'last' and self.mode != 'camera':
+            raise TransCARHipError(
+                "FramePipeline: decoder_levels='last' with outputs=%r: only a 'camera' pipeline may launch the last decoder "
+                "level's heads alone ('all' has a fixed layout, decoder levels then fusion levels; 'fusion' launches none)"
+                % (self.mode,))
+        #: 'camera' only: 'all' = the heads of every decoder level, 'last' = of the last one alone ([1,P,Q,.] outputs)
+        self.decoder_levels = decoder_levels
         self._check_outputs()
+        if self.mode == 'camera':
+            for name, v in (('radar_raw_capacity', radar_raw_capacity), ('radar_rows_capacity', radar_rows_capacity)):
+                if v:
+                    raise TransCARHipError("FramePipeline: %s=%r with outputs='camera' (a camera pipeline has no radar stage)"
+                                           % (name, v))
         self.partial_graphs = bool(partial_graphs)
         self.inputs = list(static_inputs)
         #: frames per launch = the batch size of the lanes' static inputs
@@ -133,6 +162,11 @@ class FramePipeline:
         self._status_host = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in self.inputs]
         self._status_seen = [0] * len(self.inputs)
         self._next = 0
+        # 'camera': the decoder-only forward reads no token -- the tensor only gives the workspace layout its T
+        self._cam_tokens = None
+        if self.mode == 'camera':
+            self._cam_tokens = [torch.empty((self.frames_per_launch, 64, head.radar_in_dims), dtype=torch.float32,
+                                            device=inp['l2i'].device) for inp in self.inputs]
         self._capture()
 
     def _auto_tile_rows(self, rows):
@@ -166,15 +200,35 @@ class FramePipeline:
             # the first n frame slots of the lane's static tensors (dim 0 = P or P * num_cams), as views
             def head_of(t):
                 return t[:(t.shape[0] // P) * n]
-            inp = dict(inp, nhwc=[head_of(t) for t in inp['nhwc']], l2i=inp['l2i'][:n], tokens=inp['tokens'][:n])
+            inp = dict(inp, nhwc=[head_of(t) for t in inp['nhwc']], l2i=inp['l2i'][:n])
+            if self.mode != 'camera':
+                inp['tokens'] = inp['tokens'][:n]
             if inp.get('nchw') is not None:
                 inp['nchw'] = [head_of(t) for t in self.inputs[i]['nchw']]
         if inp.get('nchw') is not None:
             ops.to_nhwc_levels(inp['nchw'], out=inp['nhwc'])
         if self.radar_stage is not None:       # raw sweeps -> this launch's tokens (first node of the graph)
             self.radar_stage[i].build(self.inputs[i]['tokens'], n=n)
-        outs = self.head.forward_nhwc(inp['nhwc'], inp['l2i'], inp['hw'], inp['tokens'],
-                                      inp['pad_mult'], lane=i, options=self._options_of(n))
+        head, options = self.head, self._options_of(n)
+        if self.mode == 'fusion':
+            outs = head.forward_nhwc(inp['nhwc'], inp['l2i'], inp['hw'], inp['tokens'],
+                                     inp['pad_mult'], lane=i, options=options)
+        elif self.mode == 'camera':
+            # the decoder alone (no radar encoders, no fusion stage), then its levels' own heads: one more launch
+            tokens = self._cam_tokens[i][:inp['l2i'].shape[0]]
+            base = head.forward_nhwc(inp['nhwc'], inp['l2i'], inp['hw'], tokens, 1, lane=i, options=options,
+                                     aux='levels', decoder_only=True)
+            cls, box = head.decoder_outputs(base['aux'], options=options,
+                                            levels='last' if self.decoder_levels == 'last' else None)
+            outs = {'all_cls_scores': cls, 'all_bbox_preds': box, 'enc_cls_scores': None, 'enc_bbox_preds': None}
+        else:
+            # 'all': decoder levels, then fusion levels, in one [L + N,P,Q,.] buffer both launches write
+            Lyr = head.transformer.decoder.num_layers
+            cls, box = head.all_outputs_buffer(inp['l2i'].shape[0], inp['l2i'].device)
+            outs = head.forward_nhwc(inp['nhwc'], inp['l2i'], inp['hw'], inp['tokens'], inp['pad_mult'], lane=i,
+                                     options=options, aux='levels', _out=(cls[Lyr:], box[Lyr:]))
+            head.decoder_outputs(outs.pop('aux'), options=options, out=(cls[:Lyr], box[:Lyr]))
+            outs['all_cls_scores'], outs['all_bbox_preds'] = cls, box
         dec = None
         if self.decode:
             dec = ops.box_decode_topk(outs['all_cls_scores'][-1], outs['all_bbox_preds'][-1],
@@ -185,18 +239,23 @@ class FramePipeline:
         return outs, dec
 
     def _check_outputs(self):
-        """The lanes capture the fusion outputs only.  ``Detr3DHead.outputs`` is a plain attribute that may change after
-        the pipeline was built: checked at construction, at every capture and at every launch."""
-        if self.head.outputs != 'fusion':
+        """The lanes capture ONE kind of outputs (``mode``).  ``Detr3DHead.outputs`` is a plain attribute that may change
+        after the pipeline was built: checked at construction, at every capture and at every launch."""
+        if self.head.outputs != self.mode:
             raise TransCARHipError(
-                "FramePipeline: Detr3DHead.outputs=%r is not supported in a pipeline (its lanes capture the fusion "
-                "outputs only); use outputs='fusion' or the eager Detr3DHead.forward" % (self.head.outputs,))
+                "FramePipeline: Detr3DHead.outputs=%r is not supported in a pipeline built for outputs=%r (its lanes "
+                "capture that mode alone); set head.outputs=%r or build a FramePipeline(outputs=%r)"
+                % (self.head.outputs, self.mode, self.mode, self.head.outputs))
 
     def _capture(self):
         self._check_outputs()
         self.graphs, self.outputs = [], []
         self._partial = {}
         with torch.no_grad():
+            if self.mode != 'fusion':
+                # the decoder levels' packed heads, before anything is captured (a later re-pack that re-allocates them
+                # bumps head.buffers_generation: the graphs below refuse to replay)
+                self.head.decoder_heads()
             for i, s in enumerate(self.streams):
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -335,6 +394,11 @@ class FramePipeline:
         P = self.frames_per_launch
         if slot is not None and not 0 <= slot < P:
             raise TransCARHipError('slot %r of %d' % (slot, P))
+        if self.mode == 'camera':
+            for name, v in (('tokens', tokens), ('pad_mult', pad_mult), ('radar_frame', radar_frame), ('radar_rows', radar_rows)):
+                if v is not None:
+                    raise TransCARHipError("FramePipeline.write_inputs: %s given to a lane of a pipeline with "
+                                           "outputs='camera' (it reads no radar)" % name)
         self.producer_wait(lane)
         if radar_rows is not None:
             # [n,F] feature rows of ONE frame (slot j; slot None: a list with one tensor per slot) for the lane's
