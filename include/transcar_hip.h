@@ -92,6 +92,17 @@ extern "C" {
 #define TC_MIN_RADAR_TOKENS 64
 #define TC_MAX_RADAR_TOKENS 4096
 #define TC_MAX_RADAR_IN_DIMS 64
+/* tc_head_weights.ffn_dims, the decoder layers' feedforward_channels (ffn0 is [ffn_dims, C], ffn1 [C, ffn_dims]): a
+ * multiple of TC_FFN_DIMS_STEP from TC_FFN_DIMS_MIN to TC_FFN_DIMS_MAX (512 in the reference's configs) for the packed
+ * (fused) entries; another width is refused as ffn_dims=<width>, the size queries return 0.  tc_head_forward on the
+ * caller's own struct (no packed view, or options.unfused) takes every multiple of 32.  The fused row chains hold 512
+ * hidden units at a time and run a wider FFN as chunks, so tc_head_pack_weights packs ffn1 as ffn_dims / 512 (rounded
+ * up) matrices [C, <= 512] one behind the other; at 512 that is the one matrix.
+ * The fusion layers' FFN (rf_linear1 / rf_linear2, HEAD:131) is TC_RADAR_FFN_DIMS wide whatever the decoder's is. */
+#define TC_FFN_DIMS_MIN 256
+#define TC_FFN_DIMS_MAX 2048
+#define TC_FFN_DIMS_STEP 256
+#define TC_RADAR_FFN_DIMS 512
 #define TC_ABI_VERSION 13
 
 typedef void* tc_stream_t;
@@ -464,7 +475,10 @@ int tc_self_attn_fwd(const tc_mha* w, const float* x, const float* pos, float* o
  * num_points = 1 only: tc_decoder_layer does not carry num_points, and a layer of a head with num_points > 1 would be read
  * as its first num_cams * num_levels attention-weight rows.  Such heads run through tc_head_forward.
  * feats->num_levels = 4 only (another level count is refused, naming it); heads with 1 .. 3 levels run through
- * tc_head_forward as well. */
+ * tc_head_forward as well.
+ * ffn_dims = 512 only: there is no width argument, and tc_decoder_layer does not carry one.  A layer of a head with
+ * another feedforward_channels would be read as a 512-wide one; such layers go through tc_decoder_layer_tail_fwd_ffn
+ * (below) or tc_head_forward. */
 int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* next_in_proj,
                               const tc_feats_nhwc* feats, int B, int Q, int num_cams,
                               int code_size, const float* attn_o, const float* x_in,
@@ -473,6 +487,16 @@ int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* ne
                               float img_h, float img_w, float* hs, float* ref_out,
                               float* qk, float* vt, int qpad,
                               int tile_rows /* 0 automatic, 4, 8, 16; | TC_MATRIX_* << 8 */, tc_stream_t stream);
+/* ... and with the width: `layer` is a layer of a packed view whose head has tc_head_weights.ffn_dims = ffn_dims (a
+ * multiple of TC_FFN_DIMS_STEP from TC_FFN_DIMS_MIN to TC_FFN_DIMS_MAX; another width is refused as ffn_dims=<width>).
+ * ffn_dims = 512 is tc_decoder_layer_tail_fwd. */
+int tc_decoder_layer_tail_fwd_ffn(const tc_decoder_layer* layer, const tc_linear* next_in_proj,
+                                  const tc_feats_nhwc* feats, int B, int Q, int num_cams,
+                                  int code_size, const float* attn_o, const float* x_in,
+                                  const float* query_embedding, const float* lidar2img,
+                                  const float* ref_in, const float* pc_range /*host[6]*/,
+                                  float img_h, float img_w, float* hs, float* ref_out,
+                                  float* qk, float* vt, int qpad, int tile_rows, int ffn_dims, tc_stream_t stream);
 
 /* The attention core of the above on already projected operands (the kernel
  * the roofline is quoted on): out = softmax(q k^T) v per (batch, head).

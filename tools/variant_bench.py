@@ -8,6 +8,7 @@ values.  The first value is the base of `relative_to_first`.
     python tools/variant_bench.py --vary num_heads 8 4 16
     python tools/variant_bench.py --vary radar_num_heads 8 4 16
     python tools/variant_bench.py --vary with_box_refine 1 0
+    python tools/variant_bench.py --vary feedforward_channels 512 256 1024 2048
     python tools/variant_bench.py --vary radar_num_tokens 1500 4096 --radar-points 255 3000
     python tools/variant_bench.py --vary radar_in_dims 36 4 --radar-num-tokens 4096 --radar-points 3000
 
@@ -24,6 +25,8 @@ radar_num_tokens the head's token count N (1500 is the headline) with --radar-po
                  frames (tc_radar_fusion_fwd on encoded tokens; with the three fills of its output tensors).
 radar_in_dims    features per token (36 is the headline) at --radar-num-tokens N: the rows are the first F of the 36 columns.
                  The fusion chain reads a token's x, y at a stride of 4 F bytes: its time against F = 4 is what the stride costs.
+feedforward_channels  the decoder layers' FFN width (512 is the headline; DESIGN.md "feedforward_channels"): the decoder chains
+                 run ceil(F / 512) chunks of the FFN's two steps.  The fusion layers' FFN stays 512 wide.
 with_box_refine  both heads carry synth.make_state_dict(with_box_refine=False)'s shared branches; the results are keyed
                  'refine' / 'norefine' and `norefine_over_refine` is reported, as profiles/box_refine_bench.json has it."""
 import argparse
@@ -43,7 +46,8 @@ import bench  # noqa: E402
 import transcar_amd as T  # noqa: E402
 from transcar_amd import configs, synth  # noqa: E402
 
-KEYWORDS = ('num_points', 'num_levels', 'num_heads', 'radar_num_heads', 'with_box_refine', 'radar_num_tokens', 'radar_in_dims')
+KEYWORDS = ('num_points', 'num_levels', 'num_heads', 'radar_num_heads', 'with_box_refine', 'radar_num_tokens', 'radar_in_dims',
+            'feedforward_channels')
 
 
 def build_head(dev, keyword, value, **cfg_kw):

@@ -126,6 +126,25 @@ def check_num_heads(num_heads):
             'head dimension 64, 32 or 16)' % (num_heads,))
 
 
+# tc_head_weights.ffn_dims, the decoder layers' feedforward_channels: what the fused row chains run (include/transcar_hip.h);
+# the width of the fusion layers' FFN, rf_linear1 / rf_linear2, whatever the decoder's is
+TC_FFN_DIMS_MIN, TC_FFN_DIMS_MAX, TC_FFN_DIMS_STEP = 256, 2048, 256
+TC_RADAR_FFN_DIMS = 512
+
+
+def check_ffn_dims(ffn_dims):
+    """The library's limit on a decoder layer's feedforward_channels (tc_head_weights.ffn_dims: a multiple of 256 from
+    256 to 2048 -- the fused chains run the FFN in chunks of 512 hidden units, the last one 256 or 512 wide), checked
+    before anything is built, packed or launched.  Returns the width."""
+    f = ffn_dims
+    if (isinstance(f, bool) or not isinstance(f, int) or not TC_FFN_DIMS_MIN <= f <= TC_FFN_DIMS_MAX
+            or f % TC_FFN_DIMS_STEP != 0):
+        raise TransCARHipError(
+            'DetrTransformerDecoderLayer(HIP): feedforward_channels, ffn_dims=%r, is not supported (the accepted set: '
+            'multiples of %d from %d to %d)' % (f, TC_FFN_DIMS_STEP, TC_FFN_DIMS_MIN, TC_FFN_DIMS_MAX))
+    return f
+
+
 def check_radar_num_heads(radar_num_heads):
     """The library's limit on the head count of the radar fusion attention (rf_multihead_attn{,2,3}: 4, 8 or 16 at
     embed_dims 256), checked before anything is built, packed or launched.  Returns the count."""
@@ -421,6 +440,10 @@ SIGNATURES = {
                                        _P(tc_feats_nhwc), _i, _i, _i, _i, _vp,
                                        _vp, _vp, _vp, _vp, _P(_f), _f, _f, _vp,
                                        _vp, _vp, _vp, _i, _i, _vp]),
+    'tc_decoder_layer_tail_fwd_ffn': (_i, [_P(tc_decoder_layer), _P(tc_linear),
+                                           _P(tc_feats_nhwc), _i, _i, _i, _i, _vp,
+                                           _vp, _vp, _vp, _vp, _P(_f), _f, _f, _vp,
+                                           _vp, _vp, _vp, _i, _i, _i, _vp]),
     'tc_sdpa_fwd': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     'tc_sdpa_f16x2_workspace_bytes': (_sz, [_i, _i, _i]),
     'tc_sdpa_fwd_f16x2': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),

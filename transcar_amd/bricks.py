@@ -195,6 +195,8 @@ class DetrTransformerDecoderLayer(BaseTransformerLayer):
     def __init__(self, attn_cfgs, feedforward_channels, ffn_dropout=0.0,
                  operation_order=None, act_cfg=None, norm_cfg=None,
                  ffn_num_fcs=2, **kwargs):
+        from ._lib import check_ffn_dims
+        check_ffn_dims(feedforward_channels)
         super().__init__(attn_cfgs=attn_cfgs,
                          feedforward_channels=feedforward_channels,
                          ffn_dropout=ffn_dropout,

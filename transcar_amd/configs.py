@@ -79,7 +79,7 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
              num_levels=None, num_heads=None, num_classes=None,
              num_fusion_layers=None, pc_range=None, post_center_range=None, radar_gate=None,
              radar_num_heads=None, radar_num_tokens=None, radar_in_dims=None, radar_point_range=None,
-             num_cams=None):
+             num_cams=None, feedforward_channels=None):
     """pts_bbox_head; num_points overrides Detr3DCrossAtten.num_points (the
     TransCAR configs use 1, CFG:75; the reference class defaults to 5);
     with_box_refine overrides the head's (the configs: True, CFG:57; the
@@ -115,7 +115,12 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
     Detr3DCrossAtten and of the transformer (the configs: the class defaults,
     6; 1 .. 16 -- the reference reads the count off ``lidar2img`` and sizes
     ``attention_weights`` as Linear(C, num_cams * num_points * num_levels),
-    XFMR:280-292): the keys are added only for a count other than 6."""
+    XFMR:280-292): the keys are added only for a count other than 6.
+    feedforward_channels sets the hidden width of every decoder layer's FFN
+    (``transformerlayers.feedforward_channels``; the configs: 512, CFG:79; a
+    multiple of 256 from 256 to 2048, ``_lib.check_ffn_dims``): the key is
+    written only for a width other than 512.  The fusion layers' FFN keeps the
+    512 the reference writes as a constant (HEAD:131)."""
     cfg = copy.deepcopy(pts_bbox_head)
     cfg['num_query'] = num_query
     if with_box_refine is not None:
@@ -133,6 +138,11 @@ def head_cfg(num_query=900, num_points=None, with_box_refine=None,
             layers = cfg['transformer']['decoder']['transformerlayers']
             layers['attn_cfgs'][1]['num_cams'] = num_cams
             cfg['transformer']['num_cams'] = num_cams
+    if feedforward_channels is not None:
+        from ._lib import check_ffn_dims
+        if check_ffn_dims(feedforward_channels) != 512:
+            layers = cfg['transformer']['decoder']['transformerlayers']
+            layers['feedforward_channels'] = feedforward_channels
     if num_heads is not None:
         from ._lib import check_num_heads
         check_num_heads(num_heads)

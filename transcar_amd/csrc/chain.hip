@@ -104,7 +104,7 @@ struct EpiRec {
   int gld, act, flags, N;
   int has_bias, woff;
   int drop_site;               // train-mode decoder dropout on this step's output: site + 1 (0: none)
-  int pad1;
+  int drop_idx;                // ... whose mask is wider than the step (an FFN hidden chunk): row stride << 16 | first column (0: N, 0)
 };
 // per wave: the next linear step of the same run in which the wave owns a column tile
 struct PreRec { const float* first; int nidx; int pad; };
@@ -459,6 +459,7 @@ struct ChainK : ChainDev {
   int npoints = 1;             // decoder: Detr3DCrossAtten.num_points (> 1: the MP instantiations, logits in unit 3)
   int refine = 1;              // decoder: the layer has a reg branch (0: reg.0 / .2 / .4 and K_REFUPD are K_NOP)
   int l0_seq = 0;              // decoder: the record sequence -- 0 PROG_DECODER_T, 1 PROG_DECODER_L0_T, 2 PROG_DECODER_L0GEN_T
+  int ffn = 0;                 // decoder: feedforward_channels (the FFN pair of the table becomes ffn_chunks(ffn) pairs of records)
 };
 
 // the decoder's cross-attention takes the generic (MP) kernels with num_points > 1, fewer than 4 levels, or more
@@ -478,7 +479,15 @@ constexpr int table_steps(int prog) {
           : prog == PROG_DECODER_HEADS ? (int)(sizeof(PROG_DECODER_HEADS_T) / sizeof(StepDesc))
                                      : (int)(sizeof(PROG_RADAR_LAYER_T) / sizeof(StepDesc))) - 1;
 }
-constexpr int rec_cap(int prog) { return table_steps(prog) * ((prog_is_radar(prog) || prog == PROG_RADAR_BWD) ? TC_MAX_RADAR_LAYERS : 1); }
+// The decoder's FFN hidden activation lives in B_A, 512 columns: a wider FFN runs as chunks of at most 512 hidden units,
+// one (ffn0_c, ffn1_c) pair of records each (resolve_program) -- up to 2 * (ffn_chunks(TC_FFN_DIMS_MAX) - 1) records more
+// than the table has steps.
+constexpr int FFN_CHUNK = 512;
+constexpr int ffn_chunks(int F) { return (F + FFN_CHUNK - 1) / FFN_CHUNK; }
+constexpr int rec_cap(int prog) {
+  return table_steps(prog) * ((prog_is_radar(prog) || prog == PROG_RADAR_BWD) ? TC_MAX_RADAR_LAYERS : 1) +
+         (prog == PROG_DECODER ? 2 * (ffn_chunks(TC_FFN_DIMS_MAX) - 1) : 0);
+}
 static_assert(sizeof(BWD_STORE) / sizeof(short) == table_steps(PROG_RADAR_BWD), "backward maps follow the step table");
 static_assert(sizeof(RADAR_TAPE) / sizeof(short) == table_steps(PROG_RADAR) && sizeof(ENC_TAPE) / sizeof(short) == table_steps(PROG_RADAR_ENC),
               "tape maps follow the step tables");
@@ -510,6 +519,7 @@ struct LinSpec {
   int drop_site;               // DROP instantiations: site + 1 of this step's output dropout (0: none)
   unsigned long long drop_seed; unsigned drop_thr; float drop_scale;
   unsigned long long drop_stride; int drop_q;     // per-sample seeds (DropK::seed_stride / rows_per_sample; 0: off)
+  unsigned drop_ld, drop_c0;   // the mask element of (row, col) is row * drop_ld + drop_c0 + col (N, 0 unless EpiRec::drop_idx)
   const int* rowg;             // radar: LDS table tile position -> global row for the gdst stores (null: m0 + i)
   int gpre;                    // F_GPRE
   const float* cmask; float cscale;   // F_CMASK: y = cmask[row, col] > 0 ? y * cscale : 0 (cmask is [M, N])
@@ -653,7 +663,7 @@ __device__ __forceinline__ void lin_epilogue(const LinSpec& s, int tile, const A
           unsigned row = (unsigned)(s.m0 + 4 * g + i);
           unsigned long long seed = s.drop_seed;
           if (s.drop_q > 0) { const unsigned b = row / (unsigned)s.drop_q; row -= b * (unsigned)s.drop_q; seed += b * s.drop_stride; }
-          const unsigned idx = row * (unsigned)s.N + (unsigned)col;
+          const unsigned idx = row * s.drop_ld + s.drop_c0 + (unsigned)col;
           y[g][i] = drop_keep(seed, (unsigned)(s.drop_site - 1), idx, s.drop_thr) ? y[g][i] * s.drop_scale : 0.0f;
         }
     }
@@ -844,7 +854,7 @@ __device__ __forceinline__ void lin_epilogue16(const LinSpec& s, int colbase, co
 #pragma unroll
         for (int jj = 0; jj < NJ; ++jj) {
           // the lane's four consecutive columns of sub-tile jj: one hash (N and colb are multiples of 4)
-          const unsigned m = drop_keep4(seed, (unsigned)(s.drop_site - 1), row * (unsigned)s.N + (unsigned)(colb + 16 * jj), s.drop_thr);
+          const unsigned m = drop_keep4(seed, (unsigned)(s.drop_site - 1), row * s.drop_ld + s.drop_c0 + (unsigned)(colb + 16 * jj), s.drop_thr);
 #pragma unroll
           for (int i = 0; i < 4; ++i) y[NJ * rg + jj][i] = ((m >> i) & 1u) ? y[NJ * rg + jj][i] * s.drop_scale : 0.0f;
         }
@@ -1180,7 +1190,7 @@ __device__ __forceinline__ void lin_epilogue32(const LinSpec& s, int colbase, co
         if (s.drop_q > 0) { const unsigned b = row / (unsigned)s.drop_q; row -= b * (unsigned)s.drop_q; seed += b * s.drop_stride; }
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
-          const unsigned m = drop_keep4(seed, (unsigned)(s.drop_site - 1), row * (unsigned)s.N + (unsigned)(colb + 16 * jj), s.drop_thr);
+          const unsigned m = drop_keep4(seed, (unsigned)(s.drop_site - 1), row * s.drop_ld + s.drop_c0 + (unsigned)(colb + 16 * jj), s.drop_thr);
 #pragma unroll
           for (int i = 0; i < 4; ++i) t[2 * rg + jj][i] = ((m >> i) & 1u) ? t[2 * rg + jj][i] * s.drop_scale : 0.0f;
         }
@@ -1928,6 +1938,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
     s.dbg = k.dbg;
     s.sub_on = 0;
     s.drop_site = 0; s.drop_seed = 0; s.drop_thr = 0; s.drop_scale = 1.0f; s.drop_stride = 0; s.drop_q = 0;
+    s.drop_ld = 0; s.drop_c0 = 0;
     s.rowg = nullptr; s.gpre = 0; s.cmask = nullptr; s.cscale = 1.0f;
     s.dst_pl = 0; s.res_pl = 0; s.range_flag = nullptr;
     return s;
@@ -1954,16 +1965,19 @@ __device__ __forceinline__ void chain_body(const ChainDev& k, const StepAllT<nw_
     s.dbg = 0;
     s.sub_on = 0;
     s.drop_site = 0; s.drop_seed = 0; s.drop_thr = 0; s.drop_scale = 1.0f; s.drop_stride = 0; s.drop_q = 0;
+    s.drop_ld = 0; s.drop_c0 = 0;
     s.rowg = (prog_is_radar(PROG) && k.row_perm != nullptr) ? &S.rowg[0] : nullptr;
     s.gpre = (e.flags & F_GPRE) ? 1 : 0;
     s.dst_pl = PL && e.dst_ld != LDL; s.res_pl = PL && e.res_ld != LDL;      // (the logit buffer stays fp32)
     s.range_flag = MM == 1 ? k.range_status : nullptr;
     if (DROP) {
+      s.drop_ld = (unsigned)e.N;
       if constexpr (PROG == PROG_RADAR_TRAIN) {      // radar dropout sites 4 r + {1, 2, 3} (HEAD:581-585)
         s.drop_site = e.drop_site; s.drop_seed = k.rdrop.seed; s.drop_thr = k.rdrop.thr; s.drop_scale = k.rdrop.scale;
       } else {
         s.drop_site = e.drop_site; s.drop_seed = k.drop.seed; s.drop_thr = k.drop.thr; s.drop_scale = k.drop.scale;
         s.drop_stride = k.drop.seed_stride; s.drop_q = (int)k.drop.rows_per_sample;
+        if (e.drop_idx != 0) { s.drop_ld = (unsigned)e.drop_idx >> 16; s.drop_c0 = (unsigned)e.drop_idx & 0xFFFFu; }
       }
     }
     return s;
@@ -2715,6 +2729,11 @@ constexpr size_t chain_lds_bytes() { return sizeof(ChainLds<R, rec_cap(PROG)>); 
 // 8 waves): at 16 rows the second workgroup of a CU would go.  (The class head's second sub-tile, 17 .. 32 classes, is a
 // second trip inside its K_NARROW step for this reason, not a step of a longer table.)
 static_assert(chain_lds_bytes<16, PROG_RADAR>() <= 80 * 1024 && chain_lds_bytes<32, PROG_RADAR>() <= 160 * 1024, "radar programs: LDS per workgroup");
+// The decoder program with its six records for the FFN chunks beyond the first (rec_cap): 1 344 / 1 728 bytes more than the
+// table's 19 steps alone; two 16-row workgroups still share a CU.
+static_assert(chain_lds_bytes<16, PROG_DECODER>() == 75616 && chain_lds_bytes<32, PROG_DECODER>() == 147232 &&
+              2 * chain_lds_bytes<16, PROG_DECODER>() <= 160 * 1024, "decoder program: LDS per workgroup");
+static_assert(chain_lds_bytes<4, PROG_DECODER>() == 23104 && chain_lds_bytes<8, PROG_DECODER>() == 40608, "decoder program: LDS per workgroup");
 inline int buf_ld_h(int id) { return id == B_A ? LD5 : id == B_L ? LDL : LD2; }
 
 template <int R, int PROG, int MM = 0>
@@ -2731,13 +2750,35 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
   if (prog_is_enc_full(PROG) || PROG == PROG_RADAR_ENC_A || PROG == PROG_RADAR_ENC_B)
     while (nsteps > 0 && table[nsteps - 1].kind == K_LINEAR && table[nsteps - 1].wp >= 7 + k.nlayers) --nsteps;
   const int nrep = (prog_is_radar(PROG) || PROG == PROG_RADAR_BWD) ? k.nlayers : 1;
-  const int total = nsteps * nrep;
+  // The decoder's FFN (pairs 10, 11) in chunks of at most FFN_CHUNK hidden units -- what B_A holds.  Chunk c is a pair
+  // of records: ffn0_c = relu(x W0[c]^T + b0[c]) -> B_A, then ffn1_c onto B_U3: chunk 0 carries the residual B_X and the
+  // bias, the later ones accumulate in place (res = dst) without a bias.  Both are plain linear steps of shapes the
+  // table already has (256 -> 512 / 256 and 512 / 256 -> 256): ffn0's chunk is FFN_CHUNK rows further into its packed
+  // tiles, ffn1's is a packed matrix of its own (tc_head_pack_weights packs ffn1 chunk by chunk).  One chunk of 512:
+  // the table's own two records.
+  int ffn_first = -1, nchunk = 1;
+  if (PROG == PROG_DECODER && k.ffn > 0)
+    for (int i = 0; i + 1 < nsteps; ++i)
+      if (table[i].kind == K_LINEAR && table[i].wp == 10 && table[i + 1].kind == K_LINEAR && table[i + 1].wp == 11) {
+        ffn_first = i; nchunk = ffn_chunks(k.ffn);
+      }
+  const int nrec = nsteps + 2 * (nchunk - 1);      // records of one pass through the table
+  const int total = nrec * nrep;
   memset(out, 0, sizeof(StepAllT<NW>) * rec_cap(PROG));
   for (int idx = 0; idx < total; ++idx) {
-    const int rep = idx / nsteps, si = idx - rep * nsteps;
+    const int rep = idx / nrec, ri = idx - rep * nrec;
+    int si = ri, chunk = 0;                        // the table's step of record ri, and the FFN chunk it belongs to
+    if (ffn_first >= 0 && ri >= ffn_first) {
+      if (ri < ffn_first + 2 * nchunk) { chunk = (ri - ffn_first) >> 1; si = ffn_first + ((ri - ffn_first) & 1); }
+      else si = ri - 2 * (nchunk - 1);
+    }
     const int layer = PROG == PROG_RADAR_BWD ? k.nlayers - 1 - rep : rep;          // the backward walks the layers down
     const int pair0 = (prog_is_radar(PROG) || PROG == PROG_RADAR_BWD) ? layer * RADAR_PAIRS : 0;
-    const StepDesc d = table[si];
+    StepDesc d = table[si];
+    const int chunk_w = ffn_first < 0 ? 0 : (k.ffn - chunk * FFN_CHUNK < FFN_CHUNK ? k.ffn - chunk * FFN_CHUNK : FFN_CHUNK);
+    const bool ffn0_rec = ffn_first >= 0 && si == ffn_first, ffn1_rec = ffn_first >= 0 && si == ffn_first + 1;
+    if (ffn0_rec) d.N = (short)chunk_w;
+    if (ffn1_rec) { d.K = (short)chunk_w; if (chunk > 0) d.res = d.dst; }
     StepRes& r = out[idx].r;
     r.K = d.K; r.N = d.N;
     r.kind = d.kind; r.src = d.src; r.src2 = d.src2; r.dst = d.dst; r.res = d.res; r.act = d.act;
@@ -2806,6 +2847,14 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
       if (R >= 16) r.p0 += (MM == 1 ? 2 : 1) * k.w16_delta;   // the 16x16x4 copy / the two-plane f16 copy behind it (pack.hip); launch_r checks delta != 0
       r.p1 = pr.b ? pr.b + woff : nullptr;
       if (PROG == PROG_RADAR_BWD) r.p1 = nullptr;         // dx = dy W: no bias
+      if (ffn0_rec) {                                      // hidden units chunk * FFN_CHUNK ..: whole 64-row tiles further
+        r.p0 += (size_t)chunk * FFN_CHUNK * ((r.K + 63) & ~63);
+        if (r.p1 != nullptr) r.p1 += chunk * FFN_CHUNK;
+      }
+      if (ffn1_rec) {                                      // the chunk's own packed [256, chunk width] matrix
+        r.p0 += (size_t)chunk * FFN_CHUNK * 256;
+        if (chunk > 0) r.p1 = nullptr;
+      }
       if (d.gsel == G_CLS) r.gd += (size_t)rep * k.M * k.ncls;
       if (taped) r.gld = r.N;                              // the taped tensor is [M, N]
     } else if (d.kind == K_NARROW) {
@@ -2832,6 +2881,7 @@ void resolve_program(ChainK& k, StepAllT<nw_of(R)>* out) {
       // mmcv MultiheadAttention's output dropout, Detr3DCrossAtten.dropout (XFMR:378), the FFN's two
       const int off = d.wp == 1 ? 1 : d.wp == 4 ? 2 : d.wp == 10 ? 3 : d.wp == 11 ? 4 : 0;
       if (off) e.drop_site = (int)k.drop.site + off + 1;
+      if (ffn0_rec) e.drop_idx = (k.ffn << 16) | (chunk * FFN_CHUNK);      // the hidden site's mask is [rows, ffn]
     }
     if (PROG == PROG_RADAR_TRAIN && d.kind == K_LINEAR) {
       // rf_dropout2 on out_proj's output (before gate-free residual, HEAD:581), rf_dropout on relu(linear1),
@@ -2969,7 +3019,7 @@ constexpr int drop_variant(int v) { return v == TV_16_F32 ? TV_8 : v; }
 template <bool MP>
 int launch_decoder(const ChainK& k, hipStream_t s, const char* what) {
   if (k.drop.thr == 0) return launch_rows<PROG_DECODER, MP>(k, s, what);
-  TC_REQUIRE((unsigned long long)(k.drop.rows_per_sample ? k.drop.rows_per_sample : k.M) * 512ull < (1ull << 32),
+  TC_REQUIRE((unsigned long long)(k.drop.rows_per_sample ? k.drop.rows_per_sample : k.M) * (unsigned long long)k.ffn < (1ull << 32),
              "decoder_chain: dropout index space");
   return with_variant(tile_variant(k.M, k.tile_rows, k.matrix_path, what), [&](auto V) {
     constexpr int W = drop_variant(V);
@@ -3168,6 +3218,10 @@ static int make_decoder_k(const DecoderChainArgs& a, ChainK& k) {
   k.pairs[3] = w.attention_weights; k.pairs[4] = w.output_proj; k.pairs[5] = pe.l0;
   k.pairs[6] = ln_pair(pe.n1); k.pairs[7] = pe.l3; k.pairs[8] = ln_pair(pe.n4);
   k.pairs[9] = ln_pair(w.norm1); k.pairs[10] = w.ffn0; k.pairs[11] = w.ffn1;
+  TC_REQUIRE(a.ffn_dims >= TC_FFN_DIMS_MIN && a.ffn_dims <= TC_FFN_DIMS_MAX && a.ffn_dims % TC_FFN_DIMS_STEP == 0,
+             "decoder_chain: ffn_dims=%d (multiples of %d from %d to %d supported)", a.ffn_dims, TC_FFN_DIMS_STEP,
+             TC_FFN_DIMS_MIN, TC_FFN_DIMS_MAX);
+  k.ffn = a.ffn_dims;
   k.pairs[12] = ln_pair(w.norm2);
   k.pairs[13] = w.reg.l0; k.pairs[14] = w.reg.l2; k.pairs[15] = w.reg.l4;
   // without a reg branch (no box refinement) the layer writes neither ref_out nor a box

@@ -141,6 +141,15 @@ static int check_dims(const tc_head_weights* w) {
   return 0;
 }
 
+// The entries that read packed weights (the fused row chains): the decoder FFN runs in chunks of 512 hidden units, the last
+// one 256 or 512 wide.  (The operator-by-operator forward on the caller's own struct takes check_dims' multiples of 32.)
+static int check_ffn_dims_fused(const tc_head_weights* w) {
+  TC_REQUIRE(w->ffn_dims >= TC_FFN_DIMS_MIN && w->ffn_dims <= TC_FFN_DIMS_MAX && w->ffn_dims % TC_FFN_DIMS_STEP == 0,
+             "ffn_dims=%d (the fused entries take multiples of %d from %d to %d)", w->ffn_dims, TC_FFN_DIMS_STEP,
+             TC_FFN_DIMS_MIN, TC_FFN_DIMS_MAX);
+  return 0;
+}
+
 // Box refinement (with_box_refine, HEAD:45): a head without it hands the decoder reg_branches=None (XFMR:183-203) --
 // layers 0 .. L-2 carry reg.l0.w == NULL, and only the last layer's branch (the head's reg_branches[-1], HEAD:287-293)
 // exists.  Mixed NULL / set branches below the last layer are refused.  A one-layer decoder always refines.
@@ -169,7 +178,9 @@ struct HeadWs {
 
 static size_t head_ws_layout(const tc_head_weights* w, int B, int T, void* base, size_t cap,
                              HeadWs* out) {
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, L = w->num_layers;
+  const int Q = w->num_query, C = w->embed_dims, L = w->num_layers;
+  // the hidden activation of the operator-by-operator FFNs: the decoder's and the fusion layers' (rf_linear1, HEAD:131)
+  const int F = w->ffn_dims > TC_RADAR_FFN_DIMS ? w->ffn_dims : TC_RADAR_FFN_DIMS;
   const size_t rows = (size_t)B * Q, rt = (size_t)B * T;
   const int qpad = ((Q + 15) / 16) * 16;
   Arena a(base, cap);
@@ -285,6 +296,7 @@ static int fused_decoder_layers(const tc_head_weights* w, const tc_feats_nhwc* f
         l0c ? w->l0_attn_out : h.attn_o, lid == 0 ? qe + C : h.hs + (size_t)(lid - 1) * rows * C, lid == 0 ? 2 * C : C, qe,
         h.hs + (size_t)lid * rows * C, ref_out, h.qk, h.vt, h.qpad);
     d.attn_mod = l0c ? Q : 0; d.ref_mod = folded && init_in ? Q : 0; d.x_mod = lid == 0 ? Q : 0;
+    d.ffn_dims = w->ffn_dims;
     d.box_m = lid == L - 1 ? h.box_m : nullptr;
     if (ddrop) {
       d.drop = make_drop(opt.decoder_dropout_p, opt.dropout_seed, 16u + 8u * (unsigned)lid, 0u);
@@ -371,17 +383,18 @@ static int head_forward_fused(const tc_head_weights* w, const tc_feats_nhwc* fea
 }
 
 // ---- packed weights for the fused chains (pack.hip) --------------------------
-struct PackItem { const float* src; int N, K; const float** slot; bool narrow; bool absent; };
+struct PackItem { const float* src; int N, K; const float** slot; bool narrow; bool absent; bool chunked; };
 
 static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, PackItem* it) {
-  const int C = w->embed_dims, F = w->ffn_dims, NL = w->num_cams * w->num_levels * head_points(w);
+  const int C = w->embed_dims, F = w->ffn_dims, RF = TC_RADAR_FFN_DIMS, NL = w->num_cams * w->num_levels * head_points(w);
   const int code = w->code_size, ncls = w->num_classes;
   int n = 0;
   // narrow: the three 10-column heads the chains evaluate as wave-per-row dot products (K_NARROW): they
   // stay in the nn.Linear layout (the view keeps the caller's pointer: nothing to re-pack after an
   // optimizer step); listed so that the item order / counts stay what tc_head_repack_trainable assumes
   auto add = [&](const tc_linear& src, tc_linear& dst, int N, int K, bool narrow = false, bool absent = false) {
-    it[n].src = src.w; it[n].N = N; it[n].K = K; it[n].slot = &dst.w; it[n].narrow = narrow; it[n].absent = absent; ++n;
+    it[n].src = src.w; it[n].N = N; it[n].K = K; it[n].slot = &dst.w; it[n].narrow = narrow; it[n].absent = absent;
+    it[n].chunked = false; ++n;
   };
   add(w->reference_points, v->reference_points, 3, C);
   for (int l = 0; l < w->num_layers; ++l) {
@@ -393,6 +406,7 @@ static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, Pack
     add(a.position_encoder.l3, b.position_encoder.l3, C, C);
     add(a.ffn0, b.ffn0, F, C);
     add(a.ffn1, b.ffn1, C, F);
+    it[n - 1].chunked = true;
     // a layer without a reg branch (no box refinement, decoder_refines): nothing to pack, the view's slots are NULL
     const bool noreg = a.reg.l0.w == nullptr;
     add(a.reg.l0, b.reg.l0, C, C, false, noreg);
@@ -408,8 +422,8 @@ static int collect_pack_items(const tc_head_weights* w, tc_head_weights* v, Pack
       const tc_radar_layer& a = w->radar[r]; tc_radar_layer& b = v->radar[r];
       add(a.attn.in_proj, b.attn.in_proj, 3 * C, C);
       add(a.attn.out_proj, b.attn.out_proj, C, C);
-      add(a.linear1, b.linear1, F, C);
-      add(a.linear2, b.linear2, C, F);
+      add(a.linear1, b.linear1, RF, C);
+      add(a.linear2, b.linear2, C, RF);
       add(a.final_cls.l0, b.final_cls.l0, C, C);
       add(a.final_cls.l3, b.final_cls.l3, C, C);
       add(a.final_cls.l6, b.final_cls.l6, ncls, C, true);
@@ -625,6 +639,18 @@ int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* ne
                               const float* ref_in, const float* pc_range, float img_h,
                               float img_w, float* hs, float* ref_out, float* qk, float* vt,
                               int qpad, int tile_rows, tc_stream_t stream) {
+  return tc_decoder_layer_tail_fwd_ffn(layer, next_in_proj, feats, B, Q, num_cams, code_size, attn_o, x_in, query_embedding,
+                                       lidar2img, ref_in, pc_range, img_h, img_w, hs, ref_out, qk, vt, qpad, tile_rows, 512,
+                                       stream);
+}
+
+int tc_decoder_layer_tail_fwd_ffn(const tc_decoder_layer* layer, const tc_linear* next_in_proj,
+                                  const tc_feats_nhwc* feats, int B, int Q, int num_cams,
+                                  int code_size, const float* attn_o, const float* x_in,
+                                  const float* query_embedding, const float* lidar2img,
+                                  const float* ref_in, const float* pc_range, float img_h,
+                                  float img_w, float* hs, float* ref_out, float* qk, float* vt,
+                                  int qpad, int tile_rows, int ffn_dims, tc_stream_t stream) {
   TC_REQUIRE(layer != nullptr && feats != nullptr, "decoder_layer_tail: null argument");
   TC_REQUIRE(feats->num_levels == 4, "decoder_layer_tail: num_levels=%d (4 supported; heads with fewer levels run "
              "through tc_head_forward)", feats->num_levels);
@@ -633,6 +659,7 @@ int tc_decoder_layer_tail_fwd(const tc_decoder_layer* layer, const tc_linear* ne
                                                                          img_h, img_w), code_size, decoder_qscale(C, H),
                                           attn_o, x_in, C, query_embedding, hs, ref_out, qk, vt, qpad);
   d.tile_rows = TC_TILE_ROWS(tile_rows); d.matrix_path = TC_TILE_MATRIX(tile_rows);
+  d.ffn_dims = ffn_dims;               // (launch_decoder_chain refuses a width the chains do not run, naming it)
   TC_REQUIRE(d.matrix_path <= TC_MATRIX_F16X2 && (tile_rows >> 10) == 0, "decoder_layer_tail: tile_rows=0x%x", tile_rows);
   TC_TRY(launch_decoder_chain(d, as_stream(stream)));
   if (layer->reg.l0.w == nullptr)      // no reg branch (a decoder without box refinement): the reference stays
@@ -802,7 +829,7 @@ int tc_box_decode_kept_path(const float* cls_scores, const float* bbox_preds, in
 }
 
 size_t tc_head_packed_bytes(const tc_head_weights* w) {
-  if (check_dims(w) != 0) return 0;
+  if (check_dims(w) != 0 || check_ffn_dims_fused(w) != 0) return 0;
   bool refine;
   if (decoder_refines(w, &refine) != 0) return 0;
   tc_head_weights view = *w;
@@ -820,6 +847,7 @@ size_t tc_head_packed_bytes(const tc_head_weights* w) {
 int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_bytes,
                          tc_head_weights* packed_view, tc_stream_t stream) {
   TC_TRY(check_dims(w));
+  TC_TRY(check_ffn_dims_fused(w));
   bool refine;
   TC_TRY(decoder_refines(w, &refine));
   TC_REQUIRE(packed != nullptr && packed_view != nullptr, "pack_weights: null output");
@@ -841,7 +869,14 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
     TC_REQUIRE(items[i].src != nullptr, "pack_weights: weight %d is null", i);
     if (items[i].narrow) continue;                     // the view keeps the nn.Linear pointer
     float* dst = a.take<float>(packed_floats(items[i].N, items[i].K));
-    TC_TRY(launch_pack_linear(items[i].src, items[i].N, items[i].K, dst, dst + delta, dst + 2 * delta, as_stream(stream)));
+    // a decoder ffn1 [C, F]: one packed matrix [C, <= 512] per chunk of hidden units the chain runs (chain.hip
+    // resolve_program), one behind the other in the weight's slice -- F <= 512 is the one matrix
+    const int kc = items[i].chunked ? 512 : items[i].K;
+    for (int k0 = 0; k0 < items[i].K; k0 += kc) {
+      const int kw = items[i].K - k0 < kc ? items[i].K - k0 : kc;
+      float* d = dst + (size_t)items[i].N * k0;
+      TC_TRY(launch_pack_linear(items[i].src + k0, items[i].N, kw, items[i].K, d, d + delta, d + 2 * delta, as_stream(stream)));
+    }
     *items[i].slot = dst;
   }
   for (int rgn = 0; rgn < 2; ++rgn)
@@ -882,7 +917,7 @@ int tc_head_pack_weights(const tc_head_weights* w, void* packed, size_t packed_b
                                                                                           init_ref, nullptr, 0.0f, 0.0f),
                                               w->code_size, pa.qscale, attn_o, w->query_embedding + C, 2 * C, w->query_embedding,
                                               nullptr, nullptr, nullptr, nullptr, qpad);
-      d.x_mod = Q;
+      d.x_mod = Q; d.ffn_dims = w->ffn_dims;
       for (int v = 0; v < TC_L0_VARIANTS; ++v)
         TC_TRY(launch_decoder_l0_consts(d, v, const_cast<float*>(l0_consts_of(packed_view, v)), s));
     }
@@ -961,11 +996,12 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
   bool refine = true;
   TC_TRY(decoder_refines(w, &refine));
   hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, L = w->num_layers, H = decoder_heads(w);
+  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, RF = TC_RADAR_FFN_DIMS, L = w->num_layers, H = decoder_heads(w);
   const int code = w->code_size, ncls = w->num_classes;
   const int rows = B * Q, rt = B * T;
   const float* pc = w->pc_range;
   unsigned long long* pairs = aux ? aux->sample_pairs : nullptr;
+  if (packed_view != nullptr && !opt.unfused) TC_TRY(check_ffn_dims_fused(w));
   if (packed_view != nullptr && !opt.unfused)
     return head_forward_fused(packed_view, feats, B, lidar2img, img_h, img_w, radar_tokens, T, pad_mult,
                               all_cls_scores, all_bbox_preds, aux, opt, h, s);
@@ -1058,8 +1094,8 @@ int tc_head_forward(const tc_head_weights* w, const tc_head_weights* packed_view
     // HEAD:581-586
     TC_TRY(linear(h.rattn, C, rl.attn.out_proj, rows, C, C, 0, h.t0, C, s, nullptr, qf, C, hits));
     TC_TRY(layernorm(h.t0, rl.norm2, h.t1, rows, 0, s));
-    TC_TRY(linear(h.t1, C, rl.linear1, rows, C, F, 1, h.ffn_h, F, s));
-    TC_TRY(linear(h.ffn_h, F, rl.linear2, rows, F, C, 0, h.t0, C, s, nullptr, h.t1, C));
+    TC_TRY(linear(h.t1, C, rl.linear1, rows, C, RF, 1, h.ffn_h, RF, s));
+    TC_TRY(linear(h.ffn_h, RF, rl.linear2, rows, RF, C, 0, h.t0, C, s, nullptr, h.t1, C));
     TC_TRY(layernorm(h.t0, rl.norm3, h.qf, rows, 0, s));
     qf = h.qf;
     // final_cls / final_reg, HEAD:592-600
@@ -1151,7 +1187,7 @@ int tc_decoder_heads_pack(const tc_decoder_heads* w, void* packed, size_t packed
     const int first = heads_first_use(it, i);
     if (first != i) { *it[i].slot = *it[first].slot; continue; }     // (a shared branch: packed once)
     float* dst = a.take<float>(packed_floats(256, 256));
-    TC_TRY(launch_pack_linear(it[i].src, 256, 256, dst, dst + delta, dst + 2 * delta, as_stream(stream)));
+    TC_TRY(launch_pack_linear(it[i].src, 256, 256, 256, dst, dst + delta, dst + 2 * delta, as_stream(stream)));
     *it[i].slot = dst;
   }
   packed_view->packed16_delta = delta;

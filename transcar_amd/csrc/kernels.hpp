@@ -109,6 +109,7 @@ struct DecoderChainArgs {
   const float* qe = nullptr; int Q = 0;
   const float* ref_in = nullptr; float* ref_out = nullptr; float* box_m = nullptr;
   const tc_decoder_layer* w = nullptr;
+  int ffn_dims = 512;                        // rows of w->ffn0 (tc_head_weights.ffn_dims); a packed ffn1 is packed in 512-column chunks
   const tc_linear* next_in_proj = nullptr;   // next layer's in_proj (null after the last layer)
   float qscale = 1.0f;
   float* hs = nullptr; float* qk = nullptr; float* vt = nullptr; int qpad = 0;
@@ -321,7 +322,8 @@ int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float l
 size_t packed_floats(int N, int K);
 // P16 (may be null): the copy for the 16-row tiles' 16x16x4 MFMA (pack.hip)
 // PH (may be null): the two-plane f16 copy for the 16-row tiles on the f16 matrix cores
-int launch_pack_linear(const float* W, int N, int K, float* P, float* P16, float* PH, hipStream_t s);
+// W is [N][K] with row stride ldw >= K (a column range of a wider matrix: ldw > K)
+int launch_pack_linear(const float* W, int N, int K, int ldw, float* P, float* P16, float* PH, hipStream_t s);
 // several weights in one launch (P16 of an item may be null: only the 4x4x1 copy)
 //   transpose: the matrix to pack is W^T -- element (n, k) = W[k * ldw + n] (the backward row chain: dx = dy W)
 struct PackJob { const float* W; float* P; float* P16; int N, K; int transpose = 0, ldw = 0; float* PH = nullptr; };

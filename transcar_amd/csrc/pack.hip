@@ -41,7 +41,7 @@ __device__ __forceinline__ unsigned pack_h_word(const float* __restrict__ W, int
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int k = k0 + e;
-    const float x = (n < N && k < K) ? (transpose ? W[(size_t)k * ldw + n] : W[(size_t)n * K + k]) : 0.0f;
+    const float x = (n < N && k < K) ? (transpose ? W[(size_t)k * ldw + n] : W[(size_t)n * (ldw > 0 ? ldw : K) + k]) : 0.0f;
     const _Float16 hi = (_Float16)x;
     const _Float16 v = p == 0 ? hi : (_Float16)((x - (float)hi) * 2048.0f);
     h[e] = __builtin_bit_cast(unsigned short, v);
@@ -49,7 +49,7 @@ __device__ __forceinline__ unsigned pack_h_word(const float* __restrict__ W, int
   return (unsigned)h[0] | ((unsigned)h[1] << 16);
 }
 
-__global__ __launch_bounds__(256) void pack_linear_kernel(const float* __restrict__ W, int N, int K,
+__global__ __launch_bounds__(256) void pack_linear_kernel(const float* __restrict__ W, int N, int K, int ldw,
                                                           float* __restrict__ P, float* __restrict__ P16,
                                                           float* __restrict__ PH, int ntile, int nkq) {
   const size_t total = (size_t)ntile * nkq * 256;
@@ -60,14 +60,14 @@ __global__ __launch_bounds__(256) void pack_linear_kernel(const float* __restric
     const int kq = tk % nkq;
     const int t = tk / nkq;
     const int n = 64 * t + lane, k = 4 * kq + j;
-    P[i] = (n < N && k < K) ? W[(size_t)n * K + k] : 0.0f;
+    P[i] = (n < N && k < K) ? W[(size_t)n * ldw + k] : 0.0f;
     if (P16 != nullptr) {
       const int g = lane >> 4, c = lane & 15;
       const int n16 = 64 * t + 16 * j + c;
       const int k16 = 64 * (kq >> 4) + 16 * ((kq & 15) >> 2) + 4 * g + (kq & 3);
-      P16[i] = (n16 < N && k16 < K) ? W[(size_t)n16 * K + k16] : 0.0f;
+      P16[i] = (n16 < N && k16 < K) ? W[(size_t)n16 * ldw + k16] : 0.0f;
     }
-    if (PH != nullptr) reinterpret_cast<unsigned*>(PH)[i] = pack_h_word(W, N, K, 0, 0, t, kq, lane, j);
+    if (PH != nullptr) reinterpret_cast<unsigned*>(PH)[i] = pack_h_word(W, N, K, 0, ldw, t, kq, lane, j);
   }
 }
 
@@ -131,12 +131,12 @@ size_t packed_floats(int N, int K) {
   return (size_t)((N + 63) / 64) * 64 * ((K + 63) / 64) * 64;
 }
 
-int launch_pack_linear(const float* W, int N, int K, float* P, float* P16, float* PH, hipStream_t s) {
-  TC_REQUIRE(W != nullptr && P != nullptr && N > 0 && K > 0, "pack_linear: bad arguments");
+int launch_pack_linear(const float* W, int N, int K, int ldw, float* P, float* P16, float* PH, hipStream_t s) {
+  TC_REQUIRE(W != nullptr && P != nullptr && N > 0 && K > 0 && ldw >= K, "pack_linear: bad arguments");
   const int ntile = (N + 63) / 64, nkq = ((K + 63) / 64) * 16;
   const size_t total = (size_t)ntile * nkq * 256;
   const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-  hipLaunchKernelGGL(pack_linear_kernel, dim3(blocks), dim3(256), 0, s, W, N, K, P, P16, PH, ntile, nkq);
+  hipLaunchKernelGGL(pack_linear_kernel, dim3(blocks), dim3(256), 0, s, W, N, K, ldw, P, P16, PH, ntile, nkq);
   return check_launch("pack_linear");
 }
 

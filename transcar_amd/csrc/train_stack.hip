@@ -28,7 +28,7 @@ struct Tape {
 
 size_t tape_layout(const tc_head_weights* w, int B, int T, void* base, size_t cap, Tape* out) {
   const size_t rows = (size_t)B * w->num_query, rt = (size_t)B * T;
-  const size_t C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
+  const size_t C = w->embed_dims, F = TC_RADAR_FFN_DIMS, code = w->code_size;
   Arena a(base, cap);
   Tape t;
   memset(&t, 0, sizeof(t));          // (the layers a shallower head does not have stay null)
@@ -155,7 +155,7 @@ struct BwdWs {
 };
 size_t bwd_ws_layout(const tc_head_weights* w, int B, int T, void* base, size_t cap, BwdWs* out) {
   const size_t rows = (size_t)B * w->num_query, rt = (size_t)B * T;
-  const size_t C = w->embed_dims, F = w->ffn_dims, code = w->code_size, ncls = w->num_classes;
+  const size_t C = w->embed_dims, F = TC_RADAR_FFN_DIMS, code = w->code_size, ncls = w->num_classes;
   Arena a(base, cap);
   BwdWs b;
   memset(&b, 0, sizeof(b));
@@ -228,7 +228,7 @@ int tc_radar_train_fwd(const tc_head_weights* w, const float* hs_last, const flo
   Tape t;
   TC_TRY(open_call("radar_train_fwd", w, B, T, tape, tape_bytes, &t));
   hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
+  const int Q = w->num_query, C = w->embed_dims, F = TC_RADAR_FFN_DIMS, code = w->code_size;
   const int ncls = w->num_classes, RI = w->radar_in_dims;
   const int rows = B * Q, rt = B * T;
   // radar encoders, HEAD:531-536 (Linear(3,C) as K = 4 with a zero column)
@@ -347,7 +347,7 @@ int tc_radar_train_bwd(const tc_head_weights* w, const tc_head_weights* grads, c
   Tape t;
   TC_TRY(open_call("radar_train_bwd", w, B, T, tape, tape_bytes, &t));
   hipStream_t s = as_stream(stream);
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
+  const int Q = w->num_query, C = w->embed_dims, F = TC_RADAR_FFN_DIMS, code = w->code_size;
   const int ncls = w->num_classes, RI = w->radar_in_dims;
   const int rows = B * Q, rt = B * T;
   TC_HIP(hipMemsetAsync(t.dmem, 0, (size_t)rt * C * 4, s));
@@ -447,7 +447,7 @@ int tc_radar_train_bwd(const tc_head_weights* w, const tc_head_weights* grads, c
 
 // the transposed packed weights of the three fusion layers (what the backward row chain multiplies by): pack jobs
 static int transposed_jobs(const tc_head_weights* w, const BwdWs& ws, PackJob* jobs) {
-  const int C = w->embed_dims, F = w->ffn_dims, code = w->code_size, ncls = w->num_classes;
+  const int C = w->embed_dims, F = TC_RADAR_FFN_DIMS, code = w->code_size, ncls = w->num_classes;
   int n = 0;
   auto add = [&](const float* W, float* P, int N_out, int K_in) {
     PackJob j;
@@ -495,7 +495,7 @@ size_t tc_radar_train_bwd_workspace_bytes(const tc_head_weights* w, int B, int T
 // token side (radar encoders).
 static int weight_gradients(const tc_head_weights* w, const tc_head_weights* grads, const float* hs_last,
                             const float* radar_tokens, int B, int T, const Tape& t, const BwdWs& ws, int group, hipStream_t s) {
-  const int Q = w->num_query, C = w->embed_dims, F = w->ffn_dims, code = w->code_size;
+  const int Q = w->num_query, C = w->embed_dims, F = TC_RADAR_FFN_DIMS, code = w->code_size;
   const int ncls = w->num_classes, RI = w->radar_in_dims;
   const int rows = B * Q, rt = B * T;
   const tc_pos_encoder& gpe = grads->radar_position_encoder;

@@ -256,7 +256,7 @@ class Detr3DHead(BaseModule):
         self.code_weights = nn.Parameter(
             torch.tensor(code_weights, requires_grad=False),
             requires_grad=False)
-        E, F = self.embed_dims, 512
+        E, F = self.embed_dims, L.TC_RADAR_FFN_DIMS
         names = [fusion_module_names(r) for r in range(self.num_fusion_layers)]
         for nm in names:
             setattr(self, nm['final_cls'], _cls_branch(E, self.cls_out_channels))
@@ -438,6 +438,9 @@ class Detr3DHead(BaseModule):
                                          % (rh, r, fusion_modules(self, r).attn.num_heads))
         w.num_heads = L.pack_num_heads(w.num_heads, rh)
         w.ffn_dims = dec.layers[0].ffns[0].feedforward_channels
+        if any(ly.ffns[0].feedforward_channels != w.ffn_dims for ly in dec.layers):
+            raise NotImplementedError('FFN: feedforward_channels (ffn_dims) differs between decoder layers')
+        L.check_ffn_dims(w.ffn_dims)
         w.num_layers = dec.num_layers
         w.num_cams = L.check_num_cams(dec.layers[0].attentions[1].num_cams)
         w.num_levels = dec.layers[0].attentions[1].num_levels

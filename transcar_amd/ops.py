@@ -256,9 +256,11 @@ def sdpa(q, k, vt, num_heads=8, matrix_path='f32', head_dim=None):
 
 def decoder_layer_tail(packed_layer, packed_next_in_proj, feats_nhwc, attn_o, x_in,
                        query_embedding, lidar2img, ref_in, pc_range, img_hw, code_size=10,
-                       num_cams=6, tile_rows=0, matrix_path=0):
+                       num_cams=6, tile_rows=0, matrix_path=0, ffn_dims=512):
     """One decoder layer after its attention core as the fused row chain
-    (tc_decoder_layer_tail_fwd).  Detr3DCrossAtten.num_points = 1 only (the C
+    (tc_decoder_layer_tail_fwd_ffn; ffn_dims: the feedforward_channels of the
+    head the packed layer comes from, which the C layer struct does not carry
+    either).  Detr3DCrossAtten.num_points = 1 only (the C
     layer struct does not carry num_points; P > 1 heads run through
     tc_head_forward).  packed_*: members of the head's packed view
     (``head._packed_view.layers[l]``, ``.layers[l + 1].self_attn.in_proj`` or
@@ -274,11 +276,12 @@ def decoder_layer_tail(packed_layer, packed_next_in_proj, feats_nhwc, attn_o, x_
     qk = torch.zeros((B, Q, 2 * Cdim), dtype=torch.float32, device=dev)
     vt = torch.zeros((B, Cdim, qpad), dtype=torch.float32, device=dev)
     fv = feats_view(feats_nhwc)
-    L.check(L.lib().tc_decoder_layer_tail_fwd(
+    L.check(L.lib().tc_decoder_layer_tail_fwd_ffn(
         C.byref(packed_layer), C.byref(packed_next_in_proj) if packed_next_in_proj is not None else None,
         C.byref(fv), B, Q, num_cams, code_size, _p(attn_o), _p(x_in), _p(query_embedding),
         _p(lidar2img), _p(ref_in), L.f6(pc_range), float(img_hw[0]), float(img_hw[1]), _p(hs),
-        _p(ref_out), _p(qk), _p(vt), qpad, int(tile_rows) | (int(matrix_path) << 8), L.stream_ptr()), 'tc_decoder_layer_tail_fwd')
+        _p(ref_out), _p(qk), _p(vt), qpad, int(tile_rows) | (int(matrix_path) << 8), int(ffn_dims), L.stream_ptr()),
+        'tc_decoder_layer_tail_fwd_ffn')
     return hs, ref_out, qk, vt
 
 

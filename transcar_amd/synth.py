@@ -61,10 +61,14 @@ def _pos_encoder(spec, name, c):
 
 def state_dict_spec(num_query=900, embed=256, ffn=512, num_layers=6,
                     num_classes=10, code_size=10, num_cams=6, num_levels=4,
-                    radar_in=36, num_points=1):
+                    radar_in=36, num_points=1, feedforward_channels=None):
     """[(key, shape, kind)] for ``pts_bbox_head.*`` (HEAD:43-238, XFMR:61-63,
-    XFMR:280-292; mmcv brick names per SURVEY.md section 8(b))."""
+    XFMR:280-292; mmcv brick names per SURVEY.md section 8(b)).
+    ``feedforward_channels`` (None: ``ffn``) sizes the decoder layers'
+    ``ffns.0.layers.*`` only; the fusion layers' ``rf_linear*`` keep ``ffn``
+    (the reference writes their 512 as a constant, HEAD:131)."""
     c = embed
+    dec_ffn = ffn if feedforward_channels is None else feedforward_channels
     s = []
     s.append(('code_weights', (code_size,), 'code_weights'))
     s.append(('query_embedding.weight', (num_query, 2 * c), 'embed'))
@@ -76,8 +80,8 @@ def state_dict_spec(num_query=900, embed=256, ffn=512, num_layers=6,
                 num_cams * num_points * num_levels, c)
         _linear(s, p + 'attentions.1.output_proj', c, c)
         _pos_encoder(s, p + 'attentions.1.position_encoder', c)
-        _linear(s, p + 'ffns.0.layers.0.0', ffn, c)
-        _linear(s, p + 'ffns.0.layers.1', c, ffn)
+        _linear(s, p + 'ffns.0.layers.0.0', dec_ffn, c)
+        _linear(s, p + 'ffns.0.layers.1', c, dec_ffn)
         for n in range(3):
             _ln(s, p + 'norms.%d' % n, c)
     for i in range(num_layers):
