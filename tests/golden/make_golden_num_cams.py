@@ -17,8 +17,8 @@ Run only in the authoring container:   python tests/golden/make_golden_num_cams.
                                (HEAD:191-192 writes 6 * 4)
   g8_train_grads_cams12.npz    one training iteration's gradients of the same head, the radar frame of the seed chosen
                                as make_golden_variants chooses one: of seeds 2 .. 39 on G5-cams12's centres the one whose
-                               closest gate decision (head_variant_rig.gate_margin, on the CPU oracle with the count
-                               bound) is farthest from its radius; seed and distance are stored (`seeds` prints them all)"""
+                               closest gate decision (head_variant_rig.gate_margin, on the CPU oracle at the ring's
+                               count) is farthest from its radius; seed and distance are stored (`seeds` prints them all)"""
 import functools
 import os
 import sys
@@ -95,9 +95,8 @@ def g8_margins():
     """{seed: gate margin} of the oracle at N cameras on G5-cams12's centres"""
     sd, feats = O.to_torch_sd(NR.state_dict(N)), NR.feats(N)
     cen = R.gold(NR.G5_CAMS12)['radar_centres']
-    with NR.bound(N):
-        return {s: R.gate_margin(sd, feats, synth.make_radar_frame(seed=s, n_per_radar=51, centres=cen), **NR.variant(N))
-                for s in NR.SEED_RANGE}
+    return {s: R.gate_margin(sd, feats, synth.make_radar_frame(seed=s, n_per_radar=51, centres=cen), **NR.variant(N))
+            for s in NR.SEED_RANGE}
 
 
 def g8():

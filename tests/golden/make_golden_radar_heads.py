@@ -15,7 +15,7 @@ Run only in the authoring container:   python tests/golden/make_golden_radar_hea
   g8_train_grads_rh{4,16}.npz     make_golden.write_g8's layout, the radar seed, its gate margin and tie sensitivity
 
 The radar seed of the forward fixtures is chosen as make_golden_radar_gate chooses one: seeds 2 .. 39 are scanned on the
-CPU oracle with its fusion attention at H heads (radar_heads_rig.gate_margin) and the one whose closest gate decision is
+CPU oracle with its fusion attention at H heads (head_variant_rig.gate_margin) and the one whose closest gate decision is
 farthest from its radius is kept; that margin is stored.
 
 The gradient fixtures need more of their frame.  A gradient is discontinuous where a ReLU input of the trainable stack
@@ -41,6 +41,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import make_golden as MG                                 # noqa: E402
+import head_variant_rig as R                             # noqa: E402
 import radar_heads_rig as RR                             # noqa: E402
 from oracle import ref_harness as RH                     # noqa: E402
 from oracle import transcar_oracle as O                  # noqa: E402
@@ -74,7 +75,7 @@ def choose_seed(H, centres):
     best = None
     for seed in SEEDS:
         frame = synth.make_radar_frame(seed=seed, n_per_radar=51, centres=centres)
-        m = RR.gate_margin(sd, feats, frame, H)
+        m = R.gate_margin(sd, feats, frame, radar_num_heads=H)
         print('H %d seed %d: margin %.3g m' % (H, seed, m))
         if best is None or m > best[1]:
             best = (seed, m)
@@ -83,12 +84,12 @@ def choose_seed(H, centres):
 
 def choose_grad_seed(centres):
     """-> (seed, {H: (gate margin, tie sensitivity)}): see the module's docstring"""
-    import head_variant_rig as R
     sd = O.to_torch_sd(synth.make_state_dict(seed=3))
     best = None
     for seed in SEEDS:
         host = R.g8_frame('g5_head_tiny.npz', radar_seed=seed, centres=centres)
-        figs = {H: (RR.gate_margin(sd, host['feats_np'], host['frame'], H), RR.tie_sensitivity(host, H)) for H in RR.HEADS}
+        figs = {H: (R.gate_margin(sd, host['feats_np'], host['frame'], radar_num_heads=H), RR.tie_sensitivity(host, H))
+                for H in RR.HEADS}
         print('seed %d:' % seed, {H: '%.3g m, %.3g' % f for H, f in figs.items()})
         margin = min(f[0] for f in figs.values())
         if max(f[1] for f in figs.values()) < RR.TIE_BOUND and (best is None or margin > best[2]):

@@ -1,17 +1,21 @@
-"""The rig the tests of the head's variants share (num_points > 1, num_levels < 4, with_box_refine=False, num_heads 4 /
-16, num_classes up to 32, num_query, num_fusion_layers 1 / 2, radar_gate, the decoder levels' own outputs and decoder
-layer 0's fold): heads and frames, the CPU oracle's forward and training iteration, and the checks every variant repeats
--- against the oracle, against the reference's fixtures, the train-mode decoder with read-back dropout masks, a training
-iteration against the reference's gradients, the plugin graphs, FramePipeline and a frame inside a nine-frame launch.
+"""The rig the tests of the head's variants share (every key of configs.head_cfg, the decoder levels' own outputs and
+decoder layer 0's fold): heads and frames, the CPU oracle's forward and training iteration, and the checks every variant
+repeats -- against the oracle, against the reference's fixtures, the train-mode decoder with read-back dropout masks, a
+training iteration against the reference's gradients, the plugin graphs, FramePipeline and a frame inside a nine-frame
+launch.  The side rigs (num_cams_rig, radar_heads_rig, radar_input_rig, ffn_dims_rig, variant_pairs_rig) keep the frames,
+seeds and case tables of their axes and build every head and make every oracle call through this module.
 
-A variant is keyword arguments named as CONFIGS' keys; what a key reaches differs (variant_kw, state_dict_kw,
-oracle_kw, oracle_forward): the state dict does not depend on num_heads or on radar_gate (the gate adds no parameter),
-the oracle reads num_levels, num_points, num_classes and num_query off the state dict and the maps, and its decoder
-reads neither the fusion stack's depth nor its gate.  One more key, `geometry`, is a Geometry: the point-cloud range of
-the coder, the attentions and the assigner, the coder's post_center_range, the image size and the cameras' intrinsics.  It reaches
-the head's config, the oracle's pc_range / img_hw arguments, lidar2img and img_metas; the state dict does not depend on
-it.  Left out, it is DEFAULT, the TransCAR configs' -- whose x and y intervals are equal and centred on 0, so that an
-x / y swap, `2 * pc[3]` for `pc[3] - pc[0]`, `-pc[3]` for `pc[0]` or a folded 51.2 compute what correct code computes.
+A variant is keyword arguments named as CONFIGS' keys; what a key reaches differs (variant_kw, state_dict_kw, decoder_kw,
+oracle_kw, oracle_forward): the state dict depends on neither head count, the gate, the token count nor a range (they
+add no parameter), the oracle reads num_levels, num_points, num_classes, num_query, radar_in_dims and
+feedforward_channels off the state dict, the maps and the radar rows, and its decoder reads nothing of the radar side.
+The oracle is told every key by argument; nothing here or in a side rig assigns to an attribute of the oracle or of the
+library.  One more key, `geometry`, is a Geometry: the point-cloud range of the coder, the attentions and the assigner,
+the coder's post_center_range, the image size, the cameras' intrinsics and -- a num_cams_rig.Ring -- their count.  It reaches
+the head's config, the oracle's pc_range / img_hw / num_cams arguments, lidar2img and img_metas; of the state dict only
+the camera count's share depends on it.  Left out, it is DEFAULT, the TransCAR configs' -- whose x and y intervals are
+equal and centred on 0, so that an x / y swap, `2 * pc[3]` for `pc[3] - pc[0]`, `-pc[3]` for `pc[0]` or a folded 51.2
+compute what correct code computes.
 GEOM has six distinct magnitudes, extents 100 / 96 / 10, and is off-centre.
 
 A plain helper module (as adverse_rig.py): the test modules import the fixtures `T` and `no_grad` by name.  The
@@ -70,7 +74,9 @@ MAX_GATE_ROWS = 6       # rows whose radar gate decisions (hit counts) may diffe
 BOX_TOL = 5e-5          # metres: fp32 spacing at 50 m is 3.8e-6, the reference and the oracle order add / sigmoid / scale differently
 # the TransCAR configs' variant
 CONFIGS = dict(num_levels=4, num_points=1, with_box_refine=True, num_heads=8, num_classes=10, num_query=900,
-               num_fusion_layers=3, radar_gate=None)
+               num_fusion_layers=3, radar_gate=None, radar_num_heads=8, radar_num_tokens=1500, radar_in_dims=36,
+               radar_point_range=None, feedforward_channels=512)
+POINT_RANGE = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0)          # the radar filter's range under radar_point_range=None: HEAD:304
 HEADS = (4, 16)         # num_heads beside the configs' 8: head dimension 64 and 16
 DEPTHS = (1, 2)         # num_fusion_layers beside the configs' 3
 CIRCLE = dict(type='circle', radii=[2.0, 2.0, 1.0])                 # the single circle of the paper: 2 / 2 / 1 m
@@ -121,15 +127,33 @@ def variant_kw(**variant):
 
 
 def state_dict_kw(**variant):
-    """variant_kw for synth.make_state_dict: the state dict does not depend on the head count, the gate or the geometry."""
-    return {k: v for k, v in variant_kw(**variant).items()
-            if k not in ('num_heads', 'radar_gate', 'pc_range', 'post_center_range')}
+    """variant_kw for synth.make_state_dict, which spells radar_in_dims `radar_in`: the state dict does not depend on the
+    head counts, the gate, the token count or a range (of the geometry it keeps a ring's camera count)."""
+    kw = {k: v for k, v in variant_kw(**variant).items()
+          if k not in ('num_heads', 'radar_num_heads', 'radar_gate', 'radar_num_tokens', 'radar_point_range', 'pc_range',
+                       'post_center_range')}
+    if 'radar_in_dims' in kw:
+        kw['radar_in'] = kw.pop('radar_in_dims')
+    return kw
+
+
+def state_dict(seed=3, **variant):
+    """the variant's seeded weights {key: float32 ndarray}"""
+    return synth.make_state_dict(seed=seed, **state_dict_kw(**variant))
+
+
+def decoder_kw(**variant):
+    """What the oracle's decoder (O.transformer) cannot read off the state dict and the maps (their defaults spelled
+    out); the camera count is the geometry's."""
+    variant_kw(**variant)
+    return dict({k: variant.get(k, CONFIGS[k]) for k in ('with_box_refine', 'num_heads')},
+                num_cams=getattr(geometry_of(variant), 'num_cams', 6))
 
 
 def oracle_kw(**variant):
-    """What the oracle's decoder cannot read off the state dict and the maps (their defaults spelled out)."""
-    variant_kw(**variant)
-    return {k: variant.get(k, CONFIGS[k]) for k in ('with_box_refine', 'num_heads')}
+    """decoder_kw and what the fusion stack of O.head_forward cannot read off the state dict and the radar rows."""
+    return dict(decoder_kw(**variant), radar_num_heads=variant.get('radar_num_heads', CONFIGS['radar_num_heads']),
+                num_radar_tokens=variant.get('radar_num_tokens', CONFIGS['radar_num_tokens']))
 
 
 def variant_key(**variant):
@@ -140,34 +164,54 @@ def variant_key(**variant):
     if 'radar_gate' in kw:
         gate = check_radar_gate(kw['radar_gate'], kw.get('num_fusion_layers', CONFIGS['num_fusion_layers']))
         kw['radar_gate'] = (gate['type'], gate['radii'])
+    if 'radar_point_range' in kw:
+        kw['radar_point_range'] = tuple(kw['radar_point_range'])
     return tuple(sorted(kw.items())) + (() if geom == DEFAULT else (('geometry', geom),))
+
+
+def _build(T, sd_np, train=False, **variant):
+    """A fresh head of the variant on the CPU with the weights sd_np, checked; train: with the configs' train_cfg."""
+    cfg = configs.head_cfg(**variant_kw(**variant))
+    if train:
+        cfg.setdefault('train_cfg', configs.train_cfg_pts)        # (head_cfg(pc_range=...) brings its own)
+    h = T.build_head(cfg)
+    h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
+    check_head(h, **variant)
+    return h
 
 
 def make_head(T, *, seed=3, shared_branches=False, **variant):
     """A fresh eval-mode head of the variant with seeded weights, and those weights as the oracle takes them.
     shared_branches: the weights of with_box_refine=False (one cls / reg branch under every index) whatever the head."""
-    sd_kw = state_dict_kw(**variant)
-    if shared_branches:
-        sd_kw['with_box_refine'] = False
-    sd_np = synth.make_state_dict(seed=seed, **sd_kw)
-    h = T.build_head(configs.head_cfg(**variant_kw(**variant)))
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
-    check_head(h, **variant)
-    return h.to(dev()).eval(), O.to_torch_sd(sd_np)
+    sd_np = state_dict(seed, **(dict(variant, with_box_refine=False) if shared_branches else variant))
+    return _build(T, sd_np, **variant).to(dev()).eval(), O.to_torch_sd(sd_np)
 
 
 def check_head(h, **variant):
-    """The head carries the variant where the kernels read it."""
-    from transcar_amd._lib import check_radar_gate
+    """The head carries every key of the variant where the kernels and the unfused path read it."""
+    from transcar_amd import _lib as L
+    from transcar_amd.detr3d_head import fusion_modules
     want = dict(CONFIGS, **variant)
     geom = geometry_of(variant)
+    w = h.weights_struct()
     assert tuple(h.pc_range) == geom.pc_range, h.pc_range
-    assert tuple(h.weights_struct().pc_range) == tuple(float(np.float32(v)) for v in geom.pc_range)
+    assert tuple(w.pc_range) == tuple(float(np.float32(v)) for v in geom.pc_range)
     assert tuple(h.bbox_coder.post_center_range) == geom.post_center_range
-    assert h.weights_struct().num_heads == want['num_heads']
-    assert h.weights_struct().num_classes == h.bbox_coder.num_classes == want['num_classes']
-    assert h.num_fusion_layers == h.weights_struct().num_radar_layers == want['num_fusion_layers']
-    assert h.radar_gate == check_radar_gate(want['radar_gate'], want['num_fusion_layers'])
+    assert (w.num_cams, w.num_levels, max(w.num_points, 1)) == (getattr(geom, 'num_cams', 6), want['num_levels'], want['num_points'])
+    H = want['radar_num_heads']
+    assert w.num_heads == L.pack_num_heads(want['num_heads'], H)
+    assert (w.num_heads & 0xffff) == want['num_heads'] and (w.num_heads >> 16) == (0 if H == 8 else H)
+    assert h.radar_num_heads == H and h.with_box_refine == want['with_box_refine']
+    for r in range(h.num_fusion_layers):
+        assert fusion_modules(h, r).attn.num_heads == H and fusion_modules(h, r).attn.head_dim == 256 // H
+    for ly in h.transformer.decoder.layers:
+        assert ly.attentions[0].num_heads == want['num_heads']
+    assert w.num_classes == h.bbox_coder.num_classes == want['num_classes'] and w.num_query == want['num_query']
+    assert h.num_fusion_layers == w.num_radar_layers == want['num_fusion_layers']
+    assert h.radar_gate == L.check_radar_gate(want['radar_gate'], want['num_fusion_layers'])
+    assert (w.num_radar_tokens_ref, w.radar_in_dims) == (h.radar_num_tokens, h.radar_in_dims) \
+        == (want['radar_num_tokens'], want['radar_in_dims'])
+    assert w.ffn_dims == want['feedforward_channels']
 
 
 _HEADS = {}
@@ -182,14 +226,9 @@ def shared_head(T, **variant):
 
 
 def train_head(**variant):
+    """A fresh head of the variant as the trainer takes it: the seed-3 weights, frozen decoder, no dropout yet."""
     import transcar_amd as T_
-    cfg = configs.head_cfg(**variant_kw(**variant))
-    cfg.setdefault('train_cfg', configs.train_cfg_pts)        # (head_cfg(pc_range=...) brings its own)
-    h = T_.build_head(cfg)
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(3, **state_dict_kw(**variant)).items()},
-                      strict=True)
-    check_head(h, **variant)
-    return h.to(dev()).freeze_decoder().set_dropout(0.0)
+    return _build(T_, state_dict(**variant), train=True, **variant).to(dev()).freeze_decoder().set_dropout(0.0)
 
 
 def g5_frame(radar_seed=2):
@@ -230,11 +269,13 @@ _ORACLE = {}
 
 def oracle_forward(sd, feats_np, frame, variant, **kw):
     """O.head_forward of the variant (its geometry, depth, gate and oracle_kw) on one frame; kw: head_forward's other
-    arguments."""
+    arguments.  frame: a raw radar frame, filtered by the variant's range, or [n, F] feature rows already filtered
+    (radar_input_rig.in_range)."""
     geom = geometry_of(variant)
     want = dict(CONFIGS, **variant)
     l2i = torch.from_numpy(geom.lidar2img()).float()[None]
-    return O.head_forward(sd, [torch.as_tensor(f) for f in feats_np], l2i, geom.hw, O.build_radar_features(frame),
+    rows = O.build_radar_features(frame, want['radar_point_range'] or POINT_RANGE) if isinstance(frame, dict) else frame
+    return O.head_forward(sd, [torch.as_tensor(f) for f in feats_np], l2i, geom.hw, rows,
                           list(geom.pc_range), num_fusion_layers=want['num_fusion_layers'], radar_gate=want['radar_gate'],
                           **oracle_kw(**variant), **kw)
 
@@ -251,13 +292,17 @@ def oracle_head(sd, feats_np, frame, key=None, **variant):
     return _ORACLE[key]
 
 
-def margin_probe(margins):
+def margin_probe(margins, masks=None):
     """A gate_probe for O.head_forward that appends, per fusion layer, the distance (m) between the layer's closest gate
     decision and its radius: the minimum over the queries, the gate's circles and the radar tokens of |distance - radius|.
-    The padding tokens are left out (they sit far outside every circle)."""
+    The padding tokens are left out (they sit far outside every circle).  masks: a list that receives the layer's gate
+    mask [Q, tokens] (True = masked)."""
     from transcar_amd._lib import TC_RADAR_GATE_CIRCLE
 
     def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
+        if masks is not None:
+            masks.append(O.single_circle_mask(centre_xy, radar_xy, rmax) if rmin == TC_RADAR_GATE_CIRCLE
+                         else O.circle_mask(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax))
         centres, radii = [centre_xy], rmax
         if rmin != TC_RADAR_GATE_CIRCLE:             # O.circle_mask's front and rear circles and its clamped radius
             length = length_log.exp()
@@ -287,13 +332,13 @@ def oracle_trace(**variant):
     -> (sd, hs [L,B,Q,C], init_ref [B,Q,3], inter_refs [L,B,Q,3])."""
     key = variant_key(**variant)
     if key not in _TRACE:
-        sd = O.to_torch_sd(synth.make_state_dict(seed=3, **state_dict_kw(**variant)))
+        sd = O.to_torch_sd(state_dict(**variant))
         feats = synth.make_feats('tiny', seed=1, smooth=SMOOTH)
         geom = geometry_of(variant)
         l2i = torch.from_numpy(geom.lidar2img()).float()[None]
         with torch.no_grad():
             hs, init_ref, inter_refs, _ = O.transformer(sd, [torch.from_numpy(f) for f in feats], list(geom.pc_range), l2i,
-                                                        geom.hw, **oracle_kw(**variant))
+                                                        geom.hw, **decoder_kw(**variant))
         _TRACE[key] = (sd, hs.permute(0, 2, 1, 3).contiguous(), init_ref, inter_refs)
     return _TRACE[key]
 
@@ -354,7 +399,7 @@ def oracle_fp64_deviation(sd, feats_np, frame, want, dbg, **variant):
     l2i = torch.from_numpy(geom.lidar2img()).float()[None]
     feats = [torch.from_numpy(f) for f in feats_np]
     trace64 = O.transformer({k: v.double() for k, v in sd.items()}, [f.double() for f in feats], list(geom.pc_range),
-                            l2i.double(), geom.hw, **oracle_kw(**variant))
+                            l2i.double(), geom.hw, **decoder_kw(**variant))
     hs_dev = (dbg['hs'].double() - trace64[0].permute(0, 2, 1, 3)).abs().amax(dim=(0, 1, 3))
     trace = tuple(t.float() if torch.is_tensor(t) else t for t in trace64)
     outs64 = oracle_forward(sd, feats, frame, variant, decoder_trace=trace)
@@ -454,6 +499,22 @@ def decoder_dropout_masks(p, seed, Q, Cd=256, Fd=512, H=8, layers=6):
                  ffn_o=m(s0 + 4, Q, 1, Cd)) for s0 in range(16, 16 + 8 * layers, 8)]
 
 
+def prob_masks(p, seed, H, Q, layers=3, tokens=1500):
+    """The multipliers on the attention probabilities of the fusion layers, one [H, Q, tokens] tensor per layer as the
+    reference's nn.MultiheadAttention(dropout=p) would draw one: site 4 r + 0, index (q * H + h) * tokens + tok."""
+    return [dropout_mask(p, seed, 4 * r + 0, Q * H * tokens).view(Q, H, tokens).permute(1, 0, 2).contiguous()
+            for r in range(layers)]
+
+
+def radar_dropout_masks(p, seed, H, Q, Cd=256, Fd=512, layers=3, tokens=1500):
+    """The oracle's ``drop`` for one frame (test_gpu_training's layout) at H radar heads and the head's padded token count:
+    per layer probs [H, Q, tokens] (site 4 r), d2 [Q, Cd] (4 r + 1), ffn [Q, Fd] (4 r + 2), d3 [Q, Cd] (4 r + 3)."""
+    probs = prob_masks(p, seed, H, Q, layers, tokens)
+    return [dict(probs=probs[r], d2=dropout_mask(p, seed, 4 * r + 1, Q * Cd).view(Q, Cd),
+                 ffn=dropout_mask(p, seed, 4 * r + 2, Q * Fd).view(Q, Fd),
+                 d3=dropout_mask(p, seed, 4 * r + 3, Q * Cd).view(Q, Cd)) for r in range(layers)]
+
+
 # ---- the checks every variant repeats ------------------------------------------------------------------------------------
 def check_train_mode_decoder(frame, rows, matrix, refs_atol=2e-4, **variant):
     """The frozen decoder's train-mode forward (dropout on, layer 0 not folded: the DROP instantiations of the chain
@@ -481,17 +542,23 @@ def check_train_mode_decoder(frame, rows, matrix, refs_atol=2e-4, **variant):
                            options=head_options(**dict(opts, tile_rows=8)))
         for k in ('inter_states', 'inter_references'):
             assert torch.equal(a['aux'][k], c['aux'][k]), k
-    okw = oracle_kw(**variant)
+    okw = decoder_kw(**variant)
     geom = geometry_of(variant)
     assert tuple(img_hw) == geom.hw             # the frame is g8_frame(..., geometry=<the variant's>)
     if not okw['with_box_refine']:
         refs_are_initial(a['aux'])
+    Fd = dict(CONFIGS, **variant)['feedforward_channels']
+    masks = decoder_dropout_masks(p, seed, h.num_query, Fd=Fd, H=okw['num_heads'])     # the hidden site's index: row * Fd + column
+    assert all(m['ffn_h'].numel() == h.num_query * Fd for m in masks)
+    keep = float(torch.stack([m['ffn_h'] for m in masks]).ne(0).float().mean())
+    assert abs(keep - (1.0 - p)) < 5e-3, keep
     want_hs, init_ref, want_refs, _ = O.transformer(
-        O.to_torch_sd(synth.make_state_dict(3, **state_dict_kw(**variant))), [torch.from_numpy(f) for f in frame['feats_np']],
-        list(geom.pc_range), torch.from_numpy(frame['l2i_np']).float()[None], geom.hw,
-        dec_drop=decoder_dropout_masks(p, seed, h.num_query, H=okw['num_heads']), **okw)
+        O.to_torch_sd(state_dict(**variant)), [torch.from_numpy(f) for f in frame['feats_np']],
+        list(geom.pc_range), torch.from_numpy(frame['l2i_np']).float()[None], geom.hw, dec_drop=masks, **okw)
     np.testing.assert_allclose(a['aux']['init_reference'].cpu().numpy(), init_ref.numpy(), atol=1e-6, rtol=0)
     np.testing.assert_allclose(a['aux']['inter_references'].cpu().numpy(), want_refs.numpy(), atol=refs_atol, rtol=0)
+    print('%r %d rows %s train mode: max|hs - oracle with the same masks| = %.3g' % (
+        variant, rows, matrix, np.abs(hs.cpu().numpy()[:, 0] - want_hs[:, :, 0].numpy()).max()))
     np.testing.assert_allclose(hs.cpu().numpy()[:, 0], want_hs[:, :, 0].numpy(), atol=2e-3, rtol=0)
 
 
@@ -572,31 +639,40 @@ def check_grads_against_g8(grads, g8, rtol, what, expected=98):
 _FORWARD, _TRAINING = {}, {}
 
 
-def oracle_training(host, levels=None, **variant):
+def _training_forward(host, variant):
+    sd = O.to_torch_sd(state_dict(**variant))
+    for k, v in sd.items():
+        if trainable(k):
+            v.requires_grad_(True)
+    with torch.enable_grad():
+        return sd, oracle_forward(sd, host['feats_np'], host['frame'], variant)
+
+
+def _training_backward(sd, outs, host, levels, variant):
+    for v in sd.values():
+        v.grad = None
+    with torch.enable_grad():
+        cut = {k: outs[k][:levels] for k in ('all_cls_scores', 'all_bbox_preds')}
+        res, matches = O.loss(cut, torch.from_numpy(host['boxes']), torch.from_numpy(host['labels']), sd['code_weights'],
+                              num_classes=dict(CONFIGS, **variant)['num_classes'])
+        sum(res.values()).backward(retain_graph=True)
+    return ({k: v.detach() for k, v in cut.items()}, {k: float(v.detach()) for k, v in res.items()}, matches,
+            {k: v.grad for k, v in sd.items() if trainable(k)})
+
+
+def oracle_training(host, levels=None, keep=True, **variant):
     """One training iteration of the oracle on the host side of a g8_frame: the variant's seed-3 weights with the
     trainable ones as autograd leaves, head_forward, O.loss at the variant's class count, backward.  levels=N: the loss
     and the backward on levels [:N] of that forward (the fusion layers are causally ordered: one forward serves every N).
     -> (outs, losses {name: float}, matched gt per level, {name: gradient or None} of the trainable parameters), kept per
-    variant, frame and levels."""
+    variant, frame and levels.  keep=False: computed now and not kept (the tie analysis runs it under its ReLU hook)."""
+    if not keep:
+        return _training_backward(*_training_forward(host, variant), host, levels, variant)
     key = (host['key'], variant_key(**variant))
     if key not in _FORWARD:
-        sd = O.to_torch_sd(synth.make_state_dict(3, **state_dict_kw(**variant)))
-        for k, v in sd.items():
-            if trainable(k):
-                v.requires_grad_(True)
-        with torch.enable_grad():
-            _FORWARD[key] = sd, oracle_forward(sd, host['feats_np'], host['frame'], variant)
+        _FORWARD[key] = _training_forward(host, variant)
     if (key, levels) not in _TRAINING:
-        sd, outs = _FORWARD[key]
-        for v in sd.values():
-            v.grad = None
-        with torch.enable_grad():
-            cut = {k: outs[k][:levels] for k in ('all_cls_scores', 'all_bbox_preds')}
-            res, matches = O.loss(cut, torch.from_numpy(host['boxes']), torch.from_numpy(host['labels']), sd['code_weights'],
-                                  num_classes=dict(CONFIGS, **variant)['num_classes'])
-            sum(res.values()).backward(retain_graph=True)
-        _TRAINING[key, levels] = ({k: v.detach() for k, v in cut.items()}, {k: float(v.detach()) for k, v in res.items()},
-                                  matches, {k: v.grad for k, v in sd.items() if trainable(k)})
+        _TRAINING[key, levels] = _training_backward(*_FORWARD[key], host, levels, variant)
     return _TRAINING[key, levels]
 
 

@@ -1,14 +1,10 @@
 """What the tests of the head's camera count (Detr3DCrossAtten.num_cams 1 .. 16; the configs: 6) add to
 head_variant_rig.py: a Geometry whose cameras are a ring of N (synth.ring_yaws) and whose head_kw carries num_cams, so
-that the rig's heads, oracle forwards, gate-margin search, frames and checkers serve a camera count as they serve a
-point-cloud range; the oracle's decoder with the count bound from outside (`bound`); the radar seeds chosen per count;
-and the coverage a rig must have before a GPU case on it proves anything (cameras with index >= 8 are the new ground).
+that the rig's heads, oracle forwards (which pass the ring's count to the oracle), gate-margin search, frames and
+checkers serve a camera count as they serve a point-cloud range; the radar seeds chosen per count; and the coverage a rig must have before a GPU case on it proves anything (cameras with index >= 8 are the new ground).
 
 Tiny level shapes, 6 decoder layers, state dict seed 3, smooth maps (4, 6) seed 1, 72 queries: two 32-row tiles and a
 ragged one.  A plain helper module; what is computed on the CPU is computed once per count and kept."""
-import contextlib
-import functools
-
 import numpy as np
 import torch
 
@@ -65,27 +61,13 @@ def variant(N, **kw):
     return dict(dict(num_query=NQ, geometry=Ring(N)), **kw)
 
 
-@contextlib.contextmanager
-def bound(N):
-    """The oracle's decoder and ops.decoder_layer_tail with num_cams=N bound from outside: O.transformer and
-    teacher_forced_checks call both without the count (the configs' 6 is their default)."""
-    from transcar_amd import ops
-    cross, tail = O.cross_atten, ops.decoder_layer_tail
-    O.cross_atten = functools.partial(cross, num_cams=N)
-    ops.decoder_layer_tail = functools.partial(tail, num_cams=N)
-    try:
-        yield
-    finally:
-        O.cross_atten, ops.decoder_layer_tail = cross, tail
-
-
 def feats(N, batch=1, num_levels=4, **_):
     """the rig's maps [batch, N, C, H, W], the first num_levels tiny levels (the other variant keys do not reach them)"""
     return synth.make_feats(R.TINY[:num_levels], seed=1, batch=batch, num_cams=N, smooth=R.SMOOTH)
 
 
 def state_dict(N, **kw):
-    return synth.make_state_dict(seed=3, **R.state_dict_kw(**variant(N, **kw)))
+    return R.state_dict(**variant(N, **kw))
 
 
 # ---- radar frames: the gate-margin search of the other variants, on the oracle's own centres ---------------------------------
@@ -113,7 +95,7 @@ def centres(N, **kw):
     """xy of the decoder's last reference points on the count's rig (a first pass of the oracle)"""
     key = _vkey(N, kw)
     if key not in _CENTRES:
-        with bound(N), torch.no_grad():
+        with torch.no_grad():
             _, dbg = R.oracle_forward(O.to_torch_sd(state_dict(N, **kw)), feats(N, **kw), synth.make_radar_frame(seed=2, n_per_radar=51),
                                       variant(N, **kw), return_debug=True)
         _CENTRES[key] = centres_of(dbg)
@@ -132,8 +114,7 @@ def search_seed(N, **kw):
     key = _vkey(N, kw)
     if key not in _SEARCH:
         sd, f = O.to_torch_sd(state_dict(N, **kw)), feats(N, **kw)
-        with bound(N):
-            margins = {s: R.gate_margin(sd, f, frame(N, s, **kw), **variant(N, **kw)) for s in SEED_RANGE}
+        margins = {s: R.gate_margin(sd, f, frame(N, s, **kw), **variant(N, **kw)) for s in SEED_RANGE}
         best = max(margins, key=margins.get)
         _SEARCH[key] = (best, margins[best])
     return _SEARCH[key]
@@ -151,7 +132,7 @@ def oracle(N, jitter_seed=None, **kw):
         f = feats(N, **kw) if jitter_seed is None else [x[1:] for x in feats(N, batch=2, **kw)]
         fr = frame(N, **kw)
         v = dict(variant(N, **kw), geometry=Ring(N, jitter_seed))
-        with bound(N), torch.no_grad():
+        with torch.no_grad():
             want, dbg = R.oracle_forward(sd, f, fr, v, return_debug=True)
         _ORACLE[key] = (sd, f, fr, want, dbg)
     return _ORACLE[key]

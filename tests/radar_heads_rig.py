@@ -1,26 +1,12 @@
-"""The rig of the radar fusion attention's head count (Detr3DHead(radar_num_heads=H), H = 4 / 16 beside the reference's
-8): heads built through configs.head_cfg(radar_num_heads=H), the CPU oracle with its fusion attention at H heads, and the
-dropout masks of the attention probabilities as the kernels index them at H heads.
-
-head_variant_rig's CONFIGS rejects keys it does not know, so the heads and the oracle calls are made here; the checks
-that take a head or tensors (run_head, check_against_oracle, check_against_fixture, check_grads_against_g8, dropout_mask,
-check_frame_of_nine, check_frame_pipeline, check_plugin_graph_replay) are head_variant_rig's, as they are.  Other variant
-keys (num_heads, num_classes, num_fusion_layers, radar_gate ...) pass through to head_variant_rig under their own names.
-
-The oracle's radar_layer calls multihead_attention at its default of 8 heads; oracle_radar_heads(H) replaces
-O.multihead_attention, for the duration of a `with`, by a wrapper that passes num_heads=H whenever the module's name
-starts with rf_multihead_attn (head_forward looks the function up when it is called)."""
-import contextlib
-
+"""What the tests of the radar fusion attention's head count (Detr3DHead(radar_num_heads=H), H = 4 / 16 beside the
+reference's 8) add to head_variant_rig.py, whose variants carry the key (heads, oracle calls, training iterations and
+dropout masks at H heads are its own): the fixtures' names and frames, and the ReLU-tie analysis of a training frame."""
 import numpy as np
-import torch
 
 import head_variant_rig as R
 from oracle import transcar_oracle as O
-from transcar_amd import configs, synth
 
 HEADS = (4, 16)         # radar_num_heads beside the reference's 8: head dimension 64 and 16
-TOKENS_REF = 1500       # the reference's padded token count: the last axis of its dropout mask on the probabilities
 
 
 def g5_name(H):
@@ -31,94 +17,6 @@ def g8_name(H):
     return 'g8_train_grads_rh%d.npz' % H
 
 
-@contextlib.contextmanager
-def oracle_radar_heads(H):
-    """The oracle's fusion attention at H heads; the decoder's self-attention keeps what its caller passes."""
-    plain = O.multihead_attention
-
-    def patched(sd, name, *args, **kw):
-        if name.startswith('rf_multihead_attn'):
-            kw['num_heads'] = H
-        return plain(sd, name, *args, **kw)
-    O.multihead_attention = patched
-    try:
-        yield
-    finally:
-        O.multihead_attention = plain
-
-
-def head_cfg(H, **variant):
-    return configs.head_cfg(radar_num_heads=H, **R.variant_kw(**variant))
-
-
-def check_head(h, H, **variant):
-    """The head carries the count where the kernels and the unfused path read it; the rest as head_variant_rig.check_head."""
-    from transcar_amd import _lib as L
-    from transcar_amd.detr3d_head import fusion_modules
-    want = dict(R.CONFIGS, **variant)
-    assert h.radar_num_heads == H
-    w = h.weights_struct()
-    assert w.num_heads == L.pack_num_heads(want['num_heads'], H)
-    assert (w.num_heads & 0xffff) == want['num_heads'] and (w.num_heads >> 16) == (0 if H == 8 else H)
-    for r in range(h.num_fusion_layers):
-        assert fusion_modules(h, r).attn.num_heads == H and fusion_modules(h, r).attn.head_dim == 256 // H
-    for ly in h.transformer.decoder.layers:
-        assert ly.attentions[0].num_heads == want['num_heads']
-    assert h.num_fusion_layers == w.num_radar_layers == want['num_fusion_layers']
-    assert w.num_classes == want['num_classes']
-
-
-def make_head(T, H, seed=3, **variant):
-    """A fresh eval-mode head of H radar heads with seeded weights (the state dict does not depend on H), and those
-    weights as the oracle takes them."""
-    sd_np = synth.make_state_dict(seed=seed, **R.state_dict_kw(**variant))
-    h = T.build_head(head_cfg(H, **variant))
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=True)
-    check_head(h, H, **variant)
-    return h.to(R.dev()).eval(), O.to_torch_sd(sd_np)
-
-
-_HEADS = {}
-
-
-def shared_head(T, H, **variant):
-    key = (H, R.variant_key(**variant))
-    if key not in _HEADS:
-        _HEADS[key] = make_head(T, H, **variant)
-    return _HEADS[key]
-
-
-def train_head(H, **variant):
-    import transcar_amd as T_
-    cfg = head_cfg(H, **variant)
-    cfg.setdefault('train_cfg', configs.train_cfg_pts)
-    h = T_.build_head(cfg)
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(3, **R.state_dict_kw(**variant)).items()},
-                      strict=True)
-    check_head(h, H, **variant)
-    return h.to(R.dev()).freeze_decoder().set_dropout(0.0)
-
-
-_ORACLE = {}
-
-
-def oracle_head(sd, feats_np, frame, H, key=None, **variant):
-    """R.oracle_head with the fusion attention at H heads (kept under `key`, H and the variant)."""
-    key = None if key is None else (key, H, R.variant_key(**variant))
-    if key is None or key not in _ORACLE:
-        with oracle_radar_heads(H), torch.no_grad():
-            res = R.oracle_forward(sd, feats_np, frame, variant, return_debug=True)
-        if key is None:
-            return res
-        _ORACLE[key] = res
-    return _ORACLE[key]
-
-
-def gate_margin(sd, feats_np, frame, H, **variant):
-    with oracle_radar_heads(H):
-        return R.gate_margin(sd, feats_np, frame, **variant)
-
-
 def g5_frame(H):
     """The frame of the H-head fixtures: G5's maps, the radar of the seed the fixture stores."""
     return R.g5_frame(int(R.gold(g5_name(H))['radar_seed']))
@@ -126,22 +24,6 @@ def g5_frame(H):
 
 def g8_frame(H):
     return R.g8_frame('g5_head_tiny.npz', radar_seed=int(R.gold(g8_name(H))['radar_seed']))
-
-
-def oracle_training(host, H, **variant):
-    """R.oracle_training with the fusion attention at H heads.  head_variant_rig keeps its results per frame and variant,
-    not per H: the entries this call makes are taken out again."""
-    keep = (dict(R._FORWARD), dict(R._TRAINING))
-    R._FORWARD.clear()
-    R._TRAINING.clear()
-    try:
-        with oracle_radar_heads(H):
-            return R.oracle_training(host, **variant)
-    finally:
-        R._FORWARD.clear()
-        R._TRAINING.clear()
-        R._FORWARD.update(keep[0])
-        R._TRAINING.update(keep[1])
 
 
 # ---- ReLU ties: how far a frame's gradients move when the inputs nearest to zero are taken on the other side ------------------
@@ -176,31 +58,12 @@ def tie_sensitivity(host, H, tau=TIE_TAU, **variant):
         return plain(x, *args, **kw)
     O.F.relu = relu
     try:
-        grads = oracle_training(host, H, **variant)[3]
+        grads = R.oracle_training(host, keep=False, radar_num_heads=H, **variant)[3]
         flip[0] = True
-        flipped = oracle_training(host, H, **variant)[3]
+        flipped = R.oracle_training(host, keep=False, radar_num_heads=H, **variant)[3]
     finally:
         O.F.relu = plain
     return g8_figures(flipped, R.GradStats(grads))
-
-
-def prob_masks(p, seed, H, Q, layers=3):
-    """The multipliers on the attention probabilities of the fusion layers, one [H, Q, 1500] tensor per layer as the
-    reference's nn.MultiheadAttention(dropout=p) would draw one: site 4 r + 0, index (q * H + h) * 1500 + tok."""
-    out = []
-    for r in range(layers):
-        flat = R.dropout_mask(p, seed, 4 * r + 0, Q * H * TOKENS_REF)
-        out.append(flat.view(Q, H, TOKENS_REF).permute(1, 0, 2).contiguous())
-    return out
-
-
-def radar_dropout_masks(p, seed, H, Q, Cd=256, Fd=512, layers=3):
-    """The oracle's ``drop`` for one frame (test_gpu_training's layout) at H radar heads: per layer probs [H, Q, 1500]
-    (site 4 r), d2 [Q, Cd] (4 r + 1), ffn [Q, Fd] (4 r + 2), d3 [Q, Cd] (4 r + 3)."""
-    probs = prob_masks(p, seed, H, Q, layers)
-    return [dict(probs=probs[r], d2=R.dropout_mask(p, seed, 4 * r + 1, Q * Cd).view(Q, Cd),
-                 ffn=R.dropout_mask(p, seed, 4 * r + 2, Q * Fd).view(Q, Fd),
-                 d3=R.dropout_mask(p, seed, 4 * r + 3, Q * Cd).view(Q, Cd)) for r in range(layers)]
 
 
 def bit_equal(a, b):

@@ -1,22 +1,20 @@
-"""The rig of the radar input's configuration (Detr3DHead(radar_num_tokens=N, radar_in_dims=F, radar_point_range=...)): heads
-at 128 queries on the tiny maps, frames of [n,F] feature rows scattered around the oracle's gate centres, and the CPU oracle
-at N tokens.
+"""What the tests of the radar input's configuration (Detr3DHead(radar_num_tokens=N, radar_in_dims=F,
+radar_point_range=...)) add to head_variant_rig.py, whose variants carry the three keys: the cases at 128 queries on the
+tiny maps, frames of [n,F] feature rows scattered around the oracle's gate centres, the rows' filter, and one decoder trace
+for all cases.
 
-head_variant_rig's CONFIGS rejects keys it does not know, so the heads and the oracle calls of this axis alone are made
-here (as radar_heads_rig does); heads that combine these keys with the other axes' are variant_pairs_rig's.  The checks that
-take a head or tensors are head_variant_rig's, as they are.  The reference writes 1500 and 36 into its program text, so there
-is no reference fixture off those values: the yardstick is the oracle, which the G5 / G8 fixtures pin to the reference at
-1500 / 36.  It reads F off the rows and the state dict and N off its module attribute NUM_RADAR_TOKENS, which `oracle_case`
-sets through the test's monkeypatch fixture for the duration of the oracle's call."""
+The reference writes 1500 and 36 into its program text, so there is no reference fixture off those values: the yardstick
+is the oracle, which the G5 / G8 fixtures pin to the reference at 1500 / 36.  It reads F off the rows and the state dict and
+is given N by argument (head_variant_rig.oracle_kw)."""
 import numpy as np
 import torch
 
 import head_variant_rig as R
 from oracle import transcar_oracle as O
-from transcar_amd import configs, synth
+from transcar_amd import synth
 
 Q = 128
-POINT_RANGE = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0)          # HEAD:304
+POINT_RANGE = R.POINT_RANGE                                    # HEAD:304
 MIN_MARGIN = 1e-3       # metres between every gate decision of the oracle and its radius on the frames below
 # case -> (N, F, n rows, seed of the frame, radar_point_range or None).  The seeds are chosen (on the CPU oracle, gate_probe)
 # so that no gate decision sits within MIN_MARGIN of its radius; `oracle_case` measures it again wherever the tests run.
@@ -37,27 +35,10 @@ BACKWARDS = {'chain': dict(chain_forward=True, chain_backward=True), 'operators'
 NEAR = 120              # rows of a frame that lie near a gate centre; the others are kept out of every gate's reach
 
 
-def state_dict(F):
-    """Seeded weights at 128 queries and F radar features.  synth draws radar_feat_encoder behind the decoder and the fusion
-    layers, so every F shares the decoder's (and one decoder trace serves them all)."""
-    return synth.make_state_dict(seed=3, num_query=Q, radar_in=F)
-
-
-def head_cfg(N=1500, F=36, point_range=None, **kw):
-    return configs.head_cfg(num_query=Q, radar_num_tokens=N, radar_in_dims=F, radar_point_range=point_range, **kw)
-
-
-def make_head(T, N=1500, F=36, point_range=None, train=False):
-    cfg = head_cfg(N, F, point_range)
-    if train:
-        cfg.setdefault('train_cfg', configs.train_cfg_pts)
-    h = T.build_head(cfg)
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in state_dict(F).items()}, strict=True)
-    assert (h.radar_num_tokens, h.radar_in_dims) == (N, F)
-    w = h.weights_struct()
-    assert (w.num_radar_tokens_ref, w.radar_in_dims) == (N, F)
-    h = h.to(R.dev())
-    return h.freeze_decoder().set_dropout(0.0) if train else h.eval()
+def variant(N=1500, F=36, point_range=None):
+    """head_variant_rig's variant of a case.  synth draws radar_feat_encoder behind the decoder and the fusion layers, so
+    every F shares the decoder's weights (and one decoder trace serves them all)."""
+    return dict(num_query=Q, radar_num_tokens=N, radar_in_dims=F, radar_point_range=point_range)
 
 
 _SHARED = {}
@@ -72,7 +53,7 @@ def feats_np():
 def decoder_trace():
     """The oracle's decoder at 128 queries on the tiny maps, once: (hs, init_ref, inter_refs, tmp) as head_forward takes it."""
     if 'trace' not in _SHARED:
-        sd = O.to_torch_sd(state_dict(36))
+        sd = O.to_torch_sd(R.state_dict(**variant()))
         with torch.no_grad():
             _SHARED['trace'] = O.transformer(sd, [torch.from_numpy(f) for f in feats_np()], list(R.PCR),
                                              torch.from_numpy(synth.make_lidar2img()).float()[None], R.HW)
@@ -117,30 +98,18 @@ def in_range(rows, point_range):
 _ORACLE = {}
 
 
-def oracle_case(name, monkeypatch):
-    """monkeypatch: the test's fixture (the oracle reads N off its module attribute).
-    -> dict(N, F, rows [n,F] float32 as the head gets them, kept: the rows its filter keeps, want, dbg, masks: the
+def oracle_case(name):
+    """-> dict(N, F, rows [n,F] float32 as the head gets them, kept: the rows its filter keeps, want, dbg, masks: the
     oracle's gate masks [Q,N] per layer (True = masked), margin: metres between its closest gate decision and the radius)."""
     if name not in _ORACLE:
         N, F, n, seed, rng = CASES[name]
         rows = make_rows(seed, n, F)
         kept = rows[in_range(rows, rng or POINT_RANGE)]
-        sd = O.to_torch_sd(state_dict(F))
+        v = variant(N, F, rng)
         masks, margins = [], []
-
-        def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
-            masks.append(O.circle_mask(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax))
-            length = length_log.exp()
-            off = torch.stack((length * 0.25 * -rot_sin, length * 0.25 * -rot_cos), -1)
-            radii = torch.clamp((length / 2.0).reshape(-1, 1), min=rmin, max=rmax)
-            live = radar_xy[0, :, 0] != O.PAD_VALUE
-            margins.append(min(float((torch.cdist(c, radar_xy, p=2.0)[0][:, live] - radii).abs().min())
-                               for c in (centre_xy, centre_xy + off, centre_xy - off)))
-        with monkeypatch.context() as m, torch.no_grad():
-            m.setattr(O, 'NUM_RADAR_TOKENS', N)
-            want, dbg = O.head_forward(sd, [torch.from_numpy(f) for f in feats_np()],
-                                       torch.from_numpy(synth.make_lidar2img()).float()[None], R.HW, kept, list(R.PCR),
-                                       return_debug=True, decoder_trace=decoder_trace(), gate_probe=probe)
+        with torch.no_grad():
+            want, dbg = R.oracle_forward(O.to_torch_sd(R.state_dict(**v)), feats_np(), kept, v, return_debug=True,
+                                         decoder_trace=decoder_trace(), gate_probe=R.margin_probe(margins, masks))
         assert dbg['fill_in'] == min(N, len(kept)) and len(masks) == 3 and masks[0].shape == (Q, N)
         _ORACLE[name] = dict(N=N, F=F, rows=rows, kept=kept, point_range=rng, want=want, dbg=dbg, masks=masks, margin=min(margins))
     return _ORACLE[name]

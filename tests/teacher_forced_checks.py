@@ -87,7 +87,8 @@ def decoder_layer_truth(rig, lid):
         ref_prev = rig['init_ref'] if lid == 0 else rig['inter_refs'][lid - 1]
         p = 'transformer.decoder.layers.%d.' % lid
         truth = O.decoder_layer(sd64, p, x_prev.permute(1, 0, 2).double(), pos.permute(1, 0, 2).double(),
-                                rig['_feats64'], ref_prev.double(), rig_pcr(rig), rig['l2i'].double(), rig_hw(rig)).permute(1, 0, 2)
+                                rig['_feats64'], ref_prev.double(), rig_pcr(rig), rig['l2i'].double(), rig_hw(rig),
+                                num_cams=rig['head'].weights_struct().num_cams).permute(1, 0, 2)
         tmp64 = O.reg_branch(sd64, 'reg_branches.%d' % lid, truth)
         new_ref = torch.zeros_like(ref_prev.double())
         new_ref[..., :2] = tmp64[..., :2] + O.inverse_sigmoid(ref_prev.double()[..., :2])
@@ -108,6 +109,7 @@ def decoder_layers_teacher_forced(rig, tile_rows, matrix, title):
     pos = qe[:, :256][None]                                   # [1,Q,C]
     l2i = gpu(rig['l2i'])
     pv = head._packed_view
+    w = head.weights_struct()          # the C layer struct carries neither the camera count nor the FFN's width
     L = 6
     report = []
     for lid in range(L):
@@ -118,7 +120,7 @@ def decoder_layers_teacher_forced(rig, tile_rows, matrix, title):
         nxt = pv.layers[lid + 1].self_attn.in_proj if lid + 1 < L else None
         hs, ref_out, qk_next, vt_next = ops.decoder_layer_tail(
             pv.layers[lid], nxt, rig['nhwc'], attn_o, gpu(x_prev), gpu(qe), l2i, gpu(ref_prev), rig_pcr(rig), rig_hw(rig),
-            tile_rows=tile_rows, matrix_path=MATRIX_PATHS[matrix])
+            num_cams=w.num_cams, tile_rows=tile_rows, matrix_path=MATRIX_PATHS[matrix], ffn_dims=w.ffn_dims)
         # the same layer: fp32 oracle (from the rig's trace) and fp64 evaluation of the same formula
         truth, truth_ref = decoder_layer_truth(rig, lid)
         oracle32 = rig['hs'][lid].permute(1, 0, 2)            # [1,Q,C]

@@ -160,7 +160,7 @@ def test_geometry_is_a_variant_key():
     assert R.variant_kw(geometry=GEOM) == kw and R.variant_kw(geometry=DEFAULT) == {}
     assert R.variant_kw(num_points=5, geometry=GEOM) == dict(num_points=5, **kw)
     assert R.state_dict_kw(num_points=5, num_heads=4, geometry=GEOM) == dict(num_points=5)
-    assert R.oracle_kw(geometry=GEOM) == dict(with_box_refine=True, num_heads=8)
+    assert R.decoder_kw(geometry=GEOM) == dict(with_box_refine=True, num_heads=8, num_cams=6)       # (a plain Geometry: six cameras)
     assert R.variant_key(geometry=DEFAULT) == R.variant_key() == ()
     keys = {R.variant_key(), R.variant_key(geometry=GEOM), R.variant_key(num_points=5, geometry=GEOM),
             R.variant_key(geometry=GEOM._replace(img_shape=(1152, 640, 3)))}

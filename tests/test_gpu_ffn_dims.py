@@ -5,8 +5,6 @@ and both matrix paths, one layer teacher-forced against fp64, the launch forms (
 the plugin graphs), outputs='all', no box refinement, the train-mode decoder with read-back masks and a training
 iteration.  Tiny maps, 900 queries (28 tiles of 32 rows + 4: every tile height has a partial last tile).  The rig is
 ffn_dims_rig.py; the checks and tolerances are head_variant_rig.py's and teacher_forced_checks.py's.  pytest -m gpu"""
-import functools
-
 import numpy as np
 import pytest
 import torch
@@ -30,9 +28,9 @@ CASES = [(F, rows, 'f16x2') for F in FR.WIDTHS for rows in (16, 32)] + \
 # ---- 1. the whole head, free-running, against the oracle --------------------------------------------------------------------
 @pytest.mark.parametrize('F,rows,matrix', CASES)
 def test_head_against_oracle(T, F, rows, matrix):
-    head, sd = FR.shared_head(T, F)
-    want, dbg = FR.oracle_head(sd, F)
+    head, sd = R.shared_head(T, **FR.variant(F))
     feats_np, frame = FR.frame(F)
+    want, dbg = R.oracle_head(sd, feats_np, frame, key='ffn_dims', **FR.variant(F))
     outs = R.run_head(head, feats_np, frame, tile_rows=rows, matrix_path=matrix)
     d = (outs['aux']['inter_states'].cpu() - dbg['hs']).abs()
     print('F=%d %d rows %s: max|hs - oracle| per layer %s' % (F, rows, matrix, ['%.2e' % float(v) for v in d.amax(dim=(1, 2, 3))]))
@@ -42,7 +40,7 @@ def test_head_against_oracle(T, F, rows, matrix):
 def test_the_width_reaches_the_kernels(T):
     """A head of 1024 hidden units parts by O(0.1) from the same head with the upper 512 switched off (ffn1's columns
     512.. zeroed): the second chunk is read, and from where the packer put it."""
-    head, _ = FR.make_head(T, 1024)
+    head, _ = R.make_head(T, **FR.variant(1024))
     feats_np, frame = FR.frame(1024)
     full = R.run_head(head, feats_np, frame, tile_rows=16, matrix_path='f16x2')['aux']['inter_states'].clone()
     for ly in head.transformer.decoder.layers:
@@ -92,21 +90,16 @@ def tf_rig():
 
 @pytest.mark.parametrize('rows', [16, 32])
 def test_decoder_layers_teacher_forced_2048(tf_rig, rows):
-    """teacher_forced_checks.decoder_layers_teacher_forced, its bounds as they are, with the width bound from outside
-    (the C layer struct carries none): four chunks per layer, each layer on the oracle's state of the layer before."""
-    ops = TF.head_ops()
-    tail = ops.decoder_layer_tail
-    ops.decoder_layer_tail = functools.partial(tail, ffn_dims=tf_rig['F'])
-    try:
-        TF.decoder_layers_teacher_forced(tf_rig, rows, 'f16x2', 'teacher-forced decoder layers, feedforward_channels=2048')
-    finally:
-        ops.decoder_layer_tail = tail
+    """teacher_forced_checks.decoder_layers_teacher_forced, its bounds as they are (it reads the width off the head: the C
+    layer struct carries none): four chunks per layer, each layer on the oracle's state of the layer before."""
+    assert tf_rig['head'].weights_struct().ffn_dims == tf_rig['F']
+    TF.decoder_layers_teacher_forced(tf_rig, rows, 'f16x2', 'teacher-forced decoder layers, feedforward_channels=2048')
 
 
 def test_one_layer_entry_refuses_other_widths(T):
     """The one-layer entry with a width refuses what the chains do not run, naming it."""
     from transcar_amd import ops
-    head, _ = FR.shared_head(T, 1024)
+    head, _ = R.shared_head(T, **FR.variant(1024))
     head.head_weights()
     pv = head._packed_view
     nhwc = [ops.to_nhwc(R.gpu(f)) for f in synth.make_feats('tiny', seed=1, smooth=R.SMOOTH)]
@@ -120,7 +113,7 @@ def test_one_layer_entry_refuses_other_widths(T):
 
 # ---- 3. the launch forms at F = 1024 -----------------------------------------------------------------------------------------
 def test_frame_of_nine_is_its_own(T):
-    R.check_frame_of_nine(FR.shared_head(T, 1024)[0])
+    R.check_frame_of_nine(R.shared_head(T, **FR.variant(1024))[0])
 
 
 @pytest.mark.parametrize('rows,matrix', [(16, 'f16x2'), (16, 'f32')])
@@ -128,7 +121,7 @@ def test_frames_of_nine_are_their_own_on_16_rows(T, rows, matrix):
     """Every frame of a nine-frame launch is bit-identical to that frame launched alone at the same tile height and
     matrix path (check_frame_of_nine: frame 4 on the 32-row tiles)."""
     from transcar_amd.detr3d_head import head_options
-    head = FR.shared_head(T, 1024)[0]
+    head = R.shared_head(T, **FR.variant(1024))[0]
     feats = [synth.make_feats('tiny', seed=40 + i, smooth=R.SMOOTH) for i in range(9)]
     frames = [synth.make_radar_frame(seed=60 + i, n_per_radar=45) for i in range(9)]
     head.forward_options = head_options(tile_rows=rows, matrix_path=matrix)
@@ -143,11 +136,11 @@ def test_frames_of_nine_are_their_own_on_16_rows(T, rows, matrix):
 
 
 def test_frame_pipeline_equals_forward_nhwc(T):
-    R.check_frame_pipeline(FR.shared_head(T, 1024)[0], 2)
+    R.check_frame_pipeline(R.shared_head(T, **FR.variant(1024))[0], 2)
 
 
 def test_plugin_graph_replay_is_the_eager_entry(T):
-    R.check_plugin_graph_replay(FR.make_head(T, 1024)[0], FR.make_head(T, 1024)[0])
+    R.check_plugin_graph_replay(R.make_head(T, **FR.variant(1024))[0], R.make_head(T, **FR.variant(1024))[0])
 
 
 # ---- 4. other paths --------------------------------------------------------------------------------------------------------
@@ -155,9 +148,9 @@ def test_all_outputs_768_against_oracle(T):
     """outputs='all' at F = 768: the decoder levels' own scores and boxes against O.decoder_outputs on the oracle's
     trace, the fusion levels behind them against the oracle's head."""
     F = 768
-    head, sd = FR.shared_head(T, F)
-    want, dbg = FR.oracle_head(sd, F)
+    head, sd = R.shared_head(T, **FR.variant(F))
     feats_np, frame = FR.frame(F)
+    want, dbg = R.oracle_head(sd, feats_np, frame, key='ffn_dims', **FR.variant(F))
     head.outputs = 'all'
     try:
         outs = R.run_head(head, feats_np, frame)
@@ -175,9 +168,9 @@ def test_all_outputs_768_against_oracle(T):
 @pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
 def test_no_box_refinement_1024_against_oracle(T, rows, matrix):
     """with_box_refine=False: the reg steps behind the FFN's records are switched off (and the layer-0 sequence's too)."""
-    head, sd = FR.shared_head(T, 1024, refine=False)
-    want, dbg = FR.oracle_head(sd, 1024, refine=False)
+    head, sd = R.shared_head(T, **FR.variant(1024, refine=False))
     feats_np, frame = FR.frame(1024, refine=False)
+    want, dbg = R.oracle_head(sd, feats_np, frame, key='ffn_dims', **FR.variant(1024, refine=False))
     outs = R.run_head(head, feats_np, frame, tile_rows=rows, matrix_path=matrix)
     R.check_against_oracle(outs, want, dbg, PATHS[rows, matrix], refs_initial=True)
 
@@ -185,7 +178,7 @@ def test_no_box_refinement_1024_against_oracle(T, rows, matrix):
 # ---- 5. train mode and training -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize('rows,matrix', [(4, 'f32'), (8, 'f32'), (16, 'f16x2'), (32, 'f16x2')])
 def test_train_mode_decoder_1024_matches_reference_formula(T, rows, matrix):
-    FR.check_train_mode_decoder(1024, rows, matrix)
+    R.check_train_mode_decoder(R.g8_frame('g5_head_tiny.npz', radar_seed=FR.SEEDS[1024, True]), rows, matrix, **FR.variant(1024))
 
 
 @pytest.mark.parametrize('mode', ['chain', 'deterministic'])
@@ -194,8 +187,8 @@ def test_training_iteration_against_oracle_autograd(T, F, mode):
     """One FusionTrainer iteration (frozen decoder of width F -> fusion stack -> loss -> backward) with the chain backward
     and with deterministic=True: the losses and the 98 gradient tensors against the oracle's autograd, within the rig's 2e-3."""
     frame = R.g8_frame('g5_head_tiny.npz', radar_seed=FR.SEEDS[F, True])
-    want_losses, want_grads = FR.oracle_training(frame, F)
-    h = FR.train_head(F)
+    _, want_losses, _, want_grads = R.oracle_training(frame, **FR.variant(F))
+    h = R.train_head(**FR.variant(F))
     assert len(h.trainable_parameters()) == 98
     kw = dict(deterministic=True) if mode == 'deterministic' else {}
     losses, grads = R.trainer_iteration(frame, head=h, **kw)

@@ -1,5 +1,5 @@
 """Detr3DCrossAtten(num_cams=N), 1 .. 16 cameras, on the MI355X: the whole head on every chain path against the CPU
-oracle (the count bound from outside, num_cams_rig.bound) on the ring rig of num_cams_rig.py, two samples per launch;
+oracle (told the ring's count by argument) on the ring rig of num_cams_rig.py, two samples per launch;
 the decoder layers teacher-forced against fp64; the other generic corners with many cameras; the reference's 12-camera
 fixtures (tests/golden/make_golden_num_cams.py); invariants that need no oracle (camera permutation, dead cameras, a
 frame inside a nine-frame launch); the entries around the forward; the refusals.  Up to 8 cameras at 4 levels and one
@@ -66,8 +66,7 @@ def tf_rig(T, N):
         head.head_weights()
         feats = [torch.from_numpy(f) for f in NR.feats(N)]
         l2i = torch.from_numpy(NR.Ring(N).lidar2img()).float()[None]
-        with NR.bound(N):
-            hs, init_ref, inter_refs, _ = O.transformer(sd, feats, list(R.PCR), l2i, R.HW)
+        hs, init_ref, inter_refs, _ = O.transformer(sd, feats, list(R.PCR), l2i, R.HW, num_cams=N)
         _TF[N] = dict(sd=sd, sd64={k: v.double() for k, v in sd.items()}, head=head, feats=feats,
                       nhwc=[ops.to_nhwc(gpu(f)) for f in feats], l2i=l2i, hs=hs, init_ref=init_ref, inter_refs=inter_refs)
     return _TF[N]
@@ -76,13 +75,12 @@ def tf_rig(T, N):
 @pytest.mark.parametrize('tile_rows,matrix', [(16, 'f32'), (32, 'f16x2')])
 @pytest.mark.parametrize('N', [12, 16])
 def test_decoder_layers_teacher_forced_many_cameras(T, N, tile_rows, matrix):
-    """teacher_forced_checks.decoder_layers_teacher_forced with the rig's count bound: tc_decoder_layer_tail_fwd (the
+    """teacher_forced_checks.decoder_layers_teacher_forced (it reads the count off the head): tc_decoder_layer_tail_fwd (the
     generic kernels at N > 8) on the oracle's previous state against the fp64 evaluation of the layer -- its constants,
     and its rule of twice the fp32 oracle's own deviation from fp64, re-measured on the same inputs.  The arbiter of the
     free-running cases.  Prints the measured pairs (pytest -s; recorded in DESIGN.md section 5)."""
     from teacher_forced_checks import decoder_layers_teacher_forced
-    with NR.bound(N):
-        report = decoder_layers_teacher_forced(tf_rig(T, N), tile_rows, matrix, 'ring rig, %d cameras' % N)
+    report = decoder_layers_teacher_forced(tf_rig(T, N), tile_rows, matrix, 'ring rig, %d cameras' % N)
     assert len(report) == 6
 
 
@@ -113,8 +111,7 @@ def test_head_twelve_cameras_golden(T, path):
     head, sd = R.shared_head(T, **NR.variant(12))
     frame = synth.make_radar_frame(seed=int(gold['radar_seed']), n_per_radar=51, centres=gold['radar_centres'])
     feats = NR.feats(12)
-    with NR.bound(12):
-        want, dbg = R.oracle_head(sd, feats, frame, key='cams12 golden', **NR.variant(12))
+    want, dbg = R.oracle_head(sd, feats, frame, key='cams12 golden', **NR.variant(12))
     outs = NR.run_head(head, 12, feats, [frame], [NR.Ring(12)], **NR.PATHS[path])
     R.check_against_fixture(outs, want, dbg, gold, tie_rule=True)
 

@@ -7,7 +7,7 @@
    with all 1700 rows near centres no seed keeps every gate decision 1e-3 m from its radius, which the hit-count cap needs
    (by the density of close query-token pairs some thirty of them would fall inside that band).  About 68 of the 128 rows hit, up to 4 tokens each.
 3. One training iteration with dropout 0.1 against the oracle's with the same masks (read back through
-   radar_heads_rig.radar_dropout_masks at stride N): FusionTrainer's chain and per-operator backward, the deterministic
+   head_variant_rig.radar_dropout_masks at stride N): FusionTrainer's chain and per-operator backward, the deterministic
    backward once, and the head's own train-mode forward (forward_train_nhwc) under torch autograd.
 4. The routes agree bit for bit: CUDA rows through the eager forward, through FramePipeline(radar_rows_capacity=), host
    pack_tokens through forward_nhwc; the plugin graphs at N = 2048 replay the eager entry.
@@ -123,7 +123,7 @@ _HEADS = {}
 
 def _head(T, N, F, rng=None):
     if (N, F, rng) not in _HEADS:
-        _HEADS[N, F, rng] = RI.make_head(T, N, F, rng)
+        _HEADS[N, F, rng] = R.make_head(T, **RI.variant(N, F, rng))[0]
     return _HEADS[N, F, rng]
 
 
@@ -140,8 +140,8 @@ def _run(head, rows, **options):
 
 @pytest.mark.parametrize('path', sorted(PATHS))
 @pytest.mark.parametrize('case', [c for c in RI.CASES if not c.startswith('train')])
-def test_forward_against_oracle(T, monkeypatch, case, path):
-    c = RI.oracle_case(case, monkeypatch)                    # (CPU: before the GPU is touched)
+def test_forward_against_oracle(T, case, path):
+    c = RI.oracle_case(case)                    # (CPU: before the GPU is touched)
     N, F, n = c['N'], c['F'], len(c['rows'])
     print('%s: the oracle\'s closest gate decision sits %.2e m from its radius; rows hit %s' % (
         case, c['margin'], [int((h > 0).sum()) for h in c['dbg']['hit_counts']]))
@@ -189,7 +189,7 @@ def _tied_inputs(c):
     decoder's last state through rf_norm2; found on the CPU).  Two fp32 evaluation orders part by that much, and the side
     such an input is taken on moves that unit's row of rf_linear1's gradient by one query's whole contribution.  On
     these frames: unit 77 at query 70, 2.1e-5 from zero (and unit 198 at query 101 on the F = 8 frame, 4.7e-6)."""
-    sd = O.to_torch_sd(RI.state_dict(c['F']))
+    sd = O.to_torch_sd(R.state_dict(**RI.variant(F=c['F'])))
     hs = RI.decoder_trace()[0].permute(0, 2, 1, 3)[-1][0]
     pre = O.linear(sd, 'rf_linear1', O.layer_norm(sd, 'rf_norm2', hs))
     no_hit = (c['dbg']['hit_counts'][0] == 0)[:, None]
@@ -203,12 +203,11 @@ def _oracle_iteration(case, seed, monkeypatch, flip=()):
     radar_heads_rig.tie_sensitivity flips inputs, here exactly these)."""
     flip = tuple(flip)
     if (case, seed, flip) not in _ORACLE_TRAIN:
-        c = RI.oracle_case(case, monkeypatch)
-        with monkeypatch.context() as m:
-            m.setattr(RR, 'TOKENS_REF', c['N'])
-            drop = RR.radar_dropout_masks(P_DROP, seed, 8, RI.Q)
+        c = RI.oracle_case(case)
+        drop = R.radar_dropout_masks(P_DROP, seed, 8, RI.Q, tokens=c['N'])
         assert drop[0]['probs'].shape == (8, RI.Q, c['N'])
-        sd = O.to_torch_sd(RI.state_dict(c['F']))
+        variant = RI.variant(c['N'], c['F'], c['point_range'])
+        sd = O.to_torch_sd(R.state_dict(**variant))
         for k, v in sd.items():
             if R.trainable(k):
                 v.requires_grad_(True)
@@ -226,11 +225,8 @@ def _oracle_iteration(case, seed, monkeypatch, flip=()):
                     return x * keep.to(x.dtype)
             return plain(x, *a, **kw)
         with monkeypatch.context() as m, torch.enable_grad():
-            m.setattr(O, 'NUM_RADAR_TOKENS', c['N'])
             m.setattr(O.F, 'relu', relu)
-            outs = O.head_forward(sd, [torch.from_numpy(f) for f in RI.feats_np()],
-                                  torch.from_numpy(synth.make_lidar2img()).float()[None], R.HW, c['kept'], list(R.PCR),
-                                  decoder_trace=RI.decoder_trace(), drop=drop)
+            outs = R.oracle_forward(sd, RI.feats_np(), c['kept'], variant, decoder_trace=RI.decoder_trace(), drop=drop)
             res, _ = O.loss(outs, torch.from_numpy(boxes), torch.from_numpy(labels), sd['code_weights'])
             sum(res.values()).backward()
         assert not flip or len(seen) == 3
@@ -245,7 +241,7 @@ def _iteration(T, c, backward):
     forward, FusionTrainer.step and step_nhwc run); else FusionTrainer.step_fused_nhwc with BACKWARDS[backward]."""
     from transcar_amd import ops
     from transcar_amd.trainer import FusionTrainer
-    h = RI.make_head(T, c['N'], c['F'], train=True)
+    h = R.train_head(**RI.variant(c['N'], c['F']))
     metas = RI.metas([c['rows']], R.dev())
     tokens, pad_mult = h.radar_tokens(metas, R.dev())
     args = ([ops.to_nhwc(gpu(f)) for f in RI.feats_np()], ops.lidar2img_tensor(metas, R.dev()), metas[0]['img_shape'][0][:2],
@@ -287,7 +283,7 @@ def test_training_iteration_with_dropout_against_oracle(T, monkeypatch, which, b
     from the oracle with query 70's input on the other side; unit 198 (F = 8) sits on the plain oracle's side (3e-6); the
     largest other element is 1.7e-3 / 1.4e-3 (rf_norm2.weight)."""
     case = TRAIN[which]
-    c = RI.oracle_case(case, monkeypatch)
+    c = RI.oracle_case(case)
     assert c['margin'] >= RI.MIN_MARGIN
     tied = _tied_inputs(c)                      # (CPU)
     assert len(tied) <= 2, tied
@@ -323,10 +319,10 @@ def test_training_iteration_with_dropout_against_oracle(T, monkeypatch, which, b
 
 
 # ---- 4. the routes agree bit for bit ------------------------------------------------------------------------------------------------
-def test_routes_agree_bit_for_bit(T, monkeypatch):
+def test_routes_agree_bit_for_bit(T):
     from transcar_amd import ops, radar
     from transcar_amd.pipeline import FramePipeline
-    c = RI.oracle_case('N2048-n1700', monkeypatch)
+    c = RI.oracle_case('N2048-n1700')
     N, rows = c['N'], c['rows']
     assert RI.in_range(rows, RI.POINT_RANGE).all()
     head = _head(T, N, 36)
@@ -363,7 +359,7 @@ def test_routes_agree_bit_for_bit(T, monkeypatch):
 
 
 def test_plugin_graphs_replay_at_2048_tokens(T):
-    hg, he = RI.make_head(T, 2048, 36), RI.make_head(T, 2048, 36)
+    hg, he = R.make_head(T, **RI.variant(2048))[0], R.make_head(T, **RI.variant(2048))[0]
     R.check_plugin_graph_replay(hg, he)
     e = next(iter(hg._plugin_graphs.entries.values()))
     assert e.pad_mult == 2048 - e.T + 1 and e.stage.num_tokens == 2048
@@ -392,15 +388,15 @@ def test_raw_sweeps_beyond_1500_points_are_attended_at_2048(T):
 
 
 # ---- 5. the default head -------------------------------------------------------------------------------------------------------------
-def test_default_head_equals_the_defaults_spelled_out(T, monkeypatch):
+def test_default_head_equals_the_defaults_spelled_out(T):
     from transcar_amd import configs
-    sd = {k: torch.from_numpy(v) for k, v in RI.state_dict(36).items()}
+    sd = {k: torch.from_numpy(v) for k, v in R.state_dict(**RI.variant()).items()}
     plain = T.build_head(configs.head_cfg(num_query=RI.Q))
     spelled = T.build_head(dict(configs.head_cfg(num_query=RI.Q), radar_num_tokens=1500, radar_in_dims=36,
                                 radar_point_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0)))
     outs = []
     frame = synth.make_radar_frame(seed=2, n_per_radar=51, centres=RI.gate_centres())
-    rows = RI.oracle_case('range', monkeypatch)['rows']
+    rows = RI.oracle_case('range')['rows']
     for h in (plain, spelled):
         h.load_state_dict(sd, strict=True)
         h = h.to(R.dev()).eval()

@@ -1,7 +1,7 @@
 """The head's configuration keys taken together, on the MI355X: every row of variant_pairs_rig's pairwise tables through the
 kernels against the CPU oracle under the same combination.
 
-Inference, per row: the head built through configs.head_cfg with all the row's keys, every key asserted on
+Inference, per row: the head built through head_variant_rig from all the row's keys, every key asserted on
 weights_struct(), one launch of one or two samples under the row's chain path, each sample against oracle_row through
 head_variant_rig.check_against_oracle with the rig's tolerances as they are; with outputs='all' the decoder levels against
 O.decoder_outputs.  The flat tolerances are the bound on every row: the project's arbiter of a query beyond them, the
@@ -52,7 +52,7 @@ def run_row(head, row, rows_per_sample):
 def test_inference_row_against_oracle(T, i):
     row = VP.INFERENCE_ROWS[i]
     oracles = [VP.oracle_row(row, b) for b in range(row['samples'])]                  # (CPU: before the GPU is touched)
-    head = VP.make_head(T, row)
+    head = R.make_head(T, **VP.variant(row))[0]
     assert head.cam_pregather_supported() == (row['num_cams'] <= 8 and row['num_levels'] == 4)
     outs = run_row(head, row, [o['rows'] for o in oracles])
     levels, L = outs['all_cls_scores'].shape[0], row['num_fusion_layers']
@@ -95,15 +95,15 @@ def _rows_of(row, seeds):
 @pytest.mark.parametrize('i', MOST, ids=[INFERENCE_IDS[i] for i in MOST])
 def test_frame_of_nine_is_its_own(T, i):
     row = VP.INFERENCE_ROWS[i]
-    R.check_frame_of_nine(VP.make_head(T, row), shapes=R.TINY[:row['num_levels']], refs_initial=not row['with_box_refine'],
+    R.check_frame_of_nine(R.make_head(T, **VP.variant(row))[0], shapes=R.TINY[:row['num_levels']], refs_initial=not row['with_box_refine'],
                           geometry=VP.ring(row), num_cams=row['num_cams'], radar=_rows_of(row, range(60, 69)))
 
 
 @pytest.mark.parametrize('i', GRAPHS, ids=[INFERENCE_IDS[i] for i in GRAPHS])
 def test_plugin_graph_replay_is_the_eager_entry(T, i):
     row = VP.INFERENCE_ROWS[i]
-    R.check_plugin_graph_replay(VP.make_head(T, row), VP.make_head(T, row), shapes=R.TINY[:row['num_levels']], geometry=VP.ring(row),
-                                num_cams=row['num_cams'])
+    R.check_plugin_graph_replay(R.make_head(T, **VP.variant(row))[0], R.make_head(T, **VP.variant(row))[0],
+                                shapes=R.TINY[:row['num_levels']], geometry=VP.ring(row), num_cams=row['num_cams'])
 
 
 # ---- 3. training ------------------------------------------------------------------------------------------------------------------
@@ -113,7 +113,7 @@ def iteration(T, row):
     from transcar_amd import ops
     from transcar_amd.trainer import FusionTrainer
     full, o = VP.full(row), VP.oracle_row(row)
-    h = VP.make_head(T, row, train=True)
+    h = R.train_head(**VP.variant(row))
     metas = VP.ring(row).metas(1, radar=gpu(o['rows']))
     tokens, pad_mult = h.radar_tokens(metas, R.dev())
     boxes, labels = VP.ground_truth(row)

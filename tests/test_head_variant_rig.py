@@ -214,14 +214,25 @@ def test_grads_check_accepts_itself_and_refuses_what_differs():
 # ---- the variant keys, and the oracle's arguments for them ---------------------------------------------------------------
 def test_variant_kw_takes_the_configs_keys_and_refuses_others():
     assert R.CONFIGS == dict(num_levels=4, num_points=1, with_box_refine=True, num_heads=8, num_classes=10, num_query=900,
-                             num_fusion_layers=3, radar_gate=None)
+                             num_fusion_layers=3, radar_gate=None, radar_num_heads=8, radar_num_tokens=1500, radar_in_dims=36,
+                             radar_point_range=None, feedforward_channels=512)
     assert R.variant_kw(**R.CONFIGS) == {} and R.variant_key(**R.CONFIGS) == ()
     kw = dict(num_heads=4, num_classes=23, num_query=37)
     assert R.variant_kw(num_points=1, **kw) == kw
     assert R.state_dict_kw(**kw) == dict(num_classes=23, num_query=37)         # the state dict has no head count
-    assert R.oracle_kw(**kw) == dict(with_box_refine=True, num_heads=4)
+    assert R.decoder_kw(**kw) == dict(with_box_refine=True, num_heads=4, num_cams=6)
+    assert R.oracle_kw(**kw) == dict(R.decoder_kw(**kw), radar_num_heads=8, num_radar_tokens=1500)
     assert R.variant_key(num_heads=4, num_classes=10) != R.variant_key(num_heads=16)
-    for fn in (R.variant_kw, R.state_dict_kw, R.oracle_kw, R.variant_key):
+    # the radar side's keys and the FFN's width: all reach configs.head_cfg, two reach the state dict (one under synth's
+    # name for it), two reach the oracle by argument (it reads the feature count and the width off the weights)
+    face = (-40.0, -30.0, -2.0, 25.0, 35.0, 1.5)
+    kw = dict(radar_num_heads=4, radar_num_tokens=64, radar_in_dims=64, radar_point_range=face, feedforward_channels=1024)
+    assert R.variant_kw(**kw) == kw
+    assert R.state_dict_kw(**kw) == dict(radar_in=64, feedforward_channels=1024)
+    assert R.oracle_kw(**kw) == dict(with_box_refine=True, num_heads=8, num_cams=6, radar_num_heads=4, num_radar_tokens=64)
+    keys = [R.variant_key(**{k: v}) for k, v in kw.items()] + [R.variant_key(), R.variant_key(**kw)]
+    assert len(set(keys)) == len(keys) and R.variant_key(radar_point_range=list(face)) == R.variant_key(radar_point_range=face)
+    for fn in (R.variant_kw, R.state_dict_kw, R.decoder_kw, R.oracle_kw, R.variant_key):
         with pytest.raises(AssertionError):
             fn(num_head=4)
 
@@ -234,7 +245,7 @@ def test_depth_and_gate_as_variant_keys():
     assert R.variant_kw(radar_gate=default3) == dict(radar_gate=default3)     # ... the default's explicit spelling too
     assert R.state_dict_kw(**kw) == dict(num_fusion_layers=2)        # the gate reaches no state dict
     assert R.state_dict_kw(radar_gate=R.WIDE3, num_heads=4) == {}
-    assert R.oracle_kw(**kw) == dict(with_box_refine=True, num_heads=8)       # the oracle's decoder reads neither
+    assert R.decoder_kw(**kw) == dict(with_box_refine=True, num_heads=8, num_cams=6)      # the oracle's decoder reads neither
     keys = [R.variant_key(**v) for v in (dict(), dict(radar_gate=R.CIRCLE), dict(radar_gate=R.WIDE3), dict(num_fusion_layers=2),
                                          dict(num_fusion_layers=1), kw, dict(num_fusion_layers=2, radar_gate=R.WIDE3),
                                          dict(radar_gate=R.CIRCLE, num_heads=4))]
@@ -243,7 +254,7 @@ def test_depth_and_gate_as_variant_keys():
     # a key holds the gate normalised: two spellings of one gate share a head, a shallower head keeps its own entries
     assert R.variant_key(radar_gate=dict(type='circle', radii=(2, 2.0, 1))) == R.variant_key(radar_gate=R.CIRCLE)
     assert R.variant_key(**kw) == R.variant_key(num_fusion_layers=2, radar_gate=dict(type='circle', radii=[2.0, 2.0]))
-    for fn in (R.variant_kw, R.state_dict_kw, R.oracle_kw, R.variant_key):
+    for fn in (R.variant_kw, R.state_dict_kw, R.decoder_kw, R.oracle_kw, R.variant_key):
         with pytest.raises(AssertionError):
             fn(fusion_layers=2)
 

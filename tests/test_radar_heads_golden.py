@@ -1,4 +1,4 @@
-"""The CPU oracle with its radar fusion attention at 4 and at 16 heads (radar_heads_rig.oracle_radar_heads) against the
+"""The CPU oracle with its radar fusion attention at 4 and at 16 heads (head_forward's radar_num_heads) against the
 reference's fixtures of those counts (tests/golden/make_golden_radar_heads.py): the forward's outputs and hit counts, and
 one training iteration's losses and gradients, with the bounds test_radar_gate_golden.py and test_fusion_depth_golden.py
 apply to their fixtures.  No GPU."""
@@ -17,18 +17,17 @@ def _sd():
 
 
 def test_the_patch_reaches_the_fusion_attention_only():
-    """Under oracle_radar_heads(8) the oracle is the unpatched one bit for bit; at 4 / 16 heads the decoder is untouched and
-    the fusion logits move by far more than any tolerance here; the function is put back afterwards."""
-    plain_fn = O.multihead_attention
+    """radar_num_heads=8 is the oracle without the argument bit for bit; at 4 / 16 heads the decoder is untouched and the
+    fusion logits move by far more than any tolerance here."""
     feats, frame = R.g5_frame()
-    want, wdbg = R.oracle_head(_sd(), feats, frame)
-    got, _ = RR.oracle_head(_sd(), feats, frame, 8)
-    assert O.multihead_attention is plain_fn
+    want, wdbg = O.head_forward(_sd(), [torch.from_numpy(f) for f in feats], torch.from_numpy(synth.make_lidar2img()).float()[None],
+                                R.HW, O.build_radar_features(frame), R.PCR, return_debug=True)
+    got, _ = R.oracle_head(_sd(), feats, frame, radar_num_heads=8)
     for k in ('all_cls_scores', 'all_bbox_preds'):
         assert torch.equal(got[k], want[k]), k
     outs = {8: want}
     for H in RR.HEADS:
-        outs[H], dbg = RR.oracle_head(_sd(), feats, frame, H)
+        outs[H], dbg = R.oracle_head(_sd(), feats, frame, radar_num_heads=H)
         assert torch.equal(dbg['hs'], wdbg['hs']) and torch.equal(dbg['inter_refs'], wdbg['inter_refs'])
     for a, b in ((4, 8), (16, 8), (4, 16)):
         assert float((outs[a]['all_cls_scores'] - outs[b]['all_cls_scores']).abs().max()) > 0.1, (a, b)
@@ -39,7 +38,7 @@ def test_oracle_forward_agrees_with_the_reference(H):
     g5 = R.gold(RR.g5_name(H))
     assert int(g5['radar_num_heads']) == H
     feats, frame = RR.g5_frame(H)
-    got, dbg = RR.oracle_head(_sd(), feats, frame, H)
+    got, dbg = R.oracle_head(_sd(), feats, frame, radar_num_heads=H)
     assert int(dbg['fill_in']) == int(g5['fill_in'])
     np.testing.assert_allclose(dbg['inter_refs'].numpy(), g5['inter_refs'], atol=R.REFS_TOL, rtol=0)
     for i in range(3):                       # hit counts identical in every layer: the stored margin leaves no tie to a CPU
@@ -53,7 +52,7 @@ def test_oracle_forward_agrees_with_the_reference(H):
     assert float(np.abs(plain['all_cls_scores'].numpy() - g5['all_cls_scores']).max()) > 0.1
     # the margin is what the rig measures, up to the bound between two fp32 orders of the box arithmetic (BOX_TOL moves a
     # gate centre), and an order of magnitude beyond that bound: no evaluation order flips a decision of this frame
-    margin, again = float(g5['gate_margin']), RR.gate_margin(_sd(), feats, frame, H)
+    margin, again = float(g5['gate_margin']), R.gate_margin(_sd(), feats, frame, radar_num_heads=H)
     assert margin > 10 * R.BOX_TOL and abs(margin - again) <= R.BOX_TOL, (margin, again)
 
 
@@ -73,11 +72,11 @@ def test_oracle_backward_matches_the_reference(H):
     # between two fp32 orders of the box arithmetic (either side moves by one, and twice that), and gradients that stay
     # inside half the bound below with every ReLU input within TIE_TAU of zero taken on the other side
     sd = O.to_torch_sd(synth.make_state_dict(seed=3))
-    margin = RR.gate_margin(sd, host['feats_np'], host['frame'], H)
+    margin = R.gate_margin(sd, host['feats_np'], host['frame'], radar_num_heads=H)
     assert margin > 4 * R.BOX_TOL and abs(margin - float(g8['gate_margin'])) <= R.BOX_TOL, margin
     ties = RR.tie_sensitivity(host, H)
     assert ties < RR.TIE_BOUND and abs(ties - float(g8['tie_sensitivity'])) < 0.25 * RR.TIE_BOUND, ties
-    cut, losses, _, grads = RR.oracle_training(host, H)
+    cut, losses, _, grads = R.oracle_training(host, radar_num_heads=H)
     for k, v in cut.items():
         assert np.abs(v.numpy() - g8[k]).max() < 5e-4, k
     assert sorted('loss__' + k.replace('.', '_') for k in losses) == sorted(k for k in g8.files if k.startswith('loss__'))

@@ -18,6 +18,7 @@ import num_cams_rig as NR
 import radar_heads_rig as RR
 import radar_input_rig as RI
 import variant_pairs_rig as VP
+from transcar_amd import configs
 
 TABLES = {'inference': (VP.INFERENCE_AXES, VP.cam_logits_ok, VP.INFERENCE_ROWS, VP.MAX_INFERENCE_ROWS, VP.INFERENCE_SEED, VP.INFERENCE_FRAMES),
           'training': (VP.TRAINING_AXES, VP.unconstrained, VP.TRAINING_ROWS, VP.MAX_TRAINING_ROWS, VP.TRAINING_SEED, VP.TRAINING_FRAMES)}
@@ -61,7 +62,7 @@ def test_generator_gives_the_committed_rows(table):
 
 @pytest.mark.parametrize('row', ALL_ROWS, ids=IDS)
 def test_head_cfg_builds_every_row(row):
-    cfg, full = VP.head_cfg(row), VP.full(row)
+    cfg, full = configs.head_cfg(**R.variant_kw(**VP.variant(row))), VP.full(row)
     layers = cfg['transformer']['decoder']['transformerlayers']['attn_cfgs']
     assert cfg['num_query'] == full['num_query'] and cfg['num_classes'] == cfg['bbox_coder']['num_classes'] == full['num_classes']
     assert layers[0]['num_heads'] == full['num_heads'] and layers[1].get('num_cams', 6) == full['num_cams']
@@ -72,7 +73,7 @@ def test_head_cfg_builds_every_row(row):
     assert (cfg.get('radar_point_range') is None) == (full['radar_point_range'] == 'default')
     assert (cfg.get('radar_gate') is None) == (full['radar_gate'] == 'default')
     assert tuple(cfg['bbox_coder']['pc_range']) == VP.ring(row).pc_range
-    sd = VP.state_dict(row)
+    sd = R.state_dict(**VP.variant(row))
     assert sd['query_embedding.weight'].shape[0] == full['num_query'] and sd['radar_feat_encoder.0.weight'].shape == (64, full['radar_in_dims'])
     assert sd['transformer.decoder.layers.0.attentions.1.attention_weights.weight'].shape[0] == \
         full['num_cams'] * full['num_levels'] * full['num_points']

@@ -3,17 +3,14 @@ tiny maps -- every admissible pair of values of two axes stands in some row -- f
 training iteration (TRAINING_ROWS), the greedy generator that produced the two tables, one radar frame per row and sample
 chosen by the gate-margin search, and one oracle driver, oracle_row.
 
-The other rigs each serve one axis and keep every other key at the TransCAR configs' value; head_variant_rig's CONFIGS
-rejects the keys of num_cams_rig, radar_heads_rig and radar_input_rig.  Here a row carries all of them: the head is built
-through configs.head_cfg with every key of the row, and the oracle composes what the side rigs do, nested --
-num_cams_rig.bound(N), radar_heads_rig.oracle_radar_heads(H), O.NUM_RADAR_TOKENS set for the call (`tokens`) and
-O.head_forward fed the [n, F] rows the row's filter range keeps.  The checkers, tolerances and the gate-margin discipline are
-head_variant_rig's and radar_input_rig's, as they are.
+The other rigs each serve one axis and keep every other key at the TransCAR configs' value.  Here a row carries all of
+them: `variant(row)` spells the row as a head_variant_rig variant, through which the head is built and the oracle told every
+key by argument, and the oracle is fed the [n, F] rows the row's filter range keeps.  The builders, checkers, tolerances and
+the gate-margin discipline are head_variant_rig's and radar_input_rig's, as they are.
 
 A row is a dict of axis -> value; gate, filter range and geometry are spelled as names (GATES, RANGES, GEOMS), the chain path
 as num_cams_rig.PATHS spells it (and 'unfused').  A training row fixes its decoder-side keys by name (DECODERS).  What is
 computed on the CPU is computed once per row and sample and kept."""
-import contextlib
 import itertools
 
 import numpy as np
@@ -25,7 +22,7 @@ import radar_heads_rig as RR
 import radar_input_rig as RI
 from oracle import transcar_oracle as O
 from radar_input_rig import BACKWARDS, FACE_RANGE
-from transcar_amd import configs, synth
+from transcar_amd import synth
 
 # ---- the axes ---------------------------------------------------------------------------------------------------------------
 INFERENCE_AXES = dict(
@@ -332,22 +329,11 @@ def ring(row, b=0):
 
 
 def variant(row, b=0):
-    """head_variant_rig's variant of the row: the keys its CONFIGS knows and the geometry"""
+    """head_variant_rig's variant of the row: every configuration key of the row, and sample b's cameras as the geometry"""
     row = full(row)
-    kw = {k: row[k] for k in ('num_levels', 'num_points', 'with_box_refine', 'num_heads', 'num_classes', 'num_query', 'num_fusion_layers')}
-    return dict(kw, radar_gate=GATES[row['radar_gate']], geometry=ring(row, b))
-
-
-def head_cfg(row):
-    """configs.head_cfg with all the row's keys"""
-    row = full(row)
-    return configs.head_cfg(radar_num_heads=row['radar_num_heads'], radar_num_tokens=row['radar_num_tokens'],
-                            radar_in_dims=row['radar_in_dims'], radar_point_range=RANGES[row['radar_point_range']],
-                            **R.variant_kw(**variant(row)))
-
-
-def state_dict(row):
-    return synth.make_state_dict(seed=3, radar_in=full(row)['radar_in_dims'], **R.state_dict_kw(**variant(row)))
+    kw = {k: row[k] for k in ('num_levels', 'num_points', 'with_box_refine', 'num_heads', 'num_classes', 'num_query',
+                              'num_fusion_layers', 'radar_num_heads', 'radar_num_tokens', 'radar_in_dims')}
+    return dict(kw, radar_gate=GATES[row['radar_gate']], radar_point_range=RANGES[row['radar_point_range']], geometry=ring(row, b))
 
 
 def feats(row):
@@ -356,56 +342,7 @@ def feats(row):
     return NR.feats(row['num_cams'], batch=row['samples'], num_levels=row['num_levels'])
 
 
-def check_head(h, row):
-    """Every key of the row arrived where the kernels read it."""
-    from transcar_amd import _lib as L
-    row = full(row)
-    w = h.weights_struct()
-    assert (w.num_cams, w.num_levels, max(w.num_points, 1)) == (row['num_cams'], row['num_levels'], row['num_points'])
-    assert w.num_heads == L.pack_num_heads(row['num_heads'], row['radar_num_heads'])
-    assert (w.num_heads & 0xffff) == row['num_heads'] and (w.num_heads >> 16) == (0 if row['radar_num_heads'] == 8 else row['radar_num_heads'])
-    assert w.num_classes == h.bbox_coder.num_classes == row['num_classes'] and w.num_query == row['num_query']
-    assert h.num_fusion_layers == w.num_radar_layers == row['num_fusion_layers']
-    assert (w.num_radar_tokens_ref, w.radar_in_dims) == (h.radar_num_tokens, h.radar_in_dims) == (row['radar_num_tokens'], row['radar_in_dims'])
-    assert h.radar_gate == L.check_radar_gate(GATES[row['radar_gate']], row['num_fusion_layers'])
-    assert h.with_box_refine == row['with_box_refine'] and h.radar_num_heads == row['radar_num_heads']
-    geom = ring(row)
-    assert tuple(h.pc_range) == geom.pc_range and tuple(h.bbox_coder.post_center_range) == geom.post_center_range
-    assert tuple(w.pc_range) == tuple(float(np.float32(v)) for v in geom.pc_range)
-
-
-def make_head(T, row, train=False):
-    """A fresh head of the row with seeded weights: eval mode, or the trainer's (frozen decoder, no dropout yet)."""
-    cfg = head_cfg(row)
-    if train:
-        cfg.setdefault('train_cfg', configs.train_cfg_pts)
-    h = T.build_head(cfg)
-    h.load_state_dict({k: torch.from_numpy(v) for k, v in state_dict(row).items()}, strict=True)
-    check_head(h, row)
-    h = h.to(R.dev())
-    return h.freeze_decoder().set_dropout(0.0) if train else h.eval()
-
-
 # ---- the oracle under a row ----------------------------------------------------------------------------------------------------
-@contextlib.contextmanager
-def tokens(n):
-    """O.NUM_RADAR_TOKENS = n for the duration of the call"""
-    plain = O.NUM_RADAR_TOKENS
-    O.NUM_RADAR_TOKENS = n
-    try:
-        yield
-    finally:
-        O.NUM_RADAR_TOKENS = plain
-
-
-@contextlib.contextmanager
-def under(row):
-    """What the oracle cannot be told by argument: the camera count, the fusion attention's heads, the token count."""
-    row = full(row)
-    with NR.bound(row['num_cams']), RR.oracle_radar_heads(row['radar_num_heads']), tokens(row['radar_num_tokens']):
-        yield
-
-
 _SD, _TRACE, _ROWS, _ORACLE, _FP64 = {}, {}, {}, {}, {}
 DECODER_KEYS = ('num_cams', 'num_levels', 'num_points', 'with_box_refine', 'num_heads', 'num_classes', 'num_query', 'geometry', 'samples')
 
@@ -417,7 +354,7 @@ def _key(row):
 def oracle_sd(row):
     """the row's weights as the oracle takes them (kept: a row's frames and checks share one dict)"""
     if _key(row) not in _SD:
-        _SD[_key(row)] = O.to_torch_sd(state_dict(row))
+        _SD[_key(row)] = O.to_torch_sd(R.state_dict(**variant(row)))
     return _SD[_key(row)]
 
 
@@ -437,8 +374,8 @@ def decoder_trace(row, b=0, double=False, sd=None):
         weights = oracle_sd(row) if sd is None else sd
         if double:
             weights, maps, l2i = {k: v.detach().double() for k, v in weights.items()}, [f.double() for f in maps], l2i.double()
-        with under(row), torch.no_grad():
-            trace = O.transformer(weights, maps, list(geom.pc_range), l2i, geom.hw, **R.oracle_kw(**variant(row, b)))
+        with torch.no_grad():
+            trace = O.transformer(weights, maps, list(geom.pc_range), l2i, geom.hw, **R.decoder_kw(**variant(row, b)))
         if sd is not None:
             return trace
         _TRACE[key] = trace
@@ -448,13 +385,8 @@ def decoder_trace(row, b=0, double=False, sd=None):
 def head_forward(row, b, kept, trace=None, sd=None, **kw):
     """O.head_forward of sample b under the row on the rows `kept` (already filtered by the row's range); kw: its other
     arguments."""
-    row = full(row)
-    geom, v = ring(row, b), variant(row, b)
-    with under(row):
-        return O.head_forward(oracle_sd(row) if sd is None else sd, sample_feats(row, b),
-                              torch.from_numpy(geom.lidar2img()).float()[None], geom.hw, kept, list(geom.pc_range),
-                              decoder_trace=decoder_trace(row, b) if trace is None else trace,
-                              num_fusion_layers=row['num_fusion_layers'], radar_gate=v['radar_gate'], **R.oracle_kw(**v), **kw)
+    return R.oracle_forward(oracle_sd(row) if sd is None else sd, sample_feats(row, b), kept, variant(row, b),
+                            decoder_trace=decoder_trace(row, b) if trace is None else trace, **kw)
 
 
 def gate_centres(row, b=0):
@@ -553,15 +485,8 @@ def oracle_row(row, b=0):
     if key not in _ORACLE:
         rows, kept = frame_rows(row, b, frame_seed(row, b)[0])
         masks, margins = [], []
-        measure = R.margin_probe(margins)
-
-        def probe(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax):
-            from transcar_amd._lib import TC_RADAR_GATE_CIRCLE
-            masks.append(O.single_circle_mask(centre_xy, radar_xy, rmax) if rmin == TC_RADAR_GATE_CIRCLE
-                         else O.circle_mask(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax))
-            measure(centre_xy, length_log, rot_sin, rot_cos, radar_xy, rmin, rmax)
         with torch.no_grad():
-            want, dbg = head_forward(row, b, kept, return_debug=True, gate_probe=probe)
+            want, dbg = head_forward(row, b, kept, return_debug=True, gate_probe=R.margin_probe(margins, masks))
         assert dbg['fill_in'] == min(full(row)['radar_num_tokens'], len(kept))
         assert all(torch.equal((~m).sum(1), h) for m, h in zip(masks, dbg['hit_counts']))
         _ORACLE[key] = dict(sd=oracle_sd(row), rows=rows, kept=kept, want=want, dbg=dbg, masks=masks, margin=min(margins))
@@ -612,12 +537,8 @@ def expected_gradients(row):
 def dropout_masks(row, seed):
     """The oracle's ``drop`` of the row as the kernels draw it with `seed` (read back through tc_dropout_mask; the
     probabilities' at the row's heads and token count)."""
-    plain = RR.TOKENS_REF
-    RR.TOKENS_REF = row['radar_num_tokens']
-    try:
-        return RR.radar_dropout_masks(row['dropout'], seed, row['radar_num_heads'], row['num_query'], layers=row['num_fusion_layers'])
-    finally:
-        RR.TOKENS_REF = plain
+    return R.radar_dropout_masks(row['dropout'], seed, row['radar_num_heads'], row['num_query'], layers=row['num_fusion_layers'],
+                                 tokens=row['radar_num_tokens'])
 
 
 MAX_TIED = 6             # influential query-side ReLU ties a training frame may have set apart
@@ -636,7 +557,7 @@ def oracle_training(row, drop=None, seed=None, flip=(), tau=None, tied=None):
     not even depend on the frame -- so these are listed, `tied` (a list that receives (call, query, unit) of every such
     input within TIE_TAU of zero), and taken on the other side one by one, `flip`.
     -> (losses {name: float}, {name: gradient or None} of the trainable parameters)"""
-    sd = O.to_torch_sd(state_dict(row))
+    sd = O.to_torch_sd(R.state_dict(**variant(row)))
     for k, v in sd.items():
         if R.trainable(k):
             v.requires_grad_(True)
